@@ -37,6 +37,16 @@ def workload():
     return mu, sig
 
 
+def initial_positions(mu, sig, C, rank):
+    """q0 ~ mu + sigma N(0,1) (in-distribution start), drawn in blocks of 4096 chains from default_rng(1 + rank)"""
+    rng = np.random.default_rng(1 + rank)
+    blk = 4096
+    q0 = np.empty((C, D))
+    for i in range(0, C, blk):
+        q0[i:i + blk] = mu + sig * rng.standard_normal((min(blk, C - i), D))
+    return q0
+
+
 def host_isa():
     """what the CPU baseline ran on: model name and the vector ISA levels /proc/cpuinfo lists"""
     model, flags = "unknown", set()
@@ -149,6 +159,28 @@ def committed_profile(name):
         return None, None, None
 
 
+DUMP_BYTES = 60_000_000             # --dump-outputs budget (64 MB at most)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(eng, out_dir):
+    """What the timed sweeps left for a caller, read right after them: q, p, grad l (chains x D) and l(q) (chains), float64.
+    When all chains exceed DUMP_BYTES, the same rows of each are kept: a sorted sample of chains drawn with DUMP_SEED, so two builds
+    run with the same arguments write arrays that compare element for element."""
+    q = eng.q
+    C, Dq = q.shape
+    n = min(C, DUMP_BYTES // ((3 * Dq + 1) * 8))
+    rows = np.arange(C) if n == C else np.sort(np.random.default_rng(DUMP_SEED).choice(C, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, get in (("q", lambda: q), ("p", lambda: eng.p), ("grad", lambda: eng.grad), ("lq", lambda: eng.lq)):
+        a = np.ascontiguousarray(get()[rows], dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = list(a.shape)
+    return {"dir": out_dir, "files": files, "chains": int(n), "of_chains": int(C),
+            "sample": None if n == C else {"seed": DUMP_SEED, "how": "sorted numpy default_rng(seed).choice(chains, n, replace=False)"}}
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -161,6 +193,8 @@ def parse_args():
     ap.add_argument("--no-cfg3", action="store_true", help="skip the configs[2] end-to-end leg (cfg3_full)")
     ap.add_argument("--cfg3-chains", type=int, default=None, help="chains of the cfg3_full leg (default: --chains)")
     ap.add_argument("--cfg3-scale", type=float, default=1.0, help="scale of the cfg3_full leg's stage lengths and draws (tests: < 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's q, p, grad, lq (a fixed sample of chains, <= 64 MB) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -285,13 +319,7 @@ def run_rank(args):
     eng = pkg.Engine(pkg.DiagGaussian(mu, sigma=sig), C, opt, seed=1, first_chain=rank * C, device=local)
     eng.set_minv(sig ** 2)
     # q0 ~ mu + sigma N(0,1) (in-distribution start), p0 ~ W N(0,1) from the engine's Philox stream
-    rng = np.random.default_rng(1 + rank)
-    blk = 4096
-    q0 = np.empty((C, D))
-    for i in range(0, C, blk):
-        q0[i:i + blk] = mu + sig * rng.standard_normal((min(blk, C - i), D))
-    eng.set_q(q0)
-    del q0
+    eng.set_q(initial_positions(mu, sig, C, rank))
     eng.refresh_momentum(1)
 
     def barrier():
@@ -320,6 +348,7 @@ def run_rank(args):
         kernel_ms_ranks = {"min": -float(tt[2]), "max": float(tt[1])}
         dist.barrier()
     finite = bool(np.isfinite(eng.lq).all())
+    dumped = dump_outputs(eng, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     # SURVEY.md 8d's second cfg2 variant, outside the timed region (rank 0 at N=1): M^-1 = I, eps = 0.1 sigma_min
     identity = None
@@ -729,6 +758,8 @@ def run_rank(args):
             "state_finite": finite,
             "state_placement": placement,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if identity is not None:
             out["identity_metric"] = identity
         if regrad is not None:

@@ -258,7 +258,7 @@ static int dalloc(idhmc_ctx *c, T **out, int64_t n, bool zero = true)
 // is taken at once when it reaches kGoodRatio x the single-array rate; otherwise the best of the candidates tried wins.
 // Bounds (round 3): every exit path frees what it does not keep (CandidateSets below); the bytes held at any one time stay below
 // IDHMC_PLACEMENT_MAX_BYTES (default 16 GiB) and a quarter of the free memory, the kept set included; at most
-// IDHMC_PLACEMENT_TRIES candidates (default 32, at most 48, 1 = take what comes).  The wall time and the peak are reported by
+// IDHMC_PLACEMENT_TRIES candidates (default 32, at most 48, 1 = take what comes); no candidate starts after kSearchMs of the call.  The wall time and the peak are reported by
 // idhmc_placement_cost.  IDHMC_PLACEMENT_VERBOSE=1 prints the candidates.
 // Candidate kinds, in order: (V) only with IDHMC_PLACEMENT_VMM=1: one physical allocation made with the virtual-memory API (hipMemCreate +
 // hipMemMap), the arrays 36 KiB (mod 64 KiB) askew inside it -- measured like any other: NOT deterministic-good (0.97-1.00 x one array alone in a
@@ -289,6 +289,10 @@ static bool vmm_make(VmmBlock &v, int device, size_t want)
 namespace {
 constexpr int kMaxTries = 48;
 constexpr double kGoodRatio = 1.10;
+// no new candidate set after this much wall time of place_state (the pair walk included).  After a pair walk that found nothing, every
+// candidate of the walk over whole sets took 0.1-0.25 s (alone the same walk tries 8-12 in 30-50 ms): idhmc_create took 0.4-2.6 s with
+// 1-9 candidates, 0.55-0.62 s with this bound, every set kept at 1.13-1.18 x one array alone either way
+constexpr double kSearchMs = 500.0;
 // the candidate sets of one place_state call; whatever is still here when the call returns -- on any path -- is freed
 struct CandidateSets {
     double *arr[kMaxTries][4] = {};
@@ -500,7 +504,8 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
             } else (void)hipGetLastError();
             if (!ok) { cs.slab[t] = nullptr; for (int k = 0; k < 4; ++k) cs.arr[t][k] = nullptr; --t; continue; }
         } else {                                      // ordinary set
-            if (t > 0 && cs.held_now + set_bytes > budget) break;       // the budget is what bounds the walk
+            if (t > 0 && cs.held_now + set_bytes > budget) break;       // the budget is what bounds the walk ...
+            if (t > 0 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() >= kSearchMs) break;   // ... and the clock
             ok = true;
             for (int k = 0; k < nvec && ok; ++k) {
                 void *p = nullptr;

@@ -98,3 +98,39 @@ def test_a_failing_rank_fails_the_launch():
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--chains", "2048"],
                          cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
     assert out.returncode != 0 and "rank 1 exited" in out.stderr and out.stdout.strip() == ""
+
+
+def test_dump_outputs_are_the_timed_sweeps(idhmc, tmp_path):
+    """--dump-outputs DIR: after the timed steps, rank 0's q, p, grad l, l(q) as float64 .npy files within 64 MB; 4096 chains are over
+    that budget, so a seeded sample of chains is kept.  Two runs with the same arguments write the same bits, and those bits are the
+    warm-up + timed sweeps replayed here on an engine set up as bench.py sets it up (seed 1, q0 = mu + sigma N(0,1), momentum of iteration 1)"""
+    import numpy as np
+    args = ["--steps", "7", "--warmup", "3", "--chains", "4096", "--no-cpu", "--no-cfg3"]
+    lines = [run([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / k)]) for k in ("a", "b")]
+    d = lines[0]
+    assert d["steps"] == 7 and d["ms_per_step"] > 0
+    du = d["dump_outputs"]
+    assert du["of_chains"] == 4096 and 0 < du["chains"] < 4096 and du["sample"]["seed"] == lines[1]["dump_outputs"]["sample"]["seed"]
+    names = ("q", "p", "grad", "lq")
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in names) <= 64 * 2 ** 20
+    for k in names:
+        assert got[k].dtype == np.float64 and np.isfinite(got[k]).all()
+        assert np.array_equal(got[k].view(np.uint64), np.load(tmp_path / "b" / (k + ".npy")).view(np.uint64)), k
+
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    C = 4096
+    mu, sig = bench.workload()
+    eng = idhmc.Engine(idhmc.DiagGaussian(mu, sigma=sig), C, idhmc.default_options(metric_mode=idhmc.METRIC_SHARED), seed=1)
+    eng.set_minv(sig ** 2)
+    eng.set_q(bench.initial_positions(mu, sig, C, 0))
+    eng.refresh_momentum(1)
+    for _ in range(3 + 7):
+        eng.leapfrog(bench.EPS, 1)
+    rows = np.sort(np.random.default_rng(du["sample"]["seed"]).choice(C, du["chains"], replace=False))
+    want = {"q": eng.q, "p": eng.p, "grad": eng.grad, "lq": eng.lq}
+    eng.close()
+    for k in names:
+        assert np.array_equal(got[k].view(np.uint64), want[k][rows].view(np.uint64)), k
