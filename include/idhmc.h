@@ -241,6 +241,8 @@ enum {
     IDHMC_T_USE_DIRECTIONS = 16,/* use injected directions (reference kwarg directions=...) */
     IDHMC_T_ACCUM_DIAG = 32     /* add the transition to the device-side diagnostics (idhmc_diag_reset first) */
 };
+/* Any other bit of `flags` is refused with IDHMC_ERR_BAD_ARG before anything is launched (by idhmc_nuts_transitions too).
+ * (Bit 30 is the test suite's: accepted only on a context created with IDHMC_TEST_XCC_MISMATCH=1 in the environment.) */
 int idhmc_nuts_transition(idhmc_ctx *ctx, uint32_t iter, uint32_t flags);
 /* n transitions of every chain, numbered iter, iter + 1, ..., iter + n - 1, in ONE launch (src/warmup.jl:288-305 and :324-330 run
  * a chain's transitions back to back; chains are independent, src/mcmc.jl:150-157).  The state afterwards is bit for bit that of n
@@ -249,7 +251,8 @@ int idhmc_nuts_transition(idhmc_ctx *ctx, uint32_t iter, uint32_t flags);
  * wavefront is free, instead of when the slowest tree of the whole launch is: with few chains per resident wavefront (configs[3]:
  * four) the end of every single-transition launch is a quarter of its time.  Only the records of the last transition are kept
  * (idhmc_get_tree_stats); IDHMC_T_USE_DIRECTIONS and IDHMC_T_KEEP_P are not allowed, nor IDHMC_T_ADAPT_EPS with the global stepsize (its exchange
- * sits between transitions).  If a chain raises the abort code no further transitions are started.
+ * sits between transitions).  If a chain raises the abort code no further transitions are started (nor any at all while the code
+ * of an earlier launch is still set: the next driver call reports and clears it).
  * The library's own drivers (idhmc_tuning_stage, idhmc_mcmc) use it where no per-transition record leaves the device and the
  * chains are few per wavefront; IDHMC_FUSE=0 / 1 in the environment forbids / forces that. */
 int idhmc_nuts_transitions(idhmc_ctx *ctx, uint32_t iter, int32_t n, uint32_t flags);
@@ -260,7 +263,7 @@ int idhmc_set_directions(idhmc_ctx *ctx, const uint32_t *directions); /* nchains
 /* The reference aborts a warm-up the moment a chain's stepsize falls below 1e-10 (src/warmup.jl:291-296).  Every
  * transition launch is followed by an asynchronous copy of the device's abort word into pinned host memory;
  * idhmc_poll_abort waits for the word of the launch `lag` launches back (0 = the newest: a synchronisation) and
- * returns its code (0 or IDHMC_ERR_EPS_UNDERFLOW) without touching the stream otherwise.  The library's own drivers
+ * returns its code (0, IDHMC_ERR_EPS_UNDERFLOW, or IDHMC_ERR_HIP from a refused launch of several transitions) without touching the stream otherwise.  The library's own drivers
  * poll with lag 8, i.e. stop within 8 transitions of the underflow and then fail with the code. */
 int idhmc_poll_abort(idhmc_ctx *ctx, int32_t lag, int32_t *code);
 int idhmc_get_tree_stats(idhmc_ctx *ctx, idhmc_tree_stats *stats);    /* nchains records of the last transition */
@@ -317,9 +320,12 @@ int idhmc_xchg_mean(int32_t kind, const double *xchg4, double *mean);
  * the stream and before what is enqueued next (RCCL on the same stream, or torch.distributed.all_reduce on a tensor
  * aliasing dev_xchg with the context on torch's stream).  dev_xchg is caller-owned device memory.
  * fn == NULL: single-rank (no exchange).
- * Errors are agreed on before they are returned: the drivers enqueue the exchange FIRST and then fail on every rank together
+ * Errors are agreed on before they are returned: idhmc_find_initial_stepsize (both eps modes), idhmc_find_local_optimum and
+ * idhmc_tuning_stage (so idhmc_mcmc_with_warmup's warm-up too) enqueue the exchange FIRST and then fail on every rank together
  * when the all-reduced slot [3] is non-zero (local code on the rank that owns the failing chain, IDHMC_ERR_PEER on the others);
  * idhmc_tuning_stage ends with one more such record (zeros but slot [3]) before its pooled-metric collectives.
+ * idhmc_mcmc has no collective to leave a peer in and checks locally: only the rank that owns the failing chain fails.
+ * idhmc_find_initial_stepsize_per_chain is the bare search for hosts that pool the stepsizes themselves: it checks locally too.
  * The hook carries ONLY this record.  IDHMC_METRIC_POOLED needs table-sized all-reduces, which go through the context's own
  * communicator (idhmc_comm_init); under a hook WITHOUT a communicator idhmc_metric_update pools the chains of this rank only
  * (rank-local metric) -- exchange the tables yourself with idhmc_pool_partials / idhmc_pool_consume for a job-wide one. */
@@ -390,7 +396,10 @@ int idhmc_get_ebfmi(idhmc_ctx *ctx, double *ebfmi);                          /* 
  * iter0 = number of transitions already made (RNG address continues at iter0+1). */
 int idhmc_tuning_stage(idhmc_ctx *ctx, int32_t N, int32_t adapt_metric, uint32_t iter0,
                        double *draws, idhmc_tree_stats *stats);
-/* mcmc! (src/warmup.jl:316-332): N transitions at fixed eps */
+/* mcmc! (src/warmup.jl:316-332): N transitions at fixed eps.  Fails with the code of any device-side error still pending when it
+ * returns -- one raised before the call (a caller's own transition whose eps fell below 1e-10, a refused launch) included: a launch of
+ * several transitions starts none while the abort code is set.  The error is reported once and cleared; the chains keep the state
+ * they hold, and the next call goes on from it.  When the call fails the contents of draws / stats are unspecified. */
 int idhmc_mcmc(idhmc_ctx *ctx, int32_t N, uint32_t iter0, double *draws, idhmc_tree_stats *stats);
 /* mcmc_with_warmup! for all chains (src/mcmc.jl:94-105 under threaded_mcmc :130-159):
  * random start, [stepsize search], default_warmup_stages, then N draws.

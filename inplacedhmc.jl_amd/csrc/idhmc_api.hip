@@ -92,6 +92,7 @@ struct idhmc_ctx {
     int force_wide = -1;                  // IDHMC_NUTS_WIDE = 0 / 1 forces one form (tests, experiments)
     int fuse = -1;                        // IDHMC_FUSE = 0 / 1: the drivers never / always make several transitions per launch (-1: yes)
     bool fuse_ok = false;                 // workgroups b and b + 8 share an XCD on this device (probed at creation): fused launches are possible
+    bool test_xcc = false;                // IDHMC_TEST_XCC_MISMATCH=1: the transition flags may carry kTestXccFlag (test suite only)
     // IDHMC_GRAD_RECOMPUTE: the single-step leapfrog of a separable density leaves the stored gradient stale; whoever
     // needs the array (get_grad, the stepsize search, the n-step kernel, the optimum stage) re-evaluates first
     bool grad_stale = false;
@@ -755,6 +756,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         for (int i = 0; i < idhmc_ctx::kRing * idhmc_ctx::kPulseWords; ++i) c->ring[i] = ~0ull;
         if (const char *w = getenv("IDHMC_NUTS_WIDE")) c->force_wide = atoi(w) != 0;
         if (const char *w = getenv("IDHMC_FUSE")) c->fuse = atoi(w) != 0;
+        if (const char *w = getenv("IDHMC_TEST_XCC_MISMATCH")) c->test_xcc = atoi(w) != 0;
         {   // several transitions per launch need workgroups b and b + 8 on one XCD (idhmc_nuts_kernel.hpp): look before relying on it
             const int g = prop.multiProcessorCount > 8 ? prop.multiProcessorCount : 8;
             uint32_t *dx = nullptr;
@@ -1057,14 +1059,25 @@ static int nuts_launch(idhmc_ctx *c, uint32_t iter, uint32_t flags, uint32_t n_i
     ++c->launches;
     return IDHMC_OK;
 }
+// the public flags: the IDHMC_T_* set, and the XCD test's bit on a context that opted in at creation
+static int check_flags(const idhmc_ctx *c, uint32_t flags)
+{
+    constexpr uint32_t kDocumented = IDHMC_T_ADAPT_EPS | IDHMC_T_ACCUM_METRIC | IDHMC_T_ACCUM_MOMENTS | IDHMC_T_KEEP_P |
+                                     IDHMC_T_USE_DIRECTIONS | IDHMC_T_ACCUM_DIAG;
+    const uint32_t unknown = flags & ~(kDocumented | (c->test_xcc ? kTestXccFlag : 0u));
+    if (unknown) return fail(IDHMC_ERR_BAD_ARG, "unknown transition flags 0x%x", unknown);
+    return IDHMC_OK;
+}
 int idhmc_nuts_transition(idhmc_ctx *c, uint32_t iter, uint32_t flags)
 {
     CTXCHK(c);
+    if (int rc = check_flags(c, flags)) return rc;
     return nuts_launch(c, iter, flags, 1);
 }
 int idhmc_nuts_transitions(idhmc_ctx *c, uint32_t iter, int32_t n, uint32_t flags)
 {
     CTXCHK(c);
+    if (int rc = check_flags(c, flags)) return rc;
     if (n < 1) return fail(IDHMC_ERR_BAD_ARG, "n must be >= 1");
     if ((uint64_t)c->s.C * (uint64_t)n >= (1ull << 31)) return fail(IDHMC_ERR_BAD_ARG, "nchains * n must be below 2^31");
     if (flags & (IDHMC_T_USE_DIRECTIONS | IDHMC_T_KEEP_P)) return fail(IDHMC_ERR_BAD_ARG, "injected directions / a kept momentum are one transition's");
@@ -1196,9 +1209,12 @@ static int status_exchange(idhmc_ctx *c, const char *what)
 int idhmc_find_initial_stepsize(idhmc_ctx *c)
 {
     CTXCHK(c);
-    if (c->s.eps_mode != IDHMC_EPS_GLOBAL) return idhmc_find_initial_stepsize_per_chain(c);
+    if (c->s.eps_mode != IDHMC_EPS_GLOBAL && !sharded(c)) return idhmc_find_initial_stepsize_per_chain(c);
     if (int rc = ensure_grad(c)) return rc;
     HIPCHK(launch_stepsize_search(c->s, c->stream));
+    // per-chain stepsizes of a sharded run: nothing to pool, but the ranks agree on the outcome (a rank that failed alone would leave
+    // the others in the next stage's collectives)
+    if (c->s.eps_mode != IDHMC_EPS_GLOBAL) return status_exchange(c, "find_initial_stepsize");
     // one eps for everybody: exp(mean log eps) over the chains of ALL ranks -- the fixed-point record is exact under
     // any all-reduce order, and the engine's own dlog / dexp run on the device, so every rank holds the same bits.
     // The exchange is enqueued BEFORE any error is looked at: a rank whose search failed still takes part, and the record's
@@ -1638,23 +1654,23 @@ int idhmc_mcmc(idhmc_ctx *c, int32_t N, uint32_t iter0, double *draws, idhmc_tre
     CTXCHK(c);
     if (N < 0) return fail(IDHMC_ERR_BAD_ARG, "N must be >= 0");
     if (draws || stats) { if (int rc = fetch_setup(c, draws != nullptr, stats != nullptr)) return rc; }
+    const uint32_t fl = (c->s.mom_mean ? IDHMC_T_ACCUM_MOMENTS : 0u) | (c->s.diag.n ? IDHMC_T_ACCUM_DIAG : 0u);
     if (const int32_t K = block_transitions(c, N, draws || stats)) {
-        const uint32_t fl = (c->s.mom_mean ? IDHMC_T_ACCUM_MOMENTS : 0u) | (c->s.diag.n ? IDHMC_T_ACCUM_DIAG : 0u);
-        return run_blocks(c, iter0 + 1u, N, fl, K, draws, stats);
-    }
-    if (!draws && !stats && fuse_transitions(c) && N > 1) {
-        const uint32_t fl = (c->s.mom_mean ? IDHMC_T_ACCUM_MOMENTS : 0u) | (c->s.diag.n ? IDHMC_T_ACCUM_DIAG : 0u);
+        if (int rc = run_blocks(c, iter0 + 1u, N, fl, K, draws, stats)) return rc;
+    } else if (!draws && !stats && fuse_transitions(c) && N > 1) {
         if (int rc = idhmc_nuts_transitions(c, iter0 + 1u, N, fl)) return rc;
-    } else
-    for (int32_t n = 0; n < N; ++n) {                                            // src/warmup.jl:324-330
-        const uint32_t fl = (c->s.mom_mean ? IDHMC_T_ACCUM_MOMENTS : 0u) | (c->s.diag.n ? IDHMC_T_ACCUM_DIAG : 0u);
-        if (int rc = one_transition(c, iter0 + 1u + (uint32_t)n, fl, 0)) return rc;
-        if (int rc = fetch_pack(c, n, draws != nullptr, stats != nullptr)) return rc;
-        if (n > 0) { if (int rc = fetch_copy(c, n - 1, draws, stats)) return rc; }   // ... while transition n computes
+    } else {
+        for (int32_t n = 0; n < N; ++n) {                                        // src/warmup.jl:324-330
+            if (int rc = one_transition(c, iter0 + 1u + (uint32_t)n, fl, 0)) return rc;
+            if (int rc = fetch_pack(c, n, draws != nullptr, stats != nullptr)) return rc;
+            if (n > 0) { if (int rc = fetch_copy(c, n - 1, draws, stats)) return rc; }   // ... while transition n computes
+        }
+        if (N > 0) { if (int rc = fetch_copy(c, N - 1, draws, stats)) return rc; }
     }
-    if (N > 0) { if (int rc = fetch_copy(c, N - 1, draws, stats)) return rc; }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return IDHMC_OK;
+    // A status still pending (a refused launch, a caller's own transition that underflowed) must not pass as success: a launch of
+    // several transitions hands out none while the abort word is set, and the staging blocks are not zeroed.  A local check (it
+    // also waits for the stream): sampling has no collective that a rank failing alone could leave the others waiting in.
+    return check_status(c, "mcmc");
 }
 int idhmc_mcmc_with_warmup(idhmc_ctx *c, int32_t N, double *draws, idhmc_tree_stats *stats)
 {

@@ -74,6 +74,9 @@ struct DevState {
                                       // chain raised: eps underflow)}; [2..9] cycle stamps of the diagnostic build (-DIDHMC_STAMPS)
 };
 constexpr int kPulseAt = 0;
+// transition flag of the test suite only (see the XCD check in k_nuts); idhmc_nuts_transition(s) accept it on a context created
+// with IDHMC_TEST_XCC_MISMATCH=1 in the environment, and refuse it, like every other bit outside the IDHMC_T_* set, otherwise
+constexpr uint32_t kTestXccFlag = 1u << 30;
 constexpr int kXchgBlocks = 64;   // workgroups of k_xchg_sum; DevState::xchg_acc holds 3 * kXchgBlocks partials + 1 ticket
 
 #ifndef __HIPCC_RTC__   // host side only (the header is also compiled by hipRTC for custom densities)

@@ -460,7 +460,6 @@ IDHMC_DEV bool nuts_wait_iter(const uint32_t *word, uint32_t need)
 // agent-scope: served by L2, never by this CU's L1, which nothing refreshes (an L1 invalidate per hand-over instead cost the cooperative
 // dense kernel ~10 %: the taker holds up its workgroup's round for the 2-7 us it takes).  Own stores are safe in any case (write-through).
 constexpr int kAuxFresh = 16;     // sc1 on gfx950's buffer loads
-constexpr uint32_t kTestXccFlag = 1u << 30;     // transition flag of the test suite only: see the XCD check in k_nuts
 template <class T>
 IDHMC_DEV T ld_fresh(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 IDHMC_DEV uint32_t nuts_peek_iter(const uint32_t *word)

@@ -251,7 +251,7 @@ class Engine:
         return bool(a.value), bool(b.value)
 
     def poll_abort(self, lag=0):
-        """abort code (0 / IDHMC_ERR_EPS_UNDERFLOW) raised up to the transition `lag` launches back (include/idhmc.h)"""
+        """abort code (0 / IDHMC_ERR_EPS_UNDERFLOW / IDHMC_ERR_HIP) raised up to the transition `lag` launches back (include/idhmc.h)"""
         code = C.c_int32()
         check(self.lib.idhmc_poll_abort(self.h, int(lag), C.byref(code)))
         return code.value

@@ -121,9 +121,11 @@ def test_bad_arguments(idhmc):
         eng.nuts_transitions(1, 4, idhmc.T_USE_DIRECTIONS)
 
 
-def test_a_range_served_from_two_xcds_is_refused(idhmc):
+def test_a_range_served_from_two_xcds_is_refused_under_the_test_opt_in(idhmc, monkeypatch):
     """the hand-over inside a launch relies on workgroups b and b + 8 sharing an XCD; the kernel checks it (HW_REG_XCC_ID) and raises the
-    abort code otherwise.  Bit 30 of the flags (test suite only) makes the workgroups of a range report different ids"""
+    abort code otherwise.  Bit 30 of the flags (test suite only, accepted on a context created with IDHMC_TEST_XCC_MISMATCH=1) makes the
+    workgroups of a range report different ids"""
+    monkeypatch.setenv("IDHMC_TEST_XCC_MISMATCH", "1")
     eng = make(idhmc, "diag", 40, 600, False)       # 38 workgroups: every range has workgroups b and b + 8
     eng.set_eps(0.3)
     eng.nuts_transitions(1, 3)

@@ -92,9 +92,11 @@ def _failing_worker(rank, world, port, out):
     mu, sig = _problem()
     first, count = pkg.distributed.shard_range(TOTAL, rank, world)
     res = []
-    for mode in ("search", "stage"):
+    for mode in ("search", "stage", "search_per_chain"):
         if mode == "search":
             opt = pkg.default_options(max_depth=6, eps_mode=pkg.EPS_GLOBAL)
+        elif mode == "search_per_chain":      # per-chain searches only: the ranks still agree on the outcome
+            opt = pkg.default_options(max_depth=6, eps_mode=pkg.EPS_PER_CHAIN)
         else:       # per-chain dual averaging; rank 1's is set up to collapse (as tests/test_gpu_edges.py::test_eps_underflow_is_reported)
             opt = pkg.default_options(max_depth=3, eps_mode=pkg.EPS_PER_CHAIN, da_gamma=1e-9 if rank == 1 else 0.05)
         eng = pkg.Engine(pkg.DiagGaussian(mu, sigma=sig), count, opt, seed=SEED, first_chain=first)
@@ -103,7 +105,7 @@ def _failing_worker(rank, world, port, out):
         eng.refresh_momentum(0)
         code = 0
         try:
-            if mode == "search":
+            if mode in ("search", "search_per_chain"):
                 if rank == 1:
                     q = eng.q
                     q[3, 0] = np.inf
@@ -131,8 +133,8 @@ def test_an_error_on_one_rank_fails_every_rank_together(idhmc, tmp_path):
     port = 29500 + (os.getpid() % 2000) + 7
     mp.spawn(_failing_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     c0, c1 = np.load(tmp_path / "codes0.npy"), np.load(tmp_path / "codes1.npy")
-    assert list(c0) == [idhmc.ERR_PEER, idhmc.ERR_PEER], c0
-    assert list(c1) == [idhmc.ERR_NONFINITE_START, idhmc.ERR_EPS_UNDERFLOW], c1
+    assert list(c0) == [idhmc.ERR_PEER, idhmc.ERR_PEER, idhmc.ERR_PEER], c0
+    assert list(c1) == [idhmc.ERR_NONFINITE_START, idhmc.ERR_EPS_UNDERFLOW, idhmc.ERR_NONFINITE_START], c1
 
 
 def test_manual_exchange_between_two_contexts_in_one_process(idhmc):
