@@ -74,22 +74,33 @@ enum {
  * (the `params` array below, in device memory), `nparams`, `D`, `lane`, and `lds` -- one L-double
  * scratch vector in LDS private to the wavefront.  Everything in inplacedhmc.jl_amd/csrc/idhmc_math.hpp
  * and idhmc_device.hpp is in scope (wave_sum, dfma, dlog, dexp, ...).  Compile errors are returned
- * through idhmc_last_error(). */
+ * through idhmc_last_error().
+ *
+ * IDHMC_MODEL_LOGISTIC_REGRESSION -- Bayesian logistic regression with a Gaussian prior, the data shared by every chain:
+ *   l(q) = sum_i [y_i z_i - softplus(z_i)] - 1/2 sum_c tau_c (q_c - mu_c)^2,   z = X q
+ *   grad l(q) = X' (y - sigma(z)) - tau .* (q - mu)
+ * `params` is [X row-major n x D | y (n)], so nparams = n (D + 1): n is nparams / (D + 1), and an nparams that is not a
+ * positive multiple of D + 1 is refused.  Each y_i is 0 or 1, each X entry finite.  `mu` and `tau` are the prior's mean and
+ * precision, each optional (NULL: 0 and 1); every tau_c must be finite and > 0, every mu_c finite.  1 <= D <= 1024, D > 512 needs
+ * a SHARED or POOLED metric; the padded length L is a power of two (128 .. 1024) and n rounded up to a multiple of 128, n_pad,
+ * satisfies n_pad L <= 2^27 (X and its transpose, kept on the device, take at most 1 GiB each).  The NUTS transition runs both
+ * products on the fp64 matrix cores, 16 chains per workgroup, at L <= 256 (D <= 256); everything else one chain per wavefront. */
 enum {
     IDHMC_MODEL_ISO_GAUSSIAN = 0,   /* l(q) = -1/2 |q|^2                       */
     IDHMC_MODEL_DIAG_GAUSSIAN = 1,  /* l(q) = -1/2 sum tau_d (q_d - mu_d)^2    */
     IDHMC_MODEL_DENSE_MVN = 2,      /* l(q) = -1/2 (q-mu)' P (q-mu), P = Sigma^-1 (fp64 MFMA) */
-    IDHMC_MODEL_CUSTOM = 3          /* user HIP source, see above */
+    IDHMC_MODEL_CUSTOM = 3,         /* user HIP source, see above */
+    IDHMC_MODEL_LOGISTIC_REGRESSION = 4   /* Bayesian logistic regression, see above (fp64 MFMA) */
 };
 typedef struct {
     int32_t kind;
     int32_t D;              /* dimension(model): 1 <= D <= 1024; ISO and DIAG up to 2048 in every metric mode, CUSTOM up to
                                2048 with a SHARED or POOLED metric */
-    const double *mu;       /* host, D  (DIAG, DENSE) */
-    const double *tau;      /* host, D  (DIAG) */
+    const double *mu;       /* host, D  (DIAG, DENSE; LOGISTIC_REGRESSION: prior mean, may be NULL) */
+    const double *tau;      /* host, D  (DIAG; LOGISTIC_REGRESSION: prior precision, may be NULL) */
     const double *prec;     /* host, D*D row-major, symmetric (DENSE) */
     const char *source;     /* CUSTOM: NUL-terminated HIP device source */
-    const double *params;   /* CUSTOM: host, nparams doubles copied to the device (may be NULL) */
+    const double *params;   /* CUSTOM: host, nparams doubles copied to the device (may be NULL); LOGISTIC_REGRESSION: [X | y] */
     int64_t nparams;
 } idhmc_model_desc;
 

@@ -652,15 +652,46 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         // two register tiles per vector; the dense MVN's matrix (32 MB at D = 2048) has no kernel built for it
         if (model->kind == IDHMC_MODEL_DENSE_MVN)
             return fail(IDHMC_ERR_BAD_ARG, "D = %d: the dense density is limited to D <= 1024", model->D);
+        if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION)
+            return fail(IDHMC_ERR_BAD_ARG, "D = %d: logistic regression is limited to D <= 1024", model->D);
     }
     if (opt_in && (opt_in->metric_mode < 0 || opt_in->metric_mode > IDHMC_METRIC_POOLED)) return fail(IDHMC_ERR_BAD_ARG, "unknown metric_mode %d", opt_in->metric_mode);
-    if (model->kind < 0 || model->kind > IDHMC_MODEL_CUSTOM) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
+    if (model->kind < 0 || model->kind > IDHMC_MODEL_LOGISTIC_REGRESSION) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
     if (model->kind == IDHMC_MODEL_CUSTOM) {
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "custom model needs HIP source");
         if (model->nparams < 0 || (model->nparams > 0 && !model->params)) return fail(IDHMC_ERR_BAD_ARG, "custom model: bad params");
         if (model->D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
             return fail(IDHMC_ERR_BAD_ARG, "custom model with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)");
-    } else if (model->kind != IDHMC_MODEL_ISO_GAUSSIAN && !model->mu) return fail(IDHMC_ERR_BAD_ARG, "model needs mu");
+    } else if (model->kind != IDHMC_MODEL_ISO_GAUSSIAN && model->kind != IDHMC_MODEL_LOGISTIC_REGRESSION && !model->mu) {
+        return fail(IDHMC_ERR_BAD_ARG, "model needs mu");
+    }
+    int64_t lr_n = 0;   // observations of a logistic regression
+    if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION) {
+        const int D = model->D;
+        if (model->nparams < 1 || model->nparams % (D + 1) != 0 || !model->params)
+            return fail(IDHMC_ERR_BAD_ARG, "logistic regression: nparams = %lld must be a positive multiple of D + 1 = %d ([X | y])",
+                        (long long)model->nparams, D + 1);
+        lr_n = model->nparams / (D + 1);
+        int L = 128;
+        while (L < D) L *= 2;
+        const int64_t npad = (lr_n + 127) / 128 * 128;
+        if (npad * L > ((int64_t)1 << 27))
+            return fail(IDHMC_ERR_BAD_ARG, "logistic regression: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
+                        (long long)lr_n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
+        const double *X = model->params, *y = model->params + lr_n * D;
+        for (int64_t k = 0; k < lr_n * D; ++k)
+            if (!std::isfinite(X[k])) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: X[%lld, %lld] is not finite", (long long)(k / D), (long long)(k % D));
+        for (int64_t i = 0; i < lr_n; ++i)
+            if (y[i] != 0.0 && y[i] != 1.0) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: y[%lld] = %g is neither 0 nor 1", (long long)i, y[i]);
+        for (int k = 0; k < D; ++k) {
+            if (model->tau && !(std::isfinite(model->tau[k]) && model->tau[k] > 0.0))
+                return fail(IDHMC_ERR_BAD_ARG, "logistic regression: prior precision tau[%d] = %g must be finite and > 0", k, model->tau[k]);
+            if (model->mu && !std::isfinite(model->mu[k]))
+                return fail(IDHMC_ERR_BAD_ARG, "logistic regression: prior mean mu[%d] is not finite", k);
+        }
+        if (D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
+            return fail(IDHMC_ERR_BAD_ARG, "logistic regression with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)");
+    }
     if (model->kind == IDHMC_MODEL_DIAG_GAUSSIAN && !model->tau) return fail(IDHMC_ERR_BAD_ARG, "diagonal model needs tau");
     if (model->kind == IDHMC_MODEL_DENSE_MVN && !model->prec) return fail(IDHMC_ERR_BAD_ARG, "dense model needs prec");
     if (model->kind == IDHMC_MODEL_DENSE_MVN) {
@@ -699,7 +730,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     // a vector is padded to the next multiple of 128 (the reference pads to its SIMD width, src/mcmc.jl:117); the
     // dense density's matrix kernels need a power-of-two number of 128-column chunks
     int nch = (model->D + 127) / 128;
-    if (model->kind == IDHMC_MODEL_DENSE_MVN) { nch = 1; while (nch * 128 < model->D) nch *= 2; }
+    if (model->kind == IDHMC_MODEL_DENSE_MVN || model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION) { nch = 1; while (nch * 128 < model->D) nch *= 2; }
     s.nch = nch;
     s.L = 128 * nch;
     s.model = model->kind;
@@ -783,6 +814,27 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
                                     sizeof(double) * s.D, s.D, hipMemcpyHostToDevice, c->stream));
         }
         s.mu = mu; s.tau = tau; s.prec = prec;
+        if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION) {
+            // the prior's defaults (mu = 0 is the zeroed allocation); X, X' and y zero-padded to [n_pad][L], [L][n_pad], [n_pad]
+            if (!model->tau) HIPCHK(launch_fill(tau, 1.0, s.D, c->stream));
+            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D;
+            std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)npad, 0.0);
+            for (int64_t i = 0; i < n; ++i)
+                for (int64_t k = 0; k < D; ++k) {
+                    const double v = model->params[i * D + k];
+                    hx[(size_t)(i * L + k)] = v;
+                    hxt[(size_t)(k * npad + i)] = v;
+                }
+            for (int64_t i = 0; i < n; ++i) hy[(size_t)i] = model->params[n * D + i];
+            double *dx = nullptr, *dxt = nullptr, *dy = nullptr;
+            DALLOC(dx, npad * L); DALLOC(dxt, npad * L); DALLOC(dy, npad);
+            HIPCHK(hipMemcpyAsync(dx, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dxt, hxt.data(), sizeof(double) * hxt.size(), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dy, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
+            s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
+            s.lr_n = (int32_t)n; s.lr_npad = (int32_t)npad;
+        }
     }
     // persistent NUTS waves and their tree arenas
     {

@@ -203,22 +203,57 @@ struct DenseMvn {
 // so a fast wavefront may write its next d while a slow one still reads its t.
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
+// The round protocol every cooperative density shares.  Impl supplies `Prefetch` (what it requests before barrier A),
+// prefetch(Prefetch &) and multiply(Prefetch &): the rest of a round after barrier A, ending with the round's last barrier.
+// A requester runs the same barrier sequence in its grad_partial: write its row, barrier A, multiply, read its row.
+template <class Impl>
+struct CoopRounds {
+    int *alive;              // LDS: chains of the current group that may still request a gradient
+    int lane, wv;
+    IDHMC_DEV const Impl &impl() const { return *static_cast<const Impl *>(this); }
+    // this wavefront's chain makes no further request
+    IDHMC_DEV void retire() const
+    {
+        if (lane == 0) atomicSub(alive, 1);
+    }
+    // one round served without a request of its own (the wavefront has a chain coming, so the group is alive)
+    IDHMC_DEV void serve_round() const
+    {
+        typename Impl::Prefetch bq;
+        impl().prefetch(bq);
+        __syncthreads();                                   // barrier A
+        impl().multiply(bq);
+    }
+    // serve the other chains' rounds until the whole group has retired
+    IDHMC_DEV void serve() const
+    {
+        for (;;) {
+            typename Impl::Prefetch bq;
+            impl().prefetch(bq);
+            __syncthreads();                               // barrier A
+            if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile int *>(alive)) == 0) break;
+            impl().multiply(bq);
+        }
+    }
+};
 #ifndef IDHMC_COOP_PD
 #define IDHMC_COOP_PD 4
 #endif
 template <int NCH>
-struct DenseMvnCoop {
+struct DenseMvnCoop : CoopRounds<DenseMvnCoop<NCH>> {
     static constexpr bool kHasParams = true;
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = true;
     static constexpr int kWaves = 16, L = 128 * NCH, DS = L + 2, KB = L / 4, kPairs = L / 32, kPrefetch = IDHMC_COOP_PD;
     static constexpr int kTileDoubles = 16 * DS;
+    static constexpr int kLdsDoubles = 2 * kTileDoubles;   // the d tile and the T tile
     typedef v2d Prefetch[kPrefetch];
+    using CoopRounds<DenseMvnCoop<NCH>>::alive;
+    using CoopRounds<DenseMvnCoop<NCH>>::lane;
+    using CoopRounds<DenseMvnCoop<NCH>>::wv;
     const double *prec;      // [L][L] row-major, device
     const double2 *mu2;      // lane-offset, device
     double *tile;            // [16][DS] in LDS, shared by the workgroup
-    int *alive;              // LDS: chains of the current group that may still request a gradient
-    int lane, wv;
     template <class State>
     IDHMC_DEV void init(const State &s, double *tile_, int *alive_, int lane_, int wv_)
     {
@@ -362,30 +397,6 @@ struct DenseMvnCoop {
             g.c[j] = make_double2(-t.x, -t.y);
             l0 = dfma(t.x, d.c[j].x, l0);
             l1 = dfma(t.y, d.c[j].y, l1);
-        }
-    }
-    // this wavefront's chain makes no further request
-    IDHMC_DEV void retire() const
-    {
-        if (lane == 0) atomicSub(alive, 1);
-    }
-    // one round served without a request of its own (the wavefront has a chain coming, so the group is alive)
-    IDHMC_DEV void serve_round() const
-    {
-        Prefetch bq;
-        prefetch(bq);
-        __syncthreads();                                   // barrier A
-        multiply(bq);
-    }
-    // serve the other chains' rounds until the whole group has retired
-    IDHMC_DEV void serve() const
-    {
-        for (;;) {
-            Prefetch bq;
-            prefetch(bq);
-            __syncthreads();                               // barrier A
-            if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile int *>(alive)) == 0) break;
-            multiply(bq);
         }
     }
 };

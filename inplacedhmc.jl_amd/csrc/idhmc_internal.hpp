@@ -36,6 +36,8 @@ struct DevState {
     int64_t minv_stride;
     const double *mu, *tau;   // [L]
     const double *prec;       // [L][L]
+    const double *lr_x, *lr_xt, *lr_y;   // IDHMC_MODEL_LOGISTIC_REGRESSION: X [lr_npad][L], X' [L][lr_npad], y [lr_npad], zero-padded
+    int32_t lr_n, lr_npad;               // observations, and rounded up to a multiple of 128
     const double *user_params;   // IDHMC_MODEL_CUSTOM: the user's parameter blob
     int64_t user_nparams;
     const void *jit;             // host only: the hipRTC module of a custom density
@@ -113,6 +115,14 @@ Comm *comm_create(int nranks, int rank, const void *id128, char *err, size_t cap
 int comm_allreduce_sum(Comm *c, double *dev_buf, int n, hipStream_t st, char *err, size_t cap);
 void comm_destroy(Comm *c);
 void comm_info(const Comm *c, int *nranks, int *rank, long long *allreduces);
+
+// ---- Bayesian logistic regression (idhmc_logistic.hip) ---------------------------------------------
+hipError_t launch_eval_logistic(const DevState &s, int random_q, hipStream_t st);
+hipError_t launch_leapfrog_logistic(const DevState &s, double eps, int own, int n_steps, hipStream_t st);
+hipError_t launch_stepsize_search_logistic(const DevState &s, hipStream_t st);
+hipError_t launch_local_optimum_logistic(const DevState &s, double penalty, int iterations, hipStream_t st);
+hipError_t launch_nuts_logistic(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+bool logistic_coop(int nch);   // NUTS gradients on the matrix cores (LogisticRegressionCoop) at this padded length
 
 // ---- launchers (idhmc_kernels.hip / idhmc_nuts.hip) ------------------------------------------------
 hipError_t launch_eval(const DevState &s, hipStream_t st);                 // lq, grad from q

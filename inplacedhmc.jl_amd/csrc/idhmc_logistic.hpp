@@ -1,0 +1,269 @@
+// idhmc_logistic.hpp -- Bayesian logistic regression (IDHMC_MODEL_LOGISTIC_REGRESSION), DESIGN section 10:
+//   l(q) = sum_i [y_i z_i - softplus(z_i)] - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q
+//   grad l(q) = X' (y - sigma(z)) - tau .* (q - mu)
+// Two forms with one arithmetic: LogisticRegression (one chain per wavefront, every kernel) and LogisticRegressionCoop
+// (the NUTS kernel at L <= 256: 16 chains per workgroup, both products on the fp64 matrix cores).  Kept out of what the
+// hipRTC build of a custom density includes.
+//
+// The arithmetic (both forms and the tests' C restatement follow it bit for bit):
+//   z_i   = fma chain over columns c ascending of X[i][c] * q_c, from +0
+//   s_i   = y_i ? -z_i : z_i;  e_i = dexp(-|s_i|)
+//   v_i   = (s_i > 0 ? s_i : 0) + dlog1p(e_i)                  = softplus(z_i) - y_i z_i
+//   r_i   = (y_i ? 1 : -1) * ((s_i >= 0 ? 1 : e_i) / (1 + e_i)) = y_i - sigma(z_i)
+//   observations i >= n: v_i = r_i = 0
+//   G_c   = fma chain over observations i ascending of X[i][c] * r_i, from +0;  g_c = dfma(-tau_c, d_c, G_c), d = q - mu
+//   lane partials (residues 2l, 2l+1 of 128): T = fma chain over chunks j of (tau_c d_c) * d_c;  A = sum over observation
+//   blocks ascending of v_i (plain additions, from +0);  P = dfma(2, A, T);  l = -1/2 wave_sum(P0, P1)
+// A chain of fmas from +0 never holds -0, so the zero padding (columns >= D, observations >= n) leaves every chain as it is:
+// the per-wave form stops at D and n, the matrix-core form runs over the padded tiles, and both give the same bits.
+#pragma once
+#include "idhmc_device.hpp"
+
+namespace idhmc {
+
+// v_i and r_i of one observation (y is 0 or 1)
+IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
+{
+    const double s = y != 0.0 ? -z : z;
+    const double e = dexp(-__builtin_fabs(s));
+    v = (s > 0.0 ? s : 0.0) + dlog1p(e);
+    const double sg = (s >= 0.0 ? 1.0 : e) / (1.0 + e);
+    r = y != 0.0 ? sg : -sg;
+}
+
+// One chain per wavefront.  Observations in blocks of 128, lane l owning observations 128 b + 2 l, 128 b + 2 l + 1: z from
+// coalesced rows of X' against q broadcast from the wavefront's LDS vector, then r is staged in that vector and g accumulates
+// over the block's observations from coalesced rows of X.  X and X' stream from L2 once per gradient.
+template <int NCH>
+struct LogisticRegression {
+    static constexpr bool kHasParams = true;
+    static constexpr bool kSeparable = false;
+    static constexpr bool kCooperative = false;
+    const double *x, *xt;    // [npad][L], [L][npad], device
+    const double2 *y2;       // [npad], lane-offset
+    const double2 *mu2, *tau2;   // lane-offset, device
+    double *buf;             // this wavefront's LDS vector, L doubles
+    int D, n, npad, lane;
+    template <class State>
+    IDHMC_DEV void init(const State &s, double *lds_vec, int lane_)
+    {
+        x = s.lr_x;
+        xt = s.lr_xt;
+        y2 = reinterpret_cast<const double2 *>(s.lr_y) + lane_;
+        mu2 = reinterpret_cast<const double2 *>(s.mu) + lane_;
+        tau2 = reinterpret_cast<const double2 *>(s.tau) + lane_;
+        buf = lds_vec;
+        D = s.D;
+        n = s.lr_n;
+        npad = s.lr_npad;
+        lane = lane_;
+    }
+    IDHMC_DEV double grad(const Vec<NCH> &q, Vec<NCH> &g) const
+    {
+        constexpr int L = 128 * NCH;
+        Vec<NCH> G = vfill<NCH>(0.0);
+        double a0 = 0.0, a1 = 0.0;
+        double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;
+        const int nb = npad >> 7;
+        for (int b = 0; b < nb; ++b) {
+            // q is staged again every block: r overwrites the first 128 doubles of the vector
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) b2[j * 64] = q.c[j];
+            const double2 *xtp = reinterpret_cast<const double2 *>(xt + 128 * b) + lane;
+            double zx = 0.0, zy = 0.0;
+#pragma unroll 4
+            for (int c = 0; c < D; ++c) {
+                const double qc = buf[c];                      // LDS broadcast
+                const double2 xv = xtp[(size_t)c * (npad / 2)];
+                zx = dfma(xv.x, qc, zx);
+                zy = dfma(xv.y, qc, zy);
+            }
+            const double2 yv = y2[b * 64];
+            const int i0 = 128 * b + 2 * lane;
+            double rx, vx, ry, vy;
+            logistic_terms(zx, yv.x, rx, vx);
+            logistic_terms(zy, yv.y, ry, vy);
+            if (i0 >= n) { rx = 0.0; vx = 0.0; }
+            if (i0 + 1 >= n) { ry = 0.0; vy = 0.0; }
+            a0 = a0 + vx;
+            a1 = a1 + vy;
+            b2[0] = make_double2(rx, ry);
+            const int m = n - 128 * b < 128 ? n - 128 * b : 128;
+            const double2 *xr = reinterpret_cast<const double2 *>(x + (size_t)128 * b * L) + lane;
+#pragma unroll 2
+            for (int ii = 0; ii < m; ++ii) {
+                const double ri = buf[ii];                     // LDS broadcast
+#pragma unroll
+                for (int j = 0; j < NCH; ++j) {
+                    const double2 xv = xr[(size_t)ii * (L / 2) + j * 64];
+                    G.c[j].x = dfma(xv.x, ri, G.c[j].x);
+                    G.c[j].y = dfma(xv.y, ri, G.c[j].y);
+                }
+            }
+        }
+        double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const double2 m = mu2[j * 64], t = tau2[j * 64];
+            const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
+            t0 = dfma(t.x * dx, dx, t0);
+            t1 = dfma(t.y * dy, dy, t1);
+            g.c[j] = make_double2(dfma(-t.x, dx, G.c[j].x), dfma(-t.y, dy, G.c[j].y));
+        }
+        const double lq = -0.5 * wave_sum(dfma(2.0, a0, t0), dfma(2.0, a1, t1));
+        return dfinite(lq) ? lq : -kInf;
+    }
+};
+
+// The same density for the NUTS kernel at L <= 256, evaluated COOPERATIVELY by the 16 wavefronts of a workgroup on the fp64
+// matrix cores, one 16-chain v_mfma_f64_16x16x4_f64 tile (the round protocol is DenseMvnCoop's, CoopRounds).  A round:
+//   (1) the requester writes q as its row of the [16][L + 2] Q tile;                                      -- barrier A --
+//   (2) per block b of 128 observations: the Z wavefronts (the last 8, one 16-observation column tile each) form
+//       Z = Q X'[:, block] (k = columns ascending), apply r = y - sigma(z) into R tile b & 1 and add v into registers;
+//   (3) the G wavefronts (the first L / 16, one 16-column tile of X each) accumulate G += R[b & 1] X[block, :] (k =
+//       observations ascending, the accumulators carried across blocks);
+//       Z of block b + 1 runs between the same barriers as G of block b (two R tiles): one barrier per block;
+//   (4) G goes into the Q tile, the per-residue sums of v into the free R tile;                            -- barrier C --
+//   (5) the requester reads its row of each: g = dfma(-tau, d, G), P = dfma(2, A, T).
+// X' and X stream through L1 once per 16 gradients instead of once per gradient.  LDS: 16 (L + 2) + 2 * 16 * 130 doubles,
+// 49.9 KB at L = 128, 66.3 KB at L = 256.
+template <int NCH>
+struct LogisticRegressionCoop : CoopRounds<LogisticRegressionCoop<NCH>> {
+    static constexpr bool kHasParams = true;
+    static constexpr bool kSeparable = false;
+    static constexpr bool kCooperative = true;
+    static constexpr int L = 128 * NCH, DS = L + 2, RS = 130, KB = L / 4;
+    static constexpr int kZT = 8, kGT = L / 16;        // Z column tiles per block (wavefronts 8..15), G column tiles (0..L/16-1)
+    static constexpr int kQ = 0, kR = 16 * DS;         // Q / G tile, then the two R tiles
+    static constexpr int kLdsDoubles = 16 * DS + 2 * 16 * RS;
+    struct Prefetch {};                                 // nothing is requested ahead of barrier A
+    using CoopRounds<LogisticRegressionCoop<NCH>>::alive;
+    using CoopRounds<LogisticRegressionCoop<NCH>>::lane;
+    using CoopRounds<LogisticRegressionCoop<NCH>>::wv;
+    const double *x, *xt, *y;
+    const double2 *mu2, *tau2;   // lane-offset, device
+    double *tile;
+    int n, npad;
+    template <class State>
+    IDHMC_DEV void init(const State &s, double *tile_, int *alive_, int lane_, int wv_)
+    {
+        x = s.lr_x;
+        xt = s.lr_xt;
+        y = s.lr_y;
+        mu2 = reinterpret_cast<const double2 *>(s.mu) + lane_;
+        tau2 = reinterpret_cast<const double2 *>(s.tau) + lane_;
+        tile = tile_;
+        n = s.lr_n;
+        npad = s.lr_npad;
+        alive = alive_;
+        lane = lane_;
+        wv = wv_;
+    }
+    IDHMC_DEV double *rtile(int b) const { return tile + kR + (b & 1) * (16 * RS); }
+    IDHMC_DEV void prefetch(Prefetch &) const {}
+    // (2) for block b: Z tile zt, r into R[b & 1], v added to vacc
+    IDHMC_DEV void zphase(int b, int zt, int kk, int jj, double (&vacc)[4]) const
+    {
+        const __amdgpu_buffer_rsrc_t rX = buf_rsrc(xt + 128 * b + 16 * zt);
+        const int vo = (kk * npad + jj) * 8;                  // B[kk][jj] = X'[4 kb + kk][128 b + 16 zt + jj]
+        const double *ap = tile + kQ + jj * DS + kk;          // A[jj][kk] = Q[chain jj][4 kb + kk]
+        v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+        for (int kb0 = 0; kb0 < KB; kb0 += 8) {
+            double bv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                bv[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rX, vo + 4 * (kb0 + u) * npad * 8, 0, 0));
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * (kb0 + u)], bv[u], acc, 0, 0, 0);
+        }
+        const int i = 128 * b + 16 * zt + jj;
+        const double yi = y[i];
+        double *rt = rtile(b) + 16 * zt + jj;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {                  // row kk + 4 reg (chain), column jj (observation)
+            double r, v;
+            logistic_terms(acc[reg], yi, r, v);
+            if (i >= n) { r = 0.0; v = 0.0; }
+            vacc[reg] = vacc[reg] + v;
+            rt[(kk + 4 * reg) * RS] = r;
+        }
+    }
+    // (3) for block b: G tile wv += R[b & 1] X[block, 16 wv ..]
+    IDHMC_DEV void gphase(int b, int kk, int jj, v4d &gacc) const
+    {
+        const __amdgpu_buffer_rsrc_t rX = buf_rsrc(x + (size_t)128 * b * L + 16 * wv);
+        const int vo = (kk * L + jj) * 8;                     // B[kk][jj] = X[128 b + 4 kb + kk][16 wv + jj]
+        const double *ap = rtile(b) + jj * RS + kk;           // A[jj][kk] = R[chain jj][4 kb + kk]
+#pragma unroll 1
+        for (int kb0 = 0; kb0 < 32; kb0 += 8) {
+            double bv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                bv[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rX, vo + 4 * (kb0 + u) * L * 8, 0, 0));
+#pragma unroll
+            for (int u = 0; u < 8; ++u) gacc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * (kb0 + u)], bv[u], gacc, 0, 0, 0);
+        }
+    }
+    // steps (2)-(4) of a round; entered after barrier A by all 16 wavefronts, left after barrier C
+    IDHMC_DEV void multiply(Prefetch &) const
+    {
+        static_assert(kGT <= 16, "one 16-column tile of G per wavefront: L <= 256");
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                          // see DenseMvnCoop::multiply
+        const int kk = ln >> 4, jj = ln & 15;
+        const int nb = npad >> 7;
+        const bool zw = wv >= 16 - kZT, gw = wv < kGT;
+        const int zt = wv - (16 - kZT);
+        v4d gacc = v4d{0.0, 0.0, 0.0, 0.0};
+        double vacc[4] = {0.0, 0.0, 0.0, 0.0};
+        if (zw) zphase(0, zt, kk, jj, vacc);
+        __syncthreads();                                      // R[0] complete
+        for (int b = 0; b < nb; ++b) {
+            if (gw) gphase(b, kk, jj, gacc);
+            if (zw && b + 1 < nb) zphase(b + 1, zt, kk, jj, vacc);
+            if (b + 1 < nb) __syncthreads();                  // R[b + 1] complete, R[b] consumed
+        }
+        // the last Z phase ran before the last barrier, so the Q tile is free; R[nb & 1] is not the one G reads now
+        if (gw) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) tile[kQ + (kk + 4 * reg) * DS + 16 * wv + jj] = gacc[reg];
+        }
+        if (zw) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) rtile(nb)[(kk + 4 * reg) * RS + 16 * zt + jj] = vacc[reg];
+        }
+        __syncthreads();                                      // barrier C
+    }
+    IDHMC_DEV double grad(const Vec<NCH> &q, Vec<NCH> &g) const
+    {
+        double l0, l1;
+        grad_partial(q, g, l0, l1);
+        const double lq = -0.5 * wave_sum(l0, l1);
+        return dfinite(lq) ? lq : -kInf;
+    }
+    // l = -1/2 wave_sum(l0, l1), as DenseMvnCoop's
+    IDHMC_DEV void grad_partial(const Vec<NCH> &q, Vec<NCH> &g, double &l0, double &l1) const
+    {
+        Prefetch pf;
+        double2 *row = reinterpret_cast<double2 *>(tile + kQ + wv * DS) + lane;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) row[j * 64] = q.c[j];
+        __syncthreads();                                      // barrier A
+        multiply(pf);
+        const double2 A = reinterpret_cast<const double2 *>(rtile(npad >> 7) + wv * RS)[lane];
+        double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const double2 m = mu2[j * 64], t = tau2[j * 64], G = row[j * 64];
+            const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
+            t0 = dfma(t.x * dx, dx, t0);
+            t1 = dfma(t.y * dy, dy, t1);
+            g.c[j] = make_double2(dfma(-t.x, dx, G.x), dfma(-t.y, dy, G.y));
+        }
+        l0 = dfma(2.0, A.x, t0);
+        l1 = dfma(2.0, A.y, t1);
+    }
+};
+
+}  // namespace idhmc

@@ -9,7 +9,7 @@ namespace idhmc {
 // the tree arena also serves as the L-BFGS history of the FindLocalOptimum stage (2 * kLbfgsR vectors)
 int arena_vectors(int max_depth, int model, int L)
 {
-    const bool separable = model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN;
+    const bool separable = model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN;     // dense, logistic, custom: not
     const int n = ArenaMap{max_depth, nuts_regenerate(separable), nuts_defer(separable) ? nuts_dl_vectors(max_depth, L) : 0}.count();
     return n > 2 * kLbfgsR ? n : 2 * kLbfgsR;
 }
@@ -23,7 +23,8 @@ static bool dense_coop(int nch)
 int nuts_waves_per_block(int nch, int model, int shared_metric)
 {
     return nuts_waves(nch, model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN,
-                      model == IDHMC_MODEL_DENSE_MVN && dense_coop(nch), shared_metric != 0);
+                      (model == IDHMC_MODEL_DENSE_MVN && dense_coop(nch)) || (model == IDHMC_MODEL_LOGISTIC_REGRESSION && logistic_coop(nch)),
+                      shared_metric != 0);
 }
 // wavefronts per workgroup of the wide form of the kernel (0: the model/shape has none); the arena is sized for it
 int nuts_wide_waves_per_block(int nch, int model)
@@ -42,26 +43,6 @@ hipError_t launch_nuts_sep_from13(const DevState &s, uint32_t iter, uint32_t fla
 hipError_t launch_stepsize_search_dense(const DevState &s, hipStream_t st);
 hipError_t launch_nuts_jit(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
 hipError_t launch_stepsize_search_jit(const DevState &s, hipStream_t st);
-
-template <int NCH, class Model, bool SHARED, int WAVES = nuts_waves(NCH, Model::kSeparable, Model::kCooperative, SHARED)>
-static hipError_t launch_nuts_t(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
-{
-    const size_t bytes = sizeof(double) * nuts_lds_doubles(128 * NCH, Model::kHasParams && Model::kSeparable, SHARED,
-                                                           Model::kSeparable, Model::kCooperative, WAVES);
-    static bool attr_done[64] = {};  // per instantiation and device (the attribute is per device)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_done[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nuts<NCH, Model, SHARED, WAVES>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
-    hipLaunchKernelGGL((k_nuts<NCH, Model, SHARED, WAVES>), dim3(grid), dim3(WAVES * 64),
-                       bytes, st,
-                       s, iter, flags);
-    return hipGetLastError();
-}
 
 // wide != 0 selects the wide form of the kernel where one exists (same arithmetic, same results)
 hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wide, hipStream_t st, uint32_t n_iter, double *fz_q, idhmc_tree_stats *fz_st)
@@ -87,6 +68,7 @@ hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wi
     const int grid = (int)(need < have ? need : have);
     const bool shared = s.minv_stride == 0;
     if (s.model == IDHMC_MODEL_CUSTOM) return launch_nuts_jit(s, iter, flags, grid, st);
+    if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_nuts_logistic(s, iter, flags, grid, st);
     if (s.model == IDHMC_MODEL_DENSE_MVN) {
         IDHMC_DISPATCH_NCH_POW2(s.nch, {
             if constexpr (NCH <= 2) {
@@ -114,6 +96,7 @@ hipError_t launch_local_optimum(const DevState &s, double penalty, int iteration
 {
     if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_local_optimum_dense(s, penalty, iterations, st);
     if (s.model == IDHMC_MODEL_CUSTOM) return launch_local_optimum_jit(s, penalty, iterations, optimum_grid(s), st);
+    if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_local_optimum_logistic(s, penalty, iterations, st);
     IDHMC_DISPATCH_NCH(s.nch, {
         if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)
             hipLaunchKernelGGL((k_local_optimum<NCH, IsoGaussian<NCH>>), dim3(optimum_grid(s)), dim3(kOptimumWaves * 64),
@@ -129,6 +112,7 @@ hipError_t launch_stepsize_search(const DevState &s, hipStream_t st)
 {
     if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_stepsize_search_dense(s, st);
     if (s.model == IDHMC_MODEL_CUSTOM) return launch_stepsize_search_jit(s, st);
+    if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_stepsize_search_logistic(s, st);
     int64_t b = (s.C + 3) / 4;
     if (b > 4096) b = 4096;
     const int grid = (int)b;

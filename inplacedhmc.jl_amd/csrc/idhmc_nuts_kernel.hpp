@@ -102,13 +102,14 @@ __host__ __device__ constexpr bool nuts_prev_regs(bool separable, bool cooperati
 {
     return IDHMC_NUTS_PREV_REGS != 0 && !rich && ((separable && !cooperative) || (cooperative && IDHMC_COOP_PREV_REGS != 0));
 }
+// coop_lds: doubles of LDS the cooperative density's gradient rounds use (Model::kLdsDoubles), 0 for every other density
 __host__ __device__ constexpr int nuts_l1_lds(int nch, bool separable, int waves, bool lds_params = true, bool shared_metric = true,
-                                              bool prev_regs = false, bool cooperative = false)
+                                              bool prev_regs = false, int coop_lds = 0)
 {
-    if (cooperative) {      // no parameters in LDS, a shared metric is read from L2; the d and T tiles of the gradient rounds
+    if (coop_lds > 0) {     // no parameters in LDS, a shared metric is read from L2; the tiles of the gradient rounds
         if (!prev_regs) return 0;
         const int base = (shared_metric ? 1 : 0) + waves * (shared_metric ? 0 : 1);
-        const int budget = (163840 - 912 * waves - 256 - 2 * 16 * (128 * nch + 2) * 8) / (1024 * nch);
+        const int budget = (163840 - 912 * waves - 256 - coop_lds * 8) / (1024 * nch);
         return base + 2 * waves <= budget ? 2 : (base + waves <= budget ? 1 : 0);
     }
     if (!separable) return 0;
@@ -364,10 +365,11 @@ struct LevelScalars {
 // dynamic LDS layout (doubles): [mu L][tau L] if the density has parameters, [M^-1 L] if the metric is
 // shared, then per wavefront [p_prev L] and, for a per-chain metric, [M^-1 L].
 // A general (non-separable) density adds one staging vector per wavefront and keeps its parameters in L2;
-// a cooperative one has the workgroup's [16][L + 2] tile instead.
+// a cooperative one has the workgroup's tiles instead (coop_lds doubles, Model::kLdsDoubles; 0: not cooperative).
 __host__ __device__ inline size_t nuts_lds_doubles(int L, bool lds_params, bool shared_metric, bool separable,
-                                                   bool cooperative = false, int waves = 0)
+                                                   int coop_lds = 0, int waves = 0)
 {
+    const bool cooperative = coop_lds > 0;
     if (waves == 0) waves = nuts_waves(L / 128, separable, cooperative, shared_metric);
     if (nuts_rich(L / 128, separable, cooperative, waves)) {    // per wavefront: p_prev, the level-1 summary, rho of level 2
         const bool cr = nuts_const_regs(L / 128, separable, cooperative, waves);
@@ -376,11 +378,18 @@ __host__ __device__ inline size_t nuts_lds_doubles(int L, bool lds_params, bool 
     }
     // per wavefront: [p_prev, or one scratch vector when nothing else is there] [per-chain M^-1] [general: staging] [level-1 rho, p#]
     const bool pr = nuts_prev_regs(separable, cooperative, false);
-    const int l1n = nuts_l1_lds(L / 128, separable, waves, lds_params, shared_metric, pr, cooperative);
+    const int l1n = nuts_l1_lds(L / 128, separable, waves, lds_params, shared_metric, pr, coop_lds);
     const int first = pr ? (l1n == 0 ? 1 : 0) : 1;
     return (size_t)L * ((lds_params ? 2 : 0) + (shared_metric ? 1 : 0) +
                         waves * (first + (shared_metric ? 0 : 1) + ((separable || cooperative) ? 0 : 1) + l1n)) +
-           (cooperative ? (size_t)2 * 16 * (L + 2) : 0);      // the d tile and the T tile
+           (size_t)coop_lds;      // the cooperative density's tiles
+}
+// LDS doubles of a density's cooperative gradient rounds (0: not cooperative)
+template <class Model>
+__host__ __device__ constexpr int coop_lds_doubles()
+{
+    if constexpr (Model::kCooperative) return Model::kLdsDoubles;
+    else return 0;
 }
 
 }  // namespace idhmc
@@ -508,7 +517,8 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
     constexpr bool kRich = nuts_rich(NCH, Model::kSeparable, kCoop, kNutsWaves);
     constexpr bool kConstRegs = nuts_const_regs(NCH, Model::kSeparable, kCoop, kNutsWaves);
     constexpr bool kPrevRegs = nuts_prev_regs(Model::kSeparable, kCoop, kRich);     // level-0 summary in registers, not LDS
-    constexpr int kL1N = kRich ? 2 : nuts_l1_lds(NCH, Model::kSeparable, kNutsWaves, Model::kHasParams && Model::kSeparable, SHARED_METRIC, kPrevRegs, kCoop);
+    constexpr int kL1N = kRich ? 2 : nuts_l1_lds(NCH, Model::kSeparable, kNutsWaves, Model::kHasParams && Model::kSeparable, SHARED_METRIC, kPrevRegs,
+                                                    coop_lds_doubles<Model>());
 #ifdef IDHMC_X3
     constexpr bool kL1Rho = kL1N >= 1, kL1Pf = kL1N >= 1;
 #else
@@ -1318,5 +1328,27 @@ __global__ __launch_bounds__(256) void k_stepsize_search(DevState s)
         }
     }
 }
+
+#ifndef __HIPCC_RTC__
+// host: launch k_nuts for one density and shape (the instantiating translation units: idhmc_nuts.hip, idhmc_nuts_sep.inc,
+// idhmc_logistic.hip)
+template <int NCH, class Model, bool SHARED, int WAVES = nuts_waves(NCH, Model::kSeparable, Model::kCooperative, SHARED)>
+static hipError_t launch_nuts_t(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
+{
+    const size_t bytes = sizeof(double) * nuts_lds_doubles(128 * NCH, Model::kHasParams && Model::kSeparable, SHARED,
+                                                           Model::kSeparable, coop_lds_doubles<Model>(), WAVES);
+    static bool attr_done[64] = {};  // per instantiation and device (the attribute is per device)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!attr_done[dev & 63]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nuts<NCH, Model, SHARED, WAVES>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+        attr_done[dev & 63] = true;
+    }
+    hipLaunchKernelGGL((k_nuts<NCH, Model, SHARED, WAVES>), dim3(grid), dim3(WAVES * 64), bytes, st, s, iter, flags);
+    return hipGetLastError();
+}
+#endif
 
 }  // namespace idhmc

@@ -4,24 +4,6 @@
 
 namespace idhmc {
 
-template <int NCH, class Model, bool SHARED, int WAVES = nuts_waves(NCH, Model::kSeparable, Model::kCooperative, SHARED)>
-static hipError_t launch_nuts_t(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
-{
-    const size_t bytes = sizeof(double) * nuts_lds_doubles(128 * NCH, Model::kHasParams && Model::kSeparable, SHARED,
-                                                           Model::kSeparable, Model::kCooperative, WAVES);
-    static bool attr_done[64] = {};  // per instantiation and device (the attribute is per device)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_done[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nuts<NCH, Model, SHARED, WAVES>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        attr_done[dev & 63] = true;
-    }
-    hipLaunchKernelGGL((k_nuts<NCH, Model, SHARED, WAVES>), dim3(grid), dim3(WAVES * 64), bytes, st, s, iter, flags);
-    return hipGetLastError();
-}
-
 template <int NCH>
 static hipError_t launch_nuts_sep_nch(const DevState &s, uint32_t iter, uint32_t flags, int wide, int grid, hipStream_t st)
 {

@@ -11,7 +11,7 @@ TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_l
                              ("term_right", "<i4"), ("depth", "<i4"), ("steps", "<i4")])
 assert TREE_STATS_DTYPE.itemsize == 32
 
-MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM = 0, 1, 2, 3
+MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION = 0, 1, 2, 3, 4
 EPS_PER_CHAIN, EPS_GLOBAL = 0, 1
 METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED = 0, 1, 2
 GRAD_STORE, GRAD_RECOMPUTE = 0, 1
@@ -99,6 +99,38 @@ def CustomDensity(D, source, params=None):
     template <int NCH> __device__ double logdensity_and_gradient(const Vec<NCH>&, Vec<NCH>&, const UserCtx&);
     it is compiled with hipRTC against the engine's kernels when the Engine is created."""
     return Model(MODEL_CUSTOM, D, source=source, params=params)
+
+
+def LogisticRegression(X, y, prior_mu=None, prior_tau=None):
+    """Bayesian logistic regression (include/idhmc.h, IDHMC_MODEL_LOGISTIC_REGRESSION), the data shared by every chain:
+    l(q) = sum_i [y_i z_i - softplus(z_i)] - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
+    X: (n, D) finite, y: (n,) of 0 and 1; prior_mu, prior_tau: (D,) or scalars, default 0 and 1, tau > 0."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be a non-empty (n, D) matrix, got shape %s" % (X.shape,))
+    n, D = X.shape
+    if D > 1024:
+        raise ValueError("logistic regression is limited to D <= 1024 (D = %d)" % D)
+    if not np.isfinite(X).all():
+        raise ValueError("X must be finite")
+    y = np.asarray(y)
+    if y.shape != (n,):
+        raise ValueError("y must have shape (%d,), got %s" % (n, y.shape))
+    y = y.astype(np.float64)
+    if not np.all((y == 0.0) | (y == 1.0)):
+        raise ValueError("every y_i must be 0 or 1")
+    mu = tau = None
+    if prior_mu is not None:
+        mu = np.array(np.broadcast_to(np.asarray(prior_mu, dtype=np.float64), (D,)))
+        if not np.isfinite(mu).all():
+            raise ValueError("prior_mu must be finite")
+    if prior_tau is not None:
+        tau = np.array(np.broadcast_to(np.asarray(prior_tau, dtype=np.float64), (D,)))
+        if not (np.isfinite(tau).all() and (tau > 0).all()):
+            raise ValueError("prior_tau must be finite and > 0")
+    m = Model(MODEL_LOGISTIC_REGRESSION, D, mu=mu, tau=tau, params=np.concatenate([X.ravel(), y]))
+    m.n = n
+    return m
 
 
 def default_options(**kw):
