@@ -9,8 +9,11 @@ N x 65 536 independent chains (weak scaling, no data-path collective).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HBM-bound fused
 leapfrog kernel; achieved = 6*D*8 bytes x chains / mean launch time measured with HIP events on the
-library's stream over the timed region) and `cpu_baseline` (the CPU oracle = a C port of the
-reference's in-place path, timed on this host's cores on a bounded sample of the same workload).
+library's stream over the timed region).  A plain run does only that: set-up, warm-up, the timed
+steps, --dump-outputs, the line.  --full adds every secondary leg, each after the timed steps:
+`cpu_baseline` (the CPU oracle = a C port of the reference's in-place path, timed on this host's cores
+on a bounded sample of the same workload), the other metric and gradient mode of the same sweep, NUTS,
+configs[2] end to end against the oracle, the dense configs[3] and the global-eps exchange.
 """
 import argparse
 import json
@@ -187,6 +190,9 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--chains", type=int, default=CHAINS_PER_GPU, help="chains per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary legs (CPU baselines, identity metric, gradient recompute, NUTS, "
+                         "cfg3_full, dense, global-eps warm-up); the options below shape them")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--global-eps-transitions", type=int, default=30)
@@ -350,9 +356,10 @@ def run_rank(args):
     finite = bool(np.isfinite(eng.lq).all())
     dumped = dump_outputs(eng, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
+    # Everything below the dump is a secondary leg of --full: a plain run goes from here to the line.
     # SURVEY.md 8d's second cfg2 variant, outside the timed region (rank 0 at N=1): M^-1 = I, eps = 0.1 sigma_min
     identity = None
-    if world == 1:
+    if world == 1 and args.full:
         eng.set_minv(np.ones(D))
         eng.refresh_momentum(2)
         eng.time_leapfrog(0.01, 20)
@@ -365,7 +372,7 @@ def run_rank(args):
     # the same sweep with the gradient stream dropped (IDHMC_GRAD_RECOMPUTE: grad l is re-derived from q, 2 flops per
     # element, and not written back): 4 D 8 bytes of actual traffic per chain-step instead of the algorithmic 6 D 8
     regrad = None
-    if world == 1:
+    if world == 1 and args.full:
         eng.set_leapfrog_grad_mode(pkg.GRAD_RECOMPUTE)
         eng.time_leapfrog(EPS, 20)
         ms_r = eng.time_leapfrog(EPS, 200)
@@ -467,7 +474,7 @@ def run_rank(args):
                 "valu_insts_per_leapfrog": d4.get("valu_insts_per_leapfrog")}
         return nuts
 
-    nuts = guarded(leg_nuts) if world == 1 else None
+    nuts = guarded(leg_nuts) if (world == 1 and args.full) else None
 
     # configs[2] end to end, outside the timed region (rank 0 at N=1): the same density, random start, the reference's default
     # warm-up schedule (InitialStepsizeSearch, 75 / 25-50-100-200-400 with metric windows / 50 transitions, per-chain eps and
@@ -560,7 +567,7 @@ def run_rank(args):
                                          "estimator": "Geyer initial positive sequence per chain and coordinate, mean over both"}
         return res
 
-    cfg3 = guarded(leg_cfg3_full) if (world == 1 and not args.no_cfg3) else None
+    cfg3 = guarded(leg_cfg3_full) if (world == 1 and args.full and not args.no_cfg3) else None
 
     # configs[3], outside the timed region (rank 0 at N=1): 256-dim dense multivariate normal, 16 384 chains, the
     # Sigma^-1 (q - mu) gradient on the fp64 matrix cores.  Both ceilings are reported: 2 D^2 flops per chain-step against
@@ -641,9 +648,9 @@ def run_rank(args):
     if world == 1:
         eng.close()
         eng = None
-    dense = guarded(leg_dense) if world == 1 else None
+    dense = guarded(leg_dense) if (world == 1 and args.full) else None
 
-    # configs[4]'s exchange, outside the timed region, at EVERY N: a global-eps NUTS warm-up leg of the same density
+    # configs[4]'s exchange, outside the timed region, at EVERY N under --full: a global-eps NUTS warm-up leg of the same density
     # (65 536 chains per GPU, random start, per-chain stepsize searches pooled into one eps, then T dual-averaging
     # transitions) through the library's OWN RCCL communicator (idhmc_comm_*): one 4-double all-reduce for the initial
     # stepsize and one per transition, enqueued by the C++ driver on the context's stream.  The record shows how many
@@ -713,7 +720,7 @@ def run_rank(args):
         geng.close()
         return global_eps
 
-    global_eps = guarded(leg_global_eps)
+    global_eps = guarded(leg_global_eps) if args.full else None
 
     if rank == 0:
         value = C * world * args.steps / elapsed
@@ -747,7 +754,7 @@ def run_rank(args):
             "config": {"workload": "configs[1]: 1024-dim diagonal Gaussian, %d chains per GPU, fixed eps=%.2f, "
                                    "M^-1=sigma^2, one fused leapfrog sweep per step" % (C, EPS),
                        "chains_per_gpu": C, "dim": D, "parallelism": "chains sharded over %d GPU(s); no collective in the timed leapfrog sweep "
-                                      "(the one RCCL exchange of the path is reported under global_eps_warmup)" % world},
+                                      "(the one RCCL exchange of the path is reported under global_eps_warmup with --full)" % world},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                          "profile_kernel_ms": profile_kernel_ms,
@@ -770,8 +777,9 @@ def run_rank(args):
             out["cfg3_full"] = cfg3
         if dense is not None:
             out["dense"] = dense
-        out["global_eps_warmup"] = global_eps
-        if world == 1 and not args.no_cpu:
+        if global_eps is not None:
+            out["global_eps_warmup"] = global_eps
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(mu, sig, args.cpu_seconds)
             if nuts is not None and "error" not in nuts:        # the same oracle build (native), a short NUTS sample beside the nuts field
                 nuts["cpu_baseline"] = cpu_nuts_baseline(mu, sig, out["cpu_baseline"]["cores"], min(4.0, args.cpu_seconds / 4))

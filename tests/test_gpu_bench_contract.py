@@ -1,6 +1,6 @@
-"""bench.py prints ONE JSON line with the contract's keys (metric/value/unit/..., roofline, cpu_baseline), and the
-2-rank launches -- `bench.py --gpus 2` starting its own ranks, and torch.distributed.run around it (gloo rehearsal: both ranks
-on the box's one GPU) -- aggregate over ranks."""
+"""bench.py prints ONE JSON line with the contract's keys (metric/value/unit/..., roofline; cpu_baseline and the other secondary
+legs with --full), and the 2-rank launches -- `bench.py --gpus 2` starting its own ranks, and torch.distributed.run around it (gloo
+rehearsal: both ranks on one GPU) -- aggregate over ranks."""
 import json
 import os
 import subprocess
@@ -25,7 +25,7 @@ def run(cmd, env=None):
 
 
 def test_single_gpu_line():
-    d = run([sys.executable, "bench.py", "--steps", "20", "--warmup", "2", "--chains", "2048", "--cpu-seconds", "1",
+    d = run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "2", "--chains", "2048", "--cpu-seconds", "1",
              "--cfg3-scale", "0.12"])
     for k in REQUIRED + ("cpu_baseline",):
         assert k in d, k
@@ -61,9 +61,20 @@ def test_single_gpu_line():
     assert g["rccl_ranks"] == 1 and g["allreduces"] == 32 and g["eps_bits_identical_across_ranks"] is True
 
 
+def test_plain_line_is_the_headline_alone():
+    """without --full the run is set-up, warm-up, the timed steps and the line: no field of a secondary leg"""
+    d = run([sys.executable, "bench.py", "--steps", "20", "--warmup", "2", "--chains", "2048"])
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 2 and d["state_finite"] is True
+    assert abs(d["value"] - 2048 * 20 / (d["ms_per_step"] * 20e-3)) < 1e-6 * d["value"]
+    for k in ("identity_metric", "leapfrog_grad_recompute", "nuts", "cfg3_full", "dense", "global_eps_warmup", "cpu_baseline"):
+        assert k not in d, k
+
+
 def test_two_rank_launch_aggregates():
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-             "--master-port", str(29600 + os.getpid() % 300), "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "2",
+             "--master-port", str(29600 + os.getpid() % 300), "bench.py", "--full", "--gpus", "2", "--steps", "20", "--warmup", "2",
              "--chains", "2048"], env={"IDHMC_DIST_BACKEND": "gloo"})
     for k in REQUIRED:
         assert k in d, k
@@ -79,7 +90,7 @@ def test_gpus_flag_starts_its_own_ranks():
     env = {"IDHMC_DIST_BACKEND": "gloo"}
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         assert k not in os.environ, "the test must not run under a launcher"
-    d = run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "2", "--chains", "2048"], env=env)
+    d = run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "20", "--warmup", "2", "--chains", "2048"], env=env)
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 2 and "cpu_baseline" not in d

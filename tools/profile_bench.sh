@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out
 mkdir -p $OUT
-ARGS="--steps 200 --warmup 20 --no-cpu --no-cfg3"
+ARGS="--full --steps 200 --warmup 20 --no-cpu --no-cfg3"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_trace -- python3 $R/bench.py $ARGS > $OUT/prof_${TAG}_trace.json 2> $OUT/prof_${TAG}_trace.log
 echo "trace pass done" 
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/prof_${TAG}_fetch -- python3 $R/bench.py $ARGS > $OUT/prof_${TAG}_fetch.json 2> $OUT/prof_${TAG}_fetch.log

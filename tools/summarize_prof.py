@@ -52,6 +52,6 @@ out = {"kernel": name, "calls": calls, "avg_duration_ns": avg_ns,
        "hbm_bytes_per_launch": fetch_b + write_b, "hbm_over_algorithmic": (fetch_b + write_b) / alg,
        "correction": "FETCH_SIZE x2 (gfx950 wide coalesced reads), WRITE_SIZE x1",
        "other_kernels": other,
-       "command": "rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE -- python3 bench.py --steps 200 --warmup 20 --no-cpu --no-cfg3"}
+       "command": "rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu --no-cfg3"}
 json.dump(out, open(f"{dst}/{tag}_leapfrog_pmc.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
