@@ -84,23 +84,41 @@ enum {
  * precision, each optional (NULL: 0 and 1); every tau_c must be finite and > 0, every mu_c finite.  1 <= D <= 1024, D > 512 needs
  * a SHARED or POOLED metric; the padded length L is a power of two (128 .. 1024) and n rounded up to a multiple of 128, n_pad,
  * satisfies n_pad L <= 2^27 (X and its transpose, kept on the device, take at most 1 GiB each).  The NUTS transition runs both
- * products on the fp64 matrix cores, 16 chains per workgroup, at L <= 256 (D <= 256); everything else one chain per wavefront. */
+ * products on the fp64 matrix cores, 16 chains per workgroup, at L <= 256 (D <= 256); everything else one chain per wavefront.
+ *
+ * IDHMC_MODEL_GLM -- a generalised linear model with the user's likelihood, the same data layout, prior, limits and kernels as
+ * LOGISTIC_REGRESSION (whose observation is replaced by the user's):
+ *   l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,   z = X q
+ * `source` defines, at namespace scope, one function per observation, compiled at idhmc_create with hipRTC:
+ *
+ *   __device__ void glm_observation(double z, const GlmObs &o, double &r, double &v);
+ *
+ * o.y[k], k < o.K: this observation's data columns (1 <= K <= 4); o.c[j], j < o.nc: the model's constants (device memory).
+ * It returns v = -log p(y | z) (up to a term that depends on the data only) and r = d log p(y | z) / dz.  It is called for
+ * padded observations too (z = 0, y = 0), whose results are then discarded.  The helpers of idhmc_math.hpp are in scope (dexp,
+ * dlog, dlog1p, dfma, ...); the build uses -ffp-contract=off, so only explicit dfma calls fuse.  Compile errors are returned
+ * through idhmc_last_error().  `params` is [K, nc, c (nc) | X row-major (n x D) | Y row-major (n x K)], so
+ * n = (nparams - 2 - nc) / (D + K).  Refused with IDHMC_ERR_BAD_ARG before the device is touched: K not an integer in 1..4,
+ * nc not an integer in 0..16, a remainder that is not a positive multiple of D + K, a non-finite value in X, Y or c, a missing
+ * or empty source, and whatever LOGISTIC_REGRESSION refuses of the prior, D and n_pad L. */
 enum {
     IDHMC_MODEL_ISO_GAUSSIAN = 0,   /* l(q) = -1/2 |q|^2                       */
     IDHMC_MODEL_DIAG_GAUSSIAN = 1,  /* l(q) = -1/2 sum tau_d (q_d - mu_d)^2    */
     IDHMC_MODEL_DENSE_MVN = 2,      /* l(q) = -1/2 (q-mu)' P (q-mu), P = Sigma^-1 (fp64 MFMA) */
     IDHMC_MODEL_CUSTOM = 3,         /* user HIP source, see above */
-    IDHMC_MODEL_LOGISTIC_REGRESSION = 4   /* Bayesian logistic regression, see above (fp64 MFMA) */
+    IDHMC_MODEL_LOGISTIC_REGRESSION = 4,  /* Bayesian logistic regression, see above (fp64 MFMA) */
+    IDHMC_MODEL_GLM = 5                   /* a GLM with the user's observation source, see above (fp64 MFMA) */
 };
 typedef struct {
     int32_t kind;
     int32_t D;              /* dimension(model): 1 <= D <= 1024; ISO and DIAG up to 2048 in every metric mode, CUSTOM up to
                                2048 with a SHARED or POOLED metric */
-    const double *mu;       /* host, D  (DIAG, DENSE; LOGISTIC_REGRESSION: prior mean, may be NULL) */
-    const double *tau;      /* host, D  (DIAG; LOGISTIC_REGRESSION: prior precision, may be NULL) */
+    const double *mu;       /* host, D  (DIAG, DENSE; LOGISTIC_REGRESSION, GLM: prior mean, may be NULL) */
+    const double *tau;      /* host, D  (DIAG; LOGISTIC_REGRESSION, GLM: prior precision, may be NULL) */
     const double *prec;     /* host, D*D row-major, symmetric (DENSE) */
-    const char *source;     /* CUSTOM: NUL-terminated HIP device source */
-    const double *params;   /* CUSTOM: host, nparams doubles copied to the device (may be NULL); LOGISTIC_REGRESSION: [X | y] */
+    const char *source;     /* CUSTOM, GLM: NUL-terminated HIP device source */
+    const double *params;   /* CUSTOM: host, nparams doubles copied to the device (may be NULL); LOGISTIC_REGRESSION: [X | y];
+                               GLM: [K, nc, c | X | Y] */
     int64_t nparams;
 } idhmc_model_desc;
 

@@ -5,8 +5,8 @@ include/idhmc.h.  The compute lives in libidhmc.so (hand-written HIP for gfx950)
 computes on the CPU and nothing falls back to a CPU path.
 """
 from ._lib import IdhmcError, LIB_PATH, load as load_library  # noqa: F401
-from .engine import (Engine, Model, IsoGaussian, DiagGaussian, DenseMVN, CustomDensity, LogisticRegression, default_options,  # noqa: F401
-                     MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION,
+from .engine import (Engine, Model, IsoGaussian, DiagGaussian, DenseMVN, CustomDensity, LogisticRegression, GLM, default_options,  # noqa: F401
+                     MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION, MODEL_GLM,
                      TREE_STATS_DTYPE, EPS_PER_CHAIN, EPS_GLOBAL, METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED, GRAD_STORE, GRAD_RECOMPUTE,
                      T_ADAPT_EPS, T_ACCUM_METRIC, T_ACCUM_MOMENTS, T_KEEP_P, T_USE_DIRECTIONS, T_ACCUM_DIAG,
                      XCHG_DOUBLES, XCHG_ACCEPT, XCHG_LOGEPS, POOL_SEGMENT, xchg_accumulate, xchg_mean,
@@ -19,5 +19,6 @@ from . import diagnostics as Diagnostics  # noqa: F401,E402
 from .diagnostics import (EBFMI, summarize_tree_statistics, summary_from_counters, ess, rhat_from_moments,  # noqa: F401,E402
                           ess_from_moments)
 from . import distributed  # noqa: F401,E402
+from . import glm  # noqa: F401,E402
 
 TreeStatisticsNUTS = TREE_STATS_DTYPE  # reference name (src/NUTS.jl:229)

@@ -654,43 +654,75 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
             return fail(IDHMC_ERR_BAD_ARG, "D = %d: the dense density is limited to D <= 1024", model->D);
         if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION)
             return fail(IDHMC_ERR_BAD_ARG, "D = %d: logistic regression is limited to D <= 1024", model->D);
+        if (model->kind == IDHMC_MODEL_GLM)
+            return fail(IDHMC_ERR_BAD_ARG, "D = %d: a GLM is limited to D <= 1024", model->D);
     }
     if (opt_in && (opt_in->metric_mode < 0 || opt_in->metric_mode > IDHMC_METRIC_POOLED)) return fail(IDHMC_ERR_BAD_ARG, "unknown metric_mode %d", opt_in->metric_mode);
-    if (model->kind < 0 || model->kind > IDHMC_MODEL_LOGISTIC_REGRESSION) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
+    if (model->kind < 0 || model->kind > IDHMC_MODEL_GLM) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
     if (model->kind == IDHMC_MODEL_CUSTOM) {
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "custom model needs HIP source");
         if (model->nparams < 0 || (model->nparams > 0 && !model->params)) return fail(IDHMC_ERR_BAD_ARG, "custom model: bad params");
         if (model->D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
             return fail(IDHMC_ERR_BAD_ARG, "custom model with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)");
-    } else if (model->kind != IDHMC_MODEL_ISO_GAUSSIAN && model->kind != IDHMC_MODEL_LOGISTIC_REGRESSION && !model->mu) {
+    } else if (model->kind != IDHMC_MODEL_ISO_GAUSSIAN && model->kind != IDHMC_MODEL_LOGISTIC_REGRESSION && model->kind != IDHMC_MODEL_GLM &&
+               !model->mu) {
         return fail(IDHMC_ERR_BAD_ARG, "model needs mu");
     }
-    int64_t lr_n = 0;   // observations of a logistic regression
-    if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION) {
+    // a logistic regression's params are [X | y]; a GLM's [K, nc, c | X | Y] (K data columns, nc constants)
+    int64_t lr_n = 0;              // observations of a logistic regression or a GLM
+    int64_t glm_k = 1, glm_nc = 0;
+    if (model->kind == IDHMC_MODEL_GLM) {
         const int D = model->D;
-        if (model->nparams < 1 || model->nparams % (D + 1) != 0 || !model->params)
-            return fail(IDHMC_ERR_BAD_ARG, "logistic regression: nparams = %lld must be a positive multiple of D + 1 = %d ([X | y])",
-                        (long long)model->nparams, D + 1);
-        lr_n = model->nparams / (D + 1);
+        if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
+        if (model->nparams < 2 || !model->params) return fail(IDHMC_ERR_BAD_ARG, "GLM: params must begin with K and nc ([K, nc, c | X | Y])");
+        const double k = model->params[0], nc = model->params[1];
+        if (!(k >= 1.0 && k <= 4.0 && k == std::floor(k))) return fail(IDHMC_ERR_BAD_ARG, "GLM: K = %g must be an integer in 1..4", k);
+        if (!(nc >= 0.0 && nc <= 16.0 && nc == std::floor(nc))) return fail(IDHMC_ERR_BAD_ARG, "GLM: nc = %g must be an integer in 0..16", nc);
+        glm_k = (int64_t)k;
+        glm_nc = (int64_t)nc;
+        const int64_t rest = model->nparams - 2 - glm_nc;
+        if (rest < 1 || rest % (D + glm_k) != 0)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: nparams - 2 - nc = %lld must be a positive multiple of D + K = %lld ([X | Y])",
+                        (long long)rest, (long long)(D + glm_k));
+        for (int64_t j = 0; j < glm_nc; ++j)
+            if (!std::isfinite(model->params[2 + j])) return fail(IDHMC_ERR_BAD_ARG, "GLM: constant c[%lld] is not finite", (long long)j);
+        lr_n = rest / (D + glm_k);
+    }
+    if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION || model->kind == IDHMC_MODEL_GLM) {
+        const bool glm = model->kind == IDHMC_MODEL_GLM;
+        const char *what = glm ? "GLM" : "logistic regression";
+        const int D = model->D;
+        if (!glm) {
+            if (model->nparams < 1 || model->nparams % (D + 1) != 0 || !model->params)
+                return fail(IDHMC_ERR_BAD_ARG, "logistic regression: nparams = %lld must be a positive multiple of D + 1 = %d ([X | y])",
+                            (long long)model->nparams, D + 1);
+            lr_n = model->nparams / (D + 1);
+        }
         int L = 128;
         while (L < D) L *= 2;
         const int64_t npad = (lr_n + 127) / 128 * 128;
         if (npad * L > ((int64_t)1 << 27))
-            return fail(IDHMC_ERR_BAD_ARG, "logistic regression: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
-                        (long long)lr_n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
-        const double *X = model->params, *y = model->params + lr_n * D;
+            return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
+                        what, (long long)lr_n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
+        const double *X = model->params + (glm ? 2 + glm_nc : 0), *y = X + lr_n * D;
         for (int64_t k = 0; k < lr_n * D; ++k)
-            if (!std::isfinite(X[k])) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: X[%lld, %lld] is not finite", (long long)(k / D), (long long)(k % D));
-        for (int64_t i = 0; i < lr_n; ++i)
-            if (y[i] != 0.0 && y[i] != 1.0) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: y[%lld] = %g is neither 0 nor 1", (long long)i, y[i]);
+            if (!std::isfinite(X[k])) return fail(IDHMC_ERR_BAD_ARG, "%s: X[%lld, %lld] is not finite", what, (long long)(k / D), (long long)(k % D));
+        if (glm) {
+            for (int64_t k = 0; k < lr_n * glm_k; ++k)
+                if (!std::isfinite(y[k]))
+                    return fail(IDHMC_ERR_BAD_ARG, "GLM: Y[%lld, %lld] is not finite", (long long)(k / glm_k), (long long)(k % glm_k));
+        } else {
+            for (int64_t i = 0; i < lr_n; ++i)
+                if (y[i] != 0.0 && y[i] != 1.0) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: y[%lld] = %g is neither 0 nor 1", (long long)i, y[i]);
+        }
         for (int k = 0; k < D; ++k) {
             if (model->tau && !(std::isfinite(model->tau[k]) && model->tau[k] > 0.0))
-                return fail(IDHMC_ERR_BAD_ARG, "logistic regression: prior precision tau[%d] = %g must be finite and > 0", k, model->tau[k]);
+                return fail(IDHMC_ERR_BAD_ARG, "%s: prior precision tau[%d] = %g must be finite and > 0", what, k, model->tau[k]);
             if (model->mu && !std::isfinite(model->mu[k]))
-                return fail(IDHMC_ERR_BAD_ARG, "logistic regression: prior mean mu[%d] is not finite", k);
+                return fail(IDHMC_ERR_BAD_ARG, "%s: prior mean mu[%d] is not finite", what, k);
         }
         if (D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
-            return fail(IDHMC_ERR_BAD_ARG, "logistic regression with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)");
+            return fail(IDHMC_ERR_BAD_ARG, "%s with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)", what);
     }
     if (model->kind == IDHMC_MODEL_DIAG_GAUSSIAN && !model->tau) return fail(IDHMC_ERR_BAD_ARG, "diagonal model needs tau");
     if (model->kind == IDHMC_MODEL_DENSE_MVN && !model->prec) return fail(IDHMC_ERR_BAD_ARG, "dense model needs prec");
@@ -730,7 +762,10 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     // a vector is padded to the next multiple of 128 (the reference pads to its SIMD width, src/mcmc.jl:117); the
     // dense density's matrix kernels need a power-of-two number of 128-column chunks
     int nch = (model->D + 127) / 128;
-    if (model->kind == IDHMC_MODEL_DENSE_MVN || model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION) { nch = 1; while (nch * 128 < model->D) nch *= 2; }
+    if (model->kind == IDHMC_MODEL_DENSE_MVN || model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION || model->kind == IDHMC_MODEL_GLM) {
+        nch = 1;
+        while (nch * 128 < model->D) nch *= 2;
+    }
     s.nch = nch;
     s.L = 128 * nch;
     s.model = model->kind;
@@ -814,20 +849,31 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
                                     sizeof(double) * s.D, s.D, hipMemcpyHostToDevice, c->stream));
         }
         s.mu = mu; s.tau = tau; s.prec = prec;
-        if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION) {
-            // the prior's defaults (mu = 0 is the zeroed allocation); X, X' and y zero-padded to [n_pad][L], [L][n_pad], [n_pad]
+        if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION || model->kind == IDHMC_MODEL_GLM) {
+            // the prior's defaults (mu = 0 is the zeroed allocation); X, X' and the K planes of Y zero-padded to [n_pad][L],
+            // [L][n_pad], [K][n_pad]; a GLM's constants
             if (!model->tau) HIPCHK(launch_fill(tau, 1.0, s.D, c->stream));
-            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D;
-            std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)npad, 0.0);
+            const bool glm = model->kind == IDHMC_MODEL_GLM;
+            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D, K = glm_k;
+            const double *X = model->params + (glm ? 2 + glm_nc : 0), *Y = X + n * D;
+            std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(K * npad), 0.0);
             for (int64_t i = 0; i < n; ++i)
                 for (int64_t k = 0; k < D; ++k) {
-                    const double v = model->params[i * D + k];
+                    const double v = X[i * D + k];
                     hx[(size_t)(i * L + k)] = v;
                     hxt[(size_t)(k * npad + i)] = v;
                 }
-            for (int64_t i = 0; i < n; ++i) hy[(size_t)i] = model->params[n * D + i];
+            for (int64_t i = 0; i < n; ++i)
+                for (int64_t k = 0; k < K; ++k) hy[(size_t)(k * npad + i)] = Y[i * K + k];
             double *dx = nullptr, *dxt = nullptr, *dy = nullptr;
-            DALLOC(dx, npad * L); DALLOC(dxt, npad * L); DALLOC(dy, npad);
+            DALLOC(dx, npad * L); DALLOC(dxt, npad * L); DALLOC(dy, K * npad);
+            if (glm) {
+                double *dc = nullptr;
+                DALLOC(dc, glm_nc > 0 ? glm_nc : 1);
+                if (glm_nc > 0) HIPCHK(hipMemcpyAsync(dc, model->params + 2, sizeof(double) * (size_t)glm_nc, hipMemcpyHostToDevice, c->stream));
+                s.user_params = dc;
+                s.user_nparams = glm_nc;
+            }
             HIPCHK(hipMemcpyAsync(dx, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(dxt, hxt.data(), sizeof(double) * hxt.size(), hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(dy, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, c->stream));
@@ -863,6 +909,14 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         jlog[0] = 0;
         const int jrc = jit_build(s, model->source, &c->jit, jlog, sizeof jlog);
         if (jrc != 0) { idhmc_destroy(c); return fail(IDHMC_ERR_BAD_ARG, "custom density did not compile (%d): %s", jrc, jlog); }
+        s.jit = c->jit;
+    }
+    // a GLM: its observation source compiled into the logistic regression's templates (hipRTC); the data went up above
+    if (model->kind == IDHMC_MODEL_GLM) {
+        static thread_local char jlog[400];
+        jlog[0] = 0;
+        const int jrc = jit_build(s, model->source, &c->jit, jlog, sizeof jlog, (int)glm_k);
+        if (jrc != 0) { idhmc_destroy(c); return fail(IDHMC_ERR_BAD_ARG, "GLM observation source did not compile (%d): %s", jrc, jlog); }
         s.jit = c->jit;
     }
     // kappa = I (GaussianKineticEnergy(sptr, Static{D}, 1.0), src/hamiltonian.jl:63-74)

@@ -1,25 +1,40 @@
-// idhmc_logistic.hpp -- Bayesian logistic regression (IDHMC_MODEL_LOGISTIC_REGRESSION), DESIGN section 10:
-//   l(q) = sum_i [y_i z_i - softplus(z_i)] - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q
-//   grad l(q) = X' (y - sigma(z)) - tau .* (q - mu)
-// Two forms with one arithmetic: LogisticRegression (one chain per wavefront, every kernel) and LogisticRegressionCoop
-// (the NUTS kernel at L <= 256: 16 chains per workgroup, both products on the fp64 matrix cores).  Kept out of what the
-// hipRTC build of a custom density includes.
+// idhmc_glm.hpp -- generalised linear models on a data matrix every chain shares, DESIGN sections 10 and 11:
+//   l(q) = -sum_i v(z_i, y_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,   z = X q,   v = -log p(y | z) up to a data-only term
+//   grad l(q) = X' r - tau .* (q - mu),   r_i = d log p(y_i | z_i) / dz_i
+// The observation is a policy type Obs: Obs::K data columns per observation (1..4) and
+//   static void terms(double z, const GlmObs &o, double &r, double &v)
+// Two forms with one arithmetic: GlmWave (one chain per wavefront, every kernel) and GlmCoop (the NUTS kernel at L <= 256:
+// 16 chains per workgroup, both products on the fp64 matrix cores).  The built-in logistic regression
+// (IDHMC_MODEL_LOGISTIC_REGRESSION) is Obs = LogisticObs, instantiated ahead of time (idhmc_logistic.hip); a user's GLM
+// (IDHMC_MODEL_GLM) is Obs = its glm_observation, instantiated by hipRTC (idhmc_jit.hip).  Kept out of what the hipRTC build of a
+// custom density includes.
 //
-// The arithmetic (both forms and the tests' C restatement follow it bit for bit):
+// The arithmetic (both forms and the tests' C restatements follow it bit for bit):
 //   z_i   = fma chain over columns c ascending of X[i][c] * q_c, from +0
-//   s_i   = y_i ? -z_i : z_i;  e_i = dexp(-|s_i|)
-//   v_i   = (s_i > 0 ? s_i : 0) + dlog1p(e_i)                  = softplus(z_i) - y_i z_i
-//   r_i   = (y_i ? 1 : -1) * ((s_i >= 0 ? 1 : e_i) / (1 + e_i)) = y_i - sigma(z_i)
-//   observations i >= n: v_i = r_i = 0
+//   (r_i, v_i) = Obs::terms(z_i, {y_i0 .. y_i,K-1; constants})
+//     logistic: s_i = y_i ? -z_i : z_i;  e_i = dexp(-|s_i|)
+//               v_i = (s_i > 0 ? s_i : 0) + dlog1p(e_i)                  = softplus(z_i) - y_i z_i
+//               r_i = (y_i ? 1 : -1) * ((s_i >= 0 ? 1 : e_i) / (1 + e_i)) = y_i - sigma(z_i)
+//   observations i >= n: v_i = r_i = 0 (the terms are computed, then overwritten: a NaN there does not leak)
 //   G_c   = fma chain over observations i ascending of X[i][c] * r_i, from +0;  g_c = dfma(-tau_c, d_c, G_c), d = q - mu
 //   lane partials (residues 2l, 2l+1 of 128): T = fma chain over chunks j of (tau_c d_c) * d_c;  A = sum over observation
 //   blocks ascending of v_i (plain additions, from +0);  P = dfma(2, A, T);  l = -1/2 wave_sum(P0, P1)
 // A chain of fmas from +0 never holds -0, so the zero padding (columns >= D, observations >= n) leaves every chain as it is:
 // the per-wave form stops at D and n, the matrix-core form runs over the padded tiles, and both give the same bits.
+//
+// Device layout (DevState): X [n_pad][L] (lr_x), X' [L][n_pad] (lr_xt), Y as K planes [K][n_pad] (lr_y), all zero-padded;
+// a GLM's constants in user_params (user_nparams of them).
 #pragma once
 #include "idhmc_device.hpp"
 
 namespace idhmc {
+
+// one observation as the policy's terms() sees it
+struct GlmObs {
+    double y[4];             // this observation's data columns, y[k] for k < K (the rest 0)
+    const double *c;         // the model's constants, c[j] for j < nc (device memory)
+    int K, nc;
+};
 
 // v_i and r_i of one observation (y is 0 or 1)
 IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
@@ -31,19 +46,26 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
     r = y != 0.0 ? sg : -sg;
 }
 
+// Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
+struct LogisticObs {
+    static constexpr int K = 1;
+    IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
+};
+
 // One chain per wavefront.  Observations in blocks of 128, lane l owning observations 128 b + 2 l, 128 b + 2 l + 1: z from
 // coalesced rows of X' against q broadcast from the wavefront's LDS vector, then r is staged in that vector and g accumulates
 // over the block's observations from coalesced rows of X.  X and X' stream from L2 once per gradient.
-template <int NCH>
-struct LogisticRegression {
+template <int NCH, class Obs>
+struct GlmWave {
     static constexpr bool kHasParams = true;
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = false;
     const double *x, *xt;    // [npad][L], [L][npad], device
-    const double2 *y2;       // [npad], lane-offset
+    const double2 *y2;       // [K][npad], lane-offset
     const double2 *mu2, *tau2;   // lane-offset, device
+    const double *cst;       // the constants, device
     double *buf;             // this wavefront's LDS vector, L doubles
-    int D, n, npad, lane;
+    int D, n, npad, nc, lane;
     template <class State>
     IDHMC_DEV void init(const State &s, double *lds_vec, int lane_)
     {
@@ -52,10 +74,12 @@ struct LogisticRegression {
         y2 = reinterpret_cast<const double2 *>(s.lr_y) + lane_;
         mu2 = reinterpret_cast<const double2 *>(s.mu) + lane_;
         tau2 = reinterpret_cast<const double2 *>(s.tau) + lane_;
+        cst = s.user_params;
         buf = lds_vec;
         D = s.D;
         n = s.lr_n;
         npad = s.lr_npad;
+        nc = (int)s.user_nparams;
         lane = lane_;
     }
     IDHMC_DEV double grad(const Vec<NCH> &q, Vec<NCH> &g) const
@@ -78,11 +102,16 @@ struct LogisticRegression {
                 zx = dfma(xv.x, qc, zx);
                 zy = dfma(xv.y, qc, zy);
             }
-            const double2 yv = y2[b * 64];
+            // the K planes of Y (written out: a loop over the planes costs the logistic kernels their register assignment)
+            const double2 p0 = y2[b * 64];
+            const double2 p1 = Obs::K > 1 ? y2[(npad >> 1) + b * 64] : make_double2(0.0, 0.0);
+            const double2 p2 = Obs::K > 2 ? y2[2 * (npad >> 1) + b * 64] : make_double2(0.0, 0.0);
+            const double2 p3 = Obs::K > 3 ? y2[3 * (npad >> 1) + b * 64] : make_double2(0.0, 0.0);
+            const GlmObs ox{{p0.x, p1.x, p2.x, p3.x}, cst, Obs::K, nc}, oy{{p0.y, p1.y, p2.y, p3.y}, cst, Obs::K, nc};
             const int i0 = 128 * b + 2 * lane;
             double rx, vx, ry, vy;
-            logistic_terms(zx, yv.x, rx, vx);
-            logistic_terms(zy, yv.y, ry, vy);
+            Obs::terms(zx, ox, rx, vx);
+            Obs::terms(zy, oy, ry, vy);
             if (i0 >= n) { rx = 0.0; vx = 0.0; }
             if (i0 + 1 >= n) { ry = 0.0; vy = 0.0; }
             a0 = a0 + vx;
@@ -119,7 +148,7 @@ struct LogisticRegression {
 // matrix cores, one 16-chain v_mfma_f64_16x16x4_f64 tile (the round protocol is DenseMvnCoop's, CoopRounds).  A round:
 //   (1) the requester writes q as its row of the [16][L + 2] Q tile;                                      -- barrier A --
 //   (2) per block b of 128 observations: the Z wavefronts (the last 8, one 16-observation column tile each) form
-//       Z = Q X'[:, block] (k = columns ascending), apply r = y - sigma(z) into R tile b & 1 and add v into registers;
+//       Z = Q X'[:, block] (k = columns ascending), apply the observation's terms, r into R tile b & 1 and v into registers;
 //   (3) the G wavefronts (the first L / 16, one 16-column tile of X each) accumulate G += R[b & 1] X[block, :] (k =
 //       observations ascending, the accumulators carried across blocks);
 //       Z of block b + 1 runs between the same barriers as G of block b (two R tiles): one barrier per block;
@@ -127,8 +156,8 @@ struct LogisticRegression {
 //   (5) the requester reads its row of each: g = dfma(-tau, d, G), P = dfma(2, A, T).
 // X' and X stream through L1 once per 16 gradients instead of once per gradient.  LDS: 16 (L + 2) + 2 * 16 * 130 doubles,
 // 49.9 KB at L = 128, 66.3 KB at L = 256.
-template <int NCH>
-struct LogisticRegressionCoop : CoopRounds<LogisticRegressionCoop<NCH>> {
+template <int NCH, class Obs>
+struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     static constexpr bool kHasParams = true;
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = true;
@@ -137,13 +166,14 @@ struct LogisticRegressionCoop : CoopRounds<LogisticRegressionCoop<NCH>> {
     static constexpr int kQ = 0, kR = 16 * DS;         // Q / G tile, then the two R tiles
     static constexpr int kLdsDoubles = 16 * DS + 2 * 16 * RS;
     struct Prefetch {};                                 // nothing is requested ahead of barrier A
-    using CoopRounds<LogisticRegressionCoop<NCH>>::alive;
-    using CoopRounds<LogisticRegressionCoop<NCH>>::lane;
-    using CoopRounds<LogisticRegressionCoop<NCH>>::wv;
+    using CoopRounds<GlmCoop<NCH, Obs>>::alive;
+    using CoopRounds<GlmCoop<NCH, Obs>>::lane;
+    using CoopRounds<GlmCoop<NCH, Obs>>::wv;
     const double *x, *xt, *y;
     const double2 *mu2, *tau2;   // lane-offset, device
+    const double *cst;           // the constants, device
     double *tile;
-    int n, npad;
+    int n, npad, nc;
     template <class State>
     IDHMC_DEV void init(const State &s, double *tile_, int *alive_, int lane_, int wv_)
     {
@@ -152,9 +182,11 @@ struct LogisticRegressionCoop : CoopRounds<LogisticRegressionCoop<NCH>> {
         y = s.lr_y;
         mu2 = reinterpret_cast<const double2 *>(s.mu) + lane_;
         tau2 = reinterpret_cast<const double2 *>(s.tau) + lane_;
+        cst = s.user_params;
         tile = tile_;
         n = s.lr_n;
         npad = s.lr_npad;
+        nc = (int)s.user_nparams;
         alive = alive_;
         lane = lane_;
         wv = wv_;
@@ -178,12 +210,17 @@ struct LogisticRegressionCoop : CoopRounds<LogisticRegressionCoop<NCH>> {
             for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * (kb0 + u)], bv[u], acc, 0, 0, 0);
         }
         const int i = 128 * b + 16 * zt + jj;
-        const double yi = y[i];
+        GlmObs o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o.y[k] = k < Obs::K ? y[k * npad + i] : 0.0;
+        o.c = cst;
+        o.K = Obs::K;
+        o.nc = nc;
         double *rt = rtile(b) + 16 * zt + jj;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {                  // row kk + 4 reg (chain), column jj (observation)
             double r, v;
-            logistic_terms(acc[reg], yi, r, v);
+            Obs::terms(acc[reg], o, r, v);
             if (i >= n) { r = 0.0; v = 0.0; }
             vacc[reg] = vacc[reg] + v;
             rt[(kk + 4 * reg) * RS] = r;
@@ -265,5 +302,11 @@ struct LogisticRegressionCoop : CoopRounds<LogisticRegressionCoop<NCH>> {
         l1 = dfma(2.0, A.y, t1);
     }
 };
+
+// the built-in logistic regression
+template <int NCH>
+using LogisticRegression = GlmWave<NCH, LogisticObs>;
+template <int NCH>
+using LogisticRegressionCoop = GlmCoop<NCH, LogisticObs>;
 
 }  // namespace idhmc

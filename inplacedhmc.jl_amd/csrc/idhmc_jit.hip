@@ -3,6 +3,8 @@
 // runs through exactly the code paths of the built-in general density (dense MVN): evaluation, fused
 // leapfrog, initial-stepsize search and the NUTS transition.  This is the device form of the reference's
 // downward boundary, logdensity_and_gradient!(grad, model, q, sptr) (src/kinetic_energy.jl:73).
+// A user's GLM (IDHMC_MODEL_GLM) is compiled the same way: its glm_observation becomes the observation policy of the
+// logistic regression's templates (idhmc_glm.hpp), the matrix-core form in the NUTS kernel where glm_coop says so.
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 #include <dlfcn.h>
@@ -44,27 +46,39 @@ static void put_log(char *log, size_t cap, const std::string &s)
     log[n] = 0;
 }
 
-int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap)
+int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k)
 {
     *out = nullptr;
     const std::string dir = library_dir();
     const bool shared = s.minv_stride == 0;
-    std::string src = "#define IDHMC_JIT_USER_DENSITY 1\n#include \"idhmc_general.hpp\"\n#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n"
-                      "namespace idhmc {\n#line 1 \"user_density.hip\"\n";
-    src += source;
-    src += "\n}\n";
+    const bool glm = s.model == IDHMC_MODEL_GLM;
+    std::string src;
+    if (!glm) {
+        src = "#define IDHMC_JIT_USER_DENSITY 1\n#include \"idhmc_general.hpp\"\n#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n"
+              "namespace idhmc {\n#line 1 \"user_density.hip\"\n";
+        src += source;
+        src += "\n}\n";
+    } else {
+        // the user's glm_observation as the observation policy of idhmc_glm.hpp, K data columns
+        src = "#include \"idhmc_general.hpp\"\n#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n#include \"idhmc_glm.hpp\"\n"
+              "namespace idhmc {\n#line 1 \"user_glm.hip\"\n";
+        src += source;
+        src += "\n#line 1 \"idhmc_glm_policy\"\nstruct UserGlmObs {\n    static constexpr int K = " + std::to_string(glm_k) + ";\n"
+               "    IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { glm_observation(z, o, r, v); }\n};\n}\n";
+    }
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "idhmc_custom_density.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+    if (hiprtcCreateProgram(&prog, src.c_str(), glm ? "idhmc_user_glm.hip" : "idhmc_custom_density.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
         put_log(log, log_cap, "hiprtcCreateProgram failed");
         return 1;
     }
     const std::string n = std::to_string(s.nch);
-    const std::string model = "idhmc::JitModel<" + n + ">";
+    const std::string model = glm ? "idhmc::GlmWave<" + n + ", idhmc::UserGlmObs>" : "idhmc::JitModel<" + n + ">";
+    const std::string nuts_model = glm && glm_coop(s.nch) ? "idhmc::GlmCoop<" + n + ", idhmc::UserGlmObs>" : model;
     constexpr int kKernels = 5;
     const std::string names[kKernels] = {"idhmc::k_eval_general<" + n + ", " + model + ">",
                                   "idhmc::k_leapfrog_general<" + n + ", " + model + ">",
                                   "idhmc::k_stepsize_general<" + n + ", " + model + ">",
-                                  "idhmc::k_nuts<" + n + ", " + model + ", " + (shared ? "true" : "false") + ">",
+                                  "idhmc::k_nuts<" + n + ", " + nuts_model + ", " + (shared ? "true" : "false") + ">",
                                   "idhmc::k_local_optimum_general<" + n + ", " + model + ">"};
     for (const std::string &nm : names) hiprtcAddNameExpression(prog, nm.c_str());
 
@@ -115,7 +129,8 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
         }
     }
     hiprtcDestroyProgram(&prog);
-    m->nuts_lds = nuts_lds_bytes(s.L, false, shared, false);
+    // a GLM's NUTS kernel may be the cooperative form: its tiles are sized by the density (kLdsDoubles), not by the general rule
+    m->nuts_lds = glm ? glm_nuts_lds_bytes(s.nch, shared) : nuts_lds_bytes(s.L, false, shared, false);
     if (m->nuts_lds > 48 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(m->f_nuts), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)m->nuts_lds) != hipSuccess) {

@@ -1,16 +1,37 @@
-// idhmc_logistic.hip -- Bayesian logistic regression (IDHMC_MODEL_LOGISTIC_REGRESSION, idhmc_logistic.hpp): ahead-of-time
-// instantiation of the general-density kernels (idhmc_general.hpp, idhmc_optimum.hpp) with the per-wave form, and of the NUTS
-// transition with the matrix-core form where it applies (L <= 256) and the per-wave form beyond.  The padded length is a power
+// idhmc_logistic.hip -- Bayesian logistic regression (IDHMC_MODEL_LOGISTIC_REGRESSION, idhmc_glm.hpp with Obs = LogisticObs):
+// ahead-of-time instantiation of the general-density kernels (idhmc_general.hpp, idhmc_optimum.hpp) with the per-wave form, and
+// of the NUTS transition with the matrix-core form where it applies (L <= 256) and the per-wave form beyond.  A user's GLM
+// (IDHMC_MODEL_GLM) instantiates the same templates through hipRTC (idhmc_jit.hip) and takes its shape decisions from here.  The padded length is a power
 // of two (L = 128, 256, 512, 1024), as for the dense density.
+#include <type_traits>
 #include "idhmc_general.hpp"
 #include "idhmc_nuts_kernel.hpp"
 #include "idhmc_optimum.hpp"
-#include "idhmc_logistic.hpp"
+#include "idhmc_glm.hpp"
 
 namespace idhmc {
 
 // one 16-column tile of G per wavefront covers L <= 256
-bool logistic_coop(int nch) { return nch <= 2; }
+bool glm_coop(int nch) { return nch <= 2; }
+
+// dynamic LDS of a GLM's NUTS kernel: the launch_nuts_t sizing of the form glm_coop picks (the tiles do not depend on the observation)
+template <int NCH>
+static size_t glm_nuts_lds_t(bool shared)
+{
+    using M = typename std::conditional<(NCH <= 2), GlmCoop<NCH, LogisticObs>, GlmWave<NCH, LogisticObs>>::type;
+    const int waves = nuts_waves(NCH, M::kSeparable, M::kCooperative, shared);
+    return sizeof(double) * nuts_lds_doubles(128 * NCH, false, shared, M::kSeparable, coop_lds_doubles<M>(), waves);
+}
+size_t glm_nuts_lds_bytes(int nch, bool shared)
+{
+    switch (nch) {
+    case 1: return glm_nuts_lds_t<1>(shared);
+    case 2: return glm_nuts_lds_t<2>(shared);
+    case 4: return glm_nuts_lds_t<4>(shared);
+    case 8: return glm_nuts_lds_t<8>(shared);
+    default: return 0;
+    }
+}
 
 hipError_t launch_eval_logistic(const DevState &s, int random_q, hipStream_t st)
 {

@@ -9,7 +9,7 @@ namespace idhmc {
 // the tree arena also serves as the L-BFGS history of the FindLocalOptimum stage (2 * kLbfgsR vectors)
 int arena_vectors(int max_depth, int model, int L)
 {
-    const bool separable = model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN;     // dense, logistic, custom: not
+    const bool separable = model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN;     // dense, logistic, GLM, custom: not
     const int n = ArenaMap{max_depth, nuts_regenerate(separable), nuts_defer(separable) ? nuts_dl_vectors(max_depth, L) : 0}.count();
     return n > 2 * kLbfgsR ? n : 2 * kLbfgsR;
 }
@@ -23,7 +23,7 @@ static bool dense_coop(int nch)
 int nuts_waves_per_block(int nch, int model, int shared_metric)
 {
     return nuts_waves(nch, model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN,
-                      (model == IDHMC_MODEL_DENSE_MVN && dense_coop(nch)) || (model == IDHMC_MODEL_LOGISTIC_REGRESSION && logistic_coop(nch)),
+                      (model == IDHMC_MODEL_DENSE_MVN && dense_coop(nch)) || ((model == IDHMC_MODEL_LOGISTIC_REGRESSION || model == IDHMC_MODEL_GLM) && glm_coop(nch)),
                       shared_metric != 0);
 }
 // wavefronts per workgroup of the wide form of the kernel (0: the model/shape has none); the arena is sized for it
@@ -67,7 +67,7 @@ hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wi
     const int64_t have = s.nslots / W;
     const int grid = (int)(need < have ? need : have);
     const bool shared = s.minv_stride == 0;
-    if (s.model == IDHMC_MODEL_CUSTOM) return launch_nuts_jit(s, iter, flags, grid, st);
+    if (s.model == IDHMC_MODEL_CUSTOM || s.model == IDHMC_MODEL_GLM) return launch_nuts_jit(s, iter, flags, grid, st);
     if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_nuts_logistic(s, iter, flags, grid, st);
     if (s.model == IDHMC_MODEL_DENSE_MVN) {
         IDHMC_DISPATCH_NCH_POW2(s.nch, {
@@ -95,7 +95,7 @@ hipError_t launch_local_optimum_jit(const DevState &s, double penalty, int itera
 hipError_t launch_local_optimum(const DevState &s, double penalty, int iterations, hipStream_t st)
 {
     if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_local_optimum_dense(s, penalty, iterations, st);
-    if (s.model == IDHMC_MODEL_CUSTOM) return launch_local_optimum_jit(s, penalty, iterations, optimum_grid(s), st);
+    if (s.model == IDHMC_MODEL_CUSTOM || s.model == IDHMC_MODEL_GLM) return launch_local_optimum_jit(s, penalty, iterations, optimum_grid(s), st);
     if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_local_optimum_logistic(s, penalty, iterations, st);
     IDHMC_DISPATCH_NCH(s.nch, {
         if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)
@@ -111,7 +111,7 @@ hipError_t launch_local_optimum(const DevState &s, double penalty, int iteration
 hipError_t launch_stepsize_search(const DevState &s, hipStream_t st)
 {
     if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_stepsize_search_dense(s, st);
-    if (s.model == IDHMC_MODEL_CUSTOM) return launch_stepsize_search_jit(s, st);
+    if (s.model == IDHMC_MODEL_CUSTOM || s.model == IDHMC_MODEL_GLM) return launch_stepsize_search_jit(s, st);
     if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_stepsize_search_logistic(s, st);
     int64_t b = (s.C + 3) / 4;
     if (b > 4096) b = 4096;

@@ -11,7 +11,7 @@ TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_l
                              ("term_right", "<i4"), ("depth", "<i4"), ("steps", "<i4")])
 assert TREE_STATS_DTYPE.itemsize == 32
 
-MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION = 0, 1, 2, 3, 4
+MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION, MODEL_GLM = 0, 1, 2, 3, 4, 5
 EPS_PER_CHAIN, EPS_GLOBAL = 0, 1
 METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED = 0, 1, 2
 GRAD_STORE, GRAD_RECOMPUTE = 0, 1
@@ -130,6 +130,56 @@ def LogisticRegression(X, y, prior_mu=None, prior_tau=None):
             raise ValueError("prior_tau must be finite and > 0")
     m = Model(MODEL_LOGISTIC_REGRESSION, D, mu=mu, tau=tau, params=np.concatenate([X.ravel(), y]))
     m.n = n
+    return m
+
+
+def _prior(D, prior_mu, prior_tau):
+    mu = tau = None
+    if prior_mu is not None:
+        mu = np.array(np.broadcast_to(np.asarray(prior_mu, dtype=np.float64), (D,)))
+        if not np.isfinite(mu).all():
+            raise ValueError("prior_mu must be finite")
+    if prior_tau is not None:
+        tau = np.array(np.broadcast_to(np.asarray(prior_tau, dtype=np.float64), (D,)))
+        if not (np.isfinite(tau).all() and (tau > 0).all()):
+            raise ValueError("prior_tau must be finite and > 0")
+    return mu, tau
+
+
+def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None):
+    """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
+    l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
+    X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
+    `source` defines  __device__ void glm_observation(double z, const GlmObs &o, double &r, double &v)  with v = -log p(y | z)
+    and r = d log p(y | z) / dz (o.y[k], k < o.K: the observation's columns; o.c[j], j < o.nc: the constants); ready-made
+    sources are in inplacedhmc_jl_amd.glm.  prior_mu, prior_tau: (D,) or scalars, default 0 and 1, tau > 0."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be a non-empty (n, D) matrix, got shape %s" % (X.shape,))
+    n, D = X.shape
+    if D > 1024:
+        raise ValueError("a GLM is limited to D <= 1024 (D = %d)" % D)
+    if not np.isfinite(X).all():
+        raise ValueError("X must be finite")
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if Y.ndim != 2 or Y.shape[0] != n or not 1 <= Y.shape[1] <= 4:
+        raise ValueError("Y must have shape (%d,) or (%d, K) with 1 <= K <= 4, got %s" % (n, n, Y.shape))
+    if not np.isfinite(Y).all():
+        raise ValueError("Y must be finite")
+    c = np.zeros(0) if constants is None else np.asarray(constants, dtype=np.float64).ravel()
+    if c.size > 16:
+        raise ValueError("at most 16 constants (got %d)" % c.size)
+    if not np.isfinite(c).all():
+        raise ValueError("the constants must be finite")
+    if not isinstance(source, str) or not source.strip():
+        raise ValueError("a GLM needs HIP source defining glm_observation")
+    mu, tau = _prior(D, prior_mu, prior_tau)
+    K = Y.shape[1]
+    m = Model(MODEL_GLM, D, mu=mu, tau=tau, source=source,
+              params=np.concatenate([[float(K), float(c.size)], c, X.ravel(), Y.ravel()]))
+    m.n, m.K, m.nc = n, K, c.size
     return m
 
 
