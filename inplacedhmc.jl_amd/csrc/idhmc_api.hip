@@ -51,19 +51,6 @@ static int lanes_join(idhmc_ctx *c);
         if (int rc_lanes_ = lanes_join(ctx)) return rc_lanes_;               \
     } while (0)
 
-struct VmmBlock {
-    void *va = nullptr;
-    size_t size = 0;
-    hipMemGenericAllocationHandle_t handle{};
-    bool mapped = false, created = false;
-    void release()
-    {
-        if (mapped) (void)hipMemUnmap(va, size);
-        if (created) (void)hipMemRelease(handle);
-        if (va) (void)hipMemAddressFree(va, size);
-        va = nullptr; mapped = created = false; size = 0;
-    }
-};
 struct idhmc_ctx {
     int device = 0;
     DevState s{};
@@ -89,10 +76,18 @@ struct idhmc_ctx {
     static constexpr int kRing = 64, kLag = 8, kPulseWords = 2;
     unsigned long long *ring = nullptr;   // pinned host memory, kRing x kPulseWords; word 0 == ~0: not yet written
     uint64_t launches = 0;
+    // switches from the environment, read once in idhmc_create
     int force_wide = -1;                  // IDHMC_NUTS_WIDE = 0 / 1 forces one form (tests, experiments)
     int fuse = -1;                        // IDHMC_FUSE = 0 / 1: the drivers never / always make several transitions per launch (-1: yes)
     bool fuse_ok = false;                 // workgroups b and b + 8 share an XCD on this device (probed at creation): fused launches are possible
     bool test_xcc = false;                // IDHMC_TEST_XCC_MISMATCH=1: the transition flags may carry kTestXccFlag (test suite only)
+    bool dense_mfma = true;               // IDHMC_DENSE_MFMA=0: the dense single-step leapfrog runs the per-wave GEMV kernel (tests)
+    int use_lanes = kLanes;               // IDHMC_DENSE_LANES = 0 switches the dense leapfrog's lanes off, n caps their number (measurements)
+    struct {                              // place_state's search, IDHMC_PLACEMENT_{TRIES, MAX_BYTES, WALK_BYTES, PAIRS, VERBOSE}
+        int tries = 32;
+        int64_t max_bytes = (int64_t)16 << 30, walk_bytes = (int64_t)64 << 30;
+        bool pairs = true, verbose = false;
+    } place;
     // IDHMC_GRAD_RECOMPUTE: the single-step leapfrog of a separable density leaves the stored gradient stale; whoever
     // needs the array (get_grad, the stepsize search, the n-step kernel, the optimum stage) re-evaluates first
     bool grad_stale = false;
@@ -122,12 +117,10 @@ struct idhmc_ctx {
     int lanes_distinct = 0;               // lanes (the context's stream included) found on different hardware queues
     double placement_GBps = 0.0;          // place_state: probe rate of the placement kept, candidates tried
     int placement_tries = 0;
-    int placement_kind = 0;               // 0 separate allocations, 1 spread-out slab, 2 one mapped physical allocation, 3 separate allocations found by the pair walk
+    int placement_kind = 0;               // 0 separate allocations, 3 separate allocations found by the pair walk (1, 2: kinds no longer built)
     double placement_single_GBps = 0.0;   // one array alone (the yardstick of "good")
     double placement_ms = 0.0;            // wall time of place_state
     int64_t placement_peak_bytes = 0;     // most device bytes held at one time during the search
-    VmmBlock vmm;                         // kind 2: unmapped / released in idhmc_destroy
-    int use_lanes = kLanes;               // IDHMC_DENSE_LANES = 0 switches them off, n caps their number (measurements)
 };
 
 static int lanes_join(idhmc_ctx *c)
@@ -213,23 +206,19 @@ static int leapfrog_lanes(idhmc_ctx *c, double eps, int own, int chunks)
         for (int k = 1; k < lanes; ++k) HIPCHK(hipStreamWaitEvent(c->lane[k], c->fork_ev, 0));
         c->lanes_open = true;
     }
-    const int64_t align = dense_mfma_tile_align(c->s), units = ((c->s.C + 15) / 16 + align - 1) / align, ntiles = (c->s.C + 15) / 16;
-    for (int j = 0; j < chunks; ++j) {
-        const int64_t t0 = align * (units * j / chunks), t1 = align * (units * (j + 1) / chunks);
-        HIPCHK(launch_leapfrog_dense_mfma_tiles(c->s, eps, own, 1, t0, t1 < ntiles ? t1 : ntiles, 256,
+    const int64_t ntiles = (c->s.C + 15) / 16;
+    for (int j = 0; j < chunks; ++j)
+        HIPCHK(launch_leapfrog_dense_mfma_tiles(c->s, eps, own, 1, ntiles * j / chunks, ntiles * (j + 1) / chunks, 256,
                                                 (j % lanes) ? c->lane[j % lanes] : c->stream));
-    }
     return IDHMC_OK;
 }
 // one fused leapfrog launch (or one per lane) for the entry points below
 static int leapfrog_any(idhmc_ctx *c, double eps, int own, int n_steps, int regrad)
 {
-    const char *e = getenv("IDHMC_DENSE_MFMA");        // read per call like launch_leapfrog_dense does (tests switch it)
-    const bool mfma_off = e && e[0] == '0';
-    const int chunks = mfma_off ? 0 : lane_chunks(c, n_steps);
+    const int chunks = c->dense_mfma ? lane_chunks(c, n_steps) : 0;
     if (chunks) return leapfrog_lanes(c, eps, own, chunks);
     if (int rc = lanes_join(c)) return rc;
-    HIPCHK(launch_leapfrog(c->s, eps, own, n_steps, regrad, c->stream));
+    HIPCHK(launch_leapfrog(c->s, eps, own, n_steps, regrad, c->dense_mfma, c->stream));
     return IDHMC_OK;
 }
 
@@ -261,32 +250,7 @@ static int dalloc(idhmc_ctx *c, T **out, int64_t n, bool zero = true)
 // IDHMC_PLACEMENT_MAX_BYTES (default 16 GiB) and a quarter of the free memory, the kept set included; at most
 // IDHMC_PLACEMENT_TRIES candidates (default 32, at most 48, 1 = take what comes); no candidate starts after kSearchMs of the call.  The wall time and the peak are reported by
 // idhmc_placement_cost.  IDHMC_PLACEMENT_VERBOSE=1 prints the candidates.
-// Candidate kinds, in order: (V) only with IDHMC_PLACEMENT_VMM=1: one physical allocation made with the virtual-memory API (hipMemCreate +
-// hipMemMap), the arrays 36 KiB (mod 64 KiB) askew inside it -- measured like any other: NOT deterministic-good (0.97-1.00 x one array alone in a
-// bad region, profiles/r03_state_layout.log), and a 2 GiB mapping faulted the GPU in the probe, so it is not tried by default; (S) only with IDHMC_PLACEMENT_SLAB=1 and arrays of >= 256 MiB: one hipMalloc with the starts
-// 2050 MiB apart -- it streamed at the full rate in round 2's bad regions (profiles/r02_state_layout.log), did not in round 3's (6 of 6
-// bad, profiles/r03_state_layout.log) and keeps (nvec - 1) x (2050 MiB - bytes) unused, so it is no longer tried by default;
-// then ordinary sets of nvec hipMallocs.
-static bool vmm_make(VmmBlock &v, int device, size_t want)
-{
-    hipMemAllocationProp prop{};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = device;
-    size_t gran = 0;
-    if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || gran == 0) { (void)hipGetLastError(); return false; }
-    v.size = (want + gran - 1) / gran * gran;
-    if (hipMemAddressReserve(&v.va, v.size, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); v.va = nullptr; return false; }
-    if (hipMemCreate(&v.handle, v.size, &prop, 0) != hipSuccess) { (void)hipGetLastError(); v.release(); return false; }
-    v.created = true;
-    if (hipMemMap(v.va, v.size, 0, v.handle, 0) != hipSuccess) { (void)hipGetLastError(); v.release(); return false; }
-    v.mapped = true;
-    hipMemAccessDesc acc{};
-    acc.location = prop.location;
-    acc.flags = hipMemAccessFlagsProtReadWrite;
-    if (hipMemSetAccess(v.va, v.size, &acc, 1) != hipSuccess) { (void)hipGetLastError(); v.release(); return false; }
-    return true;
-}
+// Candidates: the pair walk below, then ordinary sets of nvec hipMallocs (DESIGN.md 2 has the kinds tried before and why they went).
 namespace {
 constexpr int kMaxTries = 48;
 constexpr double kGoodRatio = 1.10;
@@ -297,18 +261,13 @@ constexpr double kSearchMs = 500.0;
 // the candidate sets of one place_state call; whatever is still here when the call returns -- on any path -- is freed
 struct CandidateSets {
     double *arr[kMaxTries][4] = {};
-    char *slab[kMaxTries] = {};          // set t is one hipMalloc (kind S)
-    VmmBlock vmm[kMaxTries];             // set t is one mapped physical allocation (kind V)
     float ms[kMaxTries] = {};
     int64_t held[kMaxTries] = {};        // device bytes the set occupies
     int n = 0;
     int64_t held_now = 0, held_peak = 0;
     void drop(int t, int nvec)
     {
-        if (vmm[t].va) vmm[t].release();
-        else if (slab[t]) (void)hipFree(slab[t]);
-        else for (int k = 0; k < nvec; ++k) if (arr[t][k]) (void)hipFree(arr[t][k]);
-        slab[t] = nullptr;
+        for (int k = 0; k < nvec; ++k) if (arr[t][k]) (void)hipFree(arr[t][k]);
         for (int k = 0; k < 4; ++k) arr[t][k] = nullptr;
         held_now -= held[t];
         held[t] = 0;
@@ -332,21 +291,12 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
     const auto t_begin = std::chrono::steady_clock::now();
     const size_t bytes = (size_t)n * sizeof(double);
     const int64_t set_bytes = (int64_t)nvec * (int64_t)bytes;
-    int tries = 32;
-    if (const char *e = getenv("IDHMC_PLACEMENT_TRIES")) tries = atoi(e);
-    const bool verbose = getenv("IDHMC_PLACEMENT_VERBOSE") != nullptr;
-    // a candidate set that is not the best so far is cut down to ONE of its arrays (a spacer) -- IDHMC_PLACEMENT_SPACERS=0 holds whole sets as
-    // rounds 2-3 did.  Measured after allocator churn (profiles/r03_state_layout.log): 6 of 6 contexts found a good placement (3 to 16
-    // candidates, <= 10 GiB held) where whole sets ran out of the 16 GiB budget after 10 candidates in 2 of 6
-    const char *sp_env = getenv("IDHMC_PLACEMENT_SPACERS");
-    const bool spacers = !(sp_env && sp_env[0] == '0');
-    size_t min_bytes = (size_t)64 << 20;
-    if (const char *e = getenv("IDHMC_PLACEMENT_MIN_BYTES")) min_bytes = (size_t)atoll(e);      // (experiments)
-    if (bytes < min_bytes) tries = 1;                 // small arrays: latency, not channels
+    int tries = c->place.tries;
+    const bool verbose = c->place.verbose;
+    if (bytes < ((size_t)64 << 20)) tries = 1;       // small arrays: latency, not channels
     if (tries > kMaxTries) tries = kMaxTries;
     if (tries < 1) tries = 1;
-    int64_t budget = (int64_t)16 << 30;               // bytes held at any one time, the kept set included
-    if (const char *e = getenv("IDHMC_PLACEMENT_MAX_BYTES")) budget = atoll(e);
+    int64_t budget = c->place.max_bytes;              // bytes held at any one time, the kept set included
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (int64_t)(free_b / 4) < budget) budget = (int64_t)(free_b / 4);
@@ -356,14 +306,6 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
     if (!CS) return fail(IDHMC_ERR_ALLOC, "out of host memory");
     CandidateSets &cs = *CS;
     cs.nvec_ = nvec;
-    const size_t far_stride = (size_t)2050 << 20;
-    const int64_t slab_bytes = (int64_t)((nvec - 1) * far_stride + bytes);
-    // (V) is opt-in since it cost the round's bench run a GPU memory fault: the context of configs[2] (four arrays, one mapping of 2 GiB + 2 MiB)
-    // faulted in its first probe on two boxes out of three, and the candidate is no better placed than three hipMallocs anyway
-    // (profiles/r03_state_layout.log); never more than 2 GiB in one mapping
-    bool want_vmm = tries > 1 && getenv("IDHMC_PLACEMENT_VMM") && set_bytes + (int64_t)(nvec * ((size_t)36 << 10)) < ((int64_t)2 << 30);
-    bool want_slab = tries > 1 && bytes >= ((size_t)256 << 20) && bytes <= ((size_t)2048 << 20) && getenv("IDHMC_PLACEMENT_SLAB");
-    const size_t askew = (size_t)36 << 10;
     double single_Bps = 0.0;                          // one array alone, measured on the first candidate
     int best = -1;
     const double probe_bytes = 2.0 * (double)set_bytes * 4;
@@ -380,14 +322,12 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
     // 250 ms of wall time held at one time, all of it
     // given back before the call returns.  IDHMC_PLACEMENT_PAIRS=0 goes straight to the walk over whole sets below.
     {
-        const char *pw = getenv("IDHMC_PLACEMENT_PAIRS");
-        int64_t walk_budget = (int64_t)64 << 30;
-        if (const char *e = getenv("IDHMC_PLACEMENT_WALK_BYTES")) walk_budget = atoll(e);
+        int64_t walk_budget = c->place.walk_bytes;
         {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (int64_t)(free_b / 2) < walk_budget) walk_budget = (int64_t)(free_b / 2);
         }
-        if (tries > 1 && !(pw && pw[0] == '0') && walk_budget >= 2 * set_bytes) {
+        if (tries > 1 && c->place.pairs && walk_budget >= 2 * set_bytes) {
             std::vector<void *> spacer_blocks;
             std::vector<double *> same;             // arrays of the reference's class, in the order found
             std::vector<double *> other;            // arrays of the other class
@@ -475,54 +415,23 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
         }
     }
     for (int t = 0; t < tries; ++t) {
-        const char *kind = "sets";
-        bool ok = false;
-        if (want_vmm) {                               // (V)
-            want_vmm = false;
-            kind = "vmm";
-            const int64_t need = set_bytes + (int64_t)(nvec * askew);
-            if (cs.held_now + need <= budget && vmm_make(cs.vmm[t], c->device, (size_t)need)) {
-                ok = true;
-                cs.held[t] = (int64_t)cs.vmm[t].size;
-                for (int k = 0; k < nvec && ok; ++k) {
-                    cs.arr[t][k] = (double *)((char *)cs.vmm[t].va + k * (bytes + askew));
-                    ok = hipMemsetAsync(cs.arr[t][k], 0, bytes, c->stream) == hipSuccess;
-                }
-                if (!ok) { (void)hipGetLastError(); cs.vmm[t].release(); cs.held[t] = 0; }
-            }
-            if (!ok) { for (int k = 0; k < 4; ++k) cs.arr[t][k] = nullptr; --t; continue; }    // not available here: next kind, same index
-        } else if (want_slab) {                       // (S)
-            want_slab = false;
-            kind = "slab";
-            if (cs.held_now + slab_bytes <= budget && hipMalloc((void **)&cs.slab[t], (size_t)slab_bytes) == hipSuccess) {
-                ok = true;
-                cs.held[t] = slab_bytes;
-                for (int k = 0; k < nvec && ok; ++k) {
-                    cs.arr[t][k] = (double *)(cs.slab[t] + k * far_stride);
-                    ok = hipMemsetAsync(cs.arr[t][k], 0, bytes, c->stream) == hipSuccess;
-                }
-                if (!ok) { (void)hipGetLastError(); (void)hipFree(cs.slab[t]); cs.held[t] = 0; }
-            } else (void)hipGetLastError();
-            if (!ok) { cs.slab[t] = nullptr; for (int k = 0; k < 4; ++k) cs.arr[t][k] = nullptr; --t; continue; }
-        } else {                                      // ordinary set
-            if (t > 0 && cs.held_now + set_bytes > budget) break;       // the budget is what bounds the walk ...
-            if (t > 0 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() >= kSearchMs) break;   // ... and the clock
-            ok = true;
-            for (int k = 0; k < nvec && ok; ++k) {
-                void *p = nullptr;
-                ok = hipMalloc(&p, bytes) == hipSuccess && hipMemsetAsync(p, 0, bytes, c->stream) == hipSuccess;
-                cs.arr[t][k] = (double *)p;
-            }
-            cs.held[t] = set_bytes;
-            if (!ok) {                                // out of memory: what we have is what we get
-                (void)hipGetLastError();
-                cs.n = t + 1;
-                cs.held_now += cs.held[t];
-                cs.drop(t, nvec);
-                cs.n = t;
-                if (best < 0) return fail(IDHMC_ERR_ALLOC, "hipMalloc(%zu bytes) failed for the chain state", bytes);
-                break;
-            }
+        if (t > 0 && cs.held_now + set_bytes > budget) break;       // the budget is what bounds the walk ...
+        if (t > 0 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() >= kSearchMs) break;   // ... and the clock
+        bool ok = true;
+        for (int k = 0; k < nvec && ok; ++k) {
+            void *p = nullptr;
+            ok = hipMalloc(&p, bytes) == hipSuccess && hipMemsetAsync(p, 0, bytes, c->stream) == hipSuccess;
+            cs.arr[t][k] = (double *)p;
+        }
+        cs.held[t] = set_bytes;
+        if (!ok) {                                    // out of memory: what we have is what we get
+            (void)hipGetLastError();
+            cs.n = t + 1;
+            cs.held_now += cs.held[t];
+            cs.drop(t, nvec);
+            cs.n = t;
+            if (best < 0) return fail(IDHMC_ERR_ALLOC, "hipMalloc(%zu bytes) failed for the chain state", bytes);
+            break;
         }
         cs.n = t + 1;
         cs.held_now += cs.held[t];
@@ -536,23 +445,23 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
         if (int rc = probe_ms(c, cs.arr[t], nvec, C, L, &cs.ms[t])) return rc;
         const double rate = probe_bytes / (cs.ms[t] * 1e-3);
         if (verbose) {
-            fprintf(stderr, "idhmc placement candidate %d (%s): %.1f GB/s = %.3f x one array alone (%.1f GB/s), holding %.2f GiB  at", t, kind,
+            fprintf(stderr, "idhmc placement candidate %d (sets): %.1f GB/s = %.3f x one array alone (%.1f GB/s), holding %.2f GiB  at", t,
                     rate / 1e9, rate / single_Bps, single_Bps / 1e9, cs.held_now / 1073741824.0);
             for (int k = 0; k < nvec; ++k) fprintf(stderr, " %p", (void *)cs.arr[t][k]);
             fprintf(stderr, "\n");
         }
         if (best < 0 || cs.ms[t] < cs.ms[best]) best = t;
         if (rate >= kGoodRatio * single_Bps) { best = t; break; }      // a good one: stop looking
-        if (spacers) {
-            // a candidate that is not the best so far only has to keep the allocator from handing the same memory out again: one of
-            // its arrays does that (the next set then pairs the two freed blocks with a new one) -- three times as many candidates
-            // inside the same byte budget
-            for (int u = 0; u <= t; ++u) {
-                if (u == best || !cs.held[u] || cs.slab[u] || cs.vmm[u].va || cs.held[u] <= (int64_t)bytes) continue;
-                for (int k = 1; k < nvec; ++k) if (cs.arr[u][k]) { (void)hipFree(cs.arr[u][k]); cs.arr[u][k] = nullptr; }
-                cs.held_now -= cs.held[u] - (int64_t)bytes;
-                cs.held[u] = (int64_t)bytes;
-            }
+        // a candidate that is not the best so far only has to keep the allocator from handing the same memory out again: one of its
+        // arrays (a spacer) does that (the next set then pairs the two freed blocks with a new one) -- three times as many candidates
+        // inside the same byte budget.  Measured after allocator churn (profiles/r03_state_layout.log): 6 of 6 contexts found a good
+        // placement (3 to 16 candidates, <= 10 GiB held) where whole sets, as rounds 2-3 held them, ran out of the 16 GiB budget after
+        // 10 candidates in 2 of 6
+        for (int u = 0; u <= t; ++u) {
+            if (u == best || !cs.held[u] || cs.held[u] <= (int64_t)bytes) continue;
+            for (int k = 1; k < nvec; ++k) if (cs.arr[u][k]) { (void)hipFree(cs.arr[u][k]); cs.arr[u][k] = nullptr; }
+            cs.held_now -= cs.held[u] - (int64_t)bytes;
+            cs.held[u] = (int64_t)bytes;
         }
     }
     if (best < 0) return fail(IDHMC_ERR_ALLOC, "no placement for the chain state (%zu bytes per array)", bytes);
@@ -561,11 +470,9 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
     c->placement_GBps = (cs.n > 1 || cs.ms[best] > 0.f) && cs.ms[best] > 0.f ? probe_bytes / (cs.ms[best] * 1e-3) / 1e9 : 0.0;
     c->placement_single_GBps = single_Bps / 1e9;
     c->placement_peak_bytes = cs.held_peak;
-    for (int k = 0; k < nvec; ++k) out[k] = cs.arr[best][k];
-    if (cs.vmm[best].va) { c->vmm = cs.vmm[best]; cs.vmm[best] = VmmBlock(); c->placement_kind = 2; }
-    else if (cs.slab[best]) { c->allocs.push_back(cs.slab[best]); c->placement_kind = 1; }
-    else { for (int k = 0; k < nvec; ++k) c->allocs.push_back(cs.arr[best][k]); c->placement_kind = 0; }
-    c->bytes += cs.held[best];          // (a slab's unused space between the arrays is allocated all the same)
+    for (int k = 0; k < nvec; ++k) { out[k] = cs.arr[best][k]; c->allocs.push_back(cs.arr[best][k]); }
+    c->placement_kind = 0;
+    c->bytes += cs.held[best];
     cs.held[best] = 0;                  // kept: not the holder's to free any more
     c->placement_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return IDHMC_OK;
@@ -625,7 +532,6 @@ int idhmc_destroy(idhmc_ctx *c)
     }
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     for (void *p : c->allocs) (void)hipFree(p);
-    c->vmm.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -755,6 +661,18 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     c->stream = c->own_stream;
     (void)hipEventCreate(&c->ev0);
     (void)hipEventCreate(&c->ev1);
+    // every switch the library takes from the environment, read once per context (tests and measurements set them before they
+    // create one; nothing reads the environment on the launch path)
+    if (const char *w = getenv("IDHMC_NUTS_WIDE")) c->force_wide = atoi(w) != 0;
+    if (const char *w = getenv("IDHMC_FUSE")) c->fuse = atoi(w) != 0;
+    if (const char *w = getenv("IDHMC_TEST_XCC_MISMATCH")) c->test_xcc = atoi(w) != 0;
+    if (const char *w = getenv("IDHMC_DENSE_MFMA")) c->dense_mfma = w[0] != '0';
+    if (const char *w = getenv("IDHMC_DENSE_LANES")) c->use_lanes = atoi(w) < idhmc_ctx::kLanes ? atoi(w) : idhmc_ctx::kLanes;
+    if (const char *w = getenv("IDHMC_PLACEMENT_TRIES")) c->place.tries = atoi(w);
+    if (const char *w = getenv("IDHMC_PLACEMENT_MAX_BYTES")) c->place.max_bytes = atoll(w);
+    if (const char *w = getenv("IDHMC_PLACEMENT_WALK_BYTES")) c->place.walk_bytes = atoll(w);
+    if (const char *w = getenv("IDHMC_PLACEMENT_PAIRS")) c->place.pairs = w[0] != '0';
+    c->place.verbose = getenv("IDHMC_PLACEMENT_VERBOSE") != nullptr;
 
     DevState &s = c->s;
     s.C = nchains;
@@ -820,9 +738,6 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
                                      hipHostMallocDefault);
         if (e != hipSuccess) { idhmc_destroy(c); return fail(IDHMC_ERR_ALLOC, "pinned ring: %s", hipGetErrorString(e)); }
         for (int i = 0; i < idhmc_ctx::kRing * idhmc_ctx::kPulseWords; ++i) c->ring[i] = ~0ull;
-        if (const char *w = getenv("IDHMC_NUTS_WIDE")) c->force_wide = atoi(w) != 0;
-        if (const char *w = getenv("IDHMC_FUSE")) c->fuse = atoi(w) != 0;
-        if (const char *w = getenv("IDHMC_TEST_XCC_MISMATCH")) c->test_xcc = atoi(w) != 0;
         {   // several transitions per launch need workgroups b and b + 8 on one XCD (idhmc_nuts_kernel.hpp): look before relying on it
             const int g = prop.multiProcessorCount > 8 ? prop.multiProcessorCount : 8;
             uint32_t *dx = nullptr;
@@ -835,7 +750,6 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
             if (dx) (void)hipFree(dx);
             c->fuse_ok = ok;
         }
-        if (const char *w = getenv("IDHMC_DENSE_LANES")) c->use_lanes = atoi(w) < idhmc_ctx::kLanes ? atoi(w) : idhmc_ctx::kLanes;
     }
     // model parameters, padded with zeros
     {

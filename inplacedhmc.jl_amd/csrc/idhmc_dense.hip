@@ -4,7 +4,6 @@
 // kernel (idhmc_dense_mfma.hip) when the shape allows; the NUTS transition is k_nuts<.., DenseMvn, ..>.
 #include "idhmc_general.hpp"
 #include "idhmc_optimum.hpp"
-#include <cstdlib>
 
 namespace idhmc {
 
@@ -23,11 +22,10 @@ hipError_t launch_random_position_dense(const DevState &s, hipStream_t st)
 
 hipError_t launch_leapfrog_dense_mfma(const DevState &s, double eps, int own, int n_steps, hipStream_t st);
 
-hipError_t launch_leapfrog_dense(const DevState &s, double eps, int own, int n_steps, hipStream_t st)
+// mfma: the matrix-core kernel where it covers the shape (L <= 512); 0 (or beyond): the per-wave GEMV kernel
+hipError_t launch_leapfrog_dense(const DevState &s, double eps, int own, int n_steps, int mfma, hipStream_t st)
 {
-    // the matrix-core kernel (L <= 512); IDHMC_DENSE_MFMA=0 selects the per-wave GEMV kernel
-    const char *e = getenv("IDHMC_DENSE_MFMA");
-    if (!(e && e[0] == '0')) {
+    if (mfma) {
         const hipError_t r = launch_leapfrog_dense_mfma(s, eps, own, n_steps, st);
         if (r != hipErrorNotSupported) return r;
     }

@@ -21,22 +21,9 @@ IDHMC_DEV double dpp_xor_add(double v, int m) { return v + __shfl_xor(v, m, 64);
 // barrier in the k loop, and several workgroups are resident per CU.  The phase point (q, p in VGPRs, the
 // gradient as -T in the accumulators) stays on chip for all n_steps of a call: only the first step reads and
 // only the last one writes HBM, so a multi-step call runs at the matrix-core rate.
-// TR = row tiles (16 chains each) per workgroup.  -DIDHMC_M2_TR=2 gives the single-step form 32-chain tiles, i.e. two MFMAs per
-// B operand fetched from L2 (the matrix is re-read once per tile: 512 KiB x 1024 tiles = 2.7x the state's traffic at configs[3]).
-// Measured in round 2 and not the default: the matrix traffic is not what the sweep waits for (without it the
+// TR = row tiles (16 chains each) per workgroup: 1 in every form built.  Two (32-chain tiles, two MFMAs per B operand fetched
+// from L2) were measured in round 2 and not kept: the matrix traffic is not what the sweep waits for (without it the
 // sweep is 3 % shorter), and 232 registers leave two workgroups per CU instead of three.
-#ifndef IDHMC_M2_TR
-#define IDHMC_M2_TR 1
-#endif
-#ifndef IDHMC_M2_OCC
-#define IDHMC_M2_OCC (NCH <= 2 ? (SINGLE && TR == 1 ? 3 : 2) : 1)
-#endif
-#ifndef IDHMC_M2_W
-#define IDHMC_M2_W 4
-#endif
-#ifndef IDHMC_M2_PD
-#define IDHMC_M2_PD (NCH <= 2 ? 4 : 2)
-#endif
 #ifdef IDHMC_STAMPS      // diagnostic build (tools/stamps.sh): wall-clock (100 MHz) phase sums of wavefront 0 into total_steps[2..]
 #define DSTAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); if (tid == 0) atomicAdd(s.total_steps + 2 + (i), t_ - st_t); st_t = t_; } while (0)
 #else
@@ -45,7 +32,7 @@ IDHMC_DEV double dpp_xor_add(double v, int m) { return v + __shfl_xor(v, m, 64);
 template <int NCH, bool SINGLE = false, int TR = 1> struct MfmaDims {
     static constexpr int L = 128 * NCH, KB = L / 4, DS = L + 2, ROWS = 16 * TR;
     static constexpr size_t lds_doubles = ROWS * DS + 4 * ROWS * 2;
-    static constexpr int kWavesPerSimd = IDHMC_M2_OCC;
+    static constexpr int kWavesPerSimd = NCH <= 2 ? (SINGLE && TR == 1 ? 3 : 2) : 1;
 };
 
 template <int NCH, bool SINGLE, int TR>
@@ -55,7 +42,7 @@ __global__ __launch_bounds__(256, (MfmaDims<NCH, SINGLE, TR>::kWavesPerSimd)) vo
     // SINGLE: one step per launch; q' leaves in loop A (under the matrix phase) and its registers are free from there on
     const int n_steps = SINGLE ? 1 : n_steps_arg;
     using M = MfmaDims<NCH, SINGLE, TR>;
-    constexpr int L = M::L, KB = M::KB, DS = M::DS, ROWS = M::ROWS, PD = IDHMC_M2_PD;
+    constexpr int L = M::L, KB = M::KB, DS = M::DS, ROWS = M::ROWS, PD = NCH <= 2 ? 4 : 2;
     static_assert(KB % PD == 0 && (KB & (KB - 1)) == 0, "prefetch depth must divide the k-block count (a power of two)");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *dT = lds;                 // [ROWS chains][DS] tile of d = q' - mu
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(256, (MfmaDims<NCH, SINGLE, TR>::kWavesPerSimd)) vo
         if constexpr (SINGLE) {
             // ---- load + loop A, one chain quad (this lane's row `reg` of row tile t) at a time, the loads of W quads in
             // flight: the whole tile at once would hold 3 vectors x 16 TR rows in registers next to the matrix phase's own
-            constexpr int NQ = 4 * TR, W = IDHMC_M2_W;
+            constexpr int NQ = 4 * TR, W = 4;
             v2d gb[W][NCH], pb[W][NCH], qb[W][NCH];
 #pragma unroll
             for (int i = 0; i < W; ++i)
@@ -204,21 +191,14 @@ __global__ __launch_bounds__(256, (MfmaDims<NCH, SINGLE, TR>::kWavesPerSimd)) vo
                     for (int j = 0; j < NCH; ++j)
 #pragma unroll
                         for (int t = 0; t < TR; ++t) {
-#ifdef IDHMC_DX2      // (cost attribution) no matrix-core work: one fma per operand instead
-                            acc[t][j][0][0] = dfma(a[t], bq[u][j].x, acc[t][j][0][0]);
-                            acc[t][j][1][0] = dfma(a[t], bq[u][j].y, acc[t][j][1][0]);
-#else
                             acc[t][j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], bq[u][j].x, acc[t][j][0], 0, 0, 0);
                             acc[t][j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t], bq[u][j].y, acc[t][j][1], 0, 0, 0);
-#endif
                         }
                     // unconditional (the last trips wrap around and are discarded): a branch here makes the
                     // compiler drain all outstanding loads at every trip
-#ifndef IDHMC_DX1      // (cost attribution, results wrong on purpose) IDHMC_DX1: the matrix is fetched once, not per k-block
 #pragma unroll
                     for (int j = 0; j < NCH; ++j)
                         bq[u][j] = ld2(rP, pvo + 1024 * j, 4 * ((kb + PD) & (KB - 1)) * L * 8);
-#endif
                     sched_fence();
                 }
             }
@@ -292,14 +272,13 @@ __global__ __launch_bounds__(256, (MfmaDims<NCH, SINGLE, TR>::kWavesPerSimd)) vo
     }
 }
 
-// tile_begin / tile_end count 16-chain tiles; a range handed to the 32-chain form must begin at an even tile
+// tile_begin / tile_end count 16-chain tiles
 template <int NCH>
 static hipError_t launch_mfma_t(const DevState &s, double eps, int own, int n_steps, int64_t tile_begin, int64_t tile_end,
                                 int64_t max_grid, hipStream_t st)
 {
-    constexpr int TR1 = (NCH <= 2 && IDHMC_M2_TR == 2) ? 2 : 1;     // row tiles per workgroup of the single-step form
     using M = MfmaDims<NCH, false, 1>;
-    using M1 = MfmaDims<NCH, true, TR1>;
+    using M1 = MfmaDims<NCH, true, 1>;
     static bool attr_done[64] = {};  // per instantiation and device (the attribute is per device)
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -307,21 +286,19 @@ static hipError_t launch_mfma_t(const DevState &s, double eps, int own, int n_st
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leapfrog_dense_mfma<NCH, false, 1>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(M::lds_doubles * sizeof(double)));
         if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leapfrog_dense_mfma<NCH, true, TR1>),
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_leapfrog_dense_mfma<NCH, true, 1>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(M1::lds_doubles * sizeof(double)));
         if (e != hipSuccess) return e;
         attr_done[dev & 63] = true;
     }
     if (n_steps == 1) {
-        if (tile_begin % TR1) return hipErrorInvalidValue;
-        const int64_t tb = tile_begin / TR1, te = (tile_end + TR1 - 1) / TR1;
-        int64_t grid = te - tb;
+        int64_t grid = tile_end - tile_begin;
         const int64_t resident = 256 * M1::kWavesPerSimd;
         if (grid > resident) grid = resident;
         if (max_grid > 0 && grid > max_grid) grid = max_grid;
         if (grid < 1) return hipSuccess;
-        hipLaunchKernelGGL((k_leapfrog_dense_mfma<NCH, true, TR1>), dim3((unsigned)grid), dim3(256), M1::lds_doubles * sizeof(double),
-                           st, s, eps, own, n_steps, tb, te);
+        hipLaunchKernelGGL((k_leapfrog_dense_mfma<NCH, true, 1>), dim3((unsigned)grid), dim3(256), M1::lds_doubles * sizeof(double),
+                           st, s, eps, own, n_steps, tile_begin, tile_end);
     } else {
         int64_t grid = tile_end - tile_begin;
         const int64_t resident = 256 * M::kWavesPerSimd;
@@ -343,7 +320,6 @@ hipError_t launch_leapfrog_dense_mfma_tiles(const DevState &s, double eps, int o
     if (s.nch == 4) return launch_mfma_t<4>(s, eps, own, n_steps, tile_begin, tile_end, max_grid, st);
     return hipErrorNotSupported;
 }
-int dense_mfma_tile_align(const DevState &s) { return (s.nch <= 2 && IDHMC_M2_TR == 2) ? 2 : 1; }
 hipError_t launch_leapfrog_dense_mfma(const DevState &s, double eps, int own, int n_steps, hipStream_t st)
 {
     return launch_leapfrog_dense_mfma_tiles(s, eps, own, n_steps, 0, (s.C + 15) / 16, 0, st);

@@ -56,9 +56,7 @@ IDHMC_DEV __amdgpu_buffer_rsrc_t buf_rsrc(const void *p)
     void *u = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
     return __builtin_amdgcn_make_buffer_rsrc(u, 0, -1, 0x00020000);   // raw buffer, 4 GiB window, DATA_FORMAT_32 (gfx9 family)
 }
-// AUX: the instruction's cache-policy bits; kAuxNt (nt) marks data that is touched once per launch (the chain state,
-// the regeneration checkpoints) so that it does not displace the tree arena from L2 / Infinity Cache
-constexpr int kAuxNt = 2;
+// AUX: the instruction's cache-policy bits
 template <int NCH, int AUX = 0>
 IDHMC_DEV Vec<NCH> bload(const double *base, int lane)
 {
@@ -236,15 +234,12 @@ struct CoopRounds {
         }
     }
 };
-#ifndef IDHMC_COOP_PD
-#define IDHMC_COOP_PD 4
-#endif
 template <int NCH>
 struct DenseMvnCoop : CoopRounds<DenseMvnCoop<NCH>> {
     static constexpr bool kHasParams = true;
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = true;
-    static constexpr int kWaves = 16, L = 128 * NCH, DS = L + 2, KB = L / 4, kPairs = L / 32, kPrefetch = IDHMC_COOP_PD;
+    static constexpr int kWaves = 16, L = 128 * NCH, DS = L + 2, KB = L / 4, kPairs = L / 32, kPrefetch = 4;
     static constexpr int kTileDoubles = 16 * DS;
     static constexpr int kLdsDoubles = 2 * kTileDoubles;   // the d tile and the T tile
     typedef v2d Prefetch[kPrefetch];
@@ -269,23 +264,9 @@ struct DenseMvnCoop : CoopRounds<DenseMvnCoop<NCH>> {
     // odd columns (L2 -> CU bandwidth bounds this phase: 16-byte requests move it ~30 % faster than 8-byte ones).
     // The first k-blocks do not depend on the tile: requested before barrier A, their L2 latency runs under the
     // wait for the slowest wavefront.
-#ifndef IDHMC_COOP_SPLIT16
-#define IDHMC_COOP_SPLIT16 0
-#endif
-    // IDHMC_COOP_SPLIT16 (L = 256 only): all 16 wavefronts multiply, 16 columns (one MFMA tile) each, instead of 8 wavefronts with 32
-    // columns while the other 8 wait at the barrier -- same k order per output element, so the same bits
-    static constexpr bool kSplit16 = IDHMC_COOP_SPLIT16 != 0 && L == 256;
     IDHMC_DEV void prefetch(Prefetch &bq) const
     {
         static_assert(kPairs <= kWaves, "one 32-column block per wavefront: L <= 512");
-        if constexpr (kSplit16) {
-            const __amdgpu_buffer_rsrc_t rP = buf_rsrc(prec);
-            const int vo = ((lane >> 4) * L + 16 * wv + (lane & 15)) * 8;
-#pragma unroll
-            for (int u = 0; u < kPrefetch; ++u)
-                bq[u].x = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rP, vo, 4 * u * L * 8, 0));
-            return;
-        }
         static_assert((KB & (KB - 1)) == 0 && KB % kPrefetch == 0, "k-block count: power of two, multiple of the prefetch depth");
         if (wv < kPairs) {
             const __amdgpu_buffer_rsrc_t rP = buf_rsrc(prec);
@@ -305,26 +286,6 @@ struct DenseMvnCoop : CoopRounds<DenseMvnCoop<NCH>> {
         asm volatile("" : "+v"(ln));
         const int kk = ln >> 4, jj = ln & 15;
         v4d acc0 = v4d{0.0, 0.0, 0.0, 0.0}, acc1 = v4d{0.0, 0.0, 0.0, 0.0};
-        if constexpr (kSplit16) {
-            const __amdgpu_buffer_rsrc_t rP = buf_rsrc(prec);
-            const int vo = (kk * L + 16 * wv + jj) * 8;
-            const double *ap = tile + jj * DS + kk;
-            __builtin_amdgcn_s_waitcnt(0x0F70);
-#pragma unroll 1
-            for (int kb0 = 0; kb0 < KB; kb0 += kPrefetch) {
-#pragma unroll
-                for (int u = 0; u < kPrefetch; ++u) {
-                    const int kb = kb0 + u;
-                    const double a = ap[4 * kb];
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq[u].x, acc0, 0, 0, 0);
-                    bq[u].x = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rP, vo, 4 * ((kb + kPrefetch) & (KB - 1)) * L * 8, 0));
-                }
-            }
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) tile[kTileDoubles + (kk + 4 * reg) * DS + 16 * wv + jj] = acc0[reg];
-            __syncthreads();                               // barrier C
-            return;
-        }
         if (wv < kPairs) {
             const __amdgpu_buffer_rsrc_t rP = buf_rsrc(prec);
             const int vo = (kk * L + 32 * wv + 2 * jj) * 8;
@@ -338,19 +299,12 @@ struct DenseMvnCoop : CoopRounds<DenseMvnCoop<NCH>> {
                 for (int u = 0; u < kPrefetch; ++u) {
                     const int kb = kb0 + u;
                     const double a = ap[4 * kb];
-#ifdef IDHMC_CX2      // (cost attribution, results wrong on purpose) no matrix-core work
-                    acc0[0] = dfma(a, bq[u].x, acc0[0]);
-                    acc1[0] = dfma(a, bq[u].y, acc1[0]);
-#else
                     acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq[u].x, acc0, 0, 0, 0);
                     acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq[u].y, acc1, 0, 0, 0);
-#endif
                     // unconditional (the last trips wrap around and are discarded): a branch here makes the
                     // compiler drain all outstanding loads at every trip
-#ifndef IDHMC_CX1     // (cost attribution) the matrix is fetched once per round, not per k-block
                     bq[u] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(
                         rP, vo, 4 * ((kb + kPrefetch) & (KB - 1)) * L * 8, 0));
-#endif
                 }
             }
         }
@@ -556,9 +510,7 @@ IDHMC_DEV void leapfrog_step(const Model &mdl, const Metric &minv, double eps, V
 // Gaussians: 2 flops per element): grad l(q) is re-derived from q at the start of the step, which gives
 // the very bits the previous step computed, and is not returned.  Saves a third of the phase point's
 // registers in the NUTS kernel.
-// FENCE: software pipeline over the 128-element chunks for parameters that live in LDS (see below); with the
-// parameters in registers (register-rich NUTS form) the scheduler is left free to interleave the 2 NCH element chains.
-template <int NCH, bool FENCE = true, class Model, class Metric>
+template <int NCH, class Model, class Metric>
 IDHMC_DEV void leapfrog_step_regrad(const Model &mdl, const Metric &minv, double eps, Vec<NCH> &q,
                                     Vec<NCH> &p, double &lq, double &K)
 {
@@ -567,7 +519,7 @@ IDHMC_DEV void leapfrog_step_regrad(const Model &mdl, const Metric &minv, double
     // software pipeline over the 128-element chunks: the (LDS) parameter reads of chunk j+1 are issued
     // before the arithmetic of chunk j; the scheduling fences keep the compiler from hoisting all
     // 3*NCH reads to the top (96 VGPRs at D = 1024), which is what spills this kernel otherwise.
-    if (FENCE) sched_fence();
+    sched_fence();
     double2 mu_n = mdl.mu(0), tau_n = mdl.tau(0), mv_n = minv.get(0);
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
@@ -586,14 +538,14 @@ IDHMC_DEV void leapfrog_step_regrad(const Model &mdl, const Metric &minv, double
         k1 = dfma(py * mv.y, py, k1);
         q.c[j] = make_double2(qx, qy);
         p.c[j] = make_double2(px, py);
-        if (FENCE) sched_fence();
+        sched_fence();
     }
     double sl, sk;
     wave_sum2(l0, l1, k0, k1, sl, sk);
     lq = -0.5 * sl;
     lq = dfinite(lq) ? lq : -kInf;
     K = 0.5 * sk;
-    if (FENCE) sched_fence();
+    sched_fence();
 }
 
 // rand_p! (src/kinetic_energy.jl:63): p = W .* randn, pads stay zero

@@ -3,7 +3,6 @@
 #include "idhmc_device.hpp"
 #include "idhmc_internal.hpp"
 #include "idhmc_xchg.hpp"
-#include <cstdlib>
 
 namespace idhmc {
 
@@ -492,7 +491,7 @@ __global__ void k_status_max(DevState s, int32_t *out)
 static constexpr int kMaxStreamBlocks = 256 * 16;
 
 hipError_t launch_eval_dense(const DevState &s, hipStream_t st);
-hipError_t launch_leapfrog_dense(const DevState &s, double eps, int own, int n_steps, hipStream_t st);
+hipError_t launch_leapfrog_dense(const DevState &s, double eps, int own, int n_steps, int mfma, hipStream_t st);
 hipError_t launch_random_position_dense(const DevState &s, hipStream_t st);
 
 hipError_t launch_eval(const DevState &s, hipStream_t st)
@@ -525,22 +524,15 @@ hipError_t launch_logdensity(const DevState &s, hipStream_t st)
     IDHMC_DISPATCH_NCH(s.nch, hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(256), 0, st, s, 0u, 0));
     return hipGetLastError();
 }
-static int leapfrog_blocks(int64_t C)
+hipError_t launch_leapfrog(const DevState &s, double eps, int own, int n_steps, int regrad, int dense_mfma, hipStream_t st)
 {
-    int cap = 0;
-    if (const char *e = getenv("IDHMC_LF_BLOCKS")) cap = atoi(e);
-    return blocks_for(C, 4, cap > 0 ? cap : (1 << 30));
-}
-hipError_t launch_leapfrog(const DevState &s, double eps, int own, int n_steps, int regrad, hipStream_t st)
-{
-    if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_leapfrog_dense(s, eps, own, n_steps, st);
+    if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_leapfrog_dense(s, eps, own, n_steps, dense_mfma, st);
     if (s.model == IDHMC_MODEL_CUSTOM || s.model == IDHMC_MODEL_GLM) return launch_leapfrog_jit(s, eps, own, n_steps, st);
     if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_leapfrog_logistic(s, eps, own, n_steps, st);
     if (n_steps == 1) {
-        const int grid = leapfrog_blocks(s.C);
-        // measured on MI355X (tools/tune_leapfrog.py, 65 536 chains x 1024): diag 6.03 TB/s with 3, iso 5.89 TB/s with 2
+        const int grid = blocks_for(s.C, 4, 1 << 30);     // one block per four chains, uncapped
+        // measured on MI355X (65 536 chains x 1024): diag 6.03 TB/s with 3, iso 5.89 TB/s with 2
         int var = (s.model == IDHMC_MODEL_ISO_GAUSSIAN) ? 2 : 3;
-        if (const char *e = getenv("IDHMC_LF_VARIANT")) var = 2 | (atoi(e) & 1);
         if (regrad) var = 7;
         if (s.nch > 8) var = regrad ? 6 : 2;      // L = 2048: preloading the whole chain would spill, chunk by chunk instead
 #define IDHMC_LF1(V)                                                                                          \

@@ -2,7 +2,6 @@
 // initial-stepsize search (templates in idhmc_nuts_kernel.hpp) for the built-in densities.
 #include "idhmc_nuts_kernel.hpp"
 #include "idhmc_optimum.hpp"
-#include <cstdlib>
 
 namespace idhmc {
 
@@ -14,12 +13,8 @@ int arena_vectors(int max_depth, int model, int L)
     return n > 2 * kLbfgsR ? n : 2 * kLbfgsR;
 }
 // the dense MVN runs the workgroup-cooperative matrix-core gradient (DenseMvnCoop) when one 16-column tile per
-// wavefront covers the matrix (L <= 256); IDHMC_DENSE_COOP=0 selects the per-wave GEMV (experiments)
-static bool dense_coop(int nch)
-{
-    static const bool off = [] { const char *e = getenv("IDHMC_DENSE_COOP"); return e && e[0] == '0'; }();
-    return nch <= 2 && !off;
-}
+// wavefront covers the matrix (L <= 256), the per-wave GEMV (DenseMvn) above that
+static bool dense_coop(int nch) { return nch <= 2; }
 int nuts_waves_per_block(int nch, int model, int shared_metric)
 {
     return nuts_waves(nch, model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN,
@@ -71,13 +66,12 @@ hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wi
     if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_nuts_logistic(s, iter, flags, grid, st);
     if (s.model == IDHMC_MODEL_DENSE_MVN) {
         IDHMC_DISPATCH_NCH_POW2(s.nch, {
-            if constexpr (NCH <= 2) {
-                if (dense_coop(NCH))
-                    return shared ? launch_nuts_t<NCH, DenseMvnCoop<NCH>, true>(s, iter, flags, grid, st)
-                                  : launch_nuts_t<NCH, DenseMvnCoop<NCH>, false>(s, iter, flags, grid, st);
-            }
-            return shared ? launch_nuts_t<NCH, DenseMvn<NCH>, true>(s, iter, flags, grid, st)
-                          : launch_nuts_t<NCH, DenseMvn<NCH>, false>(s, iter, flags, grid, st);
+            if constexpr (NCH <= 2)
+                return shared ? launch_nuts_t<NCH, DenseMvnCoop<NCH>, true>(s, iter, flags, grid, st)
+                              : launch_nuts_t<NCH, DenseMvnCoop<NCH>, false>(s, iter, flags, grid, st);
+            else
+                return shared ? launch_nuts_t<NCH, DenseMvn<NCH>, true>(s, iter, flags, grid, st)
+                              : launch_nuts_t<NCH, DenseMvn<NCH>, false>(s, iter, flags, grid, st);
         });
         return hipErrorInvalidValue;
     }

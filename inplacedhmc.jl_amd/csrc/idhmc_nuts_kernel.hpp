@@ -36,20 +36,14 @@ constexpr int kMaxDepth = 16;
 // (rocprofv3 PMC at D = 1024, depth 7: 9 KB written per leaf, 3.2 TB/s); the regeneration costs ~25 % more leapfrogs.
 // Separable densities only: a general density's leapfrog is expensive (the cooperative dense gradient would also
 // wait for the longest regeneration of its 16-chain group: measured 2.5e8 -> 1.7e8), so it stores its candidates.
-#ifndef IDHMC_ZETA_REGENERATE
-#define IDHMC_ZETA_REGENERATE 1
-#endif
-__host__ __device__ constexpr bool nuts_regenerate(bool separable) { return IDHMC_ZETA_REGENERATE != 0 && separable; }
+__host__ __device__ constexpr bool nuts_regenerate(bool separable) { return separable; }
 // Round 3: with regeneration a proposal candidate is a position on the trajectory, so NOTHING the tree's scalar bookkeeping
 // computes (the log-sum-exps of the weights and of the acceptance statistic, the multinomial picks and their exponential draws)
 // feeds back into the trajectory: tree shape, turn tests and divergences depend on the vectors alone.  The kernel therefore
 // only LOGS every leaf's Delta (8 bytes) while it builds the tree and evaluates the bookkeeping afterwards, in the order the
 // reference prescribes but 64 leaves per pass -- one lane per leaf (nuts_replay below).  Sequentially it was ~176 vector
 // instructions per merge, i.e. per leaf, executed identically by all 64 lanes: a quarter of the kernel's instructions.
-#ifndef IDHMC_NUTS_DEFER
-#define IDHMC_NUTS_DEFER 1
-#endif
-__host__ __device__ constexpr bool nuts_defer(bool separable) { return IDHMC_NUTS_DEFER != 0 && nuts_regenerate(separable); }
+__host__ __device__ constexpr bool nuts_defer(bool separable) { return nuts_regenerate(separable); }
 // vectors of L doubles that hold one double per possible leaf of a transition (2^max_depth - 1 of them)
 __host__ __device__ constexpr int nuts_dl_vectors(int max_depth, int L) { return ((1 << max_depth) + L - 1) / L; }
 // Wavefronts per workgroup (one workgroup per CU): the phase point of a chain lives in VGPRs, so the register
@@ -65,17 +59,13 @@ __host__ __device__ constexpr int nuts_dl_vectors(int max_depth, int L) { return
 // A general density keeps 4:
 // the dense MVN streams its 512 KiB matrix through L1 per gradient, and 8 concurrent streams per CU thrash it
 // (63 M/s with 4 wavefronts, 36 M/s with 8).  A cooperative density (DenseMvnCoop, idhmc_device.hpp) runs 16: one per
-// chain of its 16-row matrix-core tile.  IDHMC_NUTS_WAVES forces one value for the others (experiments).
+// chain of its 16-row matrix-core tile.
 // L = 2048 with a per-chain metric: 3 (mu, tau and three wavefronts' p_prev and M^-1 are 128 KB of LDS; four are 160).
 __host__ __device__ constexpr int nuts_waves(int nch, bool separable, bool cooperative = false, bool shared_metric = true)
 {
     if (cooperative) return 16;
     if (nch > 8 && !shared_metric && 10 * nch > 152) return 3;     // mu, tau + 4 x (p_prev, M^-1) must fit 152 KB
-#ifdef IDHMC_NUTS_WAVES
-    return IDHMC_NUTS_WAVES;
-#else
     return separable ? (nch <= 3 ? 16 : (nch <= 4 ? 12 : 4)) : 4;      // L = 512: three per SIMD since round 3 (167 registers): +6 % over two
-#endif
 }
 
 // Separable densities keep the level-1 sub-tree summary (rho and p#_first) in LDS next to the level-0 one: at
@@ -90,17 +80,11 @@ __host__ __device__ constexpr int nuts_waves(int nch, bool separable, bool coope
 // merge (32 VGPRs at L = 1024, live only while rho / p#_first of a merge are not).  The vector this frees per wavefront holds
 // the level-1 p#_first, which was the largest single source of arena traffic (one 8 KB store and one 8 KB load per four leaves:
 // profiles/r03_nuts_bytes_by_source.json).  The register-rich form keeps its own layout.
-#ifndef IDHMC_NUTS_PREV_REGS
-#define IDHMC_NUTS_PREV_REGS 1
-#endif
 // The cooperative dense density takes both over (round 3): its merges of level >= 1 fetched rho and p#_first from the arena one level after
 // the other -- the slowest of a workgroup's 16 wavefronts sets the pace of every gradient round -- and a CU has the LDS for the level-1 pair.
-#ifndef IDHMC_COOP_PREV_REGS
-#define IDHMC_COOP_PREV_REGS 1
-#endif
 __host__ __device__ constexpr bool nuts_prev_regs(bool separable, bool cooperative, bool rich)
 {
-    return IDHMC_NUTS_PREV_REGS != 0 && !rich && ((separable && !cooperative) || (cooperative && IDHMC_COOP_PREV_REGS != 0));
+    return !rich && (separable || cooperative);
 }
 // coop_lds: doubles of LDS the cooperative density's gradient rounds use (Model::kLdsDoubles), 0 for every other density
 __host__ __device__ constexpr int nuts_l1_lds(int nch, bool separable, int waves, bool lds_params = true, bool shared_metric = true,
@@ -121,42 +105,26 @@ __host__ __device__ constexpr int nuts_l1_lds(int nch, bool separable, int waves
 // one wavefront per SIMD (level-1 summary in LDS, inlined merge scalars; best for adapted chains, depth ~4) and a
 // WIDE one with two per SIMD (256 registers, level-1 summary in the arena; 11-18 % faster on deep trees, 3-12 %
 // slower on shallow ones).
-#ifndef IDHMC_WIDE_MAX_NCH
-#define IDHMC_WIDE_MAX_NCH 8
-#endif
 __host__ __device__ constexpr int nuts_wide_waves(int nch, bool separable, bool cooperative = false)
 {
-    return (separable && !cooperative && nch > 4 && nch <= IDHMC_WIDE_MAX_NCH) ? 8 : 0;     // 0: no wide form
+    return (separable && !cooperative && nch > 4 && nch <= 8) ? 8 : 0;     // 0: no wide form
 }
 
 // "Register-rich" form: separable density, one wavefront per SIMD (4 per workgroup), L <= 1024.  Each wavefront owns
-// the SIMD's whole 512-register file, so everything that is constant over a transition -- mu, tau and M^-1 (shared
-// or per chain) -- lives in VGPRs (96 at L = 1024) instead of LDS: the leapfrog reads no memory at all and needs no
-// scheduling fences, and the LDS they occupied holds deeper sub-tree summaries instead.
-#ifndef IDHMC_NUTS_RICH
-#define IDHMC_NUTS_RICH 1
-#endif
+// the SIMD's whole 512-register file, so the whole-tree rho and the level-2 p#_first live in registers (the compiler
+// parks them in AGPRs) and the level-1 summary and level-2 rho in LDS; mu, tau and M^-1 are staged in LDS as in the
+// other forms.
 __host__ __device__ constexpr bool nuts_rich(int nch, bool separable, bool cooperative, int waves)
 {
-    return IDHMC_NUTS_RICH != 0 && separable && !cooperative && waves == 4 && nch <= 8;
-}
-// within the register-rich form: mu, tau, M^-1 in VGPRs (1) or staged in LDS like the other forms (0)
-#ifndef IDHMC_NUTS_CONST_REGS
-#define IDHMC_NUTS_CONST_REGS 0
-#endif
-__host__ __device__ constexpr bool nuts_const_regs(int nch, bool separable, bool cooperative, int waves)
-{
-    return IDHMC_NUTS_CONST_REGS != 0 && nuts_rich(nch, separable, cooperative, waves);
+    return separable && !cooperative && waves == 4 && nch <= 8;
 }
 // register-rich form: does rho of the level-2 summary fit in LDS next to the rest (else it stays in registers like the
 // level-2 p#_first)?  Budget: 152 KB of the CU's 160 (the per-level scalars and the compiler's own use take the rest).
-__host__ __device__ constexpr bool nuts_l2_lds(int nch, bool lds_params, bool shared_metric, bool const_regs)
+__host__ __device__ constexpr bool nuts_l2_lds(int nch, bool lds_params, bool shared_metric)
 {
-    return ((const_regs ? 0 : (lds_params ? 2 : 0) + (shared_metric ? 1 : 0)) + 4 * (4 + ((const_regs || shared_metric) ? 0 : 1))) * nch <= 152;
+    return ((lds_params ? 2 : 0) + (shared_metric ? 1 : 0) + 4 * (4 + (shared_metric ? 0 : 1))) * nch <= 152;
 }
 template <bool B> struct BoolC { static constexpr bool value = B; };
-template <bool C, class A, class B> struct CondT { typedef A type; };
-template <class A, class B> struct CondT<false, A, B> { typedef B type; };
 
 // arena vector indices (each vector = L doubles); MD = max_depth
 struct ArenaMap {
@@ -183,14 +151,7 @@ struct ArenaMap {
 // Doublings of at least 2^kCheckpointDepth leaves (16: measured 2..5, within 2 % of each other) leave their starting phase point in the arena (2 vector stores): the
 // winner of the multinomial sampling lies in the last doubling with probability >= 1/2, and regenerating it from there
 // takes ~2^(d-1) leapfrogs instead of ~1.5 * 2^d from the starting point (measured: see DESIGN 3.3).
-#ifndef IDHMC_NT_STATE
-#define IDHMC_NT_STATE 0
-#endif
-constexpr int kNt = IDHMC_NT_STATE ? kAuxNt : 0;
-#ifndef IDHMC_CHECKPOINT_DEPTH
-#define IDHMC_CHECKPOINT_DEPTH 4
-#endif
-constexpr int kCheckpointDepth = IDHMC_CHECKPOINT_DEPTH;
+constexpr int kCheckpointDepth = 4;
 
 struct AccStat {  // reference AcceptanceStatistic, src/NUTS.jl:58-66
     double lsa;
@@ -230,9 +191,6 @@ IDHMC_DEV AccStat combine_acc(AccStat a, AccStat b)  // src/NUTS.jl:68-70
 struct MergeScalars { double lsa, omega; };
 __device__ __forceinline__ MergeScalars nuts_merge_scalars_body(double lsa_a, double lsa_b, double om_a, double om_b)
 {
-#ifdef IDHMC_X1
-    { MergeScalars o; o.lsa = lsa_a < lsa_b ? lsa_b : lsa_a; o.omega = (om_a < om_b ? om_b : om_a) + 0.5; return o; }
-#endif
     const bool odd = (threadIdx.x & 1) != 0;
     const double x = odd ? om_a : lsa_a, y = odd ? om_b : lsa_b;
     // dlogaddexp(x, y), opened up (idhmc_math.hpp)
@@ -372,9 +330,8 @@ __host__ __device__ inline size_t nuts_lds_doubles(int L, bool lds_params, bool 
     const bool cooperative = coop_lds > 0;
     if (waves == 0) waves = nuts_waves(L / 128, separable, cooperative, shared_metric);
     if (nuts_rich(L / 128, separable, cooperative, waves)) {    // per wavefront: p_prev, the level-1 summary, rho of level 2
-        const bool cr = nuts_const_regs(L / 128, separable, cooperative, waves);
-        const int l2 = nuts_l2_lds(L / 128, lds_params, shared_metric, cr) ? 1 : 0;
-        return (size_t)L * (waves * (3 + l2 + ((cr || shared_metric) ? 0 : 1)) + (cr ? 0 : (lds_params ? 2 : 0) + (shared_metric ? 1 : 0)));
+        const int l2 = nuts_l2_lds(L / 128, lds_params, shared_metric) ? 1 : 0;
+        return (size_t)L * (waves * (3 + l2 + (shared_metric ? 0 : 1)) + (lds_params ? 2 : 0) + (shared_metric ? 1 : 0));
     }
     // per wavefront: [p_prev, or one scratch vector when nothing else is there] [per-chain M^-1] [general: staging] [level-1 rho, p#]
     const bool pr = nuts_prev_regs(separable, cooperative, false);
@@ -476,27 +433,16 @@ IDHMC_DEV uint32_t nuts_peek_iter(const uint32_t *word)
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-#ifndef IDHMC_COOP_REFILL
-#define IDHMC_COOP_REFILL 1
-#endif
-#ifndef IDHMC_COOP_PREFETCH
-#define IDHMC_COOP_PREFETCH 0
-#endif
 template <int NCH, class Model, bool SHARED_METRIC,
           int WAVES = nuts_waves(NCH, Model::kSeparable, Model::kCooperative, SHARED_METRIC)>
-#ifdef IDHMC_NUTS_VGPR_CAP     // experiments: how many registers does the kernel really need?
-__attribute__((amdgpu_num_vgpr(IDHMC_NUTS_VGPR_CAP)))
-#endif
 __global__ __launch_bounds__(WAVES * 64, (WAVES + 3) / 4)
 void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
 {
     constexpr int kNutsWaves = WAVES;
     constexpr bool kCoop = Model::kCooperative;
-    constexpr bool kCoopRefill = IDHMC_COOP_REFILL != 0;
-    constexpr int kCoopPrefetch = IDHMC_COOP_PREFETCH;      // levels of arena summaries (2, 3) requested ahead of the gradient round
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ LevelScalars Sall[kNutsWaves];
-    __shared__ int coop_ctl[2];           // cooperative density: {chain group, chains of it still alive}
+    __shared__ int coop_ctl[2];           // cooperative density: [1] wavefronts that may still request a gradient ([0] unused: keeps the LDS layout)
     // Counters every chain adds to (leapfrog steps; the 39 scalar diagnostics counters) are summed per workgroup here and reach the global
     // words once, when the workgroup leaves: 65 536 atomics per launch on ONE address cost ~0.2 ms each hot address (3.5 -> 2.5 ms per
     // transition with IDHMC_T_ACCUM_DIAG at configs[2], tools/bench_accum.py).  Integers: the order of the additions is immaterial.
@@ -515,37 +461,26 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
     double *cursor = lds;
     Model mdl;
     constexpr bool kRich = nuts_rich(NCH, Model::kSeparable, kCoop, kNutsWaves);
-    constexpr bool kConstRegs = nuts_const_regs(NCH, Model::kSeparable, kCoop, kNutsWaves);
     constexpr bool kPrevRegs = nuts_prev_regs(Model::kSeparable, kCoop, kRich);     // level-0 summary in registers, not LDS
     constexpr int kL1N = kRich ? 2 : nuts_l1_lds(NCH, Model::kSeparable, kNutsWaves, Model::kHasParams && Model::kSeparable, SHARED_METRIC, kPrevRegs,
                                                     coop_lds_doubles<Model>());
-#ifdef IDHMC_X3
-    constexpr bool kL1Rho = kL1N >= 1, kL1Pf = kL1N >= 1;
-#else
     constexpr bool kL1Rho = kL1N >= 1, kL1Pf = kL1N >= 2;     // level-1 summary in LDS: rho / p#_first
-#endif
     constexpr bool kL2 = kRich;    // level-2 summary on chip as well: rho in LDS, p#_first in registers
     // LDS vectors per wavefront: [p_prev | scratch], [per-chain M^-1], [general density: staging], [level-1 rho, p#], [level-2 rho];
     // kPrevRegs: no p_prev vector; the momentum refresh's scratch is then the level-1 rho slot (or one vector of its own)
-    constexpr int kMetricVec = (SHARED_METRIC || kConstRegs) ? 0 : 1;
-    constexpr bool kL2Lds = kL2 && nuts_l2_lds(NCH, Model::kHasParams, SHARED_METRIC, kConstRegs);
+    constexpr int kMetricVec = SHARED_METRIC ? 0 : 1;
+    constexpr bool kL2Lds = kL2 && nuts_l2_lds(NCH, Model::kHasParams, SHARED_METRIC);
     constexpr int kFirstVec = kPrevRegs ? (kL1N == 0 ? 1 : 0) : 1;
     constexpr int kPerWave = kFirstVec + kMetricVec + ((Model::kSeparable || kCoop) ? 0 : 1) + kL1N + (kL2Lds ? 1 : 0);
     if constexpr (Model::kHasParams && Model::kSeparable) {
-        if constexpr (kConstRegs) {
-            mdl.load(s.mu, s.tau, lane);
-        } else {
-            double *lmu = cursor, *ltau = cursor + L;
-            cursor += 2 * L;
-            for (int i = threadIdx.x; i < L; i += kNutsWaves * 64) { lmu[i] = s.mu[i]; ltau[i] = s.tau[i]; }
-            mdl.m = reinterpret_cast<const double2 *>(lmu) + lane;
-            mdl.t = reinterpret_cast<const double2 *>(ltau) + lane;
-        }
+        double *lmu = cursor, *ltau = cursor + L;
+        cursor += 2 * L;
+        for (int i = threadIdx.x; i < L; i += kNutsWaves * 64) { lmu[i] = s.mu[i]; ltau[i] = s.tau[i]; }
+        mdl.m = reinterpret_cast<const double2 *>(lmu) + lane;
+        mdl.t = reinterpret_cast<const double2 *>(ltau) + lane;
     }
-    typename CondT<kConstRegs, Vec<NCH>, LdsVec>::type minv;
-    if constexpr (kConstRegs) {
-        if constexpr (SHARED_METRIC) minv = bload<NCH>(s.minv, lane);
-    } else if constexpr (SHARED_METRIC) {
+    LdsVec minv;
+    if constexpr (SHARED_METRIC) {
         double *lm = cursor;
         cursor += L;
         for (int i = threadIdx.x; i < L; i += kNutsWaves * 64) lm[i] = s.minv[i];
@@ -558,15 +493,11 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
     // level-0 summary (previous leaf's momentum) where it is staged in LDS; always the momentum refresh's scratch vector
     double2 *const pprev = reinterpret_cast<double2 *>(my + (kFirstVec ? 0 : kL1At) * L) + lane;
     double2 *const l1rho = reinterpret_cast<double2 *>(my + kL1At * L) + lane;
-#ifdef IDHMC_X3
-    double2 *const l1pf = reinterpret_cast<double2 *>(my + (kL1At + (kL1N >= 2 ? 1 : 0)) * L) + lane;
-#else
     double2 *const l1pf = reinterpret_cast<double2 *>(my + (kL1At + 1) * L) + lane;
-#endif
     double2 *const l2rho = reinterpret_cast<double2 *>(my + (kL1At + 2) * L) + lane;
     if constexpr (kCoop) mdl.init(s, cursor + (size_t)kNutsWaves * (kPerWave * L), &coop_ctl[1], lane, wv);
     else if constexpr (!Model::kSeparable) mdl.init(s, my + (kFirstVec + kMetricVec) * L, lane);   // general density: one LDS vector
-    if constexpr (kCoop && kCoopRefill) { if (threadIdx.x == 0) coop_ctl[1] = kNutsWaves; }     // wavefronts that may still request a gradient
+    if constexpr (kCoop) { if (threadIdx.x == 0) coop_ctl[1] = kNutsWaves; }
     if (threadIdx.x < kWgAcc) wg_acc[threadIdx.x] = 0ull;
     __syncthreads();
 
@@ -600,12 +531,13 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             cu += part_lo;
             return true;
         };
-        if constexpr (kCoop && kCoopRefill) {
-            // Round 3: every wavefront takes its next chain by itself, as the other forms do.  In groups of 16 (below) a wavefront whose
-            // chain finished early only served the others' rounds until the slowest of the group was done -- 15 % of its cycles at
-            // configs[3] (stamps); now it goes on with a new chain at once, and the others wait only for its epilogue and
-            // prologue (no gradient request there), once per transition.  `alive` counts the wavefronts that may still request: a
-            // wavefront leaves it when the queue is empty, and serves rounds until everybody has (all leave together).
+        if constexpr (kCoop) {
+            // Round 3: every wavefront takes its next chain by itself, as the other forms do.  When the workgroup took chains in groups
+            // of 16 (one matrix-core tile, rounds 1-2) a wavefront whose chain finished early only served the others' rounds until the
+            // slowest of the group was done -- 15 % of its cycles at configs[3] (stamps); now it goes on with a new chain at
+            // once, and the others wait only for its epilogue and prologue (no gradient request there), once per transition.  `alive`
+            // counts the wavefronts that may still request: a wavefront leaves it when the queue is empty, and serves rounds until
+            // everybody has (all leave together).
             if (!ticket()) {
                 mdl.retire();
                 mdl.serve();
@@ -615,23 +547,6 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                 // the chain's previous transition may still run elsewhere: this wavefront keeps serving the group's rounds meanwhile
                 // (waiting outside them would stop the very workgroup that may hold it)
                 while (nuts_peek_iter(s.iters_done + cu) < it) mdl.serve_round();
-            }
-        } else if constexpr (kCoop) {
-            // the workgroup takes chains in groups of 16 (one matrix-core tile); the queue counts groups
-            __syncthreads();              // every wavefront is done with the previous group's control words
-            if (threadIdx.x == 0) {
-                const uint32_t grp = atomicAdd(s.queue, 1u);
-                const int64_t left = s.C - (int64_t)grp * 16;
-                coop_ctl[0] = (int)grp;
-                coop_ctl[1] = left <= 0 ? 0 : (left > 16 ? 16 : (int)left);
-            }
-            __syncthreads();
-            const uint32_t grp = (uint32_t)usi(*reinterpret_cast<volatile int *>(&coop_ctl[0]));
-            if ((int64_t)grp * 16 >= s.C) break;
-            cu = grp * 16u + (uint32_t)wv;
-            if ((int64_t)cu >= s.C) {     // ragged last group: no chain for this wavefront, it only serves
-                mdl.serve();
-                continue;
             }
         } else {
             if (!ticket()) break;
@@ -650,13 +565,10 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         BYTES_DECL;
 
         // ---- sample_tree prologue (src/NUTS.jl:251-260) -----------------------------------------
-        Vec<NCH> q = bload<NCH, kNt | kAuxFresh>(s.q + off, lane);  BYTES(0, 1);
+        Vec<NCH> q = bload<NCH, kAuxFresh>(s.q + off, lane);  BYTES(0, 1);
         Vec<NCH> g;                     // carried only for general densities (separable ones recompute it)
-        if constexpr (!Model::kSeparable) { g = bload<NCH, kNt | kAuxFresh>(s.g + off, lane); BYTES(0, 1); }
-        if constexpr (!SHARED_METRIC) {
-            if constexpr (kConstRegs) { minv = bload<NCH>(s.minv + off, lane); BYTES(0, 1); }
-            else { lds_store<NCH>(reinterpret_cast<double2 *>(my + kFirstVec * L) + lane, bload<NCH>(s.minv + off, lane)); BYTES(0, 1); }
-        }
+        if constexpr (!Model::kSeparable) { g = bload<NCH, kAuxFresh>(s.g + off, lane); BYTES(0, 1); }
+        if constexpr (!SHARED_METRIC) { lds_store<NCH>(reinterpret_cast<double2 *>(my + kFirstVec * L) + lane, bload<NCH>(s.minv + off, lane)); BYTES(0, 1); }
         Vec<NCH> p;
         if (flags & IDHMC_T_KEEP_P) {
             p = bload<NCH, kAuxFresh>(s.p + off, lane);  BYTES(0, 1);
@@ -760,8 +672,8 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             const int sgn = fwd ? 1 : -1;
             if constexpr (kRegenerate) {
                 if (depth >= kCheckpointDepth && i_start != 0) {                  // (position 0 is the state arrays themselves)
-                    bstore<NCH, kNt>(arena + (int64_t)am.ck_q(depth) * L, lane, q);
-                    bstore<NCH, kNt>(arena + (int64_t)am.ck_p(depth) * L, lane, p);  BYTES(2, 2);
+                    bstore<NCH>(arena + (int64_t)am.ck_q(depth) * L, lane, q);
+                    bstore<NCH>(arena + (int64_t)am.ck_p(depth) * L, lane, p);  BYTES(2, 2);
                     S.ck_pos[depth] = i_start;
                     ckmask |= 1u << depth;
                 }
@@ -786,27 +698,8 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                 // kPrevRegs: the momentum this leapfrog starts from is the previous leaf's -- the level-0 summary an odd leaf merges with
                 Vec<NCH> p_in;
                 if constexpr (kPrevRegs) p_in = p;
-                // cooperative density: the level-2 (and -3) summaries this leaf's cascade will merge with are requested BEFORE the gradient
-                // round, whose ~8 us hide the arena's latency (the slowest of the workgroup's 16 cascades sets the pace of every round,
-                // and some wavefront has a level >= 2 merge in 88 % of the rounds)
-                Vec<NCH> pre_rx2, pre_pf2, pre_rx3, pre_pf3;
-                bool pre2 = false, pre3 = false;
-                if constexpr (kCoop && kCoopPrefetch >= 1) {
-                    if ((n & 7) == 7 && !(kL2)) {
-                        pre_rx2 = bload<NCH>(arena + (int64_t)am.stk_rho(2) * L, lane);
-                        pre_pf2 = bload<NCH>(arena + (int64_t)am.pf(usi(S.pf[2])) * L, lane);
-                        pre2 = true;
-                    }
-                    if constexpr (kCoopPrefetch >= 2) {
-                        if ((n & 15) == 15) {
-                            pre_rx3 = bload<NCH>(arena + (int64_t)am.stk_rho(3) * L, lane);
-                            pre_pf3 = bload<NCH>(arena + (int64_t)am.pf(usi(S.pf[3])) * L, lane);
-                            pre3 = true;
-                        }
-                    }
-                }
                 if constexpr (Model::kSeparable)                                 // leapfrog, kinetic_energy.jl:126-163
-                    leapfrog_step_regrad<NCH, !kConstRegs>(mdl, minv, eps_dir, q, p, lq, K);
+                    leapfrog_step_regrad<NCH>(mdl, minv, eps_dir, q, p, lq, K);
                 else
                     leapfrog_step_general<NCH>(mdl, minv, eps_dir, q, p, g, lq, K);
                 const double pi = phase_logdensity(lq, K);
@@ -856,10 +749,6 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                                 if constexpr (kL2Lds) rx = lds_load<NCH>(l2rho);
                                 else rx = l2rho_r;
                                 pfx = l2pf_r;
-                            } else if (kCoop && kCoopPrefetch >= 1 && k == 2 && pre2) {
-                                rx = pre_rx2; pfx = pre_pf2;
-                            } else if (kCoop && kCoopPrefetch >= 2 && k == 3 && pre3) {
-                                rx = pre_rx3; pfx = pre_pf3;
                             } else {
                                 rx = bload<NCH>(arena + (int64_t)am.stk_rho(k) * L, lane);
                                 pfx = bload<NCH>(arena + (int64_t)am.pf(usi(S.pf[k])) * L, lane);  BYTES(4, 2);
@@ -882,11 +771,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                     }
                     has_rho = true;
                     double d_first, d_last;
-#ifdef IDHMC_X2
-                    d_first = 1.0 + rho.c[0].x * 1e-300; d_last = 1.0 + pfx.c[0].x * 1e-300;
-#else
                     turn_dots<NCH>(rho, pfx, p, minv, d_first, d_last);          // is_turning, NUTS.jl:148-170
-#endif
                     if (uni((d_first < 0.0) | (d_last < 0.0))) {                 // tree.jl:358
                         invalid = true;
                         term_left = i_start + sgn * (n - (2 << k) + 2);          // first node of this sub-tree
@@ -1067,11 +952,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             ri.stop_kind = stop_kind; ri.stop_n = stop_n; ri.stop_k = stop_k;
             ri.k0 = key.k0; ri.k1 = key.k1; ri.chain = key.chain; ri.iter = iter;
             __builtin_amdgcn_s_waitcnt(0);               // the leaves' Delta (stored by lane 0) are read back by every lane
-#ifdef IDHMC_X4      // (cost attribution, results wrong on purpose) no bookkeeping at all: the last leaf of the last doubling wins
-            ReplayOut ro; ro.lsa = 0.0; ro.steps = (1 << depth) - 1 + (stop_kind ? stop_n + 1 : 0); ro.win_d = depth > 0 ? depth - 1 : -1; ro.win_n = 0;
-#else
             const ReplayOut ro = nuts_replay(ri, S);
-#endif
             v = AccStat{ro.lsa, ro.steps};
             if (ro.win_d >= 0) {
                 const int st = usi(S.z_idx[ro.win_d]);
@@ -1103,13 +984,13 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                 if constexpr (!Model::kSeparable) { g = bload<NCH, kAuxFresh>(s.g + off, lane); BYTES(2, 1); }
                 double lqw, Kw;
                 for (int t = 0; t < nw - (kDefer ? 1 : 0); ++t) {
-                    if constexpr (Model::kSeparable) leapfrog_step_regrad<NCH, !kConstRegs>(mdl, minv, eps_w, q, p, lqw, Kw);
+                    if constexpr (Model::kSeparable) leapfrog_step_regrad<NCH>(mdl, minv, eps_w, q, p, lqw, Kw);
                     else leapfrog_step_general<NCH>(mdl, minv, eps_w, q, p, g, lqw, Kw);
                 }
                 if constexpr (kDefer) {
                     // the last step is the winning leaf itself: its l(q) and pi are the leaf's, bit for bit (the steps before it
                     // drop their reductions: nothing reads them)
-                    leapfrog_step_regrad<NCH, !kConstRegs>(mdl, minv, eps_w, q, p, lqw, Kw);
+                    leapfrog_step_regrad<NCH>(mdl, minv, eps_w, q, p, lqw, Kw);
                     lq_new = lqw;
                     pi_new = phase_logdensity(lqw, Kw);
                 }
@@ -1121,8 +1002,8 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                 if constexpr (Model::kSeparable) (void)eval_density<NCH>(mdl, q, g);
                 else (void)mdl.grad(q, g);
             }
-            bstore<NCH, kNt>(s.q + off, lane, q);  BYTES(6, 1);
-            if constexpr (!(kRegenerate && Model::kSeparable)) { bstore<NCH, kNt>(s.g + off, lane, g); BYTES(6, 1); }
+            bstore<NCH>(s.q + off, lane, q);  BYTES(6, 1);
+            if constexpr (!(kRegenerate && Model::kSeparable)) { bstore<NCH>(s.g + off, lane, g); BYTES(6, 1); }
         } else if ((flags & (IDHMC_T_ACCUM_METRIC | IDHMC_T_ACCUM_MOMENTS)) || s.fz_q) {
             q = bload<NCH, kAuxFresh>(s.q + off, lane);  BYTES(6, 1);
         }
@@ -1241,10 +1122,6 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         STAMP(5);                                                                // epilogue
         STAMP_FLUSH;
         BYTES_FLUSH;
-        if constexpr (kCoop && !kCoopRefill) {
-            mdl.retire();
-            mdl.serve();
-        }
     }
     // the workgroup's sums -> the global counters (every wavefront gets here: the queue is empty for all of them in the end)
     __syncthreads();

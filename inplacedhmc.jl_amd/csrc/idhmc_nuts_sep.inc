@@ -21,16 +21,8 @@ static hipError_t launch_nuts_sep_nch(const DevState &s, uint32_t iter, uint32_t
     if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)
         return shared ? launch_nuts_t<NCH, IsoGaussian<NCH>, true>(s, iter, flags, grid, st)
                       : launch_nuts_t<NCH, IsoGaussian<NCH>, false>(s, iter, flags, grid, st);
-    // register-rich form with the constants in VGPRs (experiments): DiagGaussian; otherwise mu, tau staged in LDS
-    if constexpr (nuts_const_regs(NCH, true, false, nuts_waves(NCH, true, false, true))) {
-        if (shared) return launch_nuts_t<NCH, DiagGaussian<NCH>, true>(s, iter, flags, grid, st);
-    } else {
-        if (shared) return launch_nuts_t<NCH, DiagGaussianLds<NCH>, true>(s, iter, flags, grid, st);
-    }
-    if constexpr (nuts_const_regs(NCH, true, false, nuts_waves(NCH, true, false, false)))
-        return launch_nuts_t<NCH, DiagGaussian<NCH>, false>(s, iter, flags, grid, st);
-    else
-        return launch_nuts_t<NCH, DiagGaussianLds<NCH>, false>(s, iter, flags, grid, st);
+    return shared ? launch_nuts_t<NCH, DiagGaussianLds<NCH>, true>(s, iter, flags, grid, st)
+                  : launch_nuts_t<NCH, DiagGaussianLds<NCH>, false>(s, iter, flags, grid, st);
 }
 
 #define IDHMC_NUTS_SEP_NAME2(lo) launch_nuts_sep_from##lo
