@@ -707,6 +707,8 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         s.q = sv[0]; s.p = sv[1]; s.g = sv[2];
         if (own_minv) s.minv = sv[3];
     }
+    s.lf_stride = (3 * CL * (int64_t)sizeof(double) + kIcSliceBytes - 1) / kIcSliceBytes;
+    if (s.lf_stride < 1) s.lf_stride = 1;
     DALLOC(s.lq, nchains); DALLOC(s.pi, nchains); DALLOC(s.eps, nchains);
     if (own_minv) {
         DALLOC(s.w, CL);

@@ -34,6 +34,7 @@ struct DevState {
     double *eps;          // [C]
     double *minv, *w;     // [C][L] (minv_stride = L) or [L] shared (minv_stride = 0)
     int64_t minv_stride;
+    int64_t lf_stride;        // k_leapfrog1: chains c % lf_stride == 0 are the Infinity-Cache slice (idhmc_create, kIcSliceBytes)
     const double *mu, *tau;   // [L]
     const double *prec;       // [L][L]
     const double *lr_x, *lr_xt, *lr_y;   // IDHMC_MODEL_LOGISTIC_REGRESSION, _GLM: X [lr_npad][L], X' [L][lr_npad], Y [K][lr_npad], zero-padded
@@ -80,6 +81,10 @@ constexpr int kPulseAt = 0;
 // with IDHMC_TEST_XCC_MISMATCH=1 in the environment, and refuse it, like every other bit outside the IDHMC_T_* set, otherwise
 constexpr uint32_t kTestXccFlag = 1u << 30;
 constexpr int kXchgBlocks = 64;   // workgroups of k_xchg_sum; DevState::xchg_acc holds 3 * kXchgBlocks partials + 1 ticket
+// the most q, p, grad bytes the single-step leapfrog keeps in the 256 MiB Infinity Cache across sweeps: every lf_stride-th chain, with
+// lf_stride = ceil(C L 3 8 / kIcSliceBytes), 1 when the whole state fits (tools/ubench/ic_slice.hip: 192 MiB stays resident behind a
+// 2.6 GiB nt stream, 219 MiB only in part)
+constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
 
 #ifndef __HIPCC_RTC__   // host side only (the header is also compiled by hipRTC for custom densities)
 // ---- dispatch over the padded length: NCH = L / 128 = ceil(D / 128), every value 1..16 for the separable densities

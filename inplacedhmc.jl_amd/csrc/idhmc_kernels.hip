@@ -118,9 +118,77 @@ __global__ __launch_bounds__(256) void k_leapfrog(DevState s, double eps_arg, in
 //            before the first store, so one wave keeps 24 KiB of HBM reads in flight (2 waves/SIMD);
 //            otherwise chunk-by-chunk at 4 waves/SIMD.
 // VAR bit 1: non-temporal loads/stores for the streamed state.
+// With bit 0, the chains c % s.lf_stride == 0 (a slice of at most kIcSliceBytes of q, p, grad, spread through the sweep) use
+// default-policy loads and stores instead: behind the other chains' nt stream that slice stays in the Infinity Cache from one sweep to
+// the next, so its bytes are served on die while the rest streams from HBM (tools/ubench/ic_slice.hip).
 typedef double v2d __attribute__((ext_vector_type(2)));
 template <bool NT> IDHMC_DEV v2d ld2(const v2d *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
 template <bool NT> IDHMC_DEV void st2(v2d *p, v2d v) { if (NT) __builtin_nontemporal_store(v, p); else *p = v; }
+
+// one chain of k_leapfrog1; NT: the policy of this chain's q, p, grad loads and stores
+template <int NCH, class Model, bool PRE, bool NT, bool REGRAD>
+IDHMC_DEV void leapfrog1_chain(const DevState &s, int64_t c, int lane, double eps_arg, int own_eps)
+{
+    const v2d *__restrict__ mu2 = reinterpret_cast<const v2d *>(s.mu) + lane;
+    const v2d *__restrict__ tau2 = reinterpret_cast<const v2d *>(s.tau) + lane;
+    const int64_t off = c * s.L;
+    v2d *__restrict__ q2 = reinterpret_cast<v2d *>(s.q + off) + lane;
+    v2d *__restrict__ p2 = reinterpret_cast<v2d *>(s.p + off) + lane;
+    v2d *__restrict__ g2 = reinterpret_cast<v2d *>(s.g + off) + lane;
+    const v2d *__restrict__ m2 = reinterpret_cast<const v2d *>(s.minv + c * s.minv_stride) + lane;
+    const double eps = own_eps ? s.eps[c] : eps_arg;
+    const double eh = 0.5 * eps;
+    double l0 = 0.0, l1 = 0.0, k0 = 0.0, k1 = 0.0;
+    v2d qv[NCH], pv[NCH], gv[NCH], mvv[NCH], muv[NCH], tav[NCH];
+    if (PRE) {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            qv[j] = ld2<NT>(q2 + j * 64);
+            pv[j] = ld2<NT>(p2 + j * 64);
+            if (!REGRAD) gv[j] = ld2<NT>(g2 + j * 64);
+        }
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            mvv[j] = m2[j * 64];
+            if (Model::kHasParams) { muv[j] = mu2[j * 64]; tav[j] = tau2[j * 64]; }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        v2d q, p, g, mv, mu = {0.0, 0.0}, tau = {1.0, 1.0};
+        if (PRE) {
+            q = qv[j]; p = pv[j]; mv = mvv[j];
+            if (!REGRAD) g = gv[j];
+            if (Model::kHasParams) { mu = muv[j]; tau = tav[j]; }
+        } else {
+            q = ld2<NT>(q2 + j * 64); p = ld2<NT>(p2 + j * 64);
+            if (!REGRAD) g = ld2<NT>(g2 + j * 64);
+            mv = m2[j * 64];
+            if (Model::kHasParams) { mu = mu2[j * 64]; tau = tau2[j * 64]; }
+        }
+        if (REGRAD) g = v2d{-(tau.x * (q.x - mu.x)), -(tau.y * (q.y - mu.y))};
+        const double pmx = dfma(eh, g.x, p.x), pmy = dfma(eh, g.y, p.y);
+        const double qx = dfma(eps * mv.x, pmx, q.x), qy = dfma(eps * mv.y, pmy, q.y);
+        const double dx = qx - mu.x, dy = qy - mu.y;
+        const double tx = tau.x * dx, ty = tau.y * dy;
+        l0 = dfma(tx, dx, l0);
+        l1 = dfma(ty, dy, l1);
+        const double px = dfma(eh, -tx, pmx), py = dfma(eh, -ty, pmy);
+        k0 = dfma(px * mv.x, px, k0);
+        k1 = dfma(py * mv.y, py, k1);
+        st2<NT>(q2 + j * 64, v2d{qx, qy});
+        st2<NT>(p2 + j * 64, v2d{px, py});
+        if (!REGRAD) st2<NT>(g2 + j * 64, v2d{-tx, -ty});
+    }
+    double sl, sk;
+    wave_sum2(l0, l1, k0, k1, sl, sk);
+    double lq = -0.5 * sl;
+    lq = dfinite(lq) ? lq : -kInf;
+    if (lane == 0) {
+        s.lq[c] = lq;
+        s.pi[c] = phase_logdensity(lq, 0.5 * sk);
+    }
+}
 
 template <int NCH, class Model, int VAR>
 __global__ __launch_bounds__(256, (VAR & 1) ? 2 : 4) void k_leapfrog1(DevState s, double eps_arg, int own_eps)
@@ -131,66 +199,9 @@ __global__ __launch_bounds__(256, (VAR & 1) ? 2 : 4) void k_leapfrog1(DevState s
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const v2d *__restrict__ mu2 = reinterpret_cast<const v2d *>(s.mu) + lane;
-    const v2d *__restrict__ tau2 = reinterpret_cast<const v2d *>(s.tau) + lane;
     for (int64_t c = wave; c < s.C; c += nw) {
-        const int64_t off = c * s.L;
-        v2d *__restrict__ q2 = reinterpret_cast<v2d *>(s.q + off) + lane;
-        v2d *__restrict__ p2 = reinterpret_cast<v2d *>(s.p + off) + lane;
-        v2d *__restrict__ g2 = reinterpret_cast<v2d *>(s.g + off) + lane;
-        const v2d *__restrict__ m2 = reinterpret_cast<const v2d *>(s.minv + c * s.minv_stride) + lane;
-        const double eps = own_eps ? s.eps[c] : eps_arg;
-        const double eh = 0.5 * eps;
-        double l0 = 0.0, l1 = 0.0, k0 = 0.0, k1 = 0.0;
-        v2d qv[NCH], pv[NCH], gv[NCH], mvv[NCH], muv[NCH], tav[NCH];
-        if (PRE) {
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                qv[j] = ld2<NT>(q2 + j * 64);
-                pv[j] = ld2<NT>(p2 + j * 64);
-                if (!REGRAD) gv[j] = ld2<NT>(g2 + j * 64);
-            }
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                mvv[j] = m2[j * 64];
-                if (Model::kHasParams) { muv[j] = mu2[j * 64]; tav[j] = tau2[j * 64]; }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            v2d q, p, g, mv, mu = {0.0, 0.0}, tau = {1.0, 1.0};
-            if (PRE) {
-                q = qv[j]; p = pv[j]; mv = mvv[j];
-                if (!REGRAD) g = gv[j];
-                if (Model::kHasParams) { mu = muv[j]; tau = tav[j]; }
-            } else {
-                q = ld2<NT>(q2 + j * 64); p = ld2<NT>(p2 + j * 64);
-                if (!REGRAD) g = ld2<NT>(g2 + j * 64);
-                mv = m2[j * 64];
-                if (Model::kHasParams) { mu = mu2[j * 64]; tau = tau2[j * 64]; }
-            }
-            if (REGRAD) g = v2d{-(tau.x * (q.x - mu.x)), -(tau.y * (q.y - mu.y))};
-            const double pmx = dfma(eh, g.x, p.x), pmy = dfma(eh, g.y, p.y);
-            const double qx = dfma(eps * mv.x, pmx, q.x), qy = dfma(eps * mv.y, pmy, q.y);
-            const double dx = qx - mu.x, dy = qy - mu.y;
-            const double tx = tau.x * dx, ty = tau.y * dy;
-            l0 = dfma(tx, dx, l0);
-            l1 = dfma(ty, dy, l1);
-            const double px = dfma(eh, -tx, pmx), py = dfma(eh, -ty, pmy);
-            k0 = dfma(px * mv.x, px, k0);
-            k1 = dfma(py * mv.y, py, k1);
-            st2<NT>(q2 + j * 64, v2d{qx, qy});
-            st2<NT>(p2 + j * 64, v2d{px, py});
-            if (!REGRAD) st2<NT>(g2 + j * 64, v2d{-tx, -ty});
-        }
-        double sl, sk;
-        wave_sum2(l0, l1, k0, k1, sl, sk);
-        double lq = -0.5 * sl;
-        lq = dfinite(lq) ? lq : -kInf;
-        if (lane == 0) {
-            s.lq[c] = lq;
-            s.pi[c] = phase_logdensity(lq, 0.5 * sk);
-        }
+        if (PRE && NT && c % s.lf_stride == 0) leapfrog1_chain<NCH, Model, PRE, false, REGRAD>(s, c, lane, eps_arg, own_eps);
+        else leapfrog1_chain<NCH, Model, PRE, NT, REGRAD>(s, c, lane, eps_arg, own_eps);
     }
 }
 
