@@ -100,14 +100,32 @@ enum {
  * through idhmc_last_error().  `params` is [K, nc, c (nc) | X row-major (n x D) | Y row-major (n x K)], so
  * n = (nparams - 2 - nc) / (D + K).  Refused with IDHMC_ERR_BAD_ARG before the device is touched: K not an integer in 1..4,
  * nc not an integer in 0..16, a remainder that is not a positive multiple of D + K, a non-finite value in X, Y or c, a missing
- * or empty source, and whatever LOGISTIC_REGRESSION refuses of the prior, D and n_pad L. */
+ * or empty source, and whatever LOGISTIC_REGRESSION refuses of the prior, D and n_pad L.
+ *
+ * IDHMC_MODEL_GLM_AUX -- a GLM whose likelihood has A sampled auxiliary parameters (1 <= A <= 4: a scale, a shape, a dispersion)
+ * that every observation sees.  A chain's position is q = [beta (Dx coefficients) | a (A)], D = Dx + A, all unconstrained: the
+ * observation applies its own transform (sigma = exp(a[0]), say) and includes the a-dependent normalising terms in v.
+ *   l(q) = -sum_i v(z_i, y_i, a) - 1/2 sum_{c < D} tau_c (q_c - mu_c)^2,   z = X beta   (X is n x Dx)
+ *   dl/dbeta_c = sum_i X[i][c] r_i - tau_c (beta_c - mu_c),   dl/da_j = sum_i s_ij - tau_{Dx+j} (a_j - mu_{Dx+j})
+ *
+ *   __device__ void glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s);
+ *
+ * a[j], s[j] for j < o.A; r = d log p(y | z, a) / dz, s[j] = d log p(y | z, a) / da_j, v = -log p(y | z, a) up to a term that
+ * depends on the data only; o.y, o.c, o.K, o.nc as for GLM.  The Gaussian prior (mu, tau, length D) covers the auxiliary
+ * coordinates.  `params` is [K, nc, A, c (nc) | X row-major (n x Dx) | Y row-major (n x K)] and idhmc_model_desc.D = Dx + A, so
+ * n = (nparams - 3 - nc) / (Dx + K).  Refused with IDHMC_ERR_BAD_ARG before the device is touched: A not an integer in 1..4,
+ * Dx = D - A < 1, and everything GLM refuses (with Dx in the place of D for X; the limits on D are on the total).  The same
+ * kernels as GLM; the NUTS transition uses the matrix cores where the A further tiles fit a CU's LDS (L = 128: every A; L = 256: A = 1, or
+ * A = 2 with a SHARED or POOLED metric), one chain per wavefront elsewhere:
+ * idhmc_glm_form tells which. */
 enum {
     IDHMC_MODEL_ISO_GAUSSIAN = 0,   /* l(q) = -1/2 |q|^2                       */
     IDHMC_MODEL_DIAG_GAUSSIAN = 1,  /* l(q) = -1/2 sum tau_d (q_d - mu_d)^2    */
     IDHMC_MODEL_DENSE_MVN = 2,      /* l(q) = -1/2 (q-mu)' P (q-mu), P = Sigma^-1 (fp64 MFMA) */
     IDHMC_MODEL_CUSTOM = 3,         /* user HIP source, see above */
     IDHMC_MODEL_LOGISTIC_REGRESSION = 4,  /* Bayesian logistic regression, see above (fp64 MFMA) */
-    IDHMC_MODEL_GLM = 5                   /* a GLM with the user's observation source, see above (fp64 MFMA) */
+    IDHMC_MODEL_GLM = 5,                  /* a GLM with the user's observation source, see above (fp64 MFMA) */
+    IDHMC_MODEL_GLM_AUX = 6               /* a GLM whose likelihood has sampled auxiliary parameters (scale, shape), see above */
 };
 typedef struct {
     int32_t kind;
@@ -116,9 +134,9 @@ typedef struct {
     const double *mu;       /* host, D  (DIAG, DENSE; LOGISTIC_REGRESSION, GLM: prior mean, may be NULL) */
     const double *tau;      /* host, D  (DIAG; LOGISTIC_REGRESSION, GLM: prior precision, may be NULL) */
     const double *prec;     /* host, D*D row-major, symmetric (DENSE) */
-    const char *source;     /* CUSTOM, GLM: NUL-terminated HIP device source */
+    const char *source;     /* CUSTOM, GLM, GLM_AUX: NUL-terminated HIP device source */
     const double *params;   /* CUSTOM: host, nparams doubles copied to the device (may be NULL); LOGISTIC_REGRESSION: [X | y];
-                               GLM: [K, nc, c | X | Y] */
+                               GLM: [K, nc, c | X | Y]; GLM_AUX: [K, nc, A, c | X | Y] */
     int64_t nparams;
 } idhmc_model_desc;
 
@@ -197,6 +215,9 @@ int idhmc_synchronize(idhmc_ctx *ctx);
 int64_t idhmc_nchains(const idhmc_ctx *ctx);
 int32_t idhmc_dim(const idhmc_ctx *ctx);
 int32_t idhmc_padded_dim(const idhmc_ctx *ctx);
+/* the form of the NUTS kernel's gradient of a LOGISTIC_REGRESSION, GLM or GLM_AUX context: 0 one chain per wavefront, 1 the fp64
+ * matrix cores (16 chains per workgroup); -1 for every other model.  Both forms compute the same bits. */
+int idhmc_glm_form(const idhmc_ctx *ctx);
 int64_t idhmc_device_bytes(const idhmc_ctx *ctx);
 /* Contexts with state arrays of 64 MiB or more try several placements of q, p, grad l (and a per-chain M^-1) in HBM when they are
  * created and keep the one on which the single-step sweep's access pattern runs fastest (the same kernel differs by 10 % between

@@ -6,7 +6,7 @@ computes on the CPU and nothing falls back to a CPU path.
 """
 from ._lib import IdhmcError, LIB_PATH, load as load_library  # noqa: F401
 from .engine import (Engine, Model, IsoGaussian, DiagGaussian, DenseMVN, CustomDensity, LogisticRegression, GLM, default_options,  # noqa: F401
-                     MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION, MODEL_GLM,
+                     MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION, MODEL_GLM, MODEL_GLM_AUX,
                      TREE_STATS_DTYPE, EPS_PER_CHAIN, EPS_GLOBAL, METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED, GRAD_STORE, GRAD_RECOMPUTE,
                      T_ADAPT_EPS, T_ACCUM_METRIC, T_ACCUM_MOMENTS, T_KEEP_P, T_USE_DIRECTIONS, T_ACCUM_DIAG,
                      XCHG_DOUBLES, XCHG_ACCEPT, XCHG_LOGEPS, POOL_SEGMENT, xchg_accumulate, xchg_mean,

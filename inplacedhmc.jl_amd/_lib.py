@@ -57,6 +57,7 @@ SYMBOLS = {
     "idhmc_nchains": (_i64, [_vp]),
     "idhmc_dim": (_i32, [_vp]),
     "idhmc_padded_dim": (_i32, [_vp]),
+    "idhmc_glm_form": (C.c_int, [_vp]),
     "idhmc_device_bytes": (_i64, [_vp]),
     "idhmc_placement_info": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "idhmc_lanes_info": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -17,7 +17,7 @@
 
 namespace idhmc {
 int arena_vectors(int max_depth, int model, int L);
-int nuts_waves_per_block(int nch, int model, int shared_metric);
+int nuts_waves_per_block(int nch, int model, int shared_metric, int glm_aux);
 int nuts_wide_waves_per_block(int nch, int model);
 }
 using namespace idhmc;
@@ -554,30 +554,35 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     if (nchains < 1 || nchains > (int64_t)0x7fffffff) return fail(IDHMC_ERR_BAD_ARG, "nchains = %lld out of range", (long long)nchains);
     if (first_chain_id < 0 || first_chain_id + nchains > (int64_t)0xffffffffll) return fail(IDHMC_ERR_BAD_ARG, "chain ids must fit 32 bits");
     if (model->D < 1 || model->D > 2048) return fail(IDHMC_ERR_BAD_ARG, "D = %d unsupported (1..2048)", model->D);
+    // a GLM with auxiliary coordinates is a GLM to everything below but the parsing of its params and the choice of its kernels
+    const bool glm_aux = model->kind == IDHMC_MODEL_GLM_AUX;
+    const int kind = glm_aux ? (int)IDHMC_MODEL_GLM : model->kind;
     if (model->D > 1024) {
         // two register tiles per vector; the dense MVN's matrix (32 MB at D = 2048) has no kernel built for it
-        if (model->kind == IDHMC_MODEL_DENSE_MVN)
+        if (kind == IDHMC_MODEL_DENSE_MVN)
             return fail(IDHMC_ERR_BAD_ARG, "D = %d: the dense density is limited to D <= 1024", model->D);
-        if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION)
+        if (kind == IDHMC_MODEL_LOGISTIC_REGRESSION)
             return fail(IDHMC_ERR_BAD_ARG, "D = %d: logistic regression is limited to D <= 1024", model->D);
-        if (model->kind == IDHMC_MODEL_GLM)
+        if (kind == IDHMC_MODEL_GLM)
             return fail(IDHMC_ERR_BAD_ARG, "D = %d: a GLM is limited to D <= 1024", model->D);
     }
     if (opt_in && (opt_in->metric_mode < 0 || opt_in->metric_mode > IDHMC_METRIC_POOLED)) return fail(IDHMC_ERR_BAD_ARG, "unknown metric_mode %d", opt_in->metric_mode);
-    if (model->kind < 0 || model->kind > IDHMC_MODEL_GLM) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
-    if (model->kind == IDHMC_MODEL_CUSTOM) {
+    if (kind < 0 || kind > IDHMC_MODEL_GLM_AUX) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
+    if (kind == IDHMC_MODEL_CUSTOM) {
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "custom model needs HIP source");
         if (model->nparams < 0 || (model->nparams > 0 && !model->params)) return fail(IDHMC_ERR_BAD_ARG, "custom model: bad params");
         if (model->D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
             return fail(IDHMC_ERR_BAD_ARG, "custom model with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)");
-    } else if (model->kind != IDHMC_MODEL_ISO_GAUSSIAN && model->kind != IDHMC_MODEL_LOGISTIC_REGRESSION && model->kind != IDHMC_MODEL_GLM &&
+    } else if (kind != IDHMC_MODEL_ISO_GAUSSIAN && kind != IDHMC_MODEL_LOGISTIC_REGRESSION && kind != IDHMC_MODEL_GLM &&
                !model->mu) {
         return fail(IDHMC_ERR_BAD_ARG, "model needs mu");
     }
     // a logistic regression's params are [X | y]; a GLM's [K, nc, c | X | Y] (K data columns, nc constants)
     int64_t lr_n = 0;              // observations of a logistic regression or a GLM
-    int64_t glm_k = 1, glm_nc = 0;
-    if (model->kind == IDHMC_MODEL_GLM) {
+    // with auxiliary coordinates (GLM_AUX) [K, nc, A, c | X | Y]: X has Dx = D - A columns, the last A coordinates are not coefficients
+    int64_t glm_k = 1, glm_nc = 0, glm_a = 0;
+    int glm_head = 0;              // doubles in front of X
+    if (kind == IDHMC_MODEL_GLM && !glm_aux) {
         const int D = model->D;
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
         if (model->nparams < 2 || !model->params) return fail(IDHMC_ERR_BAD_ARG, "GLM: params must begin with K and nc ([K, nc, c | X | Y])");
@@ -593,11 +598,35 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         for (int64_t j = 0; j < glm_nc; ++j)
             if (!std::isfinite(model->params[2 + j])) return fail(IDHMC_ERR_BAD_ARG, "GLM: constant c[%lld] is not finite", (long long)j);
         lr_n = rest / (D + glm_k);
+        glm_head = 2 + (int)glm_nc;
     }
-    if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION || model->kind == IDHMC_MODEL_GLM) {
-        const bool glm = model->kind == IDHMC_MODEL_GLM;
-        const char *what = glm ? "GLM" : "logistic regression";
+    if (glm_aux) {
+        if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
+        if (model->nparams < 3 || !model->params)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: params must begin with K, nc and A ([K, nc, A, c | X | Y])");
+        const double k = model->params[0], nc = model->params[1], a = model->params[2];
+        if (!(k >= 1.0 && k <= 4.0 && k == std::floor(k))) return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: K = %g must be an integer in 1..4", k);
+        if (!(nc >= 0.0 && nc <= 16.0 && nc == std::floor(nc))) return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: nc = %g must be an integer in 0..16", nc);
+        if (!(a >= 1.0 && a <= 4.0 && a == std::floor(a))) return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: A = %g must be an integer in 1..4", a);
+        glm_k = (int64_t)k;
+        glm_nc = (int64_t)nc;
+        glm_a = (int64_t)a;
+        const int64_t Dx = model->D - glm_a;
+        if (Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: Dx = D - A = %lld: at least one coefficient is needed", (long long)Dx);
+        const int64_t rest = model->nparams - 3 - glm_nc;
+        if (rest < 1 || rest % (Dx + glm_k) != 0)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: nparams - 3 - nc = %lld must be a positive multiple of Dx + K = %lld ([X | Y])",
+                        (long long)rest, (long long)(Dx + glm_k));
+        for (int64_t j = 0; j < glm_nc; ++j)
+            if (!std::isfinite(model->params[3 + j])) return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: constant c[%lld] is not finite", (long long)j);
+        lr_n = rest / (Dx + glm_k);
+        glm_head = 3 + (int)glm_nc;
+    }
+    if (kind == IDHMC_MODEL_LOGISTIC_REGRESSION || kind == IDHMC_MODEL_GLM) {
+        const bool glm = kind == IDHMC_MODEL_GLM;
+        const char *what = glm_aux ? "GLM_AUX" : glm ? "GLM" : "logistic regression";
         const int D = model->D;
+        const int64_t Dx = D - glm_a;      // the columns of X
         if (!glm) {
             if (model->nparams < 1 || model->nparams % (D + 1) != 0 || !model->params)
                 return fail(IDHMC_ERR_BAD_ARG, "logistic regression: nparams = %lld must be a positive multiple of D + 1 = %d ([X | y])",
@@ -610,13 +639,13 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         if (npad * L > ((int64_t)1 << 27))
             return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
                         what, (long long)lr_n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
-        const double *X = model->params + (glm ? 2 + glm_nc : 0), *y = X + lr_n * D;
-        for (int64_t k = 0; k < lr_n * D; ++k)
-            if (!std::isfinite(X[k])) return fail(IDHMC_ERR_BAD_ARG, "%s: X[%lld, %lld] is not finite", what, (long long)(k / D), (long long)(k % D));
+        const double *X = model->params + glm_head, *y = X + lr_n * Dx;
+        for (int64_t k = 0; k < lr_n * Dx; ++k)
+            if (!std::isfinite(X[k])) return fail(IDHMC_ERR_BAD_ARG, "%s: X[%lld, %lld] is not finite", what, (long long)(k / Dx), (long long)(k % Dx));
         if (glm) {
             for (int64_t k = 0; k < lr_n * glm_k; ++k)
                 if (!std::isfinite(y[k]))
-                    return fail(IDHMC_ERR_BAD_ARG, "GLM: Y[%lld, %lld] is not finite", (long long)(k / glm_k), (long long)(k % glm_k));
+                    return fail(IDHMC_ERR_BAD_ARG, "%s: Y[%lld, %lld] is not finite", what, (long long)(k / glm_k), (long long)(k % glm_k));
         } else {
             for (int64_t i = 0; i < lr_n; ++i)
                 if (y[i] != 0.0 && y[i] != 1.0) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: y[%lld] = %g is neither 0 nor 1", (long long)i, y[i]);
@@ -630,9 +659,9 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         if (D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
             return fail(IDHMC_ERR_BAD_ARG, "%s with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)", what);
     }
-    if (model->kind == IDHMC_MODEL_DIAG_GAUSSIAN && !model->tau) return fail(IDHMC_ERR_BAD_ARG, "diagonal model needs tau");
-    if (model->kind == IDHMC_MODEL_DENSE_MVN && !model->prec) return fail(IDHMC_ERR_BAD_ARG, "dense model needs prec");
-    if (model->kind == IDHMC_MODEL_DENSE_MVN) {
+    if (kind == IDHMC_MODEL_DIAG_GAUSSIAN && !model->tau) return fail(IDHMC_ERR_BAD_ARG, "diagonal model needs tau");
+    if (kind == IDHMC_MODEL_DENSE_MVN && !model->prec) return fail(IDHMC_ERR_BAD_ARG, "dense model needs prec");
+    if (kind == IDHMC_MODEL_DENSE_MVN) {
         // the gradient kernel reads row c of P as column c (coalesced): P must be exactly symmetric
         const int D = model->D;
         for (int r = 0; r < D; ++r)
@@ -680,13 +709,14 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     // a vector is padded to the next multiple of 128 (the reference pads to its SIMD width, src/mcmc.jl:117); the
     // dense density's matrix kernels need a power-of-two number of 128-column chunks
     int nch = (model->D + 127) / 128;
-    if (model->kind == IDHMC_MODEL_DENSE_MVN || model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION || model->kind == IDHMC_MODEL_GLM) {
+    if (kind == IDHMC_MODEL_DENSE_MVN || kind == IDHMC_MODEL_LOGISTIC_REGRESSION || kind == IDHMC_MODEL_GLM) {
         nch = 1;
         while (nch * 128 < model->D) nch *= 2;
     }
     s.nch = nch;
     s.L = 128 * nch;
-    s.model = model->kind;
+    s.model = kind;               // a GLM_AUX runs as a GLM with lr_a > 0
+    s.lr_a = (int32_t)glm_a;
     s.k0 = (uint32_t)seed;
     s.k1 = (uint32_t)(seed >> 32);
     s.first_chain = (uint32_t)first_chain_id;
@@ -699,7 +729,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
 
     const int64_t CL = nchains * s.L;
     // the dense leapfrog's matrix-core kernel reads whole 32-chain tiles: rows past the last chain exist (zeros), see kRowPad
-    const int64_t CLp = CL + (model->kind == IDHMC_MODEL_DENSE_MVN ? (int64_t)kRowPad * s.L : 0);
+    const int64_t CLp = CL + (kind == IDHMC_MODEL_DENSE_MVN ? (int64_t)kRowPad * s.L : 0);
     const bool own_minv = opt.metric_mode == IDHMC_METRIC_PER_CHAIN;
     {
         double *sv[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -759,19 +789,19 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         DALLOC(mu, s.L); DALLOC(tau, s.L);
         if (model->mu) HIPCHK(hipMemcpyAsync(mu, model->mu, sizeof(double) * s.D, hipMemcpyHostToDevice, c->stream));
         if (model->tau) HIPCHK(hipMemcpyAsync(tau, model->tau, sizeof(double) * s.D, hipMemcpyHostToDevice, c->stream));
-        if (model->kind == IDHMC_MODEL_DENSE_MVN) {
+        if (kind == IDHMC_MODEL_DENSE_MVN) {
             DALLOC(prec, (int64_t)s.L * s.L);
             HIPCHK(hipMemcpy2DAsync(prec, sizeof(double) * s.L, model->prec, sizeof(double) * s.D,
                                     sizeof(double) * s.D, s.D, hipMemcpyHostToDevice, c->stream));
         }
         s.mu = mu; s.tau = tau; s.prec = prec;
-        if (model->kind == IDHMC_MODEL_LOGISTIC_REGRESSION || model->kind == IDHMC_MODEL_GLM) {
+        if (kind == IDHMC_MODEL_LOGISTIC_REGRESSION || kind == IDHMC_MODEL_GLM) {
             // the prior's defaults (mu = 0 is the zeroed allocation); X, X' and the K planes of Y zero-padded to [n_pad][L],
             // [L][n_pad], [K][n_pad]; a GLM's constants
             if (!model->tau) HIPCHK(launch_fill(tau, 1.0, s.D, c->stream));
-            const bool glm = model->kind == IDHMC_MODEL_GLM;
-            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D, K = glm_k;
-            const double *X = model->params + (glm ? 2 + glm_nc : 0), *Y = X + n * D;
+            const bool glm = kind == IDHMC_MODEL_GLM;
+            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - glm_a, K = glm_k;     // D: the columns of X
+            const double *X = model->params + glm_head, *Y = X + n * D;
             std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(K * npad), 0.0);
             for (int64_t i = 0; i < n; ++i)
                 for (int64_t k = 0; k < D; ++k) {
@@ -786,7 +816,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
             if (glm) {
                 double *dc = nullptr;
                 DALLOC(dc, glm_nc > 0 ? glm_nc : 1);
-                if (glm_nc > 0) HIPCHK(hipMemcpyAsync(dc, model->params + 2, sizeof(double) * (size_t)glm_nc, hipMemcpyHostToDevice, c->stream));
+                if (glm_nc > 0) HIPCHK(hipMemcpyAsync(dc, model->params + (glm_head - glm_nc), sizeof(double) * (size_t)glm_nc, hipMemcpyHostToDevice, c->stream));
                 s.user_params = dc;
                 s.user_nparams = glm_nc;
             }
@@ -802,7 +832,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     {
         // one workgroup of W wavefronts per CU (W = 4: one wavefront per SIMD with the full 512-register
         // budget; its LDS footprint and registers allow no more); slots in multiples of W
-        const int W0 = nuts_waves_per_block(s.nch, s.model, opt.metric_mode != IDHMC_METRIC_PER_CHAIN), W1 = nuts_wide_waves_per_block(s.nch, s.model);
+        const int W0 = nuts_waves_per_block(s.nch, s.model, opt.metric_mode != IDHMC_METRIC_PER_CHAIN, s.lr_a), W1 = nuts_wide_waves_per_block(s.nch, s.model);
         const int W = W1 > W0 ? W1 : W0;
         int64_t nslots = (int64_t)prop.multiProcessorCount * W;
         const int64_t need = (nchains + W - 1) / W * W;
@@ -812,7 +842,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         DALLOC(s.arena, s.arena_stride * nslots);
     }
     // a user-supplied density: upload its parameters and compile it against the kernel templates (hipRTC)
-    if (model->kind == IDHMC_MODEL_CUSTOM) {
+    if (kind == IDHMC_MODEL_CUSTOM) {
         double *up = nullptr;
         DALLOC(up, model->nparams);
         if (model->nparams > 0) {
@@ -828,10 +858,10 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         s.jit = c->jit;
     }
     // a GLM: its observation source compiled into the logistic regression's templates (hipRTC); the data went up above
-    if (model->kind == IDHMC_MODEL_GLM) {
+    if (kind == IDHMC_MODEL_GLM) {
         static thread_local char jlog[400];
         jlog[0] = 0;
-        const int jrc = jit_build(s, model->source, &c->jit, jlog, sizeof jlog, (int)glm_k);
+        const int jrc = jit_build(s, model->source, &c->jit, jlog, sizeof jlog, (int)glm_k, (int)glm_a);
         if (jrc != 0) { idhmc_destroy(c); return fail(IDHMC_ERR_BAD_ARG, "GLM observation source did not compile (%d): %s", jrc, jlog); }
         s.jit = c->jit;
     }
@@ -869,6 +899,11 @@ int idhmc_synchronize(idhmc_ctx *c)
 int64_t idhmc_nchains(const idhmc_ctx *c) { return c ? c->s.C : 0; }
 int32_t idhmc_dim(const idhmc_ctx *c) { return c ? c->s.D : 0; }
 int32_t idhmc_padded_dim(const idhmc_ctx *c) { return c ? c->s.L : 0; }
+int idhmc_glm_form(const idhmc_ctx *c)
+{
+    if (!c || (c->s.model != IDHMC_MODEL_LOGISTIC_REGRESSION && c->s.model != IDHMC_MODEL_GLM)) return -1;
+    return glm_coop(c->s.nch, c->s.lr_a, c->s.minv_stride == 0) ? 1 : 0;
+}
 int64_t idhmc_device_bytes(const idhmc_ctx *c) { return c ? c->bytes : 0; }
 int idhmc_placement_info(const idhmc_ctx *c, double *probe_GBps, int32_t *candidates)
 {

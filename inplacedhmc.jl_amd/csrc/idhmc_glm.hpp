@@ -24,6 +24,15 @@
 //
 // Device layout (DevState): X [n_pad][L] (lr_x), X' [L][n_pad] (lr_xt), Y as K planes [K][n_pad] (lr_y), all zero-padded;
 // a GLM's constants in user_params (user_nparams of them).
+//
+// Auxiliary coordinates (IDHMC_MODEL_GLM_AUX): Obs::A of them (0 for the policies above, 1..4), the last A of the
+// D sampled coordinates, q = [beta (Dx = D - A) | a (A)].  Every observation sees them, no product with X does:
+//   static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)      s[j] = d log p / d a_j
+//   z_i   = the fma chain over columns c < Dx;  (r_i, v_i, s_i0 ..) from one call, all overwritten with 0 for i >= n
+//   S_j[rho], rho = i mod 128: plain additions over observation blocks ascending, from +0, as A[rho] accumulates v
+//   G_{Dx+j} = the canonical 128-residue tree over S_j (wave_sum, lane l holding residues 2l, 2l + 1);  g = dfma(-tau, d, G) as above
+//   T runs over all D coordinates (the prior covers a), P and l unchanged.
+// X has Dx columns: its device tiles hold +0 in columns >= Dx like every padded column.
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -34,7 +43,34 @@ struct GlmObs {
     double y[4];             // this observation's data columns, y[k] for k < K (the rest 0)
     const double *c;         // the model's constants, c[j] for j < nc (device memory)
     int K, nc;
+    int A;                   // auxiliary coordinates the model samples (0: none)
 };
+
+// Coordinate c of a chain's vector lives in lane (c & 127) >> 1, chunk c >> 7, component c & 1.  Both helpers are selects over
+// the chunks: c is not known at compile time, and a register array takes no run-time index.
+// the lane's component that would be coordinate c (the value in the owner lane is the coordinate)
+template <int NCH>
+IDHMC_DEV double glm_coord(const Vec<NCH> &q, int c)
+{
+    double v = 0.0;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v = (c >> 7) == j ? ((c & 1) ? q.c[j].y : q.c[j].x) : v;
+    return v;
+}
+// G is chunk j of the lane's vector: coordinate c of it becomes x
+IDHMC_DEV void glm_place(double2 &G, int j, int c, int lane, double x)
+{
+    const bool here = (c >> 7) == j && lane == ((c & 127) >> 1);
+    G.x = here && !(c & 1) ? x : G.x;
+    G.y = here && (c & 1) ? x : G.y;
+}
+// one call of the observation policy: with auxiliary coordinates it takes a and returns the scores s as well
+template <class Obs>
+IDHMC_DEV void glm_terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+{
+    if constexpr (Obs::A > 0) Obs::terms(z, o, a, r, v, s);
+    else Obs::terms(z, o, r, v);
+}
 
 // v_i and r_i of one observation (y is 0 or 1)
 IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
@@ -48,7 +84,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
-    static constexpr int K = 1;
+    static constexpr int K = 1, A = 0;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -60,12 +96,13 @@ struct GlmWave {
     static constexpr bool kHasParams = true;
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = false;
+    static constexpr int AN = Obs::A > 0 ? Obs::A : 1;
     const double *x, *xt;    // [npad][L], [L][npad], device
     const double2 *y2;       // [K][npad], lane-offset
     const double2 *mu2, *tau2;   // lane-offset, device
     const double *cst;       // the constants, device
     double *buf;             // this wavefront's LDS vector, L doubles
-    int D, n, npad, nc, lane;
+    int D, n, npad, nc, lane;    // D: the columns of X (the coordinates D .. D + Obs::A - 1 are the auxiliary ones)
     template <class State>
     IDHMC_DEV void init(const State &s, double *lds_vec, int lane_)
     {
@@ -76,7 +113,7 @@ struct GlmWave {
         tau2 = reinterpret_cast<const double2 *>(s.tau) + lane_;
         cst = s.user_params;
         buf = lds_vec;
-        D = s.D;
+        D = s.D - Obs::A;
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -87,6 +124,11 @@ struct GlmWave {
         constexpr int L = 128 * NCH;
         Vec<NCH> G = vfill<NCH>(0.0);
         double a0 = 0.0, a1 = 0.0;
+        double s0[AN], s1[AN];                                 // lane partials of the auxiliary scores, next to a0 / a1
+        if constexpr (Obs::A > 0) {
+#pragma unroll
+            for (int j = 0; j < AN; ++j) s0[j] = s1[j] = 0.0;
+        }
         double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;
         const int nb = npad >> 7;
         for (int b = 0; b < nb; ++b) {
@@ -107,15 +149,27 @@ struct GlmWave {
             const double2 p1 = Obs::K > 1 ? y2[(npad >> 1) + b * 64] : make_double2(0.0, 0.0);
             const double2 p2 = Obs::K > 2 ? y2[2 * (npad >> 1) + b * 64] : make_double2(0.0, 0.0);
             const double2 p3 = Obs::K > 3 ? y2[3 * (npad >> 1) + b * 64] : make_double2(0.0, 0.0);
-            const GlmObs ox{{p0.x, p1.x, p2.x, p3.x}, cst, Obs::K, nc}, oy{{p0.y, p1.y, p2.y, p3.y}, cst, Obs::K, nc};
+            const GlmObs ox{{p0.x, p1.x, p2.x, p3.x}, cst, Obs::K, nc, Obs::A}, oy{{p0.y, p1.y, p2.y, p3.y}, cst, Obs::K, nc, Obs::A};
             const int i0 = 128 * b + 2 * lane;
             double rx, vx, ry, vy;
-            Obs::terms(zx, ox, rx, vx);
-            Obs::terms(zy, oy, ry, vy);
+            double av[AN], ux[AN], uy[AN];
+            if constexpr (Obs::A > 0) {
+#pragma unroll
+                for (int j = 0; j < AN; ++j) av[j] = buf[D + j];   // LDS broadcast: q is still staged
+            }
+            glm_terms<Obs>(zx, ox, av, rx, vx, ux);
+            glm_terms<Obs>(zy, oy, av, ry, vy, uy);
             if (i0 >= n) { rx = 0.0; vx = 0.0; }
             if (i0 + 1 >= n) { ry = 0.0; vy = 0.0; }
             a0 = a0 + vx;
             a1 = a1 + vy;
+            if constexpr (Obs::A > 0) {
+#pragma unroll
+                for (int j = 0; j < AN; ++j) {
+                    s0[j] = s0[j] + (i0 >= n ? 0.0 : ux[j]);
+                    s1[j] = s1[j] + (i0 + 1 >= n ? 0.0 : uy[j]);
+                }
+            }
             b2[0] = make_double2(rx, ry);
             const int m = n - 128 * b < 128 ? n - 128 * b : 128;
             const double2 *xr = reinterpret_cast<const double2 *>(x + (size_t)128 * b * L) + lane;
@@ -128,6 +182,15 @@ struct GlmWave {
                     G.c[j].x = dfma(xv.x, ri, G.c[j].x);
                     G.c[j].y = dfma(xv.y, ri, G.c[j].y);
                 }
+            }
+        }
+        if constexpr (Obs::A > 0) {
+            // G of an auxiliary coordinate: the tree over its 128 residues, into the lane that owns the coordinate
+#pragma unroll
+            for (int jx = 0; jx < AN; ++jx) {
+                const double S = wave_sum(s0[jx], s1[jx]);
+#pragma unroll
+                for (int j = 0; j < NCH; ++j) glm_place(G.c[j], j, D + jx, lane, S);
             }
         }
         double t0 = 0.0, t1 = 0.0;
@@ -156,6 +219,12 @@ struct GlmWave {
 //   (5) the requester reads its row of each: g = dfma(-tau, d, G), P = dfma(2, A, T).
 // X' and X stream through L1 once per 16 gradients instead of once per gradient.  LDS: 16 (L + 2) + 2 * 16 * 130 doubles,
 // 49.9 KB at L = 128, 66.3 KB at L = 256.
+// Auxiliary coordinates (Obs::A > 0): A further [16][129] planes, one per coordinate.  (1) the requester writes +0 into the
+// auxiliary columns of its Q row (they take no part in Z) and a_j into the padding column 128 of its row of plane j, which
+// nothing else writes; (2) the Z wavefronts read a of the chain behind each accumulator row from there and add the scores into
+// columns 0..127 of the planes, each (chain, residue) slot owned by one lane of one Z wavefront across the blocks (block 0 stores
+// 0 + s: the sum starts from +0) -- in LDS, not in registers: the kernel has 128 registers per lane and 4 A accumulators more
+// would spill; (5) the requester reduces its row of each with wave_sum.  16.5 KB per auxiliary coordinate; which (L, A, metric) fit a CU is glm_coop's table (idhmc_logistic.hip).
 template <int NCH, class Obs>
 struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     static constexpr bool kHasParams = true;
@@ -164,7 +233,10 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     static constexpr int L = 128 * NCH, DS = L + 2, RS = 130, KB = L / 4;
     static constexpr int kZT = 8, kGT = L / 16;        // Z column tiles per block (wavefronts 8..15), G column tiles (0..L/16-1)
     static constexpr int kQ = 0, kR = 16 * DS;         // Q / G tile, then the two R tiles
-    static constexpr int kLdsDoubles = 16 * DS + 2 * 16 * RS;
+    static constexpr int AN = Obs::A > 0 ? Obs::A : 1;
+    static constexpr int kS = kR + 2 * 16 * RS;        // then the Obs::A score planes, [16][PS]: 128 residues and the slot of a_j
+    static constexpr int PS = 129;                     // (one padding column, not RS's two: the 1 KB saved decides two rows of glm_coop's table)
+    static constexpr int kLdsDoubles = 16 * DS + 2 * 16 * RS + Obs::A * 16 * PS;
     struct Prefetch {};                                 // nothing is requested ahead of barrier A
     using CoopRounds<GlmCoop<NCH, Obs>>::alive;
     using CoopRounds<GlmCoop<NCH, Obs>>::lane;
@@ -173,10 +245,11 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     const double2 *mu2, *tau2;   // lane-offset, device
     const double *cst;           // the constants, device
     double *tile;
-    int n, npad, nc;
+    int n, npad, nc, dx;         // dx: the columns of X (coordinates dx .. dx + Obs::A - 1 are the auxiliary ones)
     template <class State>
     IDHMC_DEV void init(const State &s, double *tile_, int *alive_, int lane_, int wv_)
     {
+        dx = s.D - Obs::A;
         x = s.lr_x;
         xt = s.lr_xt;
         y = s.lr_y;
@@ -192,8 +265,9 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         wv = wv_;
     }
     IDHMC_DEV double *rtile(int b) const { return tile + kR + (b & 1) * (16 * RS); }
+    IDHMC_DEV double *splane(int j) const { return tile + kS + j * (16 * PS); }
     IDHMC_DEV void prefetch(Prefetch &) const {}
-    // (2) for block b: Z tile zt, r into R[b & 1], v added to vacc
+    // (2) for block b: Z tile zt, r into R[b & 1], v added to vacc, the auxiliary scores to their planes
     IDHMC_DEV void zphase(int b, int zt, int kk, int jj, double (&vacc)[4]) const
     {
         const __amdgpu_buffer_rsrc_t rX = buf_rsrc(xt + 128 * b + 16 * zt);
@@ -216,13 +290,26 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         o.c = cst;
         o.K = Obs::K;
         o.nc = nc;
+        o.A = Obs::A;
         double *rt = rtile(b) + 16 * zt + jj;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {                  // row kk + 4 reg (chain), column jj (observation)
             double r, v;
-            Obs::terms(acc[reg], o, r, v);
+            double av[AN], u[AN];
+            if constexpr (Obs::A > 0) {
+#pragma unroll
+                for (int j = 0; j < AN; ++j) av[j] = splane(j)[(kk + 4 * reg) * PS + 128];   // a_j of this row's chain
+            }
+            glm_terms<Obs>(acc[reg], o, av, r, v, u);
             if (i >= n) { r = 0.0; v = 0.0; }
             vacc[reg] = vacc[reg] + v;
+            if constexpr (Obs::A > 0) {
+#pragma unroll
+                for (int j = 0; j < AN; ++j) {
+                    double *sp = splane(j) + (kk + 4 * reg) * PS + 16 * zt + jj;
+                    *sp = (b == 0 ? 0.0 : *sp) + (i >= n ? 0.0 : u[j]);
+                }
+            }
             rt[(kk + 4 * reg) * RS] = r;
         }
     }
@@ -284,15 +371,41 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     {
         Prefetch pf;
         double2 *row = reinterpret_cast<double2 *>(tile + kQ + wv * DS) + lane;
+        if constexpr (Obs::A > 0) {
 #pragma unroll
-        for (int j = 0; j < NCH; ++j) row[j * 64] = q.c[j];
+            for (int j = 0; j < NCH; ++j) {
+                const int c0 = 128 * j + 2 * lane;
+                row[j * 64] = make_double2(c0 >= dx ? 0.0 : q.c[j].x, c0 + 1 >= dx ? 0.0 : q.c[j].y);
+            }
+#pragma unroll
+            for (int jx = 0; jx < AN; ++jx) {
+                const double a = glm_coord<NCH>(q, dx + jx);
+                if (lane == (((dx + jx) & 127) >> 1)) splane(jx)[wv * PS + 128] = a;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) row[j * 64] = q.c[j];
+        }
         __syncthreads();                                      // barrier A
         multiply(pf);
         const double2 A = reinterpret_cast<const double2 *>(rtile(npad >> 7) + wv * RS)[lane];
+        double S[AN];
+        if constexpr (Obs::A > 0) {
+#pragma unroll
+            for (int jx = 0; jx < AN; ++jx) {
+                const double *sp = splane(jx) + wv * PS + 2 * lane;      // a row of 129 doubles is not 16-byte aligned: two loads
+                S[jx] = wave_sum(sp[0], sp[1]);
+            }
+        }
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
-            const double2 m = mu2[j * 64], t = tau2[j * 64], G = row[j * 64];
+            const double2 m = mu2[j * 64], t = tau2[j * 64];
+            double2 G = row[j * 64];
+            if constexpr (Obs::A > 0) {
+#pragma unroll
+                for (int jx = 0; jx < AN; ++jx) glm_place(G, j, dx + jx, lane, S[jx]);
+            }
             const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
             t0 = dfma(t.x * dx, dx, t0);
             t1 = dfma(t.y * dy, dy, t1);

@@ -39,6 +39,7 @@ struct DevState {
     const double *prec;       // [L][L]
     const double *lr_x, *lr_xt, *lr_y;   // IDHMC_MODEL_LOGISTIC_REGRESSION, _GLM: X [lr_npad][L], X' [L][lr_npad], Y [K][lr_npad], zero-padded
     int32_t lr_n, lr_npad;               // observations, and rounded up to a multiple of 128
+    int32_t lr_a;                        // a GLM's auxiliary coordinates: X has D - lr_a columns, the last lr_a coordinates are theirs (0: none)
     const double *user_params;   // IDHMC_MODEL_CUSTOM: the user's parameter blob; IDHMC_MODEL_GLM: its constants
     int64_t user_nparams;
     const void *jit;             // host only: the hipRTC module of a custom density or a GLM
@@ -108,7 +109,7 @@ constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
 struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
-int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0);   // glm_k: K of a GLM
+int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0);   // glm_k, glm_a: K and A of a GLM
 void jit_destroy(JitModule *m);
 hipError_t launch_eval_jit(const DevState &s, int random_q, hipStream_t st);
 hipError_t launch_leapfrog_jit(const DevState &s, double eps, int own, int n_steps, hipStream_t st);
@@ -127,8 +128,10 @@ hipError_t launch_leapfrog_logistic(const DevState &s, double eps, int own, int 
 hipError_t launch_stepsize_search_logistic(const DevState &s, hipStream_t st);
 hipError_t launch_local_optimum_logistic(const DevState &s, double penalty, int iterations, hipStream_t st);
 hipError_t launch_nuts_logistic(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
-bool glm_coop(int nch);   // NUTS gradients on the matrix cores (GlmCoop: logistic regression, GLM) at this padded length
-size_t glm_nuts_lds_bytes(int nch, bool shared);   // dynamic LDS of a GLM's NUTS kernel
+// NUTS gradients on the matrix cores (GlmCoop: logistic regression, GLM) at this padded length, with `aux` auxiliary coordinates
+// and a shared (or pooled) metric or a per-chain one
+bool glm_coop(int nch, int aux, bool shared);
+size_t glm_nuts_lds_bytes(int nch, bool shared, int aux);   // dynamic LDS of a GLM's NUTS kernel
 
 // ---- launchers (idhmc_kernels.hip / idhmc_nuts.hip) ------------------------------------------------
 hipError_t launch_eval(const DevState &s, hipStream_t st);                 // lq, grad from q

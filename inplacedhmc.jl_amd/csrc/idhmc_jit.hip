@@ -4,7 +4,8 @@
 // leapfrog, initial-stepsize search and the NUTS transition.  This is the device form of the reference's
 // downward boundary, logdensity_and_gradient!(grad, model, q, sptr) (src/kinetic_energy.jl:73).
 // A user's GLM (IDHMC_MODEL_GLM) is compiled the same way: its glm_observation becomes the observation policy of the
-// logistic regression's templates (idhmc_glm.hpp), the matrix-core form in the NUTS kernel where glm_coop says so.
+// logistic regression's templates (idhmc_glm.hpp), the matrix-core form in the NUTS kernel where glm_coop says so; with auxiliary
+// coordinates (IDHMC_MODEL_GLM_AUX) their number A is a compile-time constant of the policy, like K.
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 #include <dlfcn.h>
@@ -17,7 +18,7 @@
 
 namespace idhmc {
 
-int nuts_waves_per_block(int nch, int model, int shared_metric);
+int nuts_waves_per_block(int nch, int model, int shared_metric, int glm_aux);
 size_t nuts_lds_bytes(int L, bool lds_params, bool shared_metric, bool separable);
 
 struct JitModule {
@@ -46,7 +47,7 @@ static void put_log(char *log, size_t cap, const std::string &s)
     log[n] = 0;
 }
 
-int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k)
+int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k, int glm_a)
 {
     *out = nullptr;
     const std::string dir = library_dir();
@@ -63,8 +64,12 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
         src = "#include \"idhmc_general.hpp\"\n#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n#include \"idhmc_glm.hpp\"\n"
               "namespace idhmc {\n#line 1 \"user_glm.hip\"\n";
         src += source;
-        src += "\n#line 1 \"idhmc_glm_policy\"\nstruct UserGlmObs {\n    static constexpr int K = " + std::to_string(glm_k) + ";\n"
-               "    IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { glm_observation(z, o, r, v); }\n};\n}\n";
+        src += "\n#line 1 \"idhmc_glm_policy\"\nstruct UserGlmObs {\n    static constexpr int K = " + std::to_string(glm_k) +
+               ", A = " + std::to_string(glm_a) + ";\n";
+        // with auxiliary coordinates the observation also takes a (A of them) and returns the scores s
+        src += glm_a > 0 ? "    IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s) "
+                           "{ glm_observation(z, o, a, r, v, s); }\n};\n}\n"
+                         : "    IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { glm_observation(z, o, r, v); }\n};\n}\n";
     }
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), glm ? "idhmc_user_glm.hip" : "idhmc_custom_density.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
@@ -73,7 +78,7 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
     }
     const std::string n = std::to_string(s.nch);
     const std::string model = glm ? "idhmc::GlmWave<" + n + ", idhmc::UserGlmObs>" : "idhmc::JitModel<" + n + ">";
-    const std::string nuts_model = glm && glm_coop(s.nch) ? "idhmc::GlmCoop<" + n + ", idhmc::UserGlmObs>" : model;
+    const std::string nuts_model = glm && glm_coop(s.nch, glm_a, shared) ? "idhmc::GlmCoop<" + n + ", idhmc::UserGlmObs>" : model;
     constexpr int kKernels = 5;
     const std::string names[kKernels] = {"idhmc::k_eval_general<" + n + ", " + model + ">",
                                   "idhmc::k_leapfrog_general<" + n + ", " + model + ">",
@@ -130,7 +135,16 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
     }
     hiprtcDestroyProgram(&prog);
     // a GLM's NUTS kernel may be the cooperative form: its tiles are sized by the density (kLdsDoubles), not by the general rule
-    m->nuts_lds = glm ? glm_nuts_lds_bytes(s.nch, shared) : nuts_lds_bytes(s.L, false, shared, false);
+    m->nuts_lds = glm ? glm_nuts_lds_bytes(s.nch, shared, glm_a) : nuts_lds_bytes(s.L, false, shared, false);
+    // glm_coop's table keeps the cooperative form inside a CU's LDS; a kernel whose static part outgrew it is refused here, not at its launch
+    int static_lds = 0;
+    if (glm && hipFuncGetAttribute(&static_lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, m->f_nuts) == hipSuccess &&
+        m->nuts_lds + (size_t)static_lds > 160 * 1024) {
+        put_log(log, log_cap, "the NUTS kernel needs " + std::to_string(m->nuts_lds + (size_t)static_lds) + " bytes of LDS, a CU has 163840");
+        (void)hipModuleUnload(m->mod);
+        delete m;
+        return 5;
+    }
     if (m->nuts_lds > 48 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(m->f_nuts), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)m->nuts_lds) != hipSuccess) {
@@ -196,7 +210,7 @@ hipError_t launch_nuts_jit(const DevState &s, uint32_t iter, uint32_t flags, int
     const JitModule *m = static_cast<const JitModule *>(s.jit);
     if (!m) return hipErrorInvalidValue;
     struct { DevState s; uint32_t iter; uint32_t flags; } a{s, iter, flags};
-    return launch_packed(m->f_nuts, grid, nuts_waves_per_block(s.nch, s.model, s.minv_stride == 0) * 64, m->nuts_lds, st, a);
+    return launch_packed(m->f_nuts, grid, nuts_waves_per_block(s.nch, s.model, s.minv_stride == 0, s.lr_a) * 64, m->nuts_lds, st, a);
 }
 
 }  // namespace idhmc

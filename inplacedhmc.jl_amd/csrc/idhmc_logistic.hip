@@ -11,24 +11,47 @@
 
 namespace idhmc {
 
-// one 16-column tile of G per wavefront covers L <= 256
-bool glm_coop(int nch) { return nch <= 2; }
+// One 16-column tile of G per wavefront covers L <= 256.  Each auxiliary coordinate adds a [16][129] plane (16.5 KB) to the
+// workgroup's tiles, and the whole NUTS kernel has a CU's 160 KiB: the combinations that fit are DESIGN section 12's table (a
+// per-chain metric keeps M^-1 of 16 chains in LDS, a shared one is read from L2).  Every other shape runs one chain per wavefront.
+bool glm_coop(int nch, int aux, bool shared)
+{
+    if (nch == 1) return aux <= 4;
+    if (nch == 2) return aux <= 1 || (aux == 2 && shared);
+    return false;
+}
 
-// dynamic LDS of a GLM's NUTS kernel: the launch_nuts_t sizing of the form glm_coop picks (the tiles do not depend on the observation)
-template <int NCH>
+// the tiles depend on the observation through its A alone
+template <int AUX>
+struct GlmShapeObs { static constexpr int K = 1, A = AUX; };
+// dynamic LDS of a GLM's NUTS kernel: the launch_nuts_t sizing of the form glm_coop picks
+template <int NCH, int AUX>
 static size_t glm_nuts_lds_t(bool shared)
 {
-    using M = typename std::conditional<(NCH <= 2), GlmCoop<NCH, LogisticObs>, GlmWave<NCH, LogisticObs>>::type;
-    const int waves = nuts_waves(NCH, M::kSeparable, M::kCooperative, shared);
-    return sizeof(double) * nuts_lds_doubles(128 * NCH, false, shared, M::kSeparable, coop_lds_doubles<M>(), waves);
+    const bool coop = glm_coop(NCH, AUX, shared);
+    const int tiles = coop ? GlmCoop<NCH, GlmShapeObs<AUX>>::kLdsDoubles : 0;
+    const int waves = nuts_waves(NCH, false, coop, shared);
+    return sizeof(double) * nuts_lds_doubles(128 * NCH, false, shared, false, tiles, waves);
 }
-size_t glm_nuts_lds_bytes(int nch, bool shared)
+template <int NCH>
+static size_t glm_nuts_lds_a(bool shared, int aux)
+{
+    switch (aux) {
+    case 0: return glm_nuts_lds_t<NCH, 0>(shared);
+    case 1: return glm_nuts_lds_t<NCH, 1>(shared);
+    case 2: return glm_nuts_lds_t<NCH, 2>(shared);
+    case 3: return glm_nuts_lds_t<NCH, 3>(shared);
+    case 4: return glm_nuts_lds_t<NCH, 4>(shared);
+    default: return 0;
+    }
+}
+size_t glm_nuts_lds_bytes(int nch, bool shared, int aux)
 {
     switch (nch) {
-    case 1: return glm_nuts_lds_t<1>(shared);
-    case 2: return glm_nuts_lds_t<2>(shared);
-    case 4: return glm_nuts_lds_t<4>(shared);
-    case 8: return glm_nuts_lds_t<8>(shared);
+    case 1: return glm_nuts_lds_a<1>(shared, aux);
+    case 2: return glm_nuts_lds_a<2>(shared, aux);
+    case 4: return glm_nuts_lds_a<4>(shared, aux);
+    case 8: return glm_nuts_lds_a<8>(shared, aux);
     default: return 0;
     }
 }

@@ -15,10 +15,10 @@ int arena_vectors(int max_depth, int model, int L)
 // the dense MVN runs the workgroup-cooperative matrix-core gradient (DenseMvnCoop) when one 16-column tile per
 // wavefront covers the matrix (L <= 256), the per-wave GEMV (DenseMvn) above that
 static bool dense_coop(int nch) { return nch <= 2; }
-int nuts_waves_per_block(int nch, int model, int shared_metric)
+int nuts_waves_per_block(int nch, int model, int shared_metric, int glm_aux)
 {
     return nuts_waves(nch, model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN,
-                      (model == IDHMC_MODEL_DENSE_MVN && dense_coop(nch)) || ((model == IDHMC_MODEL_LOGISTIC_REGRESSION || model == IDHMC_MODEL_GLM) && glm_coop(nch)),
+                      (model == IDHMC_MODEL_DENSE_MVN && dense_coop(nch)) || ((model == IDHMC_MODEL_LOGISTIC_REGRESSION || model == IDHMC_MODEL_GLM) && glm_coop(nch, glm_aux, shared_metric != 0)),
                       shared_metric != 0);
 }
 // wavefronts per workgroup of the wide form of the kernel (0: the model/shape has none); the arena is sized for it
@@ -57,7 +57,7 @@ hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wi
     }
     const int WW = nuts_wide_waves_per_block(s.nch, s.model);
     wide = wide && WW > 0;
-    const int W = wide ? WW : nuts_waves_per_block(s.nch, s.model, s.minv_stride == 0);
+    const int W = wide ? WW : nuts_waves_per_block(s.nch, s.model, s.minv_stride == 0, s.lr_a);
     int64_t need = (s.C + W - 1) / W;
     const int64_t have = s.nslots / W;
     const int grid = (int)(need < have ? need : have);

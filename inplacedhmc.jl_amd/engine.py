@@ -12,6 +12,7 @@ TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_l
 assert TREE_STATS_DTYPE.itemsize == 32
 
 MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION, MODEL_GLM = 0, 1, 2, 3, 4, 5
+MODEL_GLM_AUX = 6
 EPS_PER_CHAIN, EPS_GLOBAL = 0, 1
 METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED = 0, 1, 2
 GRAD_STORE, GRAD_RECOMPUTE = 0, 1
@@ -146,17 +147,27 @@ def _prior(D, prior_mu, prior_tau):
     return mu, tau
 
 
-def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None):
+def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
     `source` defines  __device__ void glm_observation(double z, const GlmObs &o, double &r, double &v)  with v = -log p(y | z)
     and r = d log p(y | z) / dz (o.y[k], k < o.K: the observation's columns; o.c[j], j < o.nc: the constants); ready-made
-    sources are in inplacedhmc_jl_amd.glm.  prior_mu, prior_tau: (D,) or scalars, default 0 and 1, tau > 0."""
+    sources are in inplacedhmc_jl_amd.glm.  prior_mu, prior_tau: (D,) or scalars, default 0 and 1, tau > 0.
+
+    aux = A (1..4): the likelihood has A sampled auxiliary parameters (IDHMC_MODEL_GLM_AUX: a scale, a shape) that every
+    observation sees.  A chain's position is [beta (Dx = X.shape[1] coefficients) | a (A)], the model's D is Dx + A, all
+    unconstrained; `source` defines  glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+    with s[j] = d log p(y | z, a) / da_j, and v includes the a-dependent normalising terms.  prior_mu, prior_tau: scalars or
+    length Dx + A (the Gaussian prior covers the auxiliary coordinates).  The Model exposes Dx and A."""
+    if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
+        raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
+    A = int(aux)
     X = np.asarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
         raise ValueError("X must be a non-empty (n, D) matrix, got shape %s" % (X.shape,))
-    n, D = X.shape
+    n, Dx = X.shape
+    D = Dx + A
     if D > 1024:
         raise ValueError("a GLM is limited to D <= 1024 (D = %d)" % D)
     if not np.isfinite(X).all():
@@ -177,9 +188,13 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None):
         raise ValueError("a GLM needs HIP source defining glm_observation")
     mu, tau = _prior(D, prior_mu, prior_tau)
     K = Y.shape[1]
-    m = Model(MODEL_GLM, D, mu=mu, tau=tau, source=source,
-              params=np.concatenate([[float(K), float(c.size)], c, X.ravel(), Y.ravel()]))
-    m.n, m.K, m.nc = n, K, c.size
+    if A == 0:
+        m = Model(MODEL_GLM, D, mu=mu, tau=tau, source=source,
+                  params=np.concatenate([[float(K), float(c.size)], c, X.ravel(), Y.ravel()]))
+    else:
+        m = Model(MODEL_GLM_AUX, D, mu=mu, tau=tau, source=source,
+                  params=np.concatenate([[float(K), float(c.size), float(A)], c, X.ravel(), Y.ravel()]))
+    m.n, m.K, m.nc, m.Dx, m.A = n, K, c.size, Dx, A
     return m
 
 
@@ -291,6 +306,11 @@ class Engine:
 
     def padded_dim(self):
         return int(self.lib.idhmc_padded_dim(self.h))
+
+    def glm_form(self):
+        """the NUTS kernel's gradient of a logistic regression or a GLM: 0 one chain per wavefront, 1 the fp64 matrix cores;
+        -1 for every other model"""
+        return int(self.lib.idhmc_glm_form(self.h))
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -9,6 +9,23 @@ predictor below 709.78; everything else: every finite z).
   BINOMIAL_LOGIT      K = 2: y = (successes, trials);       logit p = z
   BERNOULLI_LOGIT     K = 1: y = 0 or 1;                    logit p = z  (the built-in LogisticRegression's arithmetic)
   STUDENT_T_IDENTITY  K = 1, constants (nu, sigma):         y = z + sigma t_nu
+
+Sources with sampled auxiliary parameters, for GLM(..., aux=A) (IDHMC_MODEL_GLM_AUX).  Each defines
+glm_observation(z, o, a, r, v, s): a[j], j < o.A, are the chain's auxiliary coordinates (unconstrained: the source applies the
+transform), v = -log p(y | z, a) including the terms that depend on a, r = d log p / dz, s[j] = d log p / da_j.
+
+  GAUSSIAN_IDENTITY_LOGSIGMA   K = 1, A = 1 (log sigma):                    y = z + sigma eps
+  STUDENT_T_IDENTITY_LOGSIGMA  K = 1, A = 1 (log sigma), constant nu:       y = z + sigma t_nu
+  WEIBULL_LOG_LOGSHAPE         K = 2: y = (log t, event: 1 observed, 0 right-censored), A = 1 (log shape k);  log scale = z
+
+Each is finite wherever the log density itself is, and that ends at the arguments of dexp:
+  GAUSSIAN_IDENTITY_LOGSIGMA   a0 > -709.78 (exp(-a0) finite) and |y - z| exp(-a0) < 1.3e154 (its square finite); every larger a0
+                               is fine (past 708.4 exp(-a0) is 0 and v = a0).  In particular every |a0| <= 300 with |y - z| <= 1e3.
+  STUDENT_T_IDENTITY_LOGSIGMA  -708.39 < a0 < 709.78 (sigma = exp(a0) neither 0 nor inf) and (y - z) / sigma finite.  In
+                               particular every |a0| <= 700 with |y - z| <= 1e3.
+  WEIBULL_LOG_LOGSHAPE         a0 < 709.78 (k = exp(a0) finite) and w = k (log t - z) < 709.78 (the cumulative hazard exp(w)
+                               finite); every more negative w is fine.
+Past those ends v is +inf or NaN, which the engine reads as l(q) = -inf: the ordinary rejected point.
 """
 
 POISSON_LOG = r"""
@@ -79,3 +96,53 @@ __device__ void glm_observation(double z, const GlmObs &o, double &r, double &v)
 # data columns and constants each source expects
 SHAPES = {"POISSON_LOG": (1, 0), "POISSON_LOG_OFFSET": (2, 0), "BINOMIAL_LOGIT": (2, 0), "BERNOULLI_LOGIT": (1, 0),
           "STUDENT_T_IDENTITY": (1, 2)}
+
+# u = (y - z) / sigma with sigma = exp(a0);  -log p = u^2 / 2 + a0
+GAUSSIAN_IDENTITY_LOGSIGMA = r"""
+__device__ void glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+{
+    const double w = dexp(-a[0]);
+    const double u = (o.y[0] - z) * w;
+    v = 0.5 * (u * u) + a[0];
+    r = u * w;
+    s[0] = u * u - 1.0;
+}
+"""
+
+# STUDENT_T_IDENTITY with sigma = exp(a0) sampled; the 1 / u branch past |u| = 1e100 as there
+STUDENT_T_IDENTITY_LOGSIGMA = r"""
+__device__ void glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+{
+    const double nu = o.c[0], sg = dexp(a[0]);
+    const double u = (o.y[0] - z) / sg;
+    const double h = 0.5 * (nu + 1.0);
+    if (__builtin_fabs(u) < 1e100) {
+        v = h * dlog1p(u * u / nu) + a[0];
+        r = (nu + 1.0) * u / (sg * (nu + u * u));
+        s[0] = (nu + 1.0) * (u * u) / (nu + u * u) - 1.0;
+    } else {
+        const double iu = 1.0 / u;
+        v = h * (2.0 * dlog(__builtin_fabs(u)) - dlog(nu) + dlog1p(nu * iu * iu)) + a[0];
+        r = (nu + 1.0) * iu / (sg * (nu * iu * iu + 1.0));
+        s[0] = (nu + 1.0) / (nu * iu * iu + 1.0) - 1.0;
+    }
+}
+"""
+
+# accelerated failure time: shape k = exp(a0), scale exp(z);  w = k (log t - z), cumulative hazard H = exp(w)
+# log p = delta (a0 - log t + w) - H  (delta = 0: right-censored at t, log S = -H)
+WEIBULL_LOG_LOGSHAPE = r"""
+__device__ void glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+{
+    const double lt = o.y[0], dl = o.y[1];
+    const double k = dexp(a[0]);
+    const double w = k * (lt - z);
+    const double H = dexp(w);
+    v = H - dl * (a[0] - lt + w);
+    r = k * (H - dl);
+    s[0] = dl + w * (dl - H);
+}
+"""
+
+# data columns, constants and auxiliary coordinates each of these expects
+AUX_SHAPES = {"GAUSSIAN_IDENTITY_LOGSIGMA": (1, 0, 1), "STUDENT_T_IDENTITY_LOGSIGMA": (1, 1, 1), "WEIBULL_LOG_LOGSHAPE": (2, 0, 1)}
