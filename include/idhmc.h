@@ -117,7 +117,17 @@ enum {
  * Dx = D - A < 1, and everything GLM refuses (with Dx in the place of D for X; the limits on D are on the total).  The same
  * kernels as GLM; the NUTS transition uses the matrix cores where the A further tiles fit a CU's LDS (L = 128: every A; L = 256: A = 1, or
  * A = 2 with a SHARED or POOLED metric), one chain per wavefront elsewhere:
- * idhmc_glm_form tells which. */
+ * idhmc_glm_form tells which.
+ *
+ * Coefficient groups with a sampled scale (idhmc_create_glm, below) -- a hierarchical GLM: H groups (1 <= H <= 4) of columns of X,
+ * each with a standard deviation that is itself sampled, in the non-centred parameterisation.  A chain's position is
+ * q = [u (Dx) | a (A) | omega (H)], D = Dx + A + H, all unconstrained; groups[c] in {-1, 0 .. H-1} for every column c (-1: in no group):
+ *   b_c = groups[c] >= 0 ? exp(omega_groups[c]) u_c : u_c,   z = X b
+ *   l(q) = -sum_i v(z_i, y_i, a) - 1/2 sum_{c < D} tau_c (q_c - mu_c)^2
+ * The Gaussian prior is on the sampled coordinates: with the defaults (mu = 0, tau = 1) a grouped coefficient is
+ * b_c ~ N(0, sigma_g^2), sigma_g = exp(omega_g) log-normal.  glm_observation is the one of GLM (A = 0) or GLM_AUX (A > 0),
+ * untouched.  The hierarchy adds no tile: idhmc_glm_form is what it is for the same (L, A, metric) without groups.  Draws come back
+ * in the sampled coordinates (u, a, omega). */
 enum {
     IDHMC_MODEL_ISO_GAUSSIAN = 0,   /* l(q) = -1/2 |q|^2                       */
     IDHMC_MODEL_DIAG_GAUSSIAN = 1,  /* l(q) = -1/2 sum tau_d (q_d - mu_d)^2    */
@@ -206,6 +216,21 @@ const char *idhmc_build_digest(void);
  * src/warmup.jl:100-129): kappa = I, Tree arena, state vectors. */
 int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
                  const idhmc_model_desc *model, const idhmc_options *opt, uint64_t seed);
+/* A GLM from an explicit descriptor: IDHMC_MODEL_GLM (A = 0) or IDHMC_MODEL_GLM_AUX (A > 0), optionally with H coefficient groups
+ * (above).  X is n x Dx and Y n x K row-major, constants has nc entries (may be NULL when nc = 0), groups has Dx entries (NULL iff
+ * H = 0), mu / tau have Dx + A + H entries or are NULL (0 and 1).  With H = 0 the context is the one idhmc_create makes of kinds 5
+ * and 6 for the same data.  Refused with IDHMC_ERR_BAD_ARG before the device is touched: everything those kinds refuse, and H
+ * outside 0..4, groups NULL with H > 0 (or given with H = 0), an id outside -1..H-1, a group that no column uses, Dx < 1. */
+typedef struct {
+    int64_t n;
+    int32_t Dx, K, nc, A, H;
+    const double *X, *Y, *constants;
+    const int32_t *groups;
+    const double *mu, *tau;
+    const char *source;
+} idhmc_glm_desc;
+int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                     const idhmc_glm_desc *glm, const idhmc_options *opt, uint64_t seed);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

@@ -19,6 +19,13 @@ class ModelDesc(C.Structure):
                 ("source", C.c_char_p), ("params", C.POINTER(C.c_double)), ("nparams", C.c_int64)]
 
 
+class GlmDesc(C.Structure):
+    _fields_ = [("n", C.c_int64), ("Dx", C.c_int32), ("K", C.c_int32), ("nc", C.c_int32), ("A", C.c_int32), ("H", C.c_int32),
+                ("X", C.POINTER(C.c_double)), ("Y", C.POINTER(C.c_double)), ("constants", C.POINTER(C.c_double)),
+                ("groups", C.POINTER(C.c_int32)), ("mu", C.POINTER(C.c_double)), ("tau", C.POINTER(C.c_double)),
+                ("source", C.c_char_p)]
+
+
 class Options(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("min_delta", C.c_double),
                 ("da_delta", C.c_double), ("da_gamma", C.c_double), ("da_kappa", C.c_double),
@@ -51,6 +58,7 @@ SYMBOLS = {
     "idhmc_version": (C.c_int, []),
     "idhmc_build_digest": (C.c_char_p, []),
     "idhmc_create": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(ModelDesc), C.POINTER(Options), _u64]),
+    "idhmc_create_glm": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(Options), _u64]),
     "idhmc_destroy": (C.c_int, [_vp]),
     "idhmc_set_stream": (C.c_int, [_vp, _vp]),
     "idhmc_synchronize": (C.c_int, [_vp]),

@@ -544,10 +544,19 @@ int idhmc_destroy(idhmc_ctx *c)
     return IDHMC_OK;
 }
 
-int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
-                 const idhmc_model_desc *model, const idhmc_options *opt_in, uint64_t seed)
+}  // extern "C"
+
+// a GLM handed over in parts (idhmc_create_glm) instead of packed into idhmc_model_desc::params
+struct GlmParts {
+    int64_t n;
+    int32_t K, nc, A, H;
+    const double *X, *Y, *c;
+    const int32_t *grp;        // [Dx], H > 0
+};
+// idhmc_create and idhmc_create_glm: one validation, one set-up
+static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                          const idhmc_model_desc *model, const idhmc_options *opt_in, uint64_t seed, const GlmParts *parts)
 {
-    if (!out || !model) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create: null argument");
     *out = nullptr;
     idhmc_options opt;
     if (opt_in) opt = *opt_in; else idhmc_default_options(&opt);
@@ -581,8 +590,25 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     int64_t lr_n = 0;              // observations of a logistic regression or a GLM
     // with auxiliary coordinates (GLM_AUX) [K, nc, A, c | X | Y]: X has Dx = D - A columns, the last A coordinates are not coefficients
     int64_t glm_k = 1, glm_nc = 0, glm_a = 0;
+    int64_t glm_h = 0;             // coefficient groups (idhmc_create_glm): the last H coordinates are their log scales
     int glm_head = 0;              // doubles in front of X
-    if (kind == IDHMC_MODEL_GLM && !glm_aux) {
+    if (parts) {
+        const char *what = glm_aux ? "GLM_AUX" : "GLM";
+        if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
+        if (parts->K < 1 || parts->K > 4) return fail(IDHMC_ERR_BAD_ARG, "%s: K = %d must be an integer in 1..4", what, parts->K);
+        if (parts->nc < 0 || parts->nc > 16) return fail(IDHMC_ERR_BAD_ARG, "%s: nc = %d must be an integer in 0..16", what, parts->nc);
+        if (parts->n < 1) return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld: at least one observation is needed", what, (long long)parts->n);
+        if (!parts->X || !parts->Y) return fail(IDHMC_ERR_BAD_ARG, "%s: X and Y are needed", what);
+        if (parts->nc > 0 && !parts->c) return fail(IDHMC_ERR_BAD_ARG, "%s: nc = %d constants are needed", what, parts->nc);
+        for (int j = 0; j < parts->nc; ++j)
+            if (!std::isfinite(parts->c[j])) return fail(IDHMC_ERR_BAD_ARG, "%s: constant c[%d] is not finite", what, j);
+        glm_k = parts->K;
+        glm_nc = parts->nc;
+        glm_a = parts->A;
+        glm_h = parts->H;
+        lr_n = parts->n;
+    }
+    if (kind == IDHMC_MODEL_GLM && !glm_aux && !parts) {
         const int D = model->D;
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
         if (model->nparams < 2 || !model->params) return fail(IDHMC_ERR_BAD_ARG, "GLM: params must begin with K and nc ([K, nc, c | X | Y])");
@@ -600,7 +626,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         lr_n = rest / (D + glm_k);
         glm_head = 2 + (int)glm_nc;
     }
-    if (glm_aux) {
+    if (glm_aux && !parts) {
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
         if (model->nparams < 3 || !model->params)
             return fail(IDHMC_ERR_BAD_ARG, "GLM_AUX: params must begin with K, nc and A ([K, nc, A, c | X | Y])");
@@ -626,7 +652,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         const bool glm = kind == IDHMC_MODEL_GLM;
         const char *what = glm_aux ? "GLM_AUX" : glm ? "GLM" : "logistic regression";
         const int D = model->D;
-        const int64_t Dx = D - glm_a;      // the columns of X
+        const int64_t Dx = D - glm_a - glm_h;      // the columns of X
         if (!glm) {
             if (model->nparams < 1 || model->nparams % (D + 1) != 0 || !model->params)
                 return fail(IDHMC_ERR_BAD_ARG, "logistic regression: nparams = %lld must be a positive multiple of D + 1 = %d ([X | y])",
@@ -639,7 +665,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
         if (npad * L > ((int64_t)1 << 27))
             return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
                         what, (long long)lr_n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
-        const double *X = model->params + glm_head, *y = X + lr_n * Dx;
+        const double *X = parts ? parts->X : model->params + glm_head, *y = parts ? parts->Y : X + lr_n * Dx;
         for (int64_t k = 0; k < lr_n * Dx; ++k)
             if (!std::isfinite(X[k])) return fail(IDHMC_ERR_BAD_ARG, "%s: X[%lld, %lld] is not finite", what, (long long)(k / Dx), (long long)(k % Dx));
         if (glm) {
@@ -717,6 +743,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     s.L = 128 * nch;
     s.model = kind;               // a GLM_AUX runs as a GLM with lr_a > 0
     s.lr_a = (int32_t)glm_a;
+    s.lr_h = (int32_t)glm_h;
     s.k0 = (uint32_t)seed;
     s.k1 = (uint32_t)(seed >> 32);
     s.first_chain = (uint32_t)first_chain_id;
@@ -800,8 +827,8 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
             // [L][n_pad], [K][n_pad]; a GLM's constants
             if (!model->tau) HIPCHK(launch_fill(tau, 1.0, s.D, c->stream));
             const bool glm = kind == IDHMC_MODEL_GLM;
-            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - glm_a, K = glm_k;     // D: the columns of X
-            const double *X = model->params + glm_head, *Y = X + n * D;
+            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - glm_a - glm_h, K = glm_k;     // D: the columns of X
+            const double *X = parts ? parts->X : model->params + glm_head, *Y = parts ? parts->Y : X + n * D;
             std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(K * npad), 0.0);
             for (int64_t i = 0; i < n; ++i)
                 for (int64_t k = 0; k < D; ++k) {
@@ -816,13 +843,23 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
             if (glm) {
                 double *dc = nullptr;
                 DALLOC(dc, glm_nc > 0 ? glm_nc : 1);
-                if (glm_nc > 0) HIPCHK(hipMemcpyAsync(dc, model->params + (glm_head - glm_nc), sizeof(double) * (size_t)glm_nc, hipMemcpyHostToDevice, c->stream));
+                if (glm_nc > 0) HIPCHK(hipMemcpyAsync(dc, parts ? parts->c : model->params + (glm_head - glm_nc), sizeof(double) * (size_t)glm_nc, hipMemcpyHostToDevice, c->stream));
                 s.user_params = dc;
                 s.user_nparams = glm_nc;
             }
             HIPCHK(hipMemcpyAsync(dx, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(dxt, hxt.data(), sizeof(double) * hxt.size(), hipMemcpyHostToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(dy, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, c->stream));
+            std::vector<int32_t> hg;
+            if (glm_h > 0) {
+                // the group of every coordinate: -1 past the columns of X (auxiliary coordinates, log scales, padding)
+                hg.assign((size_t)L, -1);
+                for (int64_t k = 0; k < D; ++k) hg[(size_t)k] = parts->grp[k];
+                int32_t *dg = nullptr;
+                DALLOC(dg, L);
+                HIPCHK(hipMemcpyAsync(dg, hg.data(), sizeof(int32_t) * hg.size(), hipMemcpyHostToDevice, c->stream));
+                s.lr_grp = dg;
+            }
             HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
             s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
             s.lr_n = (int32_t)n; s.lr_npad = (int32_t)npad;
@@ -861,7 +898,7 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     if (kind == IDHMC_MODEL_GLM) {
         static thread_local char jlog[400];
         jlog[0] = 0;
-        const int jrc = jit_build(s, model->source, &c->jit, jlog, sizeof jlog, (int)glm_k, (int)glm_a);
+        const int jrc = jit_build(s, model->source, &c->jit, jlog, sizeof jlog, (int)glm_k, (int)glm_a, (int)glm_h);
         if (jrc != 0) { idhmc_destroy(c); return fail(IDHMC_ERR_BAD_ARG, "GLM observation source did not compile (%d): %s", jrc, jlog); }
         s.jit = c->jit;
     }
@@ -881,6 +918,48 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     }
     *out = c;
     return IDHMC_OK;
+}
+
+extern "C" {
+
+int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                 const idhmc_model_desc *model, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !model) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create: null argument");
+    return create_context(out, device, nchains, first_chain_id, model, opt_in, seed, nullptr);
+}
+
+int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                     const idhmc_glm_desc *glm, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm: null argument");
+    *out = nullptr;
+    if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
+    if (glm->A < 0 || glm->A > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: A = %d must be an integer in 0..4", glm->A);
+    if (glm->H < 0 || glm->H > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d must be an integer in 0..4", glm->H);
+    if (glm->Dx > 1024 - glm->A - glm->H)
+        return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H = %lld: a GLM is limited to D <= 1024", (long long)glm->Dx + glm->A + glm->H);
+    if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
+    if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
+    if (glm->H > 0) {
+        bool used[4] = {false, false, false, false};
+        for (int c = 0; c < glm->Dx; ++c) {
+            const int32_t g = glm->groups[c];
+            if (g < -1 || g >= glm->H) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups[%d] = %d is outside -1..%d", c, g, glm->H - 1);
+            if (g >= 0) used[g] = true;
+        }
+        for (int g = 0; g < glm->H; ++g)
+            if (!used[g]) return fail(IDHMC_ERR_BAD_ARG, "GLM: group %d has no column", g);
+    }
+    idhmc_model_desc m;
+    memset(&m, 0, sizeof m);
+    m.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM;
+    m.D = glm->Dx + glm->A + glm->H;
+    m.mu = glm->mu;
+    m.tau = glm->tau;
+    m.source = glm->source;
+    const GlmParts parts{glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups};
+    return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
 }
 
 int idhmc_set_stream(idhmc_ctx *c, void *hip_stream)

@@ -33,6 +33,18 @@
 //   G_{Dx+j} = the canonical 128-residue tree over S_j (wave_sum, lane l holding residues 2l, 2l + 1);  g = dfma(-tau, d, G) as above
 //   T runs over all D coordinates (the prior covers a), P and l unchanged.
 // X has Dx columns: its device tiles hold +0 in columns >= Dx like every padded column.
+//
+// Coefficient groups with a sampled scale (idhmc_create_glm): Obs::H of them (0 for the policies above, 1..4),
+// q = [u (Dx) | a (A) | omega (H)], grp[c] in {-1, 0 .. H-1} for every coordinate (DevState::lr_grp; -1: not in a group, and every
+// coordinate >= Dx).  Non-centred: the coefficient of column c is b_c = u_c exp(omega_grp[c]).
+//   e_g   = dexp(omega_g), once per gradient, the same bits in every lane (omega_g read from its owner lane)
+//   b_c   = grp[c] >= 0 ? u_c * e_grp[c] : u_c (a select over the groups);  z_i = the fma chain over columns c < Dx of X[i][c] * b_c
+//   G_c, S_j, A[rho] as above;  w_c = G_c * b_c for grouped c;  W_g[rho], rho = c mod 128: plain additions over chunks ascending of the
+//   members' w_c, from +0 (a non-member adds +0);  G_{Dx+A+g} = the canonical 128-residue tree over W_g;  then G_c <- G_c * e_grp[c]
+//   g = dfma(-tau, d, G) with d = q - mu on the sampled coordinates, T over all D, P and l unchanged.
+// The per-wave form stages b instead of q (coordinates >= Dx raw: a_j is still found there); in the matrix-core form the requester
+// writes b as its Q row (+0 in every column >= Dx) before barrier A and applies the chain rule to the G row it reads after barrier
+// C: nothing between the barriers changes, no LDS is added.
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -72,6 +84,74 @@ IDHMC_DEV void glm_terms(double z, const GlmObs &o, const double *a, double &r, 
     else Obs::terms(z, o, r, v);
 }
 
+// The groups' scales e_g = dexp(omega_g), g < H <= 4, are four doubles handed around by value (those past H unused): out of an array or
+// a struct the compiler makes the select over the groups an indexed load, which costs every kernel scratch or LDS.
+// omega_g is coordinate c0 + g of q: read from the lane that owns it, dexp of the same bits in every lane
+template <int NCH>
+IDHMC_DEV double glm_group_scale(const Vec<NCH> &q, int c)
+{
+    return dexp(read_lane(glm_coord<NCH>(q, c), (c & 127) >> 1));
+}
+template <int NCH, int H>
+IDHMC_DEV void glm_group_scales(const Vec<NCH> &q, int c0, double &e0, double &e1, double &e2, double &e3)
+{
+    e0 = glm_group_scale<NCH>(q, c0);
+    if constexpr (H > 1) e1 = glm_group_scale<NCH>(q, c0 + 1);
+    if constexpr (H > 2) e2 = glm_group_scale<NCH>(q, c0 + 2);
+    if constexpr (H > 3) e3 = glm_group_scale<NCH>(q, c0 + 3);
+}
+// b of one coordinate: u e_id for a member of group id (a select over the groups), u itself for id = -1
+template <int H>
+IDHMC_DEV double glm_scaled(double u, int id, double e0, double e1, double e2, double e3)
+{
+    double s = e0;
+    if constexpr (H > 1) s = id == 1 ? e1 : s;
+    if constexpr (H > 2) s = id == 2 ? e2 : s;
+    if constexpr (H > 3) s = id == 3 ? e3 : s;
+    return id >= 0 ? u * s : u;
+}
+// W_g += w of a member of group G (a non-member adds +0, which leaves a sum that started at +0 as it is)
+template <int G>
+IDHMC_DEV void glm_group_add(double2 &W, int2 id, double wx, double wy)
+{
+    W.x = W.x + (id.x == G ? wx : 0.0);
+    W.y = W.y + (id.y == G ? wy : 0.0);
+}
+// the canonical tree over W_g, into coordinate c of the lane's G
+template <int NCH>
+IDHMC_DEV void glm_group_place(Vec<NCH> &G, double2 W, int c, int lane)
+{
+    const double S = wave_sum(W.x, W.y);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) glm_place(G.c[j], j, c, lane, S);
+}
+// the chain rule on the lane's G (complete but for the log scales' coordinates c0 .. c0 + H - 1): W_g into coordinate c0 + g,
+// then G_c e_grp[c] for the members.  b is computed again from q, not kept.
+template <int NCH, int H>
+IDHMC_DEV void glm_group_chain(Vec<NCH> &G, const Vec<NCH> &q, const int2 *grp2, int c0, int lane, double e0, double e1, double e2, double e3)
+{
+    double2 W0 = make_double2(0.0, 0.0), W1 = W0, W2 = W0, W3 = W0;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 id = grp2[j * 64];
+        const double wx = G.c[j].x * glm_scaled<H>(q.c[j].x, id.x, e0, e1, e2, e3), wy = G.c[j].y * glm_scaled<H>(q.c[j].y, id.y, e0, e1, e2, e3);
+        glm_group_add<0>(W0, id, wx, wy);
+        if constexpr (H > 1) glm_group_add<1>(W1, id, wx, wy);
+        if constexpr (H > 2) glm_group_add<2>(W2, id, wx, wy);
+        if constexpr (H > 3) glm_group_add<3>(W3, id, wx, wy);
+    }
+    glm_group_place<NCH>(G, W0, c0, lane);
+    if constexpr (H > 1) glm_group_place<NCH>(G, W1, c0 + 1, lane);
+    if constexpr (H > 2) glm_group_place<NCH>(G, W2, c0 + 2, lane);
+    if constexpr (H > 3) glm_group_place<NCH>(G, W3, c0 + 3, lane);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 id = grp2[j * 64];
+        G.c[j].x = glm_scaled<H>(G.c[j].x, id.x, e0, e1, e2, e3);
+        G.c[j].y = glm_scaled<H>(G.c[j].y, id.y, e0, e1, e2, e3);
+    }
+}
+
 // v_i and r_i of one observation (y is 0 or 1)
 IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 {
@@ -84,7 +164,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
-    static constexpr int K = 1, A = 0;
+    static constexpr int K = 1, A = 0, H = 0;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -97,12 +177,14 @@ struct GlmWave {
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = false;
     static constexpr int AN = Obs::A > 0 ? Obs::A : 1;
+    static constexpr int HN = Obs::H > 0 ? Obs::H : 1;
     const double *x, *xt;    // [npad][L], [L][npad], device
     const double2 *y2;       // [K][npad], lane-offset
     const double2 *mu2, *tau2;   // lane-offset, device
     const double *cst;       // the constants, device
+    const int2 *grp2;        // the group ids, lane-offset, device (Obs::H > 0)
     double *buf;             // this wavefront's LDS vector, L doubles
-    int D, n, npad, nc, lane;    // D: the columns of X (the coordinates D .. D + Obs::A - 1 are the auxiliary ones)
+    int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, then Obs::H log scales)
     template <class State>
     IDHMC_DEV void init(const State &s, double *lds_vec, int lane_)
     {
@@ -112,8 +194,9 @@ struct GlmWave {
         mu2 = reinterpret_cast<const double2 *>(s.mu) + lane_;
         tau2 = reinterpret_cast<const double2 *>(s.tau) + lane_;
         cst = s.user_params;
+        if constexpr (Obs::H > 0) grp2 = reinterpret_cast<const int2 *>(s.lr_grp) + lane_;
         buf = lds_vec;
-        D = s.D - Obs::A;
+        D = s.D - Obs::A - Obs::H;
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -129,12 +212,22 @@ struct GlmWave {
 #pragma unroll
             for (int j = 0; j < AN; ++j) s0[j] = s1[j] = 0.0;
         }
+        double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;         // the groups' scales
+        if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, D + Obs::A, e0, e1, e2, e3);
         double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;
         const int nb = npad >> 7;
         for (int b = 0; b < nb; ++b) {
             // q is staged again every block: r overwrites the first 128 doubles of the vector
+            // (with groups b = u e is staged, computed again per block rather than kept: ids -1 past the columns of X leave a raw)
 #pragma unroll
-            for (int j = 0; j < NCH; ++j) b2[j * 64] = q.c[j];
+            for (int j = 0; j < NCH; ++j) {
+                if constexpr (Obs::H > 0) {
+                    const int2 id = grp2[j * 64];
+                    b2[j * 64] = make_double2(glm_scaled<HN>(q.c[j].x, id.x, e0, e1, e2, e3), glm_scaled<HN>(q.c[j].y, id.y, e0, e1, e2, e3));
+                } else {
+                    b2[j * 64] = q.c[j];
+                }
+            }
             const double2 *xtp = reinterpret_cast<const double2 *>(xt + 128 * b) + lane;
             double zx = 0.0, zy = 0.0;
 #pragma unroll 4
@@ -193,6 +286,7 @@ struct GlmWave {
                 for (int j = 0; j < NCH; ++j) glm_place(G.c[j], j, D + jx, lane, S);
             }
         }
+        if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, q, grp2, D + Obs::A, lane, e0, e1, e2, e3);
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
@@ -234,6 +328,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     static constexpr int kZT = 8, kGT = L / 16;        // Z column tiles per block (wavefronts 8..15), G column tiles (0..L/16-1)
     static constexpr int kQ = 0, kR = 16 * DS;         // Q / G tile, then the two R tiles
     static constexpr int AN = Obs::A > 0 ? Obs::A : 1;
+    static constexpr int HN = Obs::H > 0 ? Obs::H : 1;
     static constexpr int kS = kR + 2 * 16 * RS;        // then the Obs::A score planes, [16][PS]: 128 residues and the slot of a_j
     static constexpr int PS = 129;                     // (one padding column, not RS's two: the 1 KB saved decides two rows of glm_coop's table)
     static constexpr int kLdsDoubles = 16 * DS + 2 * 16 * RS + Obs::A * 16 * PS;
@@ -244,12 +339,14 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     const double *x, *xt, *y;
     const double2 *mu2, *tau2;   // lane-offset, device
     const double *cst;           // the constants, device
+    const int2 *grp2;            // the group ids, lane-offset, device (Obs::H > 0)
     double *tile;
-    int n, npad, nc, dx;         // dx: the columns of X (coordinates dx .. dx + Obs::A - 1 are the auxiliary ones)
+    int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, then Obs::H log scales)
     template <class State>
     IDHMC_DEV void init(const State &s, double *tile_, int *alive_, int lane_, int wv_)
     {
-        dx = s.D - Obs::A;
+        dx = s.D - Obs::A - Obs::H;
+        if constexpr (Obs::H > 0) grp2 = reinterpret_cast<const int2 *>(s.lr_grp) + lane_;
         x = s.lr_x;
         xt = s.lr_xt;
         y = s.lr_y;
@@ -371,20 +468,32 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     {
         Prefetch pf;
         double2 *row = reinterpret_cast<double2 *>(tile + kQ + wv * DS) + lane;
-        if constexpr (Obs::A > 0) {
+        double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;        // the groups' scales
+        if constexpr (Obs::H > 0) {
+            // the Q row is b = u e, +0 in every column that is not one of X (the auxiliary ones and the log scales)
+            glm_group_scales<NCH, HN>(q, dx + Obs::A, e0, e1, e2, e3);
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                const int c0 = 128 * j + 2 * lane;
+                const int2 id = grp2[j * 64];
+                row[j * 64] = make_double2(c0 >= dx ? 0.0 : glm_scaled<HN>(q.c[j].x, id.x, e0, e1, e2, e3), c0 + 1 >= dx ? 0.0 : glm_scaled<HN>(q.c[j].y, id.y, e0, e1, e2, e3));
+            }
+        } else if constexpr (Obs::A > 0) {
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 const int c0 = 128 * j + 2 * lane;
                 row[j * 64] = make_double2(c0 >= dx ? 0.0 : q.c[j].x, c0 + 1 >= dx ? 0.0 : q.c[j].y);
             }
+        } else {
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) row[j * 64] = q.c[j];
+        }
+        if constexpr (Obs::A > 0) {
 #pragma unroll
             for (int jx = 0; jx < AN; ++jx) {
                 const double a = glm_coord<NCH>(q, dx + jx);
                 if (lane == (((dx + jx) & 127) >> 1)) splane(jx)[wv * PS + 128] = a;
             }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) row[j * 64] = q.c[j];
         }
         __syncthreads();                                      // barrier A
         multiply(pf);
@@ -397,14 +506,35 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 S[jx] = wave_sum(sp[0], sp[1]);
             }
         }
+        Vec<NCH> Gh;                                          // with groups: the whole G row, for the chain rule
+        if constexpr (Obs::H > 0) {
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                Gh.c[j] = row[j * 64];
+                if constexpr (Obs::A > 0) {
+#pragma unroll
+                    for (int jx = 0; jx < AN; ++jx) glm_place(Gh.c[j], j, dx + jx, lane, S[jx]);
+                }
+            }
+            // the scales again, from q: eight registers held across the round made the matrix loops of multiply() spill
+            int c0 = dx + Obs::A;
+            asm volatile("" : "+s"(c0));                      // (not the value of before barrier A kept alive)
+            glm_group_scales<NCH, HN>(q, c0, e0, e1, e2, e3);
+            glm_group_chain<NCH, HN>(Gh, q, grp2, c0, lane, e0, e1, e2, e3);
+        }
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
-            double2 G = row[j * 64];
-            if constexpr (Obs::A > 0) {
+            double2 G;
+            if constexpr (Obs::H > 0) {
+                G = Gh.c[j];
+            } else {
+                G = row[j * 64];
+                if constexpr (Obs::A > 0) {
 #pragma unroll
-                for (int jx = 0; jx < AN; ++jx) glm_place(G, j, dx + jx, lane, S[jx]);
+                    for (int jx = 0; jx < AN; ++jx) glm_place(G, j, dx + jx, lane, S[jx]);
+                }
             }
             const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
             t0 = dfma(t.x * dx, dx, t0);

@@ -39,7 +39,8 @@ struct DevState {
     const double *prec;       // [L][L]
     const double *lr_x, *lr_xt, *lr_y;   // IDHMC_MODEL_LOGISTIC_REGRESSION, _GLM: X [lr_npad][L], X' [L][lr_npad], Y [K][lr_npad], zero-padded
     int32_t lr_n, lr_npad;               // observations, and rounded up to a multiple of 128
-    int32_t lr_a;                        // a GLM's auxiliary coordinates: X has D - lr_a columns, the last lr_a coordinates are theirs (0: none)
+    int32_t lr_a;                        // a GLM's auxiliary coordinates: X has D - lr_a - lr_h columns, lr_a coordinates after them are theirs (0: none)
+    int32_t lr_h;                        // a GLM's coefficient groups: the last lr_h coordinates are their log scales (0: none)
     const double *user_params;   // IDHMC_MODEL_CUSTOM: the user's parameter blob; IDHMC_MODEL_GLM: its constants
     int64_t user_nparams;
     const void *jit;             // host only: the hipRTC module of a custom density or a GLM
@@ -76,6 +77,7 @@ struct DevState {
     DiagArrays diag;          // all null until idhmc_diag_reset
     unsigned long long *total_steps;  // [32]: the pulse the host polls = {[0] leapfrog steps, [1] abort code (an IDHMC_ERR_* a
                                       // chain raised: eps underflow)}; [2..9] cycle stamps of the diagnostic build (-DIDHMC_STAMPS)
+    const int32_t *lr_grp;    // [L] a GLM with lr_h > 0: the group of every coordinate, -1 for ungrouped and padded ones (null otherwise)
 };
 constexpr int kPulseAt = 0;
 // transition flag of the test suite only (see the XCD check in k_nuts); idhmc_nuts_transition(s) accept it on a context created
@@ -109,7 +111,7 @@ constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
 struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
-int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0);   // glm_k, glm_a: K and A of a GLM
+int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);   // K, A and H of a GLM
 void jit_destroy(JitModule *m);
 hipError_t launch_eval_jit(const DevState &s, int random_q, hipStream_t st);
 hipError_t launch_leapfrog_jit(const DevState &s, double eps, int own, int n_steps, hipStream_t st);

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ModelDesc, Options, check
+from ._lib import GlmDesc, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -59,6 +59,19 @@ class Model:
                                  ("prec", self.prec, (self.D, self.D))):
             if arr is not None and arr.shape != shape:
                 raise ValueError("%s must have shape %s" % (name, shape))
+
+    def glm_desc(self):
+        """the descriptor of idhmc_create_glm (a GLM with coefficient groups keeps X, Y and its constants as arrays)"""
+        d = GlmDesc(n=self.n, Dx=self.Dx, K=self.K, nc=self.nc, A=self.A, H=self.H, X=_dp(self.X), Y=_dp(self.Y), source=self.source)
+        if self.nc:
+            d.constants = _dp(self.constants)
+        if self.groups is not None:
+            d.groups = self.groups.ctypes.data_as(C.POINTER(C.c_int32))
+        if self.mu is not None:
+            d.mu = _dp(self.mu)
+        if self.tau is not None:
+            d.tau = _dp(self.tau)
+        return d
 
     def desc(self):
         d = ModelDesc(kind=self.kind, D=self.D)
@@ -147,7 +160,7 @@ def _prior(D, prior_mu, prior_tau):
     return mu, tau
 
 
-def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0):
+def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -159,7 +172,15 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0):
     observation sees.  A chain's position is [beta (Dx = X.shape[1] coefficients) | a (A)], the model's D is Dx + A, all
     unconstrained; `source` defines  glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     with s[j] = d log p(y | z, a) / da_j, and v includes the a-dependent normalising terms.  prior_mu, prior_tau: scalars or
-    length Dx + A (the Gaussian prior covers the auxiliary coordinates).  The Model exposes Dx and A."""
+    length Dx + A (the Gaussian prior covers the auxiliary coordinates).  The Model exposes Dx and A.
+
+    groups: a length-Dx integer sequence, groups[c] in {-1, 0 .. H-1} (-1: column c is in no group), H <= 4 -- a hierarchical GLM
+    (idhmc_create_glm): the columns of group g share a standard deviation sigma_g = exp(omega_g) that is itself sampled, in the
+    non-centred parameterisation.  A chain's position is [u (Dx) | a (A) | omega (H)], the model's D is Dx + A + H; the coefficient
+    of a grouped column is beta_c = exp(omega_g) u_c, of any other u_c; z = X beta.  The Gaussian prior is on the sampled
+    coordinates (prior_mu, prior_tau: scalars or length Dx + A + H): with the defaults beta_c ~ N(0, sigma_g^2) and omega_g ~ N(0, 1).
+    `source` is the one the same model takes without groups.  Draws come back in the sampled coordinates:
+    glm.coefficients(model, draws) gives beta, glm.group_scales(model, draws) the sigma_g.  The Model exposes H and groups."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -167,7 +188,25 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0):
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
         raise ValueError("X must be a non-empty (n, D) matrix, got shape %s" % (X.shape,))
     n, Dx = X.shape
-    D = Dx + A
+    grp, H = None, 0
+    if groups is not None:
+        grp = np.asarray(groups)
+        if grp.ndim != 1 or grp.shape[0] != Dx:
+            raise ValueError("groups must have one entry per column of X (%d), got shape %s" % (Dx, grp.shape))
+        if grp.dtype == np.bool_ or not np.issubdtype(grp.dtype, np.integer):
+            raise ValueError("groups must be integers (-1: no group), got dtype %s" % grp.dtype)
+        if grp.min() < -1:
+            raise ValueError("a group id is -1 (no group) or 0 .. H-1, got %d" % grp.min())
+        H = int(grp.max()) + 1
+        if H > 4:
+            raise ValueError("at most 4 groups (ids 0..3), got id %d" % (H - 1))
+        for g in range(H):
+            if not (grp == g).any():
+                raise ValueError("group %d has no column (the ids in use must be 0 .. H-1)" % g)
+        grp = np.ascontiguousarray(grp, dtype=np.int32)
+        if H == 0:
+            grp = None                                          # every column ungrouped: the model without groups
+    D = Dx + A + H
     if D > 1024:
         raise ValueError("a GLM is limited to D <= 1024 (D = %d)" % D)
     if not np.isfinite(X).all():
@@ -188,13 +227,17 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0):
         raise ValueError("a GLM needs HIP source defining glm_observation")
     mu, tau = _prior(D, prior_mu, prior_tau)
     K = Y.shape[1]
-    if A == 0:
+    if H > 0:
+        # handed over in parts (idhmc_create_glm): the packed params are not stretched for the groups
+        m = Model(MODEL_GLM_AUX if A else MODEL_GLM, D, mu=mu, tau=tau, source=source)
+        m.X, m.Y, m.constants = np.ascontiguousarray(X), np.ascontiguousarray(Y), np.ascontiguousarray(c)
+    elif A == 0:
         m = Model(MODEL_GLM, D, mu=mu, tau=tau, source=source,
                   params=np.concatenate([[float(K), float(c.size)], c, X.ravel(), Y.ravel()]))
     else:
         m = Model(MODEL_GLM_AUX, D, mu=mu, tau=tau, source=source,
                   params=np.concatenate([[float(K), float(c.size), float(A)], c, X.ravel(), Y.ravel()]))
-    m.n, m.K, m.nc, m.Dx, m.A = n, K, c.size, Dx, A
+    m.n, m.K, m.nc, m.Dx, m.A, m.H, m.groups = n, K, c.size, Dx, A, H, grp
     return m
 
 
@@ -217,9 +260,13 @@ class Engine:
         self.opt = options if options is not None else default_options()
         self.C, self.D = int(nchains), model.D
         h = C.c_void_p()
-        desc = model.desc()
-        check(self.lib.idhmc_create(C.byref(h), device, self.C, first_chain, C.byref(desc),
-                                    C.byref(self.opt), seed))
+        if getattr(model, "H", 0) > 0:
+            desc = model.glm_desc()
+            check(self.lib.idhmc_create_glm(C.byref(h), device, self.C, first_chain, C.byref(desc), C.byref(self.opt), seed))
+        else:
+            desc = model.desc()
+            check(self.lib.idhmc_create(C.byref(h), device, self.C, first_chain, C.byref(desc),
+                                        C.byref(self.opt), seed))
         self.h = h
         self._hook = None
 

@@ -26,7 +26,12 @@ Each is finite wherever the log density itself is, and that ends at the argument
   WEIBULL_LOG_LOGSHAPE         a0 < 709.78 (k = exp(a0) finite) and w = k (log t - z) < 709.78 (the cumulative hazard exp(w)
                                finite); every more negative w is fine.
 Past those ends v is +inf or NaN, which the engine reads as l(q) = -inf: the ordinary rejected point.
+
+Every source above works unchanged with coefficient groups, GLM(..., groups=...): the sampled coordinates are
+[u (Dx) | a (A) | omega (H)]; coefficients(model, draws) turns draws into beta = s * u, group_scales(model, draws) into
+sigma = exp(omega).
 """
+import numpy as np
 
 POISSON_LOG = r"""
 __device__ void glm_observation(double z, const GlmObs &o, double &r, double &v)
@@ -146,3 +151,25 @@ __device__ void glm_observation(double z, const GlmObs &o, const double *a, doub
 
 # data columns, constants and auxiliary coordinates each of these expects
 AUX_SHAPES = {"GAUSSIAN_IDENTITY_LOGSIGMA": (1, 0, 1), "STUDENT_T_IDENTITY_LOGSIGMA": (1, 1, 1), "WEIBULL_LOG_LOGSHAPE": (2, 0, 1)}
+
+
+def group_scales(model, draws):
+    """sigma_g = exp(omega_g) of a GLM with coefficient groups, shape draws.shape[:-1] + (H,) (H = 0: an empty last axis)"""
+    draws = np.asarray(draws, dtype=np.float64)
+    Dx, A, H = model.Dx, model.A, getattr(model, "H", 0)
+    if draws.shape[-1] != Dx + A + H:
+        raise ValueError("draws must have %d coordinates along the last axis, got %d" % (Dx + A + H, draws.shape[-1]))
+    return np.exp(draws[..., Dx + A:])
+
+
+def coefficients(model, draws):
+    """the coefficients beta = s * u of a GLM from draws in the sampled coordinates, shape draws.shape[:-1] + (Dx,):
+    beta_c = exp(omega_g) u_c for a column of group g, u_c for a column in no group (and for a model without groups)"""
+    draws = np.asarray(draws, dtype=np.float64)
+    sigma = group_scales(model, draws)
+    u = draws[..., :model.Dx]
+    if sigma.shape[-1] == 0:
+        return u.copy()
+    grp = np.asarray(model.groups)
+    s = np.where(grp >= 0, sigma[..., np.maximum(grp, 0)], 1.0)
+    return s * u

@@ -10,8 +10,13 @@ GLM against the same arithmetic as a custom source; its shapes name the columns 
 GAUSSIAN_IDENTITY_LOGSIGMA (A = 1) and a four-parameter Gaussian (A = 4) on the same design, each with the form its NUTS kernel
 runs (idhmc_glm_form).
 
-    python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian] [--transitions 5]
-                              [--aux-cost] [--metric shared|per_chain]
+The `hier` pair (GLM(..., groups=...)): a Bernoulli regression whose last min(40, Dx - 5) columns are one-hot
+levels of one group with a sampled scale, on the matrix cores against the same arithmetic as a custom source; its shapes name the
+columns of X (the chains have one coordinate more, the group's log scale).  --hier-cost adds the same design with H = 0, 1 and 4
+groups (the one-hot columns dealt round to the groups), each started from its own Laplace approximation.
+
+    python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier] [--transitions 5]
+                              [--aux-cost] [--hier-cost] [--metric shared|per_chain] [--lockstep]
 """
 import argparse
 import json
@@ -66,6 +71,45 @@ CUSTOM_GAUSSIAN_SRC = CUSTOM_SRC.replace(_LR_TERMS, r"""__device__ void lr_terms
     }
     double t0 = 0.0, t1 = 0.0;""")
 assert CUSTOM_GAUSSIAN_SRC.count("la,") == 2 and "s1 = s1 +" in CUSTOM_GAUSSIAN_SRC and "wave_sum(s0, s1)" in CUSTOM_GAUSSIAN_SRC
+
+# the Bernoulli likelihood with one coefficient group as a custom source, section 13's arithmetic: the chain's last coordinate is the
+# group's log scale, params carry the group of every coordinate (as doubles, -1: none) behind tau; b = u e is staged instead of q,
+# the chain rule follows G
+CUSTOM_HIER_SRC = CUSTOM_SRC.replace("*mu = y + npad, *tau = mu + L;", "*mu = y + npad, *tau = mu + L, *grp = tau + L;"
+).replace("    double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;", r"""    const int co = D - 1;
+    double om = 0.0;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) om = (co >> 7) == j ? ((co & 1) ? q.c[j].y : q.c[j].x) : om;
+    const double e = dexp(read_lane(om, (co & 127) >> 1));
+    const double2 *g2 = reinterpret_cast<const double2 *>(grp) + lane;
+    double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;"""
+).replace("        for (int j = 0; j < NCH; ++j) b2[j * 64] = q.c[j];", r"""        for (int j = 0; j < NCH; ++j) {
+            const double2 id = g2[j * 64];
+            b2[j * 64] = make_double2(id.x >= 0.0 ? q.c[j].x * e : q.c[j].x, id.y >= 0.0 ? q.c[j].y * e : q.c[j].y);
+        }"""
+).replace("for (int c = 0; c < D; ++c) {", "for (int c = 0; c < D - 1; ++c) {"
+).replace("    double t0 = 0.0, t1 = 0.0;", r"""    {
+        double w0 = 0.0, w1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const double2 id = g2[j * 64];
+            const double bx = id.x >= 0.0 ? q.c[j].x * e : q.c[j].x, by = id.y >= 0.0 ? q.c[j].y * e : q.c[j].y;
+            w0 = w0 + (id.x >= 0.0 ? G.c[j].x * bx : 0.0);
+            w1 = w1 + (id.y >= 0.0 ? G.c[j].y * by : 0.0);
+        }
+        const double W = wave_sum(w0, w1);
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const bool here = (co >> 7) == j && lane == ((co & 127) >> 1);
+            G.c[j].x = here && !(co & 1) ? W : G.c[j].x;
+            G.c[j].y = here && (co & 1) ? W : G.c[j].y;
+            const double2 id = g2[j * 64];
+            G.c[j].x = id.x >= 0.0 ? G.c[j].x * e : G.c[j].x;
+            G.c[j].y = id.y >= 0.0 ? G.c[j].y * e : G.c[j].y;
+        }
+    }
+    double t0 = 0.0, t1 = 0.0;""")
+assert CUSTOM_HIER_SRC.count("g2[j * 64]") == 3 and "c < D - 1" in CUSTOM_HIER_SRC and "*grp = tau + L" in CUSTOM_HIER_SRC
 
 # a fixed-sigma Gaussian as a plain GLM (constant log sigma), and one with four auxiliary parameters (mean and log scale move with y1)
 GAUSSIAN_FIXED_SRC = r"""
@@ -128,8 +172,80 @@ def poisson_problem(n, D, seed):
     return X, y, q, np.linalg.inv(H)
 
 
+def hier_groups(Dx, H):
+    """the last min(40, Dx - 5) columns are the grouped ones, dealt round to the H groups (H = 0: no groups)"""
+    grp = np.full(Dx, -1, np.int32)
+    if H > 0:
+        k = min(40, Dx - 5)
+        grp[Dx - k:] = np.arange(k) % H
+    return grp
+
+
+def hier_density(X, y, grp, q):
+    """(l, grad l) of the Bernoulli model with groups, prior N(0, I) on the sampled coordinates q = [u | omega]"""
+    Dx, H = X.shape[1], int(grp.max()) + 1
+    s = np.where(grp >= 0, np.exp(q[Dx:])[np.maximum(grp, 0)], 1.0) if H else np.ones(Dx)
+    b = s * q[:Dx]
+    z = X @ b
+    G = X.T @ (y - 1.0 / (1.0 + np.exp(-z)))
+    g = np.concatenate([s * G, [np.sum((G * b)[grp == k]) for k in range(H)]]) - q
+    return np.sum(y * z - np.logaddexp(0.0, z)) - 0.5 * q @ q, g
+
+
+def hier_laplace(X, y, grp):
+    """the MAP in (u, omega) by damped Newton steps on a finite-difference Hessian, and the Laplace covariance there"""
+    Dx, H = X.shape[1], int(grp.max()) + 1
+    D = Dx + H
+    q = np.r_[np.zeros(Dx), np.full(H, np.log(0.6))]
+    q[:Dx] = 0.1
+
+    def hessian(q):
+        Hm = np.empty((D, D))
+        for c in range(D):
+            d = np.zeros(D)
+            d[c] = 1e-5
+            Hm[c] = (hier_density(X, y, grp, q + d)[1] - hier_density(X, y, grp, q - d)[1]) / 2e-5
+        return -0.5 * (Hm + Hm.T)
+    for _ in range(60):
+        l, g = hier_density(X, y, grp, q)
+        Hm = hessian(q)
+        w = np.linalg.eigvalsh(Hm)[0]
+        step = np.linalg.solve(Hm + max(0.0, 0.1 - w) * np.eye(D), g)      # a positive definite model of -l
+        t = 1.0
+        while not hier_density(X, y, grp, q + t * step)[0] >= l and t > 1e-6:
+            t *= 0.5
+        q = q + t * step
+        if np.abs(t * step).max() < 1e-10:
+            break
+    Hm = hessian(q)
+    w, V = np.linalg.eigh(Hm)
+    return q, (V / np.maximum(w, 1e-3)) @ V.T
+
+
+def hier_problem(n, D, seed, H=1):
+    """Bernoulli responses from a design whose grouped columns are one-hot levels (scale 0.6); (X, y, MAP, Laplace covariance)"""
+    rng = np.random.default_rng(seed)
+    grp = hier_groups(D, 1)
+    X = rng.standard_normal((n, D)) / np.sqrt(D)
+    X[:, 0] = 1.0
+    cols = np.flatnonzero(grp >= 0)
+    X[:, cols] = 0.0
+    X[np.arange(n), cols[rng.integers(0, cols.size, n)]] = 1.0
+    beta = np.where(grp >= 0, 0.6, 1.0) * rng.standard_normal(D)
+    y = (rng.uniform(size=n) < 1.0 / (1.0 + np.exp(-X @ beta))).astype(np.float64)
+    q, cov = hier_laplace(X, y, hier_groups(D, H))
+    return X, y, q, cov
+
+
 def model(form, X, y, q_map=None):
     D = X.shape[1]
+    if form.startswith("glm_hier"):                   # glm_hier (H = 1), glm_hier_h0, glm_hier_h4
+        H = int(form[-1]) if form[-2:-1] == "h" else 1
+        return pkg.GLM(X, y, pkg.glm.BERNOULLI_LOGIT, groups=hier_groups(D, H) if H else None)
+    if form == "custom_hier":                         # the chain's D + 1 coordinates: a zero column of X in the place of the log scale
+        grp = np.full(padded(D + 1), -1.0)
+        grp[:D] = hier_groups(D, 1)
+        return pkg.CustomDensity(D + 1, CUSTOM_HIER_SRC, np.concatenate([custom_params(np.c_[X, np.zeros(len(X))], y), grp]))
     if form == "glm_gaussian":
         return pkg.GLM(X, y, pkg.glm.GAUSSIAN_IDENTITY_LOGSIGMA, aux=1)
     if form == "custom_gaussian":                     # the chain's D + 1 coordinates: a zero column of X in the place of log sigma
@@ -147,10 +263,13 @@ def model(form, X, y, q_map=None):
     return pkg.LogisticRegression(X, y)
 
 
+LOCKSTEP = False    # --lockstep: every tree runs to max_depth = 6 (63 steps), see main()
+
+
 def run(form, X, y, q_map, cov, C, T, seed=1, metric=None):
     t0 = time.perf_counter()
-    eng = pkg.Engine(model(form, X, y, q_map), C, pkg.default_options(metric_mode=pkg.METRIC_SHARED if metric is None else metric, max_depth=10),
-                     seed=seed)
+    eng = pkg.Engine(model(form, X, y, q_map), C, pkg.default_options(metric_mode=pkg.METRIC_SHARED if metric is None else metric,
+                                                                      max_depth=6 if LOCKSTEP else 10), seed=seed)
     create_s = time.perf_counter() - t0
     Dx = X.shape[1]
     if form == "glm_gaussian_fixed":                  # the coefficients alone
@@ -163,7 +282,7 @@ def run(form, X, y, q_map, cov, C, T, seed=1, metric=None):
     D = q_map.size
     rng = np.random.default_rng(seed)
     eng.set_q(q_map + rng.standard_normal((C, D)) @ np.linalg.cholesky(cov).T)
-    eps = 0.5 * np.sqrt(np.linalg.eigvalsh(cov)[0])
+    eps = 0.5 * np.sqrt(np.linalg.eigvalsh(cov)[0]) * (1e-3 if LOCKSTEP else 1.0)
     eng.set_eps(eps)
     head = (eng.lq[:64].copy(), eng.grad[:64].copy())
     eng.nuts_transitions(1, 2)                        # warm-up (and the module's first launch)
@@ -183,7 +302,8 @@ def run(form, X, y, q_map, cov, C, T, seed=1, metric=None):
 
 PAIRS = {"poisson": ("glm_poisson", "custom_poisson", poisson_problem),
          "logistic": ("glm_logistic", "builtin_logistic", logistic_problem),
-         "gaussian": ("glm_gaussian", "custom_gaussian", gaussian_problem)}
+         "gaussian": ("glm_gaussian", "custom_gaussian", gaussian_problem),
+         "hier": ("glm_hier", "custom_hier", hier_problem)}
 
 
 def main():
@@ -193,8 +313,13 @@ def main():
     ap.add_argument("--pairs", default="poisson,logistic")
     ap.add_argument("--transitions", type=int, default=5)
     ap.add_argument("--aux-cost", action="store_true", help="the fixed-sigma, A = 1 and A = 4 Gaussians per shape (DESIGN section 12)")
+    ap.add_argument("--hier-cost", action="store_true", help="the hier pair's design with H = 0, 1 and 4 groups per shape (DESIGN section 13)")
     ap.add_argument("--metric", default="shared", choices=["shared", "per_chain"])
+    ap.add_argument("--lockstep", action="store_true", help="eps / 1000 and max_depth = 6: every tree of every density takes the same 63 "
+                    "steps, so steps/s compares the cost per gradient and not the trees")
     a = ap.parse_args()
+    global LOCKSTEP
+    LOCKSTEP = a.lockstep
     metric = pkg.METRIC_SHARED if a.metric == "shared" else pkg.METRIC_PER_CHAIN
     res = dict(device_peak_fp64_mfma_flops=PEAK_FP64_MFMA, transitions_per_launch=a.transitions, results=[])
     for shape in a.shapes.split(","):
@@ -206,6 +331,16 @@ def main():
             for C in (int(c) for c in a.chains.split(",")):
                 row = dict(pair="aux_cost", D=D, n=n, chains=C, metric=a.metric)
                 for f in ("glm_gaussian_fixed", "glm_gaussian", "glm_gaussian_a4"):
+                    row[f] = run(f, X, y, q_map, cov, C, a.transitions, metric=metric)[0]
+                    print("# D=%d n=%d C=%d %s (form %d): %.3e leapfrog steps/s, depth %.2f" %
+                          (D, n, C, f, row[f]["glm_form"], row[f]["leapfrog_steps_per_s"], row[f]["mean_depth"]), file=sys.stderr, flush=True)
+                res["results"].append(row)
+        if a.hier_cost:
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="hier_cost", D=D, n=n, chains=C, metric=a.metric)
+                for H in (0, 1, 4):
+                    f = "glm_hier_h%d" % H
+                    X, y, q_map, cov = hier_problem(n, D, seed=D * 7919 + n, H=H)
                     row[f] = run(f, X, y, q_map, cov, C, a.transitions, metric=metric)[0]
                     print("# D=%d n=%d C=%d %s (form %d): %.3e leapfrog steps/s, depth %.2f" %
                           (D, n, C, f, row[f]["glm_form"], row[f]["leapfrog_steps_per_s"], row[f]["mean_depth"]), file=sys.stderr, flush=True)
