@@ -73,8 +73,8 @@ enum {
  * a non-finite return value is treated as -Inf (src/kinetic_energy.jl:80-84).  ctx gives `params`
  * (the `params` array below, in device memory), `nparams`, `D`, `lane`, and `lds` -- one L-double
  * scratch vector in LDS private to the wavefront.  Everything in inplacedhmc.jl_amd/csrc/idhmc_math.hpp
- * and idhmc_device.hpp is in scope (wave_sum, dfma, dlog, dexp, ...).  Compile errors are returned
- * through idhmc_last_error().
+ * and idhmc_device.hpp is in scope (wave_sum, dfma, dlog, dexp, dlog1p, dlgamma_psi, dlgamma, ddigamma, ...).
+ * Compile errors are returned through idhmc_last_error().
  *
  * IDHMC_MODEL_LOGISTIC_REGRESSION -- Bayesian logistic regression with a Gaussian prior, the data shared by every chain:
  *   l(q) = sum_i [y_i z_i - softplus(z_i)] - 1/2 sum_c tau_c (q_c - mu_c)^2,   z = X q
@@ -96,8 +96,9 @@ enum {
  * o.y[k], k < o.K: this observation's data columns (1 <= K <= 4); o.c[j], j < o.nc: the model's constants (device memory).
  * It returns v = -log p(y | z) (up to a term that depends on the data only) and r = d log p(y | z) / dz.  It is called for
  * padded observations too (z = 0, y = 0), whose results are then discarded.  The helpers of idhmc_math.hpp are in scope (dexp,
- * dlog, dlog1p, dfma, ...); the build uses -ffp-contract=off, so only explicit dfma calls fuse.  Compile errors are returned
- * through idhmc_last_error().  `params` is [K, nc, c (nc) | X row-major (n x D) | Y row-major (n x K)], so
+ * dlog, dlog1p, dfma, ...; dlgamma_psi(x, lg, psi) gives ln Gamma(x) and its derivative psi(x) for x > 0 from one call, dlgamma(x)
+ * and ddigamma(x) one of the two: +inf and NaN for x <= 0, so a dispersion that underflows is a rejected point); the build uses
+ * -ffp-contract=off, so only explicit dfma calls fuse.  Compile errors are returned through idhmc_last_error().  `params` is [K, nc, c (nc) | X row-major (n x D) | Y row-major (n x K)], so
  * n = (nparams - 2 - nc) / (D + K).  Refused with IDHMC_ERR_BAD_ARG before the device is touched: K not an integer in 1..4,
  * nc not an integer in 0..16, a remainder that is not a positive multiple of D + K, a non-finite value in X, Y or c, a missing
  * or empty source, and whatever LOGISTIC_REGRESSION refuses of the prior, D and n_pad L.

@@ -43,6 +43,7 @@ constexpr double kLn2Lo = 1.90821492927058770002e-10;
 constexpr double kInvLn2 = 1.44269504088896338700e+00;
 constexpr double kHalfPi = 1.57079632679489661923;
 constexpr double kInf = __builtin_huge_val();
+constexpr double kHalfLn2Pi = 9.18938533204672741780e-01;   // ln(2 pi) / 2
 
 // ln x: x = 2^e m with m in (sqrt(1/2), sqrt(2)];  ln m = 2 atanh((m-1)/(m+1)), series to s^23
 IDHMC_DEV double dlog(double x)
@@ -112,6 +113,58 @@ IDHMC_DEV double dlog1p(double x)
     if (u == kInf) return u;
     const double d = u - 1.0;
     return dlog(u) * (x / d);
+}
+
+// ln Gamma(x) and psi(x) = d/dx ln Gamma(x) for x > 0, both from one call: the recurrence shifts x to w >= 8
+// (p the product and h the harmonic sum of the steps), then the Stirling series in z = 1 / w^2, seven terms each.  Built from
+// add / mul / div / fma and dlog only, with the association fixed, so a host restatement gives the same bits.  x <= 0 (either
+// zero included): lg = +inf, psi = NaN; x = +inf: both +inf; NaN: both NaN.  Below 2^-1024 1 / x overflows and psi is -inf.
+// The shift is a loop on purpose (at most 8 rounds per lane): unrolled it is eight divisions' worth of registers in kernels that
+// are capped at 128.
+IDHMC_DEV void dlgamma_psi(double x, double &lg, double &psi)
+{
+    if (x != x) { lg = x; psi = x; return; }
+    if (!(x > 0.0)) { lg = kInf; psi = __builtin_nan(""); return; }
+    if (x == kInf) { lg = x; psi = x; return; }
+    double w = x, p = 1.0, h = 0.0;
+#pragma clang loop unroll(disable)
+    while (w < 8.0) {
+        p = p * w;
+        h = h + 1.0 / w;
+        w = w + 1.0;
+    }
+    const double lw = dlog(w);
+    const double iw = 1.0 / w;
+    const double z = iw * iw;
+    double S = 1.0 / 156.0;
+    S = dfma_c(S, z, -691.0 / 360360.0);
+    S = dfma_c(S, z, 1.0 / 1188.0);
+    S = dfma_c(S, z, -1.0 / 1680.0);
+    S = dfma_c(S, z, 1.0 / 1260.0);
+    S = dfma_c(S, z, -1.0 / 360.0);
+    S = dfma_c(S, z, 1.0 / 12.0);
+    double T = 1.0 / 12.0;
+    T = dfma_c(T, z, -691.0 / 32760.0);
+    T = dfma_c(T, z, 1.0 / 132.0);
+    T = dfma_c(T, z, -1.0 / 240.0);
+    T = dfma_c(T, z, 1.0 / 252.0);
+    T = dfma_c(T, z, -1.0 / 120.0);
+    T = dfma_c(T, z, 1.0 / 12.0);
+    lg = (((w - 0.5) * lw - w) + kHalfLn2Pi) + iw * S;
+    if (x < 8.0) lg = lg - dlog(p);
+    psi = ((lw - 0.5 * iw) - z * T) - h;
+}
+IDHMC_DEV double dlgamma(double x)
+{
+    double lg, psi;
+    dlgamma_psi(x, lg, psi);
+    return lg;
+}
+IDHMC_DEV double ddigamma(double x)
+{
+    double lg, psi;
+    dlgamma_psi(x, lg, psi);
+    return psi;
 }
 
 // (sin, cos)(2 pi u), u in [0,1): quadrant by rint(4u), exact remainder, Taylor to x^17 / x^16

@@ -27,6 +27,27 @@ Each is finite wherever the log density itself is, and that ends at the argument
                                finite); every more negative w is fine.
 Past those ends v is +inf or NaN, which the engine reads as l(q) = -inf: the ordinary rejected point.
 
+Sources whose sampled dispersion sits inside a gamma function, for GLM(..., aux=1); a[0] is the log of the
+dispersion.  They call dlgamma_psi(x, lg, psi) of idhmc_math.hpp: ln Gamma(x) and psi(x) = d/dx ln Gamma(x), x > 0, from one call
+(dlgamma(x) and ddigamma(x) return one of the two).  A source of the user's, GLM or CustomDensity, may call all three.
+
+  NEG_BINOMIAL_LOG_LOGPHI  K = 1: y = count, A = 1 (log phi);  log mu = z, variance mu + mu^2 / phi   (drops -ln Gamma(y + 1))
+  GAMMA_LOG_LOGSHAPE       K = 1: y = log of the response (gamma_response), A = 1 (log shape k);  log mu = z   (drops -log y)
+  BETA_LOGIT_LOGPHI        K = 2: y = (log y, log(1 - y)) (beta_response), A = 1 (log precision phi);  logit mu = z; the
+                           density's shapes are p = phi mu, q = phi (1 - mu)   (drops -log y - log(1 - y))
+
+Each is finite wherever the log density itself is, and that ends at:
+  NEG_BINOMIAL_LOG_LOGPHI  -708.39 < a0 < 703 (phi = exp(a0) not 0, ln Gamma(phi) finite); every |a0| <= 700 with |z| <= 700.
+                           At large phi the score phi (psi(y + phi) - psi(phi) - softplus(z - a0)) is a difference of terms of
+                           size phi |psi(phi)| and loses about phi 1e-16 |psi(phi)| absolutely as the model approaches its
+                           Poisson limit (1e-10 at phi = 1e5): stated, not engineered around.
+  GAMMA_LOG_LOGSHAPE       -708.39 < a0 < 703 (k = exp(a0) not 0, ln Gamma(k) finite) and k exp(log y - z) finite: w = log y - z
+                           below 709.78 and a0 + w below 709.78; every more negative w is fine.
+  BETA_LOGIT_LOGPHI        -708.39 < a0 < 703 (phi not 0, ln Gamma(phi) finite) and p = phi sigma(z), q = phi sigma(-z) both at
+                           least 2.3e-308 (a p or q that underflows to 0 has ln Gamma = +inf, a subnormal one psi = -inf):
+                           -|z| + a0 > -708.  In particular |z| <= 700 with -5 <= a0 <= 700, and |z| <= 40 with |a0| <= 650.
+Past those ends v is +inf or NaN as above.
+
 Every source above works unchanged with coefficient groups, GLM(..., groups=...): the sampled coordinates are
 [u (Dx) | a (A) | omega (H)]; coefficients(model, draws) turns draws into beta = s * u, group_scales(model, draws) into
 sigma = exp(omega).
@@ -151,6 +172,88 @@ __device__ void glm_observation(double z, const GlmObs &o, const double *a, doub
 
 # data columns, constants and auxiliary coordinates each of these expects
 AUX_SHAPES = {"GAUSSIAN_IDENTITY_LOGSIGMA": (1, 0, 1), "STUDENT_T_IDENTITY_LOGSIGMA": (1, 1, 1), "WEIBULL_LOG_LOGSHAPE": (2, 0, 1)}
+
+# phi = exp(a0), t = z - a0 = log(mu / phi);  -log p = (y + phi) softplus(t) - y t - (ln Gamma(y + phi) - ln Gamma(phi))
+# softplus and the sigmoid in BINOMIAL_LOGIT's stable forms; y = 0 gives ln Gamma(phi) - ln Gamma(phi) = 0 exactly
+NEG_BINOMIAL_LOG_LOGPHI = r"""
+__device__ void glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+{
+    const double y = o.y[0];
+    const double ph = dexp(a[0]);
+    const double t = z - a[0];
+    const double e = dexp(-__builtin_fabs(t));
+    const double sp = (t > 0.0 ? t : 0.0) + dlog1p(e);
+    const double sg = (t >= 0.0 ? 1.0 : e) / (1.0 + e);
+    const double yp = y + ph;
+    double l1, p1, l0, p0;
+    dlgamma_psi(yp, l1, p1);
+    dlgamma_psi(ph, l0, p0);
+    v = (yp * sp - y * t) - (l1 - l0);
+    r = y - yp * sg;
+    s[0] = ph * ((p1 - p0) - sp) - r;
+}
+"""
+
+# shape k = exp(a0), mean exp(z);  w = log(y / mu), E = y / mu;  log p = k (a0 + w - E) - ln Gamma(k) - log y
+GAMMA_LOG_LOGSHAPE = r"""
+__device__ void glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+{
+    const double k = dexp(a[0]);
+    const double w = o.y[0] - z;
+    const double E = dexp(w);
+    const double u = (a[0] + w) - E;
+    double lg, ps;
+    dlgamma_psi(k, lg, ps);
+    v = lg - k * u;
+    r = k * (E - 1.0);
+    s[0] = k * ((u + 1.0) - ps);
+}
+"""
+
+# precision phi = exp(a0), mean sigma(z);  p = phi sigma(z) and q = phi sigma(-z), each from its own sigmoid (phi - p would lose q
+# where sigma(z) is near 1);  log p(y) = ln Gamma(phi) - ln Gamma(p) - ln Gamma(q) + (p - 1) log y + (q - 1) log(1 - y)
+BETA_LOGIT_LOGPHI = r"""
+__device__ void glm_observation(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
+{
+    const double y0 = o.y[0], y1 = o.y[1];
+    const double ph = dexp(a[0]);
+    const double e = dexp(-__builtin_fabs(z));
+    const double d = 1.0 + e;
+    const double sz = (z >= 0.0 ? 1.0 : e) / d, sn = (z >= 0.0 ? e : 1.0) / d;
+    const double p = ph * sz, q = ph * sn;
+    const double m = p * sn;
+    double lp, pp, lq, pq, lf, pf;
+    dlgamma_psi(p, lp, pp);
+    dlgamma_psi(q, lq, pq);
+    dlgamma_psi(ph, lf, pf);
+    v = (((lp + lq) - lf) - p * y0) - q * y1;
+    r = m * (((y0 - y1) - pp) + pq);
+    s[0] = (((ph * pf - p * pp) - q * pq) + p * y0) + q * y1;
+}
+"""
+
+# data columns, constants and auxiliary coordinates each of these expects
+DISPERSION_SHAPES = {"NEG_BINOMIAL_LOG_LOGPHI": (1, 0, 1), "GAMMA_LOG_LOGSHAPE": (1, 0, 1), "BETA_LOGIT_LOGPHI": (2, 0, 1)}
+
+
+def gamma_response(y):
+    """Y of GAMMA_LOG_LOGSHAPE from positive responses: log y, shape (n,)"""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.size == 0:
+        raise ValueError("gamma_response: y must be a non-empty 1-D sequence")
+    if not (np.isfinite(y).all() and (y > 0.0).all()):
+        raise ValueError("gamma_response: every y must be finite and > 0 (the gamma density's support)")
+    return np.log(y)
+
+
+def beta_response(y):
+    """Y of BETA_LOGIT_LOGPHI from proportions strictly inside (0, 1): the columns (log y, log(1 - y)), shape (n, 2)"""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.size == 0:
+        raise ValueError("beta_response: y must be a non-empty 1-D sequence")
+    if not (np.isfinite(y).all() and (y > 0.0).all() and (y < 1.0).all()):
+        raise ValueError("beta_response: every y must be finite and strictly between 0 and 1 (the beta density's support)")
+    return np.stack([np.log(y), np.log1p(-y)], 1)
 
 
 def group_scales(model, draws):

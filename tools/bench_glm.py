@@ -15,8 +15,14 @@ levels of one group with a sampled scale, on the matrix cores against the same a
 columns of X (the chains have one coordinate more, the group's log scale).  --hier-cost adds the same design with H = 0, 1 and 4
 groups (the one-hot columns dealt round to the groups), each started from its own Laplace approximation.
 
-    python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier] [--transitions 5]
-                              [--aux-cost] [--hier-cost] [--metric shared|per_chain] [--lockstep]
+The `negbin` pair (NEG_BINOMIAL_LOG_LOGPHI): a negative-binomial regression with a sampled log dispersion on the
+matrix cores against the same arithmetic (dlgamma_psi included) as a custom source; its shapes name the columns of X.
+--dispersion-cost adds, per shape and chain count, the price of the gamma functions: the negative binomial next to POISSON_LOG on
+the same design and counts (each started from its own Laplace approximation; different densities and trees, so steps/s), and a
+beta regression (BETA_LOGIT_LOGPHI, three dlgamma_psi calls per observation) on the same design.
+
+    python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
+                              [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
 """
 import argparse
 import json
@@ -71,6 +77,27 @@ CUSTOM_GAUSSIAN_SRC = CUSTOM_SRC.replace(_LR_TERMS, r"""__device__ void lr_terms
     }
     double t0 = 0.0, t1 = 0.0;""")
 assert CUSTOM_GAUSSIAN_SRC.count("la,") == 2 and "s1 = s1 +" in CUSTOM_GAUSSIAN_SRC and "wave_sum(s0, s1)" in CUSTOM_GAUSSIAN_SRC
+
+# the negative binomial with a sampled log phi as a custom source: the Gaussian's frame (section 12's order) around
+# NEG_BINOMIAL_LOG_LOGPHI's arithmetic, statement for statement
+_G_TERMS = CUSTOM_GAUSSIAN_SRC[CUSTOM_GAUSSIAN_SRC.index("__device__ void lr_terms"):CUSTOM_GAUSSIAN_SRC.index("template <int NCH>")]
+CUSTOM_NEGBIN_SRC = CUSTOM_GAUSSIAN_SRC.replace(_G_TERMS, r"""__device__ void lr_terms(double z, double y, double a, double &r, double &v, double &s)
+{
+    const double ph = dexp(a);
+    const double t = z - a;
+    const double e = dexp(-__builtin_fabs(t));
+    const double sp = (t > 0.0 ? t : 0.0) + dlog1p(e);
+    const double sg = (t >= 0.0 ? 1.0 : e) / (1.0 + e);
+    const double yp = y + ph;
+    double l1, p1, l0, p0;
+    dlgamma_psi(yp, l1, p1);
+    dlgamma_psi(ph, l0, p0);
+    v = (yp * sp - y * t) - (l1 - l0);
+    r = y - yp * sg;
+    s = ph * ((p1 - p0) - sp) - r;
+}
+""")
+assert CUSTOM_NEGBIN_SRC.count("dlgamma_psi(") == 2 and "wave_sum(s0, s1)" in CUSTOM_NEGBIN_SRC and "u * u" not in CUSTOM_NEGBIN_SRC
 
 # the Bernoulli likelihood with one coefficient group as a custom source, section 13's arithmetic: the chain's last coordinate is the
 # group's log scale, params carry the group of every coordinate (as doubles, -1: none) behind tau; b = u e is staged instead of q,
@@ -172,6 +199,92 @@ def poisson_problem(n, D, seed):
     return X, y, q, np.linalg.inv(H)
 
 
+def newton_laplace(density, q):
+    """the maximum of density(q) -> (l, grad l) by damped Newton steps on a finite-difference Hessian, and the Laplace covariance there"""
+    D = q.size
+
+    def hessian(q):
+        Hm = np.empty((D, D))
+        for c in range(D):
+            d = np.zeros(D)
+            d[c] = 1e-5
+            Hm[c] = (density(q + d)[1] - density(q - d)[1]) / 2e-5
+        return -0.5 * (Hm + Hm.T)
+    for _ in range(60):
+        l, g = density(q)
+        Hm = hessian(q)
+        w = np.linalg.eigvalsh(Hm)[0]
+        step = np.linalg.solve(Hm + max(0.0, 0.1 - w) * np.eye(D), g)
+        t = 1.0
+        with np.errstate(all="ignore"):                # a full step may leave the support: the density is then NaN and the step is halved
+            while not density(q + t * step)[0] >= l and t > 1e-6:
+                t *= 0.5
+        q = q + t * step
+        if np.abs(t * step).max() < 1e-10:
+            break
+    w, V = np.linalg.eigh(hessian(q))
+    return q, (V / np.maximum(w, 1e-3)) @ V.T
+
+
+def negbin_density(X, y, q):
+    """(l, grad l) of the negative-binomial regression, q = [beta | log phi], prior N(0, I)"""
+    from scipy import special
+    D = X.shape[1]
+    ph, t = np.exp(q[D]), X @ q[:D] - q[D]
+    sp, r = np.logaddexp(0.0, t), y - (y + ph) * special.expit(t)
+    l = np.sum(special.gammaln(y + ph) - special.gammaln(ph) - (y + ph) * sp + y * t)
+    s = np.sum(ph * (special.digamma(y + ph) - special.digamma(ph) - sp) - r)
+    return l - 0.5 * q @ q, np.r_[X.T @ r, s] - q
+
+
+def beta_density(X, Y, q):
+    """(l, grad l) of the beta regression, Y = (log y, log(1 - y)), q = [beta | log phi], prior N(0, I)"""
+    from scipy import special
+    D = X.shape[1]
+    z, ph = X @ q[:D], np.exp(q[D])
+    p, k = ph * special.expit(z), ph * special.expit(-z)
+    dg = special.digamma
+    l = np.sum(special.gammaln(ph) - special.gammaln(p) - special.gammaln(k) + p * Y[:, 0] + k * Y[:, 1])
+    r = p * special.expit(-z) * (Y[:, 0] - Y[:, 1] - dg(p) + dg(k))
+    s = np.sum(ph * dg(ph) - p * dg(p) - k * dg(k) + p * Y[:, 0] + k * Y[:, 1])
+    return l - 0.5 * q @ q, np.r_[X.T @ r, s] - q
+
+
+def dispersion_design(n, D, seed):
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, D)) / np.sqrt(D)
+    X[:, 0] = 1.0
+    return rng, X, X @ (rng.standard_normal(D) * 0.5)
+
+
+def negbin_problem(n, D, seed):
+    """counts with mean exp(X beta) and dispersion phi = 3; the Laplace approximation at the MAP in (beta, log phi), prior N(0, I)"""
+    rng, X, z = dispersion_design(n, D, seed)
+    y = rng.negative_binomial(3.0, 3.0 / (3.0 + np.exp(z))).astype(np.float64)
+    q, cov = newton_laplace(lambda q: negbin_density(X, y, q), np.r_[np.zeros(D), np.log(3.0)])
+    return X, y, q, cov
+
+
+def poisson_laplace(X, y):
+    """the Poisson regression's own MAP and Laplace covariance on a design and counts given (prior N(0, I))"""
+    D = X.shape[1]
+    q = np.zeros(D)
+    for _ in range(60):
+        m = np.exp(X @ q)
+        H = (X.T * m) @ X + np.eye(D)
+        q = q + np.linalg.solve(H, X.T @ (y - m) - q)
+    return q, np.linalg.inv(H)
+
+
+def beta_problem(n, D, seed):
+    """proportions with mean sigma(X beta) and precision phi = 8 as (log y, log(1 - y)); MAP and Laplace covariance in (beta, log phi)"""
+    rng, X, z = dispersion_design(n, D, seed)
+    m = 1.0 / (1.0 + np.exp(-z))
+    Y = pkg.glm.beta_response(np.clip(rng.beta(8.0 * m, 8.0 * (1.0 - m)), 1e-12, 1.0 - 1e-12))
+    q, cov = newton_laplace(lambda q: beta_density(X, Y, q), np.r_[np.zeros(D), np.log(8.0)])
+    return X, Y, q, cov
+
+
 def hier_groups(Dx, H):
     """the last min(40, Dx - 5) columns are the grouped ones, dealt round to the H groups (H = 0: no groups)"""
     grp = np.full(Dx, -1, np.int32)
@@ -246,6 +359,12 @@ def model(form, X, y, q_map=None):
         grp = np.full(padded(D + 1), -1.0)
         grp[:D] = hier_groups(D, 1)
         return pkg.CustomDensity(D + 1, CUSTOM_HIER_SRC, np.concatenate([custom_params(np.c_[X, np.zeros(len(X))], y), grp]))
+    if form == "glm_negbin":
+        return pkg.GLM(X, y, pkg.glm.NEG_BINOMIAL_LOG_LOGPHI, aux=1)
+    if form == "custom_negbin":                       # the chain's D + 1 coordinates: a zero column of X in the place of log phi
+        return pkg.CustomDensity(D + 1, CUSTOM_NEGBIN_SRC, custom_params(np.c_[X, np.zeros(len(X))], y))
+    if form == "glm_beta":
+        return pkg.GLM(X, y, pkg.glm.BETA_LOGIT_LOGPHI, aux=1)
     if form == "glm_gaussian":
         return pkg.GLM(X, y, pkg.glm.GAUSSIAN_IDENTITY_LOGSIGMA, aux=1)
     if form == "custom_gaussian":                     # the chain's D + 1 coordinates: a zero column of X in the place of log sigma
@@ -303,7 +422,8 @@ def run(form, X, y, q_map, cov, C, T, seed=1, metric=None):
 PAIRS = {"poisson": ("glm_poisson", "custom_poisson", poisson_problem),
          "logistic": ("glm_logistic", "builtin_logistic", logistic_problem),
          "gaussian": ("glm_gaussian", "custom_gaussian", gaussian_problem),
-         "hier": ("glm_hier", "custom_hier", hier_problem)}
+         "hier": ("glm_hier", "custom_hier", hier_problem),
+         "negbin": ("glm_negbin", "custom_negbin", negbin_problem)}
 
 
 def main():
@@ -314,6 +434,8 @@ def main():
     ap.add_argument("--transitions", type=int, default=5)
     ap.add_argument("--aux-cost", action="store_true", help="the fixed-sigma, A = 1 and A = 4 Gaussians per shape (DESIGN section 12)")
     ap.add_argument("--hier-cost", action="store_true", help="the hier pair's design with H = 0, 1 and 4 groups per shape (DESIGN section 13)")
+    ap.add_argument("--dispersion-cost", action="store_true", help="the negative binomial next to POISSON_LOG on the same design and counts, "
+                    "and a beta regression, per shape (DESIGN section 14)")
     ap.add_argument("--metric", default="shared", choices=["shared", "per_chain"])
     ap.add_argument("--lockstep", action="store_true", help="eps / 1000 and max_depth = 6: every tree of every density takes the same 63 "
                     "steps, so steps/s compares the cost per gradient and not the trees")
@@ -345,6 +467,18 @@ def main():
                     print("# D=%d n=%d C=%d %s (form %d): %.3e leapfrog steps/s, depth %.2f" %
                           (D, n, C, f, row[f]["glm_form"], row[f]["leapfrog_steps_per_s"], row[f]["mean_depth"]), file=sys.stderr, flush=True)
                 res["results"].append(row)
+        if a.dispersion_cost:
+            X, y, q_nb, cov_nb = negbin_problem(n, D, seed=D * 7919 + n)
+            q_po, cov_po = poisson_laplace(X, y)
+            Xb, Yb, q_be, cov_be = beta_problem(n, D, seed=D * 7919 + n)
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="dispersion_cost", D=D, n=n, chains=C, metric=a.metric)
+                for f, args in (("glm_negbin", (X, y, q_nb, cov_nb)), ("glm_poisson", (X, y, q_po, cov_po)), ("glm_beta", (Xb, Yb, q_be, cov_be))):
+                    row[f] = run(f, *args, C, a.transitions, metric=metric)[0]
+                    print("# D=%d n=%d C=%d %s (form %d): %.3e leapfrog steps/s, depth %.2f" %
+                          (D, n, C, f, row[f]["glm_form"], row[f]["leapfrog_steps_per_s"], row[f]["mean_depth"]), file=sys.stderr, flush=True)
+                row["negbin_over_poisson"] = row["glm_negbin"]["leapfrog_steps_per_s"] / row["glm_poisson"]["leapfrog_steps_per_s"]
+                res["results"].append(row)
         for pair in [p for p in a.pairs.split(",") if p]:
             fa, fb, prob = PAIRS[pair]
             X, y, q_map, cov = prob(n, D, seed=D * 7919 + n)
@@ -360,6 +494,7 @@ def main():
                           (D, n, C, f, r["leapfrog_steps_per_s"], r["ms_per_transition"], r["mean_depth"], r["create_s"]),
                           file=sys.stderr, flush=True)
                 row["same_bits"] = bool(all(np.array_equal(u.view(np.uint64), v.view(np.uint64)) for u, v in zip(seen[fa], seen[fb])))
+                row["same_steps"] = row[fa]["steps"] == row[fb]["steps"]
                 row["speedup_%s_over_%s" % (fa, fb)] = row[fa]["leapfrog_steps_per_s"] / row[fb]["leapfrog_steps_per_s"]
                 res["results"].append(row)
     print(json.dumps(res, indent=1))
