@@ -182,11 +182,12 @@ typedef struct {
                                         added in segment order on every rank (see idhmc_pool_partials) */
     int32_t local_opt_iterations;    /* FindLocalOptimum stage of idhmc_mcmc_with_warmup (src/warmup.jl:137-150,
                                         362): 0 = skipped (default at this level), reference default 50 */
-    int32_t leapfrog_grad_mode;      /* IDHMC_GRAD_STORE (default): idhmc_leapfrog(eps, 1) streams q, p, grad l in and out
-                                        (6 D 8 bytes per chain-step, the reference's data movement);
-                                        IDHMC_GRAD_RECOMPUTE: a separable density re-derives grad l(q) from q and does not
-                                        write grad l(q') -- 4 D 8 bytes; idhmc_get_grad and every call that needs the
-                                        array re-evaluate it first, results are bit-identical */
+    int32_t leapfrog_grad_mode;      /* IDHMC_GRAD_RECOMPUTE (what idhmc_default_options sets): in idhmc_leapfrog(eps, 1) a
+                                        separable density re-derives grad l(q) from q and does not write grad l(q') -- 4 D 8
+                                        bytes per chain-step; idhmc_get_grad and every call that needs the array re-evaluate
+                                        it first, results are bit-identical.  Every other density and n_steps > 1 ignore it;
+                                        IDHMC_GRAD_STORE (= 0, what a zero-initialised struct holds): the sweep streams q, p,
+                                        grad l in and out (6 D 8 bytes per chain-step, the reference's data movement) */
     double  local_opt_penalty;       /* magnitude_penalty, reference default 1e-4 */
 } idhmc_options;
 
@@ -263,6 +264,11 @@ int idhmc_placement_cost(const idhmc_ctx *ctx, double *create_ms, int64_t *peak_
  * Reports the lanes in use (0 before the first sweep or when the sweep is one kernel) and how many of them were found on
  * different hardware queues (fewer than `lanes` under a profiler that serialises streams). */
 int idhmc_lanes_info(const idhmc_ctx *ctx, int32_t *lanes, int32_t *on_distinct_queues);
+/* The single-step leapfrog of a separable density keeps every stride-th chain in the Infinity Cache from one sweep to the next
+ * (default-policy loads and stores behind the other chains' non-temporal stream): the stride of the IDHMC_GRAD_STORE sweep
+ * (three arrays, ceil(3 C L 8 / 192 MiB)) and of the IDHMC_GRAD_RECOMPUTE sweep (q and p only, ceil(2 C L 8 / 192 MiB));
+ * 1 = the whole state fits.  Read-only. */
+int idhmc_leapfrog_slice_info(const idhmc_ctx *ctx, int32_t *stride_store, int32_t *stride_recompute);
 
 /* ---- state (PhasePoint / EvaluatedLogDensity, src/hamiltonian.jl:237-276) - */
 /* q <- host[nchains*D]; evaluates l(q), grad l(q) (evaluate_l!, src/kinetic_energy.jl:72-85) */
@@ -279,7 +285,7 @@ int idhmc_get_q(idhmc_ctx *ctx, double *q);                   /* nchains*D */
 int idhmc_get_p(idhmc_ctx *ctx, double *p);
 int idhmc_get_grad(idhmc_ctx *ctx, double *g);   /* grad l(q) of the current state; re-evaluated first when the device copy is stale: a NUTS transition of a
                                                      separable density does not write it back (nothing on the sampling path reads it), nor does the
-                                                     IDHMC_GRAD_RECOMPUTE leapfrog */
+                                                     single-step leapfrog in its default mode, IDHMC_GRAD_RECOMPUTE */
 int idhmc_get_minv(idhmc_ctx *ctx, double *minv);             /* nchains*D (shared metric is broadcast) */
 int idhmc_get_lq(idhmc_ctx *ctx, double *lq);                 /* nchains: l(q) */
 int idhmc_get_eps(idhmc_ctx *ctx, double *eps);               /* nchains */

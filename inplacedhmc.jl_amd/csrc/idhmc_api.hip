@@ -88,8 +88,12 @@ struct idhmc_ctx {
         int64_t max_bytes = (int64_t)16 << 30, walk_bytes = (int64_t)64 << 30;
         bool pairs = true, verbose = false;
     } place;
-    // IDHMC_GRAD_RECOMPUTE: the single-step leapfrog of a separable density leaves the stored gradient stale; whoever
-    // needs the array (get_grad, the stepsize search, the n-step kernel, the optimum stage) re-evaluates first
+    // The device copy of grad l lags behind q after (a) the single-step leapfrog of a separable density in its default mode,
+    // IDHMC_GRAD_RECOMPUTE, and (b) every NUTS transition of a separable density: neither writes the array.  Every host entry
+    // point whose kernel reads s.g goes through ensure_grad first -- idhmc_get_grad, both stepsize searches, find_local_optimum,
+    // the n-step leapfrog, the IDHMC_GRAD_STORE single step and idhmc_time_leapfrog in that mode; set_q and random_position
+    // evaluate and clear the flag.  The other readers of s.g (dense, JIT / GLM, logistic kernels, k_nuts of a non-separable
+    // density) are unreachable for a separable model, and nothing else ever sets the flag (the list is in DESIGN 3.1)
     bool grad_stale = false;
     double *pool_scratch = nullptr;       // IDHMC_METRIC_POOLED: {acc0, acc1, mean}
     double *pool_table = nullptr;         // [segments][L + 1] partial sums (grown on demand)
@@ -382,7 +386,9 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
                 else jump = 0;
             }
             if (ok && !other.empty()) {
-                // q: the reference; p: the partner; grad: one of the reference's class (a rejected one, else new); a per-chain M^-1: the other class
+                // q: the reference; p: the partner; grad: one of the reference's class (a rejected one, else new); a per-chain M^-1: the other class.
+                // Invariant (both walks): out[0], out[1] -- q and p -- are a pair of DIFFERENT classes, because the default single-step
+                // sweep streams those two alone (IDHMC_GRAD_RECOMPUTE) and a same-class pair runs at the rate of one array
                 double *setv[4] = {ref, other[0], nullptr, nullptr};
                 auto pick = [&](std::vector<double *> &from) -> double * {
                     if (!from.empty()) { double *p = from.back(); from.pop_back(); return p; }
@@ -466,6 +472,28 @@ static int place_state(idhmc_ctx *c, double **out, int nvec, int64_t n, int64_t 
     }
     if (best < 0) return fail(IDHMC_ERR_ALLOC, "no placement for the chain state (%zu bytes per array)", bytes);
     for (int t = 0; t < cs.n; ++t) if (t != best && cs.held[t]) cs.drop(t, nvec);
+    // (R) the set to keep is known; which of its arrays become q and p is not indifferent: the default single-step sweep streams q and p
+    // alone, and a mixed set of three holds one pair of the same class (0.97-1.02 x one array alone) and two pairs of different classes.
+    // Allocation order may make q, p the same-class pair, so the three pairs are probed (3 x 5 launches) and the fastest becomes out[0],
+    // out[1], the remaining array grad l; a per-chain M^-1 keeps its slot.  Only pointers the holder owns are permuted.
+    if (nvec >= 3 && cs.ms[best] > 0.f) {
+        static const int kPair[3][3] = {{0, 1, 2}, {0, 2, 1}, {1, 2, 0}};
+        float pms[3] = {0.f, 0.f, 0.f};
+        int fastest = 0;
+        for (int i = 0; i < 3; ++i) {
+            double *v2[2] = {cs.arr[best][kPair[i][0]], cs.arr[best][kPair[i][1]]};
+            if (int rc = probe_ms(c, v2, 2, C, L, &pms[i])) return rc;       // (the holder frees every set, this one included)
+            if (pms[i] < pms[fastest]) fastest = i;
+        }
+        double *const a[3] = {cs.arr[best][kPair[fastest][0]], cs.arr[best][kPair[fastest][1]], cs.arr[best][kPair[fastest][2]]};
+        if (verbose) {
+            const double pair_bytes = 2.0 * 2.0 * (double)bytes * 4;
+            fprintf(stderr, "idhmc placement pairs of the kept set: (0,1) %.1f (0,2) %.1f (1,2) %.1f GB/s, one array alone %.1f GB/s: q, p = arrays %d, %d, grad = array %d\n",
+                    pair_bytes / (pms[0] * 1e-3) / 1e9, pair_bytes / (pms[1] * 1e-3) / 1e9, pair_bytes / (pms[2] * 1e-3) / 1e9, single_Bps / 1e9,
+                    kPair[fastest][0], kPair[fastest][1], kPair[fastest][2]);
+        }
+        for (int k = 0; k < 3; ++k) cs.arr[best][k] = a[k];
+    }
     c->placement_tries = cs.n;
     c->placement_GBps = (cs.n > 1 || cs.ms[best] > 0.f) && cs.ms[best] > 0.f ? probe_bytes / (cs.ms[best] * 1e-3) / 1e9 : 0.0;
     c->placement_single_GBps = single_Bps / 1e9;
@@ -510,7 +538,7 @@ void idhmc_default_options(idhmc_options *o)
     o->eps_mode = IDHMC_EPS_PER_CHAIN;
     o->metric_mode = IDHMC_METRIC_PER_CHAIN;
     o->local_opt_iterations = 0;          // the FindLocalOptimum stage is opt-in at this level (own optimiser)
-    o->leapfrog_grad_mode = IDHMC_GRAD_STORE;
+    o->leapfrog_grad_mode = IDHMC_GRAD_RECOMPUTE;   // separable densities: 4 streams instead of 6, the same bits
     o->local_opt_penalty = 1e-4;          // src/warmup.jl:143
 }
 const char *idhmc_last_error(void) { return g_err; }
@@ -766,6 +794,8 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
     }
     s.lf_stride = (3 * CL * (int64_t)sizeof(double) + kIcSliceBytes - 1) / kIcSliceBytes;
     if (s.lf_stride < 1) s.lf_stride = 1;
+    s.lf_stride2 = (2 * CL * (int64_t)sizeof(double) + kIcSliceBytes - 1) / kIcSliceBytes;
+    if (s.lf_stride2 < 1) s.lf_stride2 = 1;
     DALLOC(s.lq, nchains); DALLOC(s.pi, nchains); DALLOC(s.eps, nchains);
     if (own_minv) {
         DALLOC(s.w, CL);
@@ -989,6 +1019,13 @@ int idhmc_placement_info(const idhmc_ctx *c, double *probe_GBps, int32_t *candid
     if (!c) return fail(IDHMC_ERR_BAD_ARG, "null context");
     if (probe_GBps) *probe_GBps = c->placement_GBps;
     if (candidates) *candidates = c->placement_tries;
+    return IDHMC_OK;
+}
+int idhmc_leapfrog_slice_info(const idhmc_ctx *c, int32_t *stride_store, int32_t *stride_recompute)
+{
+    if (!c) return fail(IDHMC_ERR_BAD_ARG, "null context");
+    if (stride_store) *stride_store = (int32_t)c->s.lf_stride;
+    if (stride_recompute) *stride_recompute = (int32_t)c->s.lf_stride2;
     return IDHMC_OK;
 }
 int idhmc_lanes_info(const idhmc_ctx *c, int32_t *lanes, int32_t *on_distinct_queues)
@@ -1840,9 +1877,9 @@ int idhmc_time_leapfrog(idhmc_ctx *c, double eps, int32_t sweeps, float *ms_per_
 {
     CTXCHK(c);
     if (sweeps < 1 || !ms_per_sweep) return fail(IDHMC_ERR_BAD_ARG, "bad arguments");
-    HIPCHK(hipEventRecord(c->ev0, c->stream));
     const int regrad = leapfrog_regrad(c, 1);
-    if (!regrad) { if (int rc = ensure_grad(c)) return rc; }
+    if (!regrad) { if (int rc = ensure_grad(c)) return rc; }     // (before the first event: the pair brackets the sweeps alone)
+    HIPCHK(hipEventRecord(c->ev0, c->stream));
     for (int i = 0; i < sweeps; ++i) { if (int rc = leapfrog_any(c, eps, 0, 1, regrad)) return rc; }
     if (regrad) c->grad_stale = true;
     if (int rc = lanes_join(c)) return rc;

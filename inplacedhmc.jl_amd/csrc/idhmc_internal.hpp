@@ -35,6 +35,7 @@ struct DevState {
     double *minv, *w;     // [C][L] (minv_stride = L) or [L] shared (minv_stride = 0)
     int64_t minv_stride;
     int64_t lf_stride;        // k_leapfrog1: chains c % lf_stride == 0 are the Infinity-Cache slice (idhmc_create, kIcSliceBytes)
+    int64_t lf_stride2;       // the same for the REGRAD variants, which touch q and p only: a slice of two arrays
     const double *mu, *tau;   // [L]
     const double *prec;       // [L][L]
     const double *lr_x, *lr_xt, *lr_y;   // IDHMC_MODEL_LOGISTIC_REGRESSION, _GLM: X [lr_npad][L], X' [L][lr_npad], Y [K][lr_npad], zero-padded
@@ -86,7 +87,8 @@ constexpr uint32_t kTestXccFlag = 1u << 30;
 constexpr int kXchgBlocks = 64;   // workgroups of k_xchg_sum; DevState::xchg_acc holds 3 * kXchgBlocks partials + 1 ticket
 // the most q, p, grad bytes the single-step leapfrog keeps in the 256 MiB Infinity Cache across sweeps: every lf_stride-th chain, with
 // lf_stride = ceil(C L 3 8 / kIcSliceBytes), 1 when the whole state fits (tools/ubench/ic_slice.hip: 192 MiB stays resident behind a
-// 2.6 GiB nt stream, 219 MiB only in part)
+// 2.6 GiB nt stream, 219 MiB only in part); the sweep that re-derives the gradient touches q and p only and sizes its slice for
+// those: lf_stride2 = ceil(C L 2 8 / kIcSliceBytes) (profiles/r05_ic_slice_two_arrays.log)
 constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
 
 #ifndef __HIPCC_RTC__   // host side only (the header is also compiled by hipRTC for custom densities)

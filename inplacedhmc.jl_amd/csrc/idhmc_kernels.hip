@@ -120,7 +120,8 @@ __global__ __launch_bounds__(256) void k_leapfrog(DevState s, double eps_arg, in
 // VAR bit 1: non-temporal loads/stores for the streamed state.
 // With bit 0, the chains c % s.lf_stride == 0 (a slice of at most kIcSliceBytes of q, p, grad, spread through the sweep) use
 // default-policy loads and stores instead: behind the other chains' nt stream that slice stays in the Infinity Cache from one sweep to
-// the next, so its bytes are served on die while the rest streams from HBM (tools/ubench/ic_slice.hip).
+// the next, so its bytes are served on die while the rest streams from HBM (tools/ubench/ic_slice.hip).  The REGRAD
+// variants never touch grad: their slice is sized for q and p alone (s.lf_stride2).
 typedef double v2d __attribute__((ext_vector_type(2)));
 template <bool NT> IDHMC_DEV v2d ld2(const v2d *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
 template <bool NT> IDHMC_DEV void st2(v2d *p, v2d v) { if (NT) __builtin_nontemporal_store(v, p); else *p = v; }
@@ -199,8 +200,9 @@ __global__ __launch_bounds__(256, (VAR & 1) ? 2 : 4) void k_leapfrog1(DevState s
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t stride = REGRAD ? s.lf_stride2 : s.lf_stride;
     for (int64_t c = wave; c < s.C; c += nw) {
-        if (PRE && NT && c % s.lf_stride == 0) leapfrog1_chain<NCH, Model, PRE, false, REGRAD>(s, c, lane, eps_arg, own_eps);
+        if (PRE && NT && c % stride == 0) leapfrog1_chain<NCH, Model, PRE, false, REGRAD>(s, c, lane, eps_arg, own_eps);
         else leapfrog1_chain<NCH, Model, PRE, NT, REGRAD>(s, c, lane, eps_arg, own_eps);
     }
 }

@@ -348,6 +348,12 @@ class Engine:
         check(self.lib.idhmc_lanes_info(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def leapfrog_slice_info(self):
+        """(stride of the single-step leapfrog's Infinity-Cache slice in GRAD_STORE mode, in GRAD_RECOMPUTE mode); 1: every chain"""
+        a, b = C.c_int32(0), C.c_int32(0)
+        check(self.lib.idhmc_leapfrog_slice_info(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def device_bytes(self):
         return int(self.lib.idhmc_device_bytes(self.h))
 

@@ -8,7 +8,7 @@ FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports half the bytes 
 import collections, csv, glob, json, os, shutil, sys
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 tag = args[0] if args else "r03"
-kernel = args[1] if len(args) > 1 else "k_leapfrog1<8, idhmc::DiagGaussian<8>, 3>"   # the headline variant (7 = gradient-recompute mode)
+kernel = args[1] if len(args) > 1 else "k_leapfrog1<8, idhmc::DiagGaussian<8>, 7>"   # the headline variant (7: grad l re-derived, the default; 3: the store mode)
 src = "gpurun_out"
 dst = "gpurun_out" if "--stage-only" in sys.argv else "profiles"
 staged = f"{src}/{tag}_leapfrog_pmc.json"

@@ -9,9 +9,12 @@
 //   H   stream + table both with the stream policy (the table's bytes at the stream's rate; for the nt stream: today's sweep).
 // The table is resident when ST <= 1.02 x S.  Arrays: one set of three that streams in the good placement mode (pair probe as in
 // placement_pingpong.hip).
+// `ic_slice two`: the sweep of the REGRAD variants, which touch q and p only -- a0 and a1 (classes A B) are swept, a2 is left alone, with
+// the one policy pair the kernel uses (nt stream, default-policy table) at strides 8, 6 and 5: 128, 170.7 and 204.8 MiB of table.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/ubench/ic_slice tools/ubench/ic_slice.hip
 #include "../../inplacedhmc.jl_amd/csrc/idhmc_device.hpp"
 #include <cstdio>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -32,7 +35,27 @@ IDHMC_DEV void chain_pass(double *a0, double *a1, double *a2, int lane)
     bstore<NCH, ST>(a1, lane, x1);
     bstore<NCH, ST>(a2, lane, x2);
 }
+template <int POL>
+IDHMC_DEV void chain_pass2(double *a0, double *a1, int lane)
+{
+    constexpr int LD = POL & 255, ST = POL >> 8;
+    Vec<NCH> x0 = bload<NCH, LD>(a0, lane), x1 = bload<NCH, LD>(a1, lane);
+    bstore<NCH, ST>(a0, lane, x0);
+    bstore<NCH, ST>(a1, lane, x1);
+}
 // mode 0: stream chains only; 1: every chain; 2: table chains only
+template <int TPOL, int SPOL>
+__global__ __launch_bounds__(256, 2) void sweep2(double *a0, double *a1, double *, long long C, int stride, int mode)
+{
+    const int lane = threadIdx.x & 63;
+    const long long c = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (c >= C) return;
+    const bool table = (c % stride) == 0;
+    if ((mode == 0 && table) || (mode == 2 && !table)) return;
+    const long long off = c * L;
+    if (table) chain_pass2<TPOL>(a0 + off, a1 + off, lane);
+    else chain_pass2<SPOL>(a0 + off, a1 + off, lane);
+}
 template <int TPOL, int SPOL>
 __global__ __launch_bounds__(256, 2) void sweep(double *a0, double *a1, double *a2, long long C, int stride, int mode)
 {
@@ -64,6 +87,8 @@ static SweepFn g_fn[8][8];
 template <size_t I> static void fill_one() { g_fn[I / 8][I % 8] = sweep<kPol[I / 8], kPol[I % 8]>; }
 template <size_t... I> static void fill_all(std::index_sequence<I...>) { (fill_one<I>(), ...); }
 
+static SweepFn g_fn2[2][2];      // two-array mode: [table policy][stream policy] over {default, nt}
+static bool g_two = false;
 static const long long C = 65536;
 static const int kWarm = 3, kRuns = 20;
 
@@ -72,9 +97,10 @@ static double us_sweep(int ti, int si, double *a0, double *a1, double *a2, int s
 {
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     const dim3 grid((unsigned)((C + 3) / 4));
-    for (int i = 0; i < kWarm; ++i) hipLaunchKernelGGL(g_fn[ti][si], grid, dim3(256), 0, 0, a0, a1, a2, C, stride, mode);
+    const SweepFn fn = g_two ? g_fn2[ti][si] : g_fn[ti][si];
+    for (int i = 0; i < kWarm; ++i) hipLaunchKernelGGL(fn, grid, dim3(256), 0, 0, a0, a1, a2, C, stride, mode);
     (void)hipEventRecord(e0);
-    for (int i = 0; i < kRuns; ++i) hipLaunchKernelGGL(g_fn[ti][si], grid, dim3(256), 0, 0, a0, a1, a2, C, stride, mode);
+    for (int i = 0; i < kRuns; ++i) hipLaunchKernelGGL(fn, grid, dim3(256), 0, 0, a0, a1, a2, C, stride, mode);
     (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
     float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -96,6 +122,9 @@ static double probe_gbps(double *a0, double *a1, int nvec)
 int main(int argc, char **argv)
 {
     fill_all(std::make_index_sequence<64>{});
+    g_fn2[0][0] = sweep2<kPol[0], kPol[0]>; g_fn2[0][1] = sweep2<kPol[0], kPol[1]>;
+    g_fn2[1][0] = sweep2<kPol[1], kPol[0]>; g_fn2[1][1] = sweep2<kPol[1], kPol[1]>;
+    g_two = argc > 1 && std::string(argv[1]) == "two";
     const size_t A = sizeof(double) * C * L;
     // arrays of both placement classes (a set streams well when it mixes them); the sweep uses classes A B A like place_state
     std::vector<double *> a, b;
@@ -118,6 +147,23 @@ int main(int argc, char **argv)
     printf("state: %lld chains x %d doubles x 3 arrays = %.0f MiB; %d warm-up + %d timed sweeps back to back per cell (mean)\n\n",
            C, L, 3.0 * A / 1048576.0, kWarm, kRuns);
 
+    if (g_two) {
+        printf("two-array mode: a0 (class A) and a1 (class B) are swept, %.0f MiB; stream policy nt, table policy default\n\n", 2.0 * A / 1048576.0);
+        const int strides2[] = {8, 6, 5};
+        for (int rep = 0; rep < 2; ++rep)
+            for (int stride : strides2) {
+                const long long nt = (C + stride - 1) / stride;
+                const double tab_mib = nt * 2.0 * L * 8 / 1048576.0, str_gib = (C - nt) * 4.0 * L * 8 / 1073741824.0;
+                const double S = us_sweep(1, 1, q, p, g, stride, 0), H = us_sweep(1, 1, q, p, g, stride, 1);
+                const double T = us_sweep(0, 0, q, p, g, stride, 2), ST = us_sweep(0, 1, q, p, g, stride, 1);
+                printf("stride %d: table %lld chains = %.1f MiB held; stream %.2f GiB moved per sweep\n", stride, nt, tab_mib, str_gib);
+                printf("   S  stream alone (nt)            %7.1f us\n   ST stream nt + table default    %7.1f us = %.3f x S%s\n"
+                       "   H  stream + table both nt       %7.1f us = %.3f x S\n   T  table alone (default)        %7.1f us\n"
+                       "   ST / H = %.3f: %s by the criterion ST <= 1.02 S\n",
+                       S, ST, ST / S, ST <= 1.02 * S ? " *" : "", H, H / S, T, ST / H, ST <= 1.02 * S ? "RESIDENT" : "not resident");
+            }
+        return 0;
+    }
     const int strides[] = {24, 12, 8, 7};
     for (int stride : strides) {
         const long long nt = (C + stride - 1) / stride;
