@@ -128,7 +128,17 @@ enum {
  * The Gaussian prior is on the sampled coordinates: with the defaults (mu = 0, tau = 1) a grouped coefficient is
  * b_c ~ N(0, sigma_g^2), sigma_g = exp(omega_g) log-normal.  glm_observation is the one of GLM (A = 0) or GLM_AUX (A > 0),
  * untouched.  The hierarchy adds no tile: idhmc_glm_form is what it is for the same (L, A, metric) without groups.  Draws come back
- * in the sampled coordinates (u, a, omega). */
+ * in the sampled coordinates (u, a, omega).
+ *
+ * Several responses on one design matrix (idhmc_create_glm_responses, below) -- one context samples M posteriors that share X, the
+ * prior, the constants, the source and the groups and differ in Y alone: a regression per gene, per voxel, per metric.  Y is
+ * M x n x K row-major and the chain of GLOBAL id g (first_chain_id + c) samples response g / chains_per_response -- a function of the
+ * global id only, like the address of its random numbers, so the shards of a run and one context holding all of it compute the same
+ * bits.  For one chain every operation is the one a single-response context with Y[g / chains_per_response] performs: the draws are
+ * bit-identical to that context's.  The matrix-core form takes 16 chains of any responses per tile and needs no further LDS:
+ * idhmc_glm_form is what it is for the same (L, A, metric) with one response.  Stepsize and metric are per chain (or the fixed
+ * SHARED metric); the statistics pooled over chains (IDHMC_EPS_GLOBAL, IDHMC_METRIC_POOLED) would mix posteriors and are refused
+ * with M > 1.  The diagnostics counters stay context-wide. */
 enum {
     IDHMC_MODEL_ISO_GAUSSIAN = 0,   /* l(q) = -1/2 |q|^2                       */
     IDHMC_MODEL_DIAG_GAUSSIAN = 1,  /* l(q) = -1/2 sum tau_d (q_d - mu_d)^2    */
@@ -233,6 +243,17 @@ typedef struct {
 } idhmc_glm_desc;
 int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
                      const idhmc_glm_desc *glm, const idhmc_options *opt, uint64_t seed);
+/* The same GLM with M responses (above): glm->Y is M x n x K row-major, everything else in *glm is as for idhmc_create_glm, and the
+ * chain of global id g samples response g / chains_per_response.  With M = 1 the context is bit for bit the one idhmc_create_glm
+ * makes.  Refused with IDHMC_ERR_BAD_ARG before the device is touched: everything idhmc_create_glm refuses (a non-finite value in any
+ * of the M planes of Y), M < 1, chains_per_response < 1, first_chain_id + nchains > M * chains_per_response (a chain without a
+ * response), M * K * n_pad > 2^27 (Y on the device takes at most 1 GiB, as X does), and M > 1 together with IDHMC_EPS_GLOBAL or
+ * IDHMC_METRIC_POOLED. */
+int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                               const idhmc_glm_desc *glm, int64_t M, int64_t chains_per_response,
+                               const idhmc_options *opt, uint64_t seed);
+/* M and chains_per_response of a context made by idhmc_create_glm_responses; 1 and 0 for every other context */
+int idhmc_glm_responses(const idhmc_ctx *ctx, int64_t *M, int64_t *chains_per_response);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

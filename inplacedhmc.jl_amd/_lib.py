@@ -59,6 +59,8 @@ SYMBOLS = {
     "idhmc_build_digest": (C.c_char_p, []),
     "idhmc_create": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(ModelDesc), C.POINTER(Options), _u64]),
     "idhmc_create_glm": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(Options), _u64]),
+    "idhmc_create_glm_responses": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_glm_responses": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "idhmc_destroy": (C.c_int, [_vp]),
     "idhmc_set_stream": (C.c_int, [_vp, _vp]),
     "idhmc_synchronize": (C.c_int, [_vp]),

@@ -59,6 +59,7 @@ struct idhmc_ctx {
     hipStream_t own_stream = nullptr;
     std::vector<void *> allocs;
     int64_t bytes = 0;
+    int64_t glm_r = 0;             // idhmc_create_glm_responses: chains per response as given (0: any other context)
     double *xchg = nullptr;        // library-owned exchange record (IDHMC_XCHG_DOUBLES)
     int32_t *status_out = nullptr; // device scalar
     double *scratch = nullptr;     // [C][L] staging for broadcasts / moments
@@ -580,6 +581,8 @@ struct GlmParts {
     int32_t K, nc, A, H;
     const double *X, *Y, *c;
     const int32_t *grp;        // [Dx], H > 0
+    bool responses;            // idhmc_create_glm_responses: Y is [M][n][K], global chain g samples response g / R
+    int64_t M, R;              // (1, 0 otherwise)
 };
 // idhmc_create and idhmc_create_glm: one validation, one set-up
 static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -635,7 +638,23 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
         glm_a = parts->A;
         glm_h = parts->H;
         lr_n = parts->n;
+        if (parts->responses) {
+            const int64_t M = parts->M, R = parts->R;
+            if (M < 1) return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld: at least one response is needed", what, (long long)M);
+            if (R < 1) return fail(IDHMC_ERR_BAD_ARG, "%s: chains_per_response = %lld: at least one chain per response is needed", what, (long long)R);
+            if ((__int128)first_chain_id + nchains > (__int128)M * R)
+                return fail(IDHMC_ERR_BAD_ARG, "%s: first_chain_id + nchains = %lld is past the M * chains_per_response = %lld * %lld chains of the model",
+                            what, (long long)(first_chain_id + nchains), (long long)M, (long long)R);
+            // both pool statistics over every chain of the context, and the chains of different responses sample different posteriors
+            if (M > 1 && opt.eps_mode == IDHMC_EPS_GLOBAL)
+                return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses with eps_mode = GLOBAL: the global stepsize pools the acceptance of chains "
+                            "that sample different posteriors (use PER_CHAIN)", what, (long long)M);
+            if (M > 1 && opt.metric_mode == IDHMC_METRIC_POOLED)
+                return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses with metric_mode = POOLED: the pooled metric pools the windows of chains "
+                            "that sample different posteriors (use PER_CHAIN or SHARED)", what, (long long)M);
+        }
     }
+    const int64_t glm_m = parts && parts->responses ? parts->M : 1;      // responses: planes of Y
     if (kind == IDHMC_MODEL_GLM && !glm_aux && !parts) {
         const int D = model->D;
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
@@ -693,6 +712,9 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
         if (npad * L > ((int64_t)1 << 27))
             return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
                         what, (long long)lr_n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
+        if (glm_m > ((int64_t)1 << 27) || glm_m * glm_k * npad > ((int64_t)1 << 27))
+            return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses of K = %lld columns and n = %lld observations exceed M * K * n_pad <= 2^27",
+                        what, (long long)glm_m, (long long)glm_k, (long long)lr_n);
         const double *X = parts ? parts->X : model->params + glm_head, *y = parts ? parts->Y : X + lr_n * Dx;
         for (int64_t k = 0; k < lr_n * Dx; ++k)
             if (!std::isfinite(X[k])) return fail(IDHMC_ERR_BAD_ARG, "%s: X[%lld, %lld] is not finite", what, (long long)(k / Dx), (long long)(k % Dx));
@@ -700,6 +722,10 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
             for (int64_t k = 0; k < lr_n * glm_k; ++k)
                 if (!std::isfinite(y[k]))
                     return fail(IDHMC_ERR_BAD_ARG, "%s: Y[%lld, %lld] is not finite", what, (long long)(k / glm_k), (long long)(k % glm_k));
+            for (int64_t k = lr_n * glm_k; k < glm_m * lr_n * glm_k; ++k)           // the further responses' planes
+                if (!std::isfinite(y[k]))
+                    return fail(IDHMC_ERR_BAD_ARG, "%s: Y[%lld, %lld, %lld] is not finite", what, (long long)(k / (lr_n * glm_k)),
+                                (long long)(k / glm_k % lr_n), (long long)(k % glm_k));
         } else {
             for (int64_t i = 0; i < lr_n; ++i)
                 if (y[i] != 0.0 && y[i] != 1.0) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: y[%lld] = %g is neither 0 nor 1", (long long)i, y[i]);
@@ -772,6 +798,9 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
     s.model = kind;               // a GLM_AUX runs as a GLM with lr_a > 0
     s.lr_a = (int32_t)glm_a;
     s.lr_h = (int32_t)glm_h;
+    s.lr_m = (int32_t)glm_m;
+    s.lr_r = parts && parts->responses ? (uint32_t)(parts->R > (int64_t)0xffffffffll ? (int64_t)0xffffffffll : parts->R) : 0u;
+    c->glm_r = parts && parts->responses ? parts->R : 0;
     s.k0 = (uint32_t)seed;
     s.k1 = (uint32_t)(seed >> 32);
     s.first_chain = (uint32_t)first_chain_id;
@@ -854,22 +883,23 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
         s.mu = mu; s.tau = tau; s.prec = prec;
         if (kind == IDHMC_MODEL_LOGISTIC_REGRESSION || kind == IDHMC_MODEL_GLM) {
             // the prior's defaults (mu = 0 is the zeroed allocation); X, X' and the K planes of Y zero-padded to [n_pad][L],
-            // [L][n_pad], [K][n_pad]; a GLM's constants
+            // [L][n_pad], [K][n_pad] (one set of planes per response, [M][K][n_pad]); a GLM's constants
             if (!model->tau) HIPCHK(launch_fill(tau, 1.0, s.D, c->stream));
             const bool glm = kind == IDHMC_MODEL_GLM;
-            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - glm_a - glm_h, K = glm_k;     // D: the columns of X
+            const int64_t n = lr_n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - glm_a - glm_h, K = glm_k, M = glm_m;     // D: the columns of X
             const double *X = parts ? parts->X : model->params + glm_head, *Y = parts ? parts->Y : X + n * D;
-            std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(K * npad), 0.0);
+            std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(M * K * npad), 0.0);
             for (int64_t i = 0; i < n; ++i)
                 for (int64_t k = 0; k < D; ++k) {
                     const double v = X[i * D + k];
                     hx[(size_t)(i * L + k)] = v;
                     hxt[(size_t)(k * npad + i)] = v;
                 }
-            for (int64_t i = 0; i < n; ++i)
-                for (int64_t k = 0; k < K; ++k) hy[(size_t)(k * npad + i)] = Y[i * K + k];
+            for (int64_t m = 0; m < M; ++m)
+                for (int64_t i = 0; i < n; ++i)
+                    for (int64_t k = 0; k < K; ++k) hy[(size_t)((m * K + k) * npad + i)] = Y[(m * n + i) * K + k];
             double *dx = nullptr, *dxt = nullptr, *dy = nullptr;
-            DALLOC(dx, npad * L); DALLOC(dxt, npad * L); DALLOC(dy, K * npad);
+            DALLOC(dx, npad * L); DALLOC(dxt, npad * L); DALLOC(dy, M * K * npad);
             if (glm) {
                 double *dc = nullptr;
                 DALLOC(dc, glm_nc > 0 ? glm_nc : 1);
@@ -959,10 +989,10 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     return create_context(out, device, nchains, first_chain_id, model, opt_in, seed, nullptr);
 }
 
-int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
-                     const idhmc_glm_desc *glm, const idhmc_options *opt_in, uint64_t seed)
+// idhmc_create_glm and idhmc_create_glm_responses
+static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
+                      bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed)
 {
-    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm: null argument");
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
     if (glm->A < 0 || glm->A > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: A = %d must be an integer in 0..4", glm->A);
@@ -988,8 +1018,31 @@ int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first
     m.mu = glm->mu;
     m.tau = glm->tau;
     m.source = glm->source;
-    const GlmParts parts{glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups};
+    const GlmParts parts{glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
     return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
+}
+
+int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                     const idhmc_glm_desc *glm, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm: null argument");
+    return create_glm(out, device, nchains, first_chain_id, glm, false, 1, 0, opt_in, seed);
+}
+
+int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                               const idhmc_glm_desc *glm, int64_t M, int64_t chains_per_response,
+                               const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_responses: null argument");
+    return create_glm(out, device, nchains, first_chain_id, glm, true, M, chains_per_response, opt_in, seed);
+}
+
+int idhmc_glm_responses(const idhmc_ctx *c, int64_t *M, int64_t *chains_per_response)
+{
+    if (!c || !M || !chains_per_response) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_responses: null argument");
+    *M = c->glm_r > 0 ? c->s.lr_m : 1;
+    *chains_per_response = c->glm_r;
+    return IDHMC_OK;
 }
 
 int idhmc_set_stream(idhmc_ctx *c, void *hip_stream)

@@ -24,6 +24,7 @@ IDHMC_DEV void eval_general_body(const DevState &s, int random_q, double *lds_ve
     Model mdl;
     mdl.init(s, lds_vec, lane);
     for (int64_t c = wave; c < s.C; c += nw) {
+        bind_chain(mdl, s, s.first_chain + (uint32_t)c);       // a GLM with several responses: this chain's Y
         Vec<NCH> q, g;
         if (random_q) {
             const RngKey key{s.k0, s.k1, s.first_chain + (uint32_t)c};
@@ -55,6 +56,7 @@ IDHMC_DEV void leapfrog_general_body(const DevState &s, double eps_arg, int own_
     Model mdl;
     mdl.init(s, lds_vec, lane);
     for (int64_t c = wave; c < s.C; c += nw) {
+        bind_chain(mdl, s, s.first_chain + (uint32_t)c);       // a GLM with several responses: this chain's Y
         const int64_t off = c * s.L;
         Vec<NCH> q = vload<NCH>(s.q + off, lane);
         Vec<NCH> p = vload<NCH>(s.p + off, lane);
@@ -94,6 +96,7 @@ IDHMC_DEV void stepsize_general_body(const DevState &s, double *lds_vec)
     Model mdl;
     mdl.init(s, lds_vec, lane);
     for (int64_t c = wave; c < s.C; c += nw) {
+        bind_chain(mdl, s, s.first_chain + (uint32_t)c);       // a GLM with several responses: this chain's Y
         const int64_t off = c * s.L;
         const Vec<NCH> q = vload<NCH>(s.q + off, lane);
         const Vec<NCH> p = vload<NCH>(s.p + off, lane);

@@ -22,7 +22,7 @@
 // A chain of fmas from +0 never holds -0, so the zero padding (columns >= D, observations >= n) leaves every chain as it is:
 // the per-wave form stops at D and n, the matrix-core form runs over the padded tiles, and both give the same bits.
 //
-// Device layout (DevState): X [n_pad][L] (lr_x), X' [L][n_pad] (lr_xt), Y as K planes [K][n_pad] (lr_y), all zero-padded;
+// Device layout (DevState): X [n_pad][L] (lr_x), X' [L][n_pad] (lr_xt), Y as K planes [K][n_pad] per response (lr_y), all zero-padded;
 // a GLM's constants in user_params (user_nparams of them).
 //
 // Auxiliary coordinates (IDHMC_MODEL_GLM_AUX): Obs::A of them (0 for the policies above, 1..4), the last A of the
@@ -45,6 +45,15 @@
 // The per-wave form stages b instead of q (coordinates >= Dx raw: a_j is still found there); in the matrix-core form the requester
 // writes b as its Q row (+0 in every column >= Dx) before barrier A and applies the chain rule to the G row it reads after barrier
 // C: nothing between the barriers changes, no LDS is added.
+//
+// Several responses on one design matrix (idhmc_create_glm_responses): Obs::kResponses, a compile-time flag of the
+// policy (false for the policies above: none of their instructions changes).  Y is M sets of K planes, [M][K][n_pad], and the chain of GLOBAL id
+// g samples response g / R (DevState::lr_r), whatever context or tile it runs in.  X, X', the prior, the constants and the groups are
+// shared, and for one chain the operations are those of a single-response model on its Y: only the address of y_i differs.  A kernel
+// binds the chain it takes (bind_chain, idhmc_internal.hpp) before it evaluates anything: the per-wave form offsets its pointer to
+// Y; in the matrix-core form the 16 rows of a tile are 16 chains of any responses, so the requester publishes its offset in
+// column L of its Q row (padding: zphase, gphase and both row accesses of the requester touch columns < L only) and the Z wavefronts
+// read y per accumulator row instead of once per lane.  No LDS, no tile, no barrier is added.
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -165,6 +174,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
+    static constexpr bool kResponses = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -176,10 +186,11 @@ struct GlmWave {
     static constexpr bool kHasParams = true;
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = false;
+    static constexpr bool kBindsChain = Obs::kResponses;
     static constexpr int AN = Obs::A > 0 ? Obs::A : 1;
     static constexpr int HN = Obs::H > 0 ? Obs::H : 1;
     const double *x, *xt;    // [npad][L], [L][npad], device
-    const double2 *y2;       // [K][npad], lane-offset
+    const double2 *y2;       // [K][npad], lane-offset (Obs::kResponses: of the bound chain's response)
     const double2 *mu2, *tau2;   // lane-offset, device
     const double *cst;       // the constants, device
     const int2 *grp2;        // the group ids, lane-offset, device (Obs::H > 0)
@@ -201,6 +212,13 @@ struct GlmWave {
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
         lane = lane_;
+    }
+    // Obs::kResponses: the chain of global id gc is evaluated next
+    template <class State>
+    IDHMC_DEV void bind_chain(const State &s, uint32_t gc)
+    {
+        const uint32_t resp = gc / s.lr_r;
+        y2 = reinterpret_cast<const double2 *>(s.lr_y) + lane + (size_t)resp * (size_t)(Obs::K * (npad >> 1));
     }
     IDHMC_DEV double grad(const Vec<NCH> &q, Vec<NCH> &g) const
     {
@@ -324,6 +342,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     static constexpr bool kHasParams = true;
     static constexpr bool kSeparable = false;
     static constexpr bool kCooperative = true;
+    static constexpr bool kBindsChain = Obs::kResponses;
     static constexpr int L = 128 * NCH, DS = L + 2, RS = 130, KB = L / 4;
     static constexpr int kZT = 8, kGT = L / 16;        // Z column tiles per block (wavefronts 8..15), G column tiles (0..L/16-1)
     static constexpr int kQ = 0, kR = 16 * DS;         // Q / G tile, then the two R tiles
@@ -360,6 +379,18 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         alive = alive_;
         lane = lane_;
         wv = wv_;
+        // a row that never holds a chain is still multiplied: its offset into Y must be a valid one (the kernel's first barrier follows)
+        if constexpr (Obs::kResponses) { if (lane == 0) *yslot(wv) = 0; }
+    }
+    // Obs::kResponses: row's offset into Y (doubles), kept in the padding column L of its Q row
+    IDHMC_DEV int *yslot(int row) const { return reinterpret_cast<int *>(tile + kQ + row * DS + L); }
+    // the chain of global id gc is this wavefront's next requester.  Called between rounds (every wavefront of the workgroup is in
+    // every round, so none reads the slot now), ahead of barrier A of the chain's first request.
+    template <class State>
+    IDHMC_DEV void bind_chain(const State &s, uint32_t gc)
+    {
+        const uint32_t resp = gc / s.lr_r;
+        if (lane == 0) *yslot(wv) = (int)(resp * (uint32_t)(Obs::K * npad));      // M K n_pad <= 2^27
     }
     IDHMC_DEV double *rtile(int b) const { return tile + kR + (b & 1) * (16 * RS); }
     IDHMC_DEV double *splane(int j) const { return tile + kS + j * (16 * PS); }
@@ -382,8 +413,10 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         }
         const int i = 128 * b + 16 * zt + jj;
         GlmObs o;
+        if constexpr (!Obs::kResponses) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o.y[k] = k < Obs::K ? y[k * npad + i] : 0.0;
+            for (int k = 0; k < 4; ++k) o.y[k] = k < Obs::K ? y[k * npad + i] : 0.0;
+        }
         o.c = cst;
         o.K = Obs::K;
         o.nc = nc;
@@ -393,6 +426,11 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         for (int reg = 0; reg < 4; ++reg) {                  // row kk + 4 reg (chain), column jj (observation)
             double r, v;
             double av[AN], u[AN];
+            if constexpr (Obs::kResponses) {
+                const double *yr = y + *yslot(kk + 4 * reg) + i;                             // Y of this row's chain
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o.y[k] = k < Obs::K ? yr[k * npad] : 0.0;
+            }
             if constexpr (Obs::A > 0) {
 #pragma unroll
                 for (int j = 0; j < AN; ++j) av[j] = splane(j)[(kk + 4 * reg) * PS + 128];   // a_j of this row's chain

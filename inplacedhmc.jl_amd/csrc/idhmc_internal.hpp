@@ -29,6 +29,11 @@ struct DevState {
     int32_t model;        // IDHMC_MODEL_*
     uint32_t k0, k1;      // Philox key = seed
     uint32_t first_chain; // global id of chain 0
+    // A GLM with several responses (idhmc_create_glm_responses): lr_y is [lr_m][K][lr_npad] and the chain of GLOBAL id
+    // g = first_chain + c samples response g / lr_r (chains_per_response, capped at 2^32 - 1: chain ids fit 32 bits, so a larger one is one
+    // response all the same).  lr_m = 1, lr_r = 0 for every other context.  Both sit where the struct had alignment padding: its size and
+    // every other offset are what they were, so no ahead-of-time kernel changes (tools/kres.py, profiles/r09_kres_*.txt).
+    uint32_t lr_r;
     double *q, *p, *g;    // [C][L]
     double *lq, *pi;      // [C]  l(q),  pi = l(q) - K(p)
     double *eps;          // [C]
@@ -38,7 +43,7 @@ struct DevState {
     int64_t lf_stride2;       // the same for the REGRAD variants, which touch q and p only: a slice of two arrays
     const double *mu, *tau;   // [L]
     const double *prec;       // [L][L]
-    const double *lr_x, *lr_xt, *lr_y;   // IDHMC_MODEL_LOGISTIC_REGRESSION, _GLM: X [lr_npad][L], X' [L][lr_npad], Y [K][lr_npad], zero-padded
+    const double *lr_x, *lr_xt, *lr_y;   // IDHMC_MODEL_LOGISTIC_REGRESSION, _GLM: X [lr_npad][L], X' [L][lr_npad], Y [lr_m][K][lr_npad], zero-padded
     int32_t lr_n, lr_npad;               // observations, and rounded up to a multiple of 128
     int32_t lr_a;                        // a GLM's auxiliary coordinates: X has D - lr_a - lr_h columns, lr_a coordinates after them are theirs (0: none)
     int32_t lr_h;                        // a GLM's coefficient groups: the last lr_h coordinates are their log scales (0: none)
@@ -47,6 +52,7 @@ struct DevState {
     const void *jit;             // host only: the hipRTC module of a custom density or a GLM
     // NUTS
     int32_t max_depth;
+    int32_t lr_m;             // responses of a GLM (see lr_r)
     double min_delta;
     idhmc_tree_stats *stats;  // [C]
     uint32_t *directions;     // [C] injected directions
@@ -80,6 +86,17 @@ struct DevState {
                                       // chain raised: eps underflow)}; [2..9] cycle stamps of the diagnostic build (-DIDHMC_STAMPS)
     const int32_t *lr_grp;    // [L] a GLM with lr_h > 0: the group of every coordinate, -1 for ungrouped and padded ones (null otherwise)
 };
+// A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
+// kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
+template <class Model, class = void>
+struct BindsChain { static constexpr bool value = false; };
+template <class Model>
+struct BindsChain<Model, decltype(void(Model::kBindsChain))> { static constexpr bool value = Model::kBindsChain; };
+template <class Model>
+__device__ __forceinline__ void bind_chain(Model &mdl, const DevState &s, uint32_t global_chain)
+{
+    if constexpr (BindsChain<Model>::value) mdl.bind_chain(s, global_chain);
+}
 constexpr int kPulseAt = 0;
 // transition flag of the test suite only (see the XCD check in k_nuts); idhmc_nuts_transition(s) accept it on a context created
 // with IDHMC_TEST_XCC_MISMATCH=1 in the environment, and refuse it, like every other bit outside the IDHMC_T_* set, otherwise
@@ -113,7 +130,8 @@ constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
 struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
-int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);   // K, A and H of a GLM
+// K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses)
+int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 hipError_t launch_eval_jit(const DevState &s, int random_q, hipStream_t st);
 hipError_t launch_leapfrog_jit(const DevState &s, double eps, int own, int n_steps, hipStream_t st);

@@ -560,6 +560,9 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         const uint32_t iter = iter0 + it;
         const int64_t c = (int64_t)cu;
         const RngKey key{s.k0, s.k1, s.first_chain + cu};
+        // a GLM with several responses: the chain's Y.  Per ticket, not at init: with several transitions per launch a wavefront changes
+        // chain, and response, inside the launch
+        bind_chain(mdl, s, key.chain);
         const int64_t off = c * L;
         STAMP_DECL;
         BYTES_DECL;

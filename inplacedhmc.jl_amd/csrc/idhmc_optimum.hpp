@@ -82,7 +82,7 @@ IDHMC_DEV double density_eval(const Model &mdl, const Vec<NCH> &q, Vec<NCH> &g)
 }
 
 template <int NCH, class Model>
-IDHMC_DEV void local_optimum_body(const DevState &s, const Model &mdl, double penalty, int iterations, double *hist)
+IDHMC_DEV void local_optimum_body(const DevState &s, Model &mdl, double penalty, int iterations, double *hist)
 {
     constexpr int L = 128 * NCH, M = kLbfgsM, R = kLbfgsR;
     const int lane = threadIdx.x & 63;
@@ -92,6 +92,7 @@ IDHMC_DEV void local_optimum_body(const DevState &s, const Model &mdl, double pe
     for (int64_t c = wave; c < s.C; c += nw) {
         const int64_t off = c * L;
         const RngKey key{s.k0, s.k1, s.first_chain + (uint32_t)c};
+        bind_chain(mdl, s, key.chain);                         // a GLM with several responses: this chain's Y
         Vec<NCH> x = vload<NCH>(s.q + off, lane);
         Vec<NCH> gl = vload<NCH>(s.g + off, lane);
         double lq = s.lq[c];

@@ -111,6 +111,18 @@ def rhat_from_moments(mean, var, n):
     return np.sqrt(((n - 1.0) / n * W + Bn) / W)
 
 
+def rhat_by_response(model, mean, var, n, first_chain=0):
+    """rhat_from_moments for each response of a GLM with several (GLM(..., chains_per_response=R)): mean, var of shape (C, D) over
+    chains that cover whole responses (glm.by_response), n the draws per chain (a scalar or one per chain); shape (C // R, D), all M
+    responses for a context that holds every chain.  The between-chain variance needs R >= 2."""
+    from . import glm
+    m, v = glm.by_response(model, mean, first_chain), glm.by_response(model, var, first_chain)
+    if m.shape != v.shape or m.ndim != 3:
+        raise ValueError("mean and var must both have shape (chains, D), got %s and %s" % (np.shape(mean), np.shape(var)))
+    nn = np.broadcast_to(np.asarray(n, dtype=np.float64), (m.shape[0] * m.shape[1],)).reshape(m.shape[:2])
+    return np.stack([rhat_from_moments(m[k], v[k], nn[k]) for k in range(m.shape[0])])
+
+
 def ess_from_moments(mean, var, n, cap=False):
     """Total effective sample size per coordinate from the same moments, by replicated batch means with every chain as
     one batch (Vats, Flegal & Jones): the variance of the chain means estimates sigma^2 / ESS_chain directly, so

@@ -61,7 +61,8 @@ class Model:
                 raise ValueError("%s must have shape %s" % (name, shape))
 
     def glm_desc(self):
-        """the descriptor of idhmc_create_glm (a GLM with coefficient groups keeps X, Y and its constants as arrays)"""
+        """the descriptor of idhmc_create_glm and idhmc_create_glm_responses (a GLM with coefficient groups or several responses keeps
+        X, Y and its constants as arrays; with responses Y is (M, n, K))"""
         d = GlmDesc(n=self.n, Dx=self.Dx, K=self.K, nc=self.nc, A=self.A, H=self.H, X=_dp(self.X), Y=_dp(self.Y), source=self.source)
         if self.nc:
             d.constants = _dp(self.constants)
@@ -160,7 +161,7 @@ def _prior(D, prior_mu, prior_tau):
     return mu, tau
 
 
-def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None):
+def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -180,7 +181,14 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     of a grouped column is beta_c = exp(omega_g) u_c, of any other u_c; z = X beta.  The Gaussian prior is on the sampled
     coordinates (prior_mu, prior_tau: scalars or length Dx + A + H): with the defaults beta_c ~ N(0, sigma_g^2) and omega_g ~ N(0, 1).
     `source` is the one the same model takes without groups.  Draws come back in the sampled coordinates:
-    glm.coefficients(model, draws) gives beta, glm.group_scales(model, draws) the sigma_g.  The Model exposes H and groups."""
+    glm.coefficients(model, draws) gives beta, glm.group_scales(model, draws) the sigma_g.  The Model exposes H and groups.
+
+    chains_per_response = R (a positive integer): M responses on the one design matrix (idhmc_create_glm_responses) -- Y is 3-D,
+    (M, n, K), and the chain of global id g samples the posterior of Y[g // R]; X, the prior, the constants, the source and the groups
+    are shared.  An Engine (or the shards of a run, through first_chain) holds at most M * R chains, with a per-chain stepsize and a
+    per-chain or SHARED metric (EPS_GLOBAL and METRIC_POOLED pool over chains of different posteriors and are refused with M > 1).
+    Each chain's draws are bit-identical to those of a single-response model on its Y.  glm.response_of_chain, glm.by_response and
+    diagnostics.rhat_by_response sort chains and draws by response.  The Model exposes M and R (1 and None without the keyword)."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -212,9 +220,20 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     if not np.isfinite(X).all():
         raise ValueError("X must be finite")
     Y = np.asarray(Y, dtype=np.float64)
-    if Y.ndim == 1:
+    M, R = 1, None
+    if chains_per_response is not None:
+        if isinstance(chains_per_response, bool) or not isinstance(chains_per_response, (int, np.integer)) or chains_per_response < 1:
+            raise ValueError("chains_per_response must be a positive integer (got %r)" % (chains_per_response,))
+        R = int(chains_per_response)
+        if Y.ndim == 2:
+            raise ValueError("with chains_per_response Y must have shape (M, n, K); a 2-D Y of shape %s could be (M, n) or (n, K): add the "
+                             "K axis (Y[:, :, None] for M responses of one column, Y[None] for one response)" % (Y.shape,))
+        if Y.ndim != 3 or Y.shape[0] < 1 or Y.shape[1] != n or not 1 <= Y.shape[2] <= 4:
+            raise ValueError("with chains_per_response Y must have shape (M, %d, K) with M >= 1 and 1 <= K <= 4, got %s" % (n, Y.shape))
+        M = Y.shape[0]
+    elif Y.ndim == 1:
         Y = Y[:, None]
-    if Y.ndim != 2 or Y.shape[0] != n or not 1 <= Y.shape[1] <= 4:
+    if R is None and (Y.ndim != 2 or Y.shape[0] != n or not 1 <= Y.shape[1] <= 4):
         raise ValueError("Y must have shape (%d,) or (%d, K) with 1 <= K <= 4, got %s" % (n, n, Y.shape))
     if not np.isfinite(Y).all():
         raise ValueError("Y must be finite")
@@ -226,9 +245,9 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     if not isinstance(source, str) or not source.strip():
         raise ValueError("a GLM needs HIP source defining glm_observation")
     mu, tau = _prior(D, prior_mu, prior_tau)
-    K = Y.shape[1]
-    if H > 0:
-        # handed over in parts (idhmc_create_glm): the packed params are not stretched for the groups
+    K = Y.shape[-1]
+    if H > 0 or R is not None:
+        # handed over in parts (idhmc_create_glm, idhmc_create_glm_responses): the packed params are not stretched for the groups or the responses
         m = Model(MODEL_GLM_AUX if A else MODEL_GLM, D, mu=mu, tau=tau, source=source)
         m.X, m.Y, m.constants = np.ascontiguousarray(X), np.ascontiguousarray(Y), np.ascontiguousarray(c)
     elif A == 0:
@@ -238,6 +257,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
         m = Model(MODEL_GLM_AUX, D, mu=mu, tau=tau, source=source,
                   params=np.concatenate([[float(K), float(c.size), float(A)], c, X.ravel(), Y.ravel()]))
     m.n, m.K, m.nc, m.Dx, m.A, m.H, m.groups = n, K, c.size, Dx, A, H, grp
+    m.M, m.R = M, R
     return m
 
 
@@ -260,7 +280,11 @@ class Engine:
         self.opt = options if options is not None else default_options()
         self.C, self.D = int(nchains), model.D
         h = C.c_void_p()
-        if getattr(model, "H", 0) > 0:
+        if getattr(model, "R", None) is not None:
+            desc = model.glm_desc()
+            check(self.lib.idhmc_create_glm_responses(C.byref(h), device, self.C, first_chain, C.byref(desc), model.M, model.R,
+                                                      C.byref(self.opt), seed))
+        elif getattr(model, "H", 0) > 0:
             desc = model.glm_desc()
             check(self.lib.idhmc_create_glm(C.byref(h), device, self.C, first_chain, C.byref(desc), C.byref(self.opt), seed))
         else:
@@ -364,6 +388,12 @@ class Engine:
         """the NUTS kernel's gradient of a logistic regression or a GLM: 0 one chain per wavefront, 1 the fp64 matrix cores;
         -1 for every other model"""
         return int(self.lib.idhmc_glm_form(self.h))
+
+    def glm_responses(self):
+        """(M, chains_per_response) of a GLM with several responses (GLM(..., chains_per_response=R)); (1, 0) for every other model"""
+        m, r = C.c_int64(0), C.c_int64(0)
+        check(self.lib.idhmc_glm_responses(self.h, C.byref(m), C.byref(r)))
+        return int(m.value), int(r.value)
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -51,6 +51,10 @@ Past those ends v is +inf or NaN as above.
 Every source above works unchanged with coefficient groups, GLM(..., groups=...): the sampled coordinates are
 [u (Dx) | a (A) | omega (H)]; coefficients(model, draws) turns draws into beta = s * u, group_scales(model, draws) into
 sigma = exp(omega).
+
+Every source above also works unchanged with several responses, GLM(..., chains_per_response=R): Y is (M, n, K)
+and the chain of global id g samples the posterior of Y[g // R].  response_of_chain(model, nchains, first_chain) names each chain's
+response and by_response(model, draws, first_chain) sorts draws (or any per-chain array) by it.
 """
 import numpy as np
 
@@ -256,8 +260,45 @@ def beta_response(y):
     return np.stack([np.log(y), np.log1p(-y)], 1)
 
 
+def _responses(model):
+    R = getattr(model, "R", None)
+    if R is None:
+        raise ValueError("the model has one response (GLM(..., chains_per_response=R) makes one with several)")
+    return int(model.M), int(R)
+
+
+def response_of_chain(model, nchains, first_chain=0):
+    """the response each chain of a context samples: integer ids, shape (nchains,), chain c being global chain first_chain + c
+    (response = global id // chains_per_response)"""
+    M, R = _responses(model)
+    nchains, first_chain = int(nchains), int(first_chain)
+    if nchains < 1 or first_chain < 0 or first_chain + nchains > M * R:
+        raise ValueError("chains %d .. %d are not among the M * chains_per_response = %d * %d chains of the model"
+                         % (first_chain, first_chain + nchains - 1, M, R))
+    return (first_chain + np.arange(nchains, dtype=np.int64)) // R
+
+
+def by_response(model, draws, first_chain=0):
+    """per-chain values sorted by response: (..., C, D) becomes (C // R, ..., R, D), R = chains_per_response, the leading axis running
+    over the responses the C chains cover (all M of them for a context that holds every chain; response first_chain // R comes
+    first).  The chains must cover whole responses: first_chain and C multiples of R."""
+    M, R = _responses(model)
+    draws = np.asarray(draws)
+    if draws.ndim < 2:
+        raise ValueError("draws must have shape (..., chains, D), got %s" % (draws.shape,))
+    C = draws.shape[-2]
+    first_chain = int(first_chain)
+    response_of_chain(model, C, first_chain)                    # the range check
+    if first_chain % R or C % R:
+        raise ValueError("chains %d .. %d cover a part of a response only (chains_per_response = %d): whole responses are needed"
+                         % (first_chain, first_chain + C - 1, R))
+    out = draws.reshape(draws.shape[:-2] + (C // R, R, draws.shape[-1]))
+    return np.moveaxis(out, -3, 0)
+
+
 def group_scales(model, draws):
-    """sigma_g = exp(omega_g) of a GLM with coefficient groups, shape draws.shape[:-1] + (H,) (H = 0: an empty last axis)"""
+    """sigma_g = exp(omega_g) of a GLM with coefficient groups, shape draws.shape[:-1] + (H,) (H = 0: an empty last axis).  Any
+    leading axes: (M, ..., R, D) from by_response works as (..., C, D) does."""
     draws = np.asarray(draws, dtype=np.float64)
     Dx, A, H = model.Dx, model.A, getattr(model, "H", 0)
     if draws.shape[-1] != Dx + A + H:
@@ -267,7 +308,8 @@ def group_scales(model, draws):
 
 def coefficients(model, draws):
     """the coefficients beta = s * u of a GLM from draws in the sampled coordinates, shape draws.shape[:-1] + (Dx,):
-    beta_c = exp(omega_g) u_c for a column of group g, u_c for a column in no group (and for a model without groups)"""
+    beta_c = exp(omega_g) u_c for a column of group g, u_c for a column in no group (and for a model without groups).  Any leading
+    axes: (M, ..., R, D) from by_response works as (..., C, D) does."""
     draws = np.asarray(draws, dtype=np.float64)
     sigma = group_scales(model, draws)
     u = draws[..., :model.Dx]

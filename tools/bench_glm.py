@@ -21,8 +21,15 @@ matrix cores against the same arithmetic (dlgamma_psi included) as a custom sour
 the same design and counts (each started from its own Laplace approximation; different densities and trees, so steps/s), and a
 beta regression (BETA_LOGIT_LOGPHI, three dlgamma_psi calls per observation) on the same design.
 
+--responses M,... (GLM(..., chains_per_response=R)) adds, per shape and chain count C, the Poisson regression with
+M responses of C / M chains each on the one design (the first response is the poisson pair's, the others are drawn from its fitted
+model, each with its own seed; every chain starts from the first response's Laplace approximation): M = 1 is the plain GLM of the
+existing entry point, the poisson pair's glm_poisson.  --chains-per-response R,... names the same rows by R (M = C / R).  --repeats K
+makes K engines per row, for the run-to-run spread.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
+                              [--responses 1,4096] [--chains-per-response 16] [--repeats 1]
 """
 import argparse
 import json
@@ -385,9 +392,19 @@ def model(form, X, y, q_map=None):
 LOCKSTEP = False    # --lockstep: every tree runs to max_depth = 6 (63 steps), see main()
 
 
-def run(form, X, y, q_map, cov, C, T, seed=1, metric=None):
+def responses_model(X, y, q_map, M, C):
+    """the Poisson regression with M responses of C / M chains: Y[0] = y, the others drawn from the fitted model"""
+    Y = np.empty((M, len(y), 1))
+    Y[0, :, 0] = y
+    mean = np.exp(X @ q_map)
+    for m in range(1, M):
+        Y[m, :, 0] = np.random.default_rng(1000003 * m + len(y)).poisson(mean)
+    return pkg.GLM(X, Y, pkg.glm.POISSON_LOG, chains_per_response=C // M)
+
+
+def run(form, X, y, q_map, cov, C, T, seed=1, metric=None, mdl=None):
     t0 = time.perf_counter()
-    eng = pkg.Engine(model(form, X, y, q_map), C, pkg.default_options(metric_mode=pkg.METRIC_SHARED if metric is None else metric,
+    eng = pkg.Engine(model(form, X, y, q_map) if mdl is None else mdl, C, pkg.default_options(metric_mode=pkg.METRIC_SHARED if metric is None else metric,
                                                                       max_depth=6 if LOCKSTEP else 10), seed=seed)
     create_s = time.perf_counter() - t0
     Dx = X.shape[1]
@@ -436,6 +453,10 @@ def main():
     ap.add_argument("--hier-cost", action="store_true", help="the hier pair's design with H = 0, 1 and 4 groups per shape (DESIGN section 13)")
     ap.add_argument("--dispersion-cost", action="store_true", help="the negative binomial next to POISSON_LOG on the same design and counts, "
                     "and a beta regression, per shape (DESIGN section 14)")
+    ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
+                    "(DESIGN section 15); 1 is the plain GLM")
+    ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
+    ap.add_argument("--repeats", type=int, default=1, help="engines per row of --responses (the run-to-run spread)")
     ap.add_argument("--metric", default="shared", choices=["shared", "per_chain"])
     ap.add_argument("--lockstep", action="store_true", help="eps / 1000 and max_depth = 6: every tree of every density takes the same 63 "
                     "steps, so steps/s compares the cost per gradient and not the trees")
@@ -479,6 +500,21 @@ def main():
                           (D, n, C, f, row[f]["glm_form"], row[f]["leapfrog_steps_per_s"], row[f]["mean_depth"]), file=sys.stderr, flush=True)
                 row["negbin_over_poisson"] = row["glm_negbin"]["leapfrog_steps_per_s"] / row["glm_poisson"]["leapfrog_steps_per_s"]
                 res["results"].append(row)
+        if a.responses or a.chains_per_response:
+            X, y, q_map, cov = poisson_problem(n, D, seed=D * 7919 + n)
+            for C in (int(c) for c in a.chains.split(",")):
+                for M in [int(m) for m in a.responses.split(",") if m] + [C // int(r) for r in a.chains_per_response.split(",") if r]:
+                    if M < 1 or C % M:
+                        raise SystemExit("--responses: M = %d does not divide %d chains" % (M, C))
+                    row = dict(pair="responses", D=D, n=n, chains=C, M=M, chains_per_response=C // M, metric=a.metric, runs=[])
+                    for _ in range(a.repeats):
+                        mdl = None if M == 1 else responses_model(X, y, q_map, M, C)
+                        row["runs"].append(run("glm_poisson", X, y, q_map, cov, C, a.transitions, metric=metric, mdl=mdl)[0])
+                        r = row["runs"][-1]
+                        print("# D=%d n=%d C=%d M=%d (form %d): %.4e leapfrog steps/s, %.2f ms/transition, depth %.2f, create %.2f s" %
+                              (D, n, C, M, r["glm_form"], r["leapfrog_steps_per_s"], r["ms_per_transition"], r["mean_depth"], r["create_s"]),
+                              file=sys.stderr, flush=True)
+                    res["results"].append(row)
         for pair in [p for p in a.pairs.split(",") if p]:
             fa, fb, prob = PAIRS[pair]
             X, y, q_map, cov = prob(n, D, seed=D * 7919 + n)
