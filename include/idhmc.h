@@ -490,7 +490,8 @@ int idhmc_diag_reset(idhmc_ctx *ctx);
 int idhmc_get_diag_counters(idhmc_ctx *ctx, uint64_t *counters);            /* IDHMC_DIAG_COUNTERS values */
 /* host only, no context: the summary of (summed) counters */
 int idhmc_tree_summary_from_counters(const uint64_t *counters, idhmc_tree_summary *out);
-/* EBFMI per chain = mean(abs2, diff(pi)) / var(pi) over the accumulated transitions (src/diagnostics.jl:28-32) */
+/* EBFMI per chain = mean(abs2, diff(pi)) / var(pi) over the accumulated transitions (src/diagnostics.jl:28-32); NaN for a chain with
+ * fewer than two of them (0 / 0, as the reference's formula gives on one record) */
 int idhmc_get_ebfmi(idhmc_ctx *ctx, double *ebfmi);                          /* nchains */
 
 /* ---- drivers: the reference's caller loops, run by the library -------------- */

@@ -1670,6 +1670,11 @@ int idhmc_diag_reset(idhmc_ctx *c)
         if (int rc = dalloc(c, &c->ebfmi_out, s.C)) return rc;
     } else {
         HIPCHK(hipMemsetAsync(s.diag.n, 0, sizeof(int32_t) * s.C, c->stream));
+        // (the sums too: the kernel writes them with a window's first record, and idhmc_get_ebfmi on an empty window must find what a
+        // fresh context has -- zeros, hence NaN -- not the previous window's)
+        HIPCHK(hipMemsetAsync(s.diag.s1, 0, sizeof(double) * s.C, c->stream));
+        HIPCHK(hipMemsetAsync(s.diag.s2, 0, sizeof(double) * s.C, c->stream));
+        HIPCHK(hipMemsetAsync(s.diag.d2, 0, sizeof(double) * s.C, c->stream));
         HIPCHK(hipMemsetAsync(s.diag.counters, 0, sizeof(unsigned long long) * IDHMC_DIAG_COUNTERS, c->stream));
     }
     return IDHMC_OK;
@@ -1691,22 +1696,24 @@ int idhmc_tree_summary_from_counters(const uint64_t *cn, idhmc_tree_summary *out
     for (int d = 0; d < 33; ++d) out->depth_counts[d] = (int64_t)cn[6 + d];
     if (N == 0) return IDHMC_OK;
     out->a_mean = xchg_mean(IDHMC_XCHG_ACCEPT, (double)(int64_t)cn[1], (double)cn[2], (double)N);
-    // sample quantile (linear interpolation between order statistics, position q (N - 1)) located in the histogram,
-    // order statistics taken as equally spaced inside their bin
+    // sample quantile (linear interpolation between the order statistics on either side of position q (N - 1)), each order statistic
+    // located in the histogram and taken as equally spaced inside its bin: both are within a bin's width of the sample's, so their
+    // interpolation is too -- also when they lie in different bins with empty ones between them
+    auto order_statistic = [cn](uint64_t i) {
+        uint64_t below = 0;
+        for (int b = 0; b < IDHMC_DIAG_ACC_BINS; ++b) {
+            const uint64_t nb = cn[39 + b];
+            if (i < below + nb) return ((double)b + ((double)(i - below) + 0.5) / (double)nb) / (double)IDHMC_DIAG_ACC_BINS;
+            below += nb;
+        }
+        return 1.0;
+    };
     static const double qs[5] = {0.05, 0.25, 0.5, 0.75, 0.95};       // ACCEPTANCE_QUANTILES, src/diagnostics.jl:35
     for (int k = 0; k < 5; ++k) {
         const double pos = qs[k] * (double)(N - 1);
-        uint64_t below = 0;
-        double val = 1.0;
-        for (int b = 0; b < IDHMC_DIAG_ACC_BINS; ++b) {
-            const uint64_t nb = cn[39 + b];
-            if (nb && pos < (double)(below + nb)) {
-                val = ((double)b + (pos - (double)below + 0.5) / (double)nb) / (double)IDHMC_DIAG_ACC_BINS;
-                break;
-            }
-            below += nb;
-        }
-        out->a_quantiles[k] = val;
+        const uint64_t i = (uint64_t)pos;
+        const double lo = order_statistic(i), frac = pos - (double)i;
+        out->a_quantiles[k] = frac > 0.0 && i + 1 < N ? lo + frac * (order_statistic(i + 1) - lo) : lo;
     }
     return IDHMC_OK;
 }

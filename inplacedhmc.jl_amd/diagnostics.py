@@ -15,7 +15,7 @@ def EBFMI(tree_statistics):
     ts = np.asarray(tree_statistics)
     if ts.ndim == 2:
         return np.array([EBFMI(r) for r in ts])
-    pis = ts["pi"].astype(np.float64)
+    pis = ts["pi"] if ts["pi"].dtype == np.longdouble else ts["pi"].astype(np.float64)      # (long double in: long double arithmetic)
     return float(np.mean(np.diff(pis) ** 2) / np.var(pis, ddof=1))
 
 

@@ -5,21 +5,7 @@ a GPU; the device accumulation is checked on the GPU against numpy on the very r
 import numpy as np
 import pytest
 
-
-def _counters_from_records(idhmc, ts):
-    """what the kernel epilogue accumulates, restated in numpy (integers only)"""
-    from inplacedhmc_jl_amd import _lib
-    ts = np.asarray(ts).ravel()
-    cn = np.zeros(_lib.DIAG_COUNTERS, dtype=np.uint64)
-    rec = idhmc.xchg_accumulate(idhmc.XCHG_ACCEPT, ts["acceptance_rate"])
-    cn[0], cn[1], cn[2] = len(ts), int(rec[0]), int(rec[1])
-    maxd = (ts["term_left"] == 1) & (ts["term_right"] == 0)
-    div = (ts["term_left"] == ts["term_right"])
-    cn[3], cn[4], cn[5] = maxd.sum(), div.sum(), len(ts) - maxd.sum() - div.sum()
-    cn[6:39] = np.bincount(np.minimum(ts["depth"], 32), minlength=33)
-    bins = np.clip((ts["acceptance_rate"] * 1024).astype(np.int64), 0, 1023)
-    cn[39:] = np.bincount(bins, minlength=1024)
-    return cn
+from test_accumulators_cpu import _counters_from_records      # the epilogue's counters restated in numpy
 
 
 def test_summary_from_counters_matches_the_record_summary():
