@@ -1,0 +1,560 @@
+// idhmc_create.hip -- a context's life: the argument checks of the three creation entry points (every one answers before the
+// device is looked for), set-up, idhmc_destroy, the default options and what a context can be asked about itself.
+#include "idhmc_host.hpp"
+
+void idhmc_default_options(idhmc_options *o)
+{
+    if (!o) return;
+    o->max_depth = 10;                    // DEFAULT_MAX_TREE_DEPTH, src/tree.jl:2
+    o->min_delta = -1000.0;               // src/NUTS.jl:214
+    o->da_delta = 0.8; o->da_gamma = 0.05; o->da_kappa = 0.75; o->da_t0 = 10;   // src/stepsize.jl:191
+    o->ss_a_min = 0.25; o->ss_a_max = 0.75; o->ss_eps0 = 1.0; o->ss_C = 2.0;    // src/stepsize.jl:29
+    o->ss_maxiter_crossing = 400; o->ss_maxiter_bisect = 400;
+    o->init_steps = 75; o->middle_steps = 25; o->doubling_stages = 5; o->terminating_steps = 50;  // src/warmup.jl:366
+    o->adapt_metric = 1;
+    o->stepsize_search = 1;
+    o->eps_init = 1.0;
+    o->eps_mode = IDHMC_EPS_PER_CHAIN;
+    o->metric_mode = IDHMC_METRIC_PER_CHAIN;
+    o->local_opt_iterations = 0;          // the FindLocalOptimum stage is opt-in at this level (own optimiser)
+    o->leapfrog_grad_mode = IDHMC_GRAD_RECOMPUTE;   // separable densities: 4 streams instead of 6, the same bits
+    o->local_opt_penalty = 1e-4;          // src/warmup.jl:143
+}
+
+int idhmc_destroy(idhmc_ctx *c)
+{
+    if (!c) return IDHMC_OK;
+    (void)hipSetDevice(c->device);
+    for (int k = 1; k < idhmc_ctx::kLanes; ++k) if (c->lane[k]) (void)hipStreamSynchronize(c->lane[k]);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (int k = 1; k < idhmc_ctx::kLanes; ++k) {
+        if (c->lane[k]) (void)hipStreamDestroy(c->lane[k]);
+        if (c->lane_ev[k]) (void)hipEventDestroy(c->lane_ev[k]);
+    }
+    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+    for (void *p : c->allocs) (void)hipFree(p);
+    if (c->ev0) (void)hipEventDestroy(c->ev0);
+    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    for (int b = 0; b < 2; ++b) if (c->ev_packed[b]) (void)hipEventDestroy(c->ev_packed[b]);
+    if (c->ring) (void)hipHostFree(c->ring);
+    jit_destroy(c->jit);
+    comm_destroy(c->comm);
+    delete c;
+    return IDHMC_OK;
+}
+
+
+// The data of a regression model -- a logistic regression ([X | y] in idhmc_model_desc::params), a GLM packed into params
+// ([K, nc, c | X | Y]; with auxiliary coordinates [K, nc, A, c | X | Y]) or handed over in parts (idhmc_create_glm,
+// idhmc_create_glm_responses) -- as the one validation and the one upload below read it.  Any other model: the defaults.
+struct GlmParts {
+    const char *what = "";     // the model's name in messages
+    int64_t n = 0;             // observations
+    int32_t K = 1, nc = 0;     // data columns of Y, constants
+    int32_t A = 0;             // auxiliary coordinates: X has Dx = D - A - H columns, the A coordinates after them are not coefficients
+    int32_t H = 0;             // coefficient groups (idhmc_create_glm): the last H coordinates are their log scales
+    const double *X = nullptr, *Y = nullptr, *c = nullptr;
+    const int32_t *grp = nullptr;        // [Dx], H > 0
+    bool responses = false;    // idhmc_create_glm_responses: Y is [M][n][K], global chain g samples response g / R
+    int64_t M = 1, R = 0;      // (1, 0 otherwise)
+};
+// The head of a packed params array into *g: `head` = 0 (a logistic regression's [X | y]), 2 ([K, nc, c | X | Y]) or 3
+// ([K, nc, A, c | X | Y]) doubles in front of the constants.  The entries are checked as doubles (integral, hence finite, and in
+// range) before they are converted, and nothing at or past nparams is read: X, Y and c point at exactly the nparams - head doubles
+// that follow the head.
+static int unpack_params(const idhmc_model_desc *model, int head, GlmParts *g)
+{
+    const double *p = model->params;
+    const int64_t np = model->nparams;
+    const int D = model->D;
+    const bool aux = head == 3;
+    if (head == 0) {            // (K = 1 column, no constants: what follows holds, and fills *g, as for a GLM)
+        if (np < 1 || np % (D + 1) != 0 || !p)
+            return fail(IDHMC_ERR_BAD_ARG, "logistic regression: nparams = %lld must be a positive multiple of D + 1 = %d ([X | y])", (long long)np, D + 1);
+    } else if (np < head || !p)
+        return fail(IDHMC_ERR_BAD_ARG, "%s: params must begin with %s ([%s, c | X | Y])", g->what, aux ? "K, nc and A" : "K and nc", aux ? "K, nc, A" : "K, nc");
+    static const struct { const char *name; double lo, hi; } kEntry[3] = {{"K", 1.0, 4.0}, {"nc", 0.0, 16.0}, {"A", 1.0, 4.0}};
+    int32_t *const v[3] = {&g->K, &g->nc, &g->A};
+    for (int i = 0; i < head; ++i) {
+        if (!(p[i] >= kEntry[i].lo && p[i] <= kEntry[i].hi && p[i] == std::floor(p[i])))
+            return fail(IDHMC_ERR_BAD_ARG, "%s: %s = %g must be an integer in %g..%g", g->what, kEntry[i].name, p[i], kEntry[i].lo, kEntry[i].hi);
+        *v[i] = (int32_t)p[i];
+    }
+    const int64_t Dx = D - g->A;
+    if (Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "%s: Dx = D - A = %lld: at least one coefficient is needed", g->what, (long long)Dx);
+    const int64_t rest = np - head - g->nc;
+    if (rest < 1 || rest % (Dx + g->K) != 0)
+        return fail(IDHMC_ERR_BAD_ARG, "%s: nparams - %d - nc = %lld must be a positive multiple of %s + K = %lld ([X | Y])",
+                    g->what, head, (long long)rest, aux ? "Dx" : "D", (long long)(Dx + g->K));
+    g->n = rest / (Dx + g->K);
+    g->c = p + head;
+    g->X = g->c + g->nc;
+    g->Y = g->X + g->n * Dx;
+    return IDHMC_OK;
+}
+// every check of a regression's data; `glm`: anything but a logistic regression
+static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_desc *model, const idhmc_options &opt, int64_t nchains, int64_t first_chain_id)
+{
+    const char *what = g.what;
+    const int D = model->D;
+    if (glm) {
+        if (g.K < 1 || g.K > 4) return fail(IDHMC_ERR_BAD_ARG, "%s: K = %d must be an integer in 1..4", what, g.K);
+        if (g.nc < 0 || g.nc > 16) return fail(IDHMC_ERR_BAD_ARG, "%s: nc = %d must be an integer in 0..16", what, g.nc);
+        if (g.n < 1) return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld: at least one observation is needed", what, (long long)g.n);
+        if (!g.X || !g.Y) return fail(IDHMC_ERR_BAD_ARG, "%s: X and Y are needed", what);
+        if (g.nc > 0 && !g.c) return fail(IDHMC_ERR_BAD_ARG, "%s: nc = %d constants are needed", what, g.nc);
+        for (int j = 0; j < g.nc; ++j)
+            if (!std::isfinite(g.c[j])) return fail(IDHMC_ERR_BAD_ARG, "%s: constant c[%d] is not finite", what, j);
+    }
+    if (g.responses) {
+        const int64_t M = g.M, R = g.R;
+        if (M < 1) return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld: at least one response is needed", what, (long long)M);
+        if (R < 1) return fail(IDHMC_ERR_BAD_ARG, "%s: chains_per_response = %lld: at least one chain per response is needed", what, (long long)R);
+        if ((__int128)first_chain_id + nchains > (__int128)M * R)
+            return fail(IDHMC_ERR_BAD_ARG, "%s: first_chain_id + nchains = %lld is past the M * chains_per_response = %lld * %lld chains of the model",
+                        what, (long long)(first_chain_id + nchains), (long long)M, (long long)R);
+        // both pool statistics over every chain of the context, and the chains of different responses sample different posteriors
+        if (M > 1 && opt.eps_mode == IDHMC_EPS_GLOBAL)
+            return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses with eps_mode = GLOBAL: the global stepsize pools the acceptance of chains "
+                        "that sample different posteriors (use PER_CHAIN)", what, (long long)M);
+        if (M > 1 && opt.metric_mode == IDHMC_METRIC_POOLED)
+            return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses with metric_mode = POOLED: the pooled metric pools the windows of chains "
+                        "that sample different posteriors (use PER_CHAIN or SHARED)", what, (long long)M);
+    }
+    const int64_t n = g.n, K = g.K, M = g.M;
+    const int64_t Dx = D - g.A - g.H;      // the columns of X
+    int L = 128;
+    while (L < D) L *= 2;
+    const int64_t npad = (n + 127) / 128 * 128;
+    if (npad * L > ((int64_t)1 << 27))
+        return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
+                    what, (long long)n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
+    if (M > ((int64_t)1 << 27) || M * K * npad > ((int64_t)1 << 27))
+        return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses of K = %lld columns and n = %lld observations exceed M * K * n_pad <= 2^27",
+                    what, (long long)M, (long long)K, (long long)n);
+    for (int64_t k = 0; k < n * Dx; ++k)
+        if (!std::isfinite(g.X[k])) return fail(IDHMC_ERR_BAD_ARG, "%s: X[%lld, %lld] is not finite", what, (long long)(k / Dx), (long long)(k % Dx));
+    if (glm) {
+        for (int64_t k = 0; k < n * K; ++k)
+            if (!std::isfinite(g.Y[k]))
+                return fail(IDHMC_ERR_BAD_ARG, "%s: Y[%lld, %lld] is not finite", what, (long long)(k / K), (long long)(k % K));
+        for (int64_t k = n * K; k < M * n * K; ++k)           // the further responses' planes
+            if (!std::isfinite(g.Y[k]))
+                return fail(IDHMC_ERR_BAD_ARG, "%s: Y[%lld, %lld, %lld] is not finite", what, (long long)(k / (n * K)),
+                            (long long)(k / K % n), (long long)(k % K));
+    } else {
+        for (int64_t i = 0; i < n; ++i)
+            if (g.Y[i] != 0.0 && g.Y[i] != 1.0) return fail(IDHMC_ERR_BAD_ARG, "logistic regression: y[%lld] = %g is neither 0 nor 1", (long long)i, g.Y[i]);
+    }
+    for (int k = 0; k < D; ++k) {
+        if (model->tau && !(std::isfinite(model->tau[k]) && model->tau[k] > 0.0))
+            return fail(IDHMC_ERR_BAD_ARG, "%s: prior precision tau[%d] = %g must be finite and > 0", what, k, model->tau[k]);
+        if (model->mu && !std::isfinite(model->mu[k]))
+            return fail(IDHMC_ERR_BAD_ARG, "%s: prior mean mu[%d] is not finite", what, k);
+    }
+    if (D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
+        return fail(IDHMC_ERR_BAD_ARG, "%s with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)", what);
+    return IDHMC_OK;
+}
+// X, X' and the K planes of Y zero-padded to [n_pad][L], [L][n_pad], [K][n_pad] (one set of planes per response, [M][K][n_pad]);
+// a GLM's constants and groups
+static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
+{
+    DevState &s = c->s;
+    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - g.A - g.H, K = g.K, M = g.M;     // D: the columns of X
+    std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(M * K * npad), 0.0);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t k = 0; k < D; ++k) {
+            const double v = g.X[i * D + k];
+            hx[(size_t)(i * L + k)] = v;
+            hxt[(size_t)(k * npad + i)] = v;
+        }
+    for (int64_t m = 0; m < M; ++m)
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t k = 0; k < K; ++k) hy[(size_t)((m * K + k) * npad + i)] = g.Y[(m * n + i) * K + k];
+    double *dx = nullptr, *dxt = nullptr, *dy = nullptr;
+    if (int rc = dalloc(c, &dx, npad * L)) return rc;
+    if (int rc = dalloc(c, &dxt, npad * L)) return rc;
+    if (int rc = dalloc(c, &dy, M * K * npad)) return rc;
+    if (glm) {
+        double *dc = nullptr;
+        if (int rc = dalloc(c, &dc, g.nc > 0 ? g.nc : 1)) return rc;
+        if (g.nc > 0) HIPCHK(hipMemcpyAsync(dc, g.c, sizeof(double) * (size_t)g.nc, hipMemcpyHostToDevice, c->stream));
+        s.user_params = dc;
+        s.user_nparams = g.nc;
+    }
+    HIPCHK(hipMemcpyAsync(dx, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dxt, hxt.data(), sizeof(double) * hxt.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dy, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> hg;
+    if (g.H > 0) {
+        // the group of every coordinate: -1 past the columns of X (auxiliary coordinates, log scales, padding)
+        hg.assign((size_t)L, -1);
+        for (int64_t k = 0; k < D; ++k) hg[(size_t)k] = g.grp[k];
+        int32_t *dg = nullptr;
+        if (int rc = dalloc(c, &dg, L)) return rc;
+        HIPCHK(hipMemcpyAsync(dg, hg.data(), sizeof(int32_t) * hg.size(), hipMemcpyHostToDevice, c->stream));
+        s.lr_grp = dg;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
+    s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
+    s.lr_n = (int32_t)n; s.lr_npad = (int32_t)npad;
+    return IDHMC_OK;
+}
+// every switch the library takes from the environment, read once per context (tests and measurements set them before they
+// create one; nothing reads the environment on the launch path)
+static void read_environment(idhmc_ctx *c)
+{
+    if (const char *w = getenv("IDHMC_NUTS_WIDE")) c->force_wide = atoi(w) != 0;
+    if (const char *w = getenv("IDHMC_FUSE")) c->fuse = atoi(w) != 0;
+    if (const char *w = getenv("IDHMC_TEST_XCC_MISMATCH")) c->test_xcc = atoi(w) != 0;
+    if (const char *w = getenv("IDHMC_DENSE_MFMA")) c->dense_mfma = w[0] != '0';
+    if (const char *w = getenv("IDHMC_DENSE_LANES")) c->use_lanes = atoi(w) < idhmc_ctx::kLanes ? atoi(w) : idhmc_ctx::kLanes;
+    if (const char *w = getenv("IDHMC_PLACEMENT_TRIES")) c->place.tries = atoi(w);
+    if (const char *w = getenv("IDHMC_PLACEMENT_MAX_BYTES")) c->place.max_bytes = atoll(w);
+    if (const char *w = getenv("IDHMC_PLACEMENT_WALK_BYTES")) c->place.walk_bytes = atoll(w);
+    if (const char *w = getenv("IDHMC_PLACEMENT_PAIRS")) c->place.pairs = w[0] != '0';
+    c->place.verbose = getenv("IDHMC_PLACEMENT_VERBOSE") != nullptr;
+}
+#define DALLOC(ptr, n)                                       \
+    do {                                                     \
+        if (int rc_ = dalloc(c, &(ptr), (n))) return rc_;    \
+    } while (0)
+// idhmc_create and idhmc_create_glm: one validation, one set-up.  `parts`: a GLM handed over in parts (else its data is in params)
+static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                          const idhmc_model_desc *model, const idhmc_options *opt_in, uint64_t seed, const GlmParts *parts)
+{
+    *out = nullptr;
+    idhmc_options opt;
+    if (opt_in) opt = *opt_in; else idhmc_default_options(&opt);
+    if (nchains < 1 || nchains > (int64_t)0x7fffffff) return fail(IDHMC_ERR_BAD_ARG, "nchains = %lld out of range", (long long)nchains);
+    if (first_chain_id < 0 || first_chain_id + nchains > (int64_t)0xffffffffll) return fail(IDHMC_ERR_BAD_ARG, "chain ids must fit 32 bits");
+    if (model->D < 1 || model->D > 2048) return fail(IDHMC_ERR_BAD_ARG, "D = %d unsupported (1..2048)", model->D);
+    // a GLM with auxiliary coordinates is a GLM to everything below but the parsing of its params and the choice of its kernels
+    const bool glm_aux = model->kind == IDHMC_MODEL_GLM_AUX;
+    const int kind = glm_aux ? (int)IDHMC_MODEL_GLM : model->kind;
+    if (model->D > 1024) {
+        // two register tiles per vector; the dense MVN's matrix (32 MB at D = 2048) has no kernel built for it
+        if (kind == IDHMC_MODEL_DENSE_MVN)
+            return fail(IDHMC_ERR_BAD_ARG, "D = %d: the dense density is limited to D <= 1024", model->D);
+        if (kind == IDHMC_MODEL_LOGISTIC_REGRESSION)
+            return fail(IDHMC_ERR_BAD_ARG, "D = %d: logistic regression is limited to D <= 1024", model->D);
+        if (kind == IDHMC_MODEL_GLM)
+            return fail(IDHMC_ERR_BAD_ARG, "D = %d: a GLM is limited to D <= 1024", model->D);
+    }
+    if (opt_in && (opt_in->metric_mode < 0 || opt_in->metric_mode > IDHMC_METRIC_POOLED)) return fail(IDHMC_ERR_BAD_ARG, "unknown metric_mode %d", opt_in->metric_mode);
+    if (kind < 0 || kind > IDHMC_MODEL_GLM_AUX) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
+    if (kind == IDHMC_MODEL_CUSTOM) {
+        if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "custom model needs HIP source");
+        if (model->nparams < 0 || (model->nparams > 0 && !model->params)) return fail(IDHMC_ERR_BAD_ARG, "custom model: bad params");
+        if (model->D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
+            return fail(IDHMC_ERR_BAD_ARG, "custom model with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)");
+    } else if (kind != IDHMC_MODEL_ISO_GAUSSIAN && kind != IDHMC_MODEL_LOGISTIC_REGRESSION && kind != IDHMC_MODEL_GLM &&
+               !model->mu) {
+        return fail(IDHMC_ERR_BAD_ARG, "model needs mu");
+    }
+    const bool glm = kind == IDHMC_MODEL_GLM, regression = glm || kind == IDHMC_MODEL_LOGISTIC_REGRESSION;
+    GlmParts g = parts ? *parts : GlmParts{};
+    if (regression) {
+        g.what = glm_aux ? "GLM_AUX" : glm ? "GLM" : "logistic regression";
+        if (glm && (!model->source || !model->source[0])) return fail(IDHMC_ERR_BAD_ARG, "GLM needs HIP source (glm_observation)");
+        if (!parts) { if (int rc = unpack_params(model, glm_aux ? 3 : glm ? 2 : 0, &g)) return rc; }
+        if (int rc = validate_regression(g, glm, model, opt, nchains, first_chain_id)) return rc;
+    }
+    if (kind == IDHMC_MODEL_DIAG_GAUSSIAN && !model->tau) return fail(IDHMC_ERR_BAD_ARG, "diagonal model needs tau");
+    if (kind == IDHMC_MODEL_DENSE_MVN && !model->prec) return fail(IDHMC_ERR_BAD_ARG, "dense model needs prec");
+    if (kind == IDHMC_MODEL_DENSE_MVN) {
+        // the gradient kernel reads row c of P as column c (coalesced): P must be exactly symmetric
+        const int D = model->D;
+        for (int r = 0; r < D; ++r)
+            for (int c2 = r + 1; c2 < D; ++c2)
+                if (model->prec[(size_t)r * D + c2] != model->prec[(size_t)c2 * D + r])
+                    return fail(IDHMC_ERR_BAD_ARG, "prec must be exactly symmetric (differs at [%d,%d]); pass (P+P')/2", r, c2);
+        if (D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
+            return fail(IDHMC_ERR_BAD_ARG, "dense model with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)");
+    }
+    if (opt.max_depth < 1 || opt.max_depth > 15) return fail(IDHMC_ERR_BAD_ARG, "max_depth = %d unsupported (1..15)", opt.max_depth);
+    if (!(opt.min_delta < 0)) return fail(IDHMC_ERR_BAD_ARG, "min_delta must be negative");
+    if (!(opt.eps_init > 0)) return fail(IDHMC_ERR_BAD_ARG, "eps_init must be positive");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(IDHMC_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(IDHMC_ERR_BAD_ARG, "device %d out of range (%d visible)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+
+    // the context is the guard's until it is the caller's: every return below frees it and all it has allocated
+    struct Destroy { void operator()(idhmc_ctx *p) const { (void)idhmc_destroy(p); } };
+    std::unique_ptr<idhmc_ctx, Destroy> guard(new (std::nothrow) idhmc_ctx());
+    idhmc_ctx *c = guard.get();
+    if (!c) return fail(IDHMC_ERR_ALLOC, "out of host memory");
+    c->device = device;
+    c->opt = opt;
+    hipError_t se = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
+    if (se != hipSuccess) return fail(IDHMC_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(se));
+    c->stream = c->own_stream;
+    (void)hipEventCreate(&c->ev0);
+    (void)hipEventCreate(&c->ev1);
+    read_environment(c);
+
+    DevState &s = c->s;
+    s.C = nchains;
+    s.D = model->D;
+    // a vector is padded to the next multiple of 128 (the reference pads to its SIMD width, src/mcmc.jl:117); the
+    // dense density's matrix kernels need a power-of-two number of 128-column chunks
+    int nch = (model->D + 127) / 128;
+    if (kind == IDHMC_MODEL_DENSE_MVN || regression) {
+        nch = 1;
+        while (nch * 128 < model->D) nch *= 2;
+    }
+    s.nch = nch;
+    s.L = 128 * nch;
+    s.model = kind;               // a GLM_AUX runs as a GLM with lr_a > 0
+    s.lr_a = g.A;
+    s.lr_h = g.H;
+    s.lr_m = (int32_t)g.M;
+    s.lr_r = g.responses ? (uint32_t)(g.R > (int64_t)0xffffffffll ? (int64_t)0xffffffffll : g.R) : 0u;
+    c->glm_r = g.responses ? g.R : 0;
+    s.k0 = (uint32_t)seed;
+    s.k1 = (uint32_t)(seed >> 32);
+    s.first_chain = (uint32_t)first_chain_id;
+    s.max_depth = opt.max_depth;
+    s.min_delta = opt.min_delta;
+    s.da_delta = opt.da_delta; s.da_gamma = opt.da_gamma; s.da_kappa = opt.da_kappa; s.da_t0 = opt.da_t0;
+    s.eps_mode = opt.eps_mode;
+    s.ss_a_min = opt.ss_a_min; s.ss_a_max = opt.ss_a_max; s.ss_eps0 = opt.ss_eps0; s.ss_C = opt.ss_C;
+    s.ss_maxiter_crossing = opt.ss_maxiter_crossing; s.ss_maxiter_bisect = opt.ss_maxiter_bisect;
+
+    const int64_t CL = nchains * s.L;
+    // the dense leapfrog's matrix-core kernel reads whole 32-chain tiles: rows past the last chain exist (zeros), see kRowPad
+    const int64_t CLp = CL + (kind == IDHMC_MODEL_DENSE_MVN ? (int64_t)kRowPad * s.L : 0);
+    const bool own_minv = opt.metric_mode == IDHMC_METRIC_PER_CHAIN;
+    {
+        double *sv[4] = {nullptr, nullptr, nullptr, nullptr};
+        if (int rc = place_state(c, sv, own_minv ? 4 : 3, CLp, nchains, s.L)) return rc;
+        s.q = sv[0]; s.p = sv[1]; s.g = sv[2];
+        if (own_minv) s.minv = sv[3];
+    }
+    s.lf_stride = (3 * CL * (int64_t)sizeof(double) + kIcSliceBytes - 1) / kIcSliceBytes;
+    if (s.lf_stride < 1) s.lf_stride = 1;
+    s.lf_stride2 = (2 * CL * (int64_t)sizeof(double) + kIcSliceBytes - 1) / kIcSliceBytes;
+    if (s.lf_stride2 < 1) s.lf_stride2 = 1;
+    DALLOC(s.lq, nchains); DALLOC(s.pi, nchains); DALLOC(s.eps, nchains);
+    if (own_minv) {
+        DALLOC(s.w, CL);
+        s.minv_stride = s.L;
+        DALLOC(s.mw_x1, CL); DALLOC(s.mw_s1, CL); DALLOC(s.mw_s2, CL);
+    } else {
+        DALLOC(s.minv, s.L); DALLOC(s.w, s.L);
+        s.minv_stride = 0;
+        if (opt.metric_mode == IDHMC_METRIC_POOLED) {       // one M^-1, adapted from every chain's window
+            DALLOC(s.mw_x1, CL); DALLOC(s.mw_s1, CL); DALLOC(s.mw_s2, CL);
+            DALLOC(c->pool_scratch, (int64_t)pool_scratch_doubles(s.L));
+        }
+    }
+    DALLOC(s.mw_n, nchains);
+    DALLOC(s.stats, nchains);
+    DALLOC(s.directions, nchains);
+    DALLOC(s.queue, 16);
+    DALLOC(s.iters_done, nchains);
+    DALLOC(s.da.mu, nchains); DALLOC(s.da.Hbar, nchains); DALLOC(s.da.logeps, nchains);
+    DALLOC(s.da.logeps_bar, nchains); DALLOC(s.da.m, nchains);
+    DALLOC(s.da_global, 8);
+    DALLOC(s.xchg_acc, 3 * kXchgBlocks + 1);
+    DALLOC(s.status, nchains);
+    DALLOC(s.total_steps, 32);
+    DALLOC(c->xchg, IDHMC_XCHG_DOUBLES);
+    DALLOC(c->status_out, 1);
+    {
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&c->ring), sizeof(unsigned long long) * idhmc_ctx::kRing * idhmc_ctx::kPulseWords,
+                                     hipHostMallocDefault);
+        if (e != hipSuccess) return fail(IDHMC_ERR_ALLOC, "pinned ring: %s", hipGetErrorString(e));
+        for (int i = 0; i < idhmc_ctx::kRing * idhmc_ctx::kPulseWords; ++i) c->ring[i] = ~0ull;
+        {   // several transitions per launch need workgroups b and b + 8 on one XCD (idhmc_nuts_kernel.hpp): look before relying on it
+            const int g8 = prop.multiProcessorCount > 8 ? prop.multiProcessorCount : 8;
+            uint32_t *dx = nullptr;
+            std::vector<uint32_t> hx((size_t)g8, 0u);
+            bool ok = hipMalloc(&dx, sizeof(uint32_t) * g8) == hipSuccess;
+            ok = ok && launch_xcc_probe(dx, g8, c->stream) == hipSuccess;
+            ok = ok && hipMemcpyAsync(hx.data(), dx, sizeof(uint32_t) * g8, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+            ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+            for (int b = 8; ok && b < g8; ++b) ok = hx[(size_t)b] == hx[(size_t)(b & 7)];
+            if (dx) (void)hipFree(dx);
+            c->fuse_ok = ok;
+        }
+    }
+    // model parameters, padded with zeros
+    {
+        double *mu = nullptr, *tau = nullptr, *prec = nullptr;
+        DALLOC(mu, s.L); DALLOC(tau, s.L);
+        if (model->mu) HIPCHK(hipMemcpyAsync(mu, model->mu, sizeof(double) * s.D, hipMemcpyHostToDevice, c->stream));
+        if (model->tau) HIPCHK(hipMemcpyAsync(tau, model->tau, sizeof(double) * s.D, hipMemcpyHostToDevice, c->stream));
+        if (kind == IDHMC_MODEL_DENSE_MVN) {
+            DALLOC(prec, (int64_t)s.L * s.L);
+            HIPCHK(hipMemcpy2DAsync(prec, sizeof(double) * s.L, model->prec, sizeof(double) * s.D,
+                                    sizeof(double) * s.D, s.D, hipMemcpyHostToDevice, c->stream));
+        }
+        s.mu = mu; s.tau = tau; s.prec = prec;
+        if (regression) {
+            // the prior's defaults (mu = 0 is the zeroed allocation), then the data
+            if (!model->tau) HIPCHK(launch_fill(tau, 1.0, s.D, c->stream));
+            if (int rc = upload_regression(c, g, glm)) return rc;
+        }
+    }
+    // persistent NUTS waves and their tree arenas
+    {
+        // one workgroup of W wavefronts per CU (W = 4: one wavefront per SIMD with the full 512-register
+        // budget; its LDS footprint and registers allow no more); slots in multiples of W
+        const int W0 = nuts_waves_per_block(s.nch, s.model, opt.metric_mode != IDHMC_METRIC_PER_CHAIN, s.lr_a), W1 = nuts_wide_waves_per_block(s.nch, s.model);
+        const int W = W1 > W0 ? W1 : W0;
+        int64_t nslots = (int64_t)prop.multiProcessorCount * W;
+        const int64_t need = (nchains + W - 1) / W * W;
+        if (nslots > need) nslots = need;
+        s.nslots = (int32_t)nslots;
+        s.arena_stride = (int64_t)arena_vectors(opt.max_depth, s.model, s.L) * s.L;
+        DALLOC(s.arena, s.arena_stride * nslots);
+    }
+    // a user-supplied density: upload its parameters ...
+    if (kind == IDHMC_MODEL_CUSTOM) {
+        double *up = nullptr;
+        DALLOC(up, model->nparams);
+        if (model->nparams > 0) {
+            hipError_t e = hipMemcpyAsync(up, model->params, sizeof(double) * (size_t)model->nparams, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) return fail(IDHMC_ERR_HIP, "params upload failed: %s", hipGetErrorString(e));
+        }
+        s.user_params = up;
+        s.user_nparams = model->nparams;
+    }
+    // ... and compile it against the kernel templates; a GLM: its observation source compiled into the logistic regression's templates
+    // (hipRTC); the data went up above
+    if (kind == IDHMC_MODEL_CUSTOM || glm) {
+        static thread_local char jlog[400];
+        jlog[0] = 0;
+        const int jrc = jit_build(s, model->source, &c->jit, jlog, sizeof jlog, glm ? g.K : 0, g.A, g.H);
+        if (jrc != 0) return fail(IDHMC_ERR_BAD_ARG, "%s did not compile (%d): %s", glm ? "GLM observation source" : "custom density", jrc, jlog);
+        s.jit = c->jit;
+    }
+    // kappa = I (GaussianKineticEnergy(sptr, Static{D}, 1.0), src/hamiltonian.jl:63-74)
+    {
+        const int64_t n = s.minv_stride ? CL : (int64_t)s.L;
+        hipError_t e = launch_fill(s.minv, 1.0, n, c->stream);
+        if (e == hipSuccess) e = launch_fill(s.w, 1.0, n, c->stream);
+        if (e == hipSuccess) e = launch_fill(s.eps, opt.eps_init, nchains, c->stream);
+        if (e != hipSuccess) return fail(IDHMC_ERR_HIP, "init kernels failed: %s", hipGetErrorString(e));
+    }
+    {
+        hipError_t e = launch_eval(s, c->stream);   // q = 0: consistent (lq, grad)
+        if (e != hipSuccess && e != hipErrorNotSupported) return fail(IDHMC_ERR_HIP, "eval failed: %s", hipGetErrorString(e));
+        e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return fail(IDHMC_ERR_HIP, "init sync failed: %s", hipGetErrorString(e));
+    }
+    *out = guard.release();
+    return IDHMC_OK;
+}
+
+int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                 const idhmc_model_desc *model, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !model) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create: null argument");
+    return create_context(out, device, nchains, first_chain_id, model, opt_in, seed, nullptr);
+}
+
+// idhmc_create_glm and idhmc_create_glm_responses
+static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
+                      bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed)
+{
+    *out = nullptr;
+    if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
+    if (glm->A < 0 || glm->A > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: A = %d must be an integer in 0..4", glm->A);
+    if (glm->H < 0 || glm->H > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d must be an integer in 0..4", glm->H);
+    if (glm->Dx > 1024 - glm->A - glm->H)
+        return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H = %lld: a GLM is limited to D <= 1024", (long long)glm->Dx + glm->A + glm->H);
+    if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
+    if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
+    if (glm->H > 0) {
+        bool used[4] = {false, false, false, false};
+        for (int c = 0; c < glm->Dx; ++c) {
+            const int32_t g = glm->groups[c];
+            if (g < -1 || g >= glm->H) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups[%d] = %d is outside -1..%d", c, g, glm->H - 1);
+            if (g >= 0) used[g] = true;
+        }
+        for (int g = 0; g < glm->H; ++g)
+            if (!used[g]) return fail(IDHMC_ERR_BAD_ARG, "GLM: group %d has no column", g);
+    }
+    idhmc_model_desc m;
+    memset(&m, 0, sizeof m);
+    m.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM;
+    m.D = glm->Dx + glm->A + glm->H;
+    m.mu = glm->mu;
+    m.tau = glm->tau;
+    m.source = glm->source;
+    const GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
+    return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
+}
+
+int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                     const idhmc_glm_desc *glm, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm: null argument");
+    return create_glm(out, device, nchains, first_chain_id, glm, false, 1, 0, opt_in, seed);
+}
+
+int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                               const idhmc_glm_desc *glm, int64_t M, int64_t chains_per_response,
+                               const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_responses: null argument");
+    return create_glm(out, device, nchains, first_chain_id, glm, true, M, chains_per_response, opt_in, seed);
+}
+
+int idhmc_glm_responses(const idhmc_ctx *c, int64_t *M, int64_t *chains_per_response)
+{
+    if (!c || !M || !chains_per_response) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_responses: null argument");
+    *M = c->glm_r > 0 ? c->s.lr_m : 1;
+    *chains_per_response = c->glm_r;
+    return IDHMC_OK;
+}
+int64_t idhmc_nchains(const idhmc_ctx *c) { return c ? c->s.C : 0; }
+int32_t idhmc_dim(const idhmc_ctx *c) { return c ? c->s.D : 0; }
+int32_t idhmc_padded_dim(const idhmc_ctx *c) { return c ? c->s.L : 0; }
+int idhmc_glm_form(const idhmc_ctx *c)
+{
+    if (!c || (c->s.model != IDHMC_MODEL_LOGISTIC_REGRESSION && c->s.model != IDHMC_MODEL_GLM)) return -1;
+    return glm_coop(c->s.nch, c->s.lr_a, c->s.minv_stride == 0) ? 1 : 0;
+}
+int64_t idhmc_device_bytes(const idhmc_ctx *c) { return c ? c->bytes : 0; }
+int idhmc_placement_info(const idhmc_ctx *c, double *probe_GBps, int32_t *candidates)
+{
+    if (!c) return fail(IDHMC_ERR_BAD_ARG, "null context");
+    if (probe_GBps) *probe_GBps = c->placement_GBps;
+    if (candidates) *candidates = c->placement_tries;
+    return IDHMC_OK;
+}
+int idhmc_leapfrog_slice_info(const idhmc_ctx *c, int32_t *stride_store, int32_t *stride_recompute)
+{
+    if (!c) return fail(IDHMC_ERR_BAD_ARG, "null context");
+    if (stride_store) *stride_store = (int32_t)c->s.lf_stride;
+    if (stride_recompute) *stride_recompute = (int32_t)c->s.lf_stride2;
+    return IDHMC_OK;
+}
+int idhmc_lanes_info(const idhmc_ctx *c, int32_t *lanes, int32_t *on_distinct_queues)
+{
+    if (!c) return fail(IDHMC_ERR_BAD_ARG, "null context");
+    int n = c->lane[1] ? 1 : 0;
+    for (int k = 1; k < idhmc_ctx::kLanes; ++k) n += c->lane[k] != nullptr;
+    if (lanes) *lanes = n;
+    if (on_distinct_queues) *on_distinct_queues = c->lanes_distinct;
+    return IDHMC_OK;
+}
+int idhmc_placement_cost(const idhmc_ctx *c, double *create_ms, int64_t *peak_transient_bytes, double *single_array_GBps, int32_t *kind)
+{
+    if (!c) return fail(IDHMC_ERR_BAD_ARG, "null context");
+    if (create_ms) *create_ms = c->placement_ms;
+    if (peak_transient_bytes) *peak_transient_bytes = c->placement_peak_bytes;
+    if (single_array_GBps) *single_array_GBps = c->placement_single_GBps;
+    if (kind) *kind = c->placement_kind;
+    return IDHMC_OK;
+}
+

@@ -176,3 +176,97 @@ def test_drivers_fuse_and_still_match_the_oracle(idhmc, oracle, monkeypatch):
     for n in range(N):
         assert same_bits(draws[n], och[:, n, :D])
     assert np.array_equal(stats.T, ost[:, :N])
+
+
+# ---- the driver loop of idhmc_tuning_stage and idhmc_mcmc: the same result on each of its three paths ------------------------------------
+def diag_pair(idhmc, monkeypatch, D=40, C=37, **opts):
+    """(one launch per transition, fused drivers): two engines on the same diagonal Gaussian, seed and start"""
+    rng = np.random.default_rng(4)
+    model = idhmc.DiagGaussian(rng.standard_normal(D), np.exp(rng.standard_normal(D)))
+    monkeypatch.setenv("IDHMC_FUSE", "0")
+    plain = idhmc.Engine(model, C, idhmc.default_options(max_depth=7, **opts), seed=9)
+    monkeypatch.delenv("IDHMC_FUSE")
+    fused = idhmc.Engine(model, C, idhmc.default_options(max_depth=7, **opts), seed=9)
+    assert plain.fused_launch_info() == (True, False) and fused.fused_launch_info() == (True, True)
+    for e in (plain, fused):
+        e.random_position()
+        e.set_eps(0.2)
+    return plain, fused
+
+
+def assert_same_state(a, b):
+    for k in ("q", "eps", "minv"):
+        assert same_bits(getattr(a, k), getattr(b, k)), k
+
+
+def assert_same_output(a, b):
+    (d0, s0), (d1, s1) = a, b
+    assert (d0 is None) == (d1 is None) and (s0 is None) == (s1 is None)
+    assert d0 is None or same_bits(d0, d1)
+    assert s0 is None or np.array_equal(s0, s1)
+
+
+@pytest.mark.parametrize("adapt_metric", [0, 1])
+@pytest.mark.parametrize("eps_mode", ["PER_CHAIN", "GLOBAL"])
+def test_tuning_stage_with_host_arrays(idhmc, monkeypatch, adapt_metric, eps_mode):
+    """idhmc_tuning_stage with draws and / or records wanted: N = 70 leaves in blocks of K = 64 transitions and a ragged second block of 6
+    from the fused drivers, per transition with IDHMC_FUSE=0 -- and per transition from both when the stepsize is global (it adapts
+    between transitions).  Draws, records, q, eps and M^-1 afterwards: the same bits"""
+    plain, fused = diag_pair(idhmc, monkeypatch, eps_mode=getattr(idhmc, "EPS_" + eps_mode))
+    it = 0
+    for store in (dict(store_draws=True, store_stats=True), dict(store_draws=True, store_stats=False), dict(store_draws=False, store_stats=True)):
+        out = [e.tuning_stage(70, adapt_metric, it, **store) for e in (plain, fused)]
+        assert (out[0][0] is not None) == store["store_draws"] and (out[0][1] is not None) == store["store_stats"]
+        assert_same_output(*out)
+        assert_same_state(plain, fused)
+        it += 70
+    if adapt_metric:
+        assert not same_bits(fused.minv, np.ones_like(fused.minv))
+    plain.close()
+    fused.close()
+
+
+def test_staging_grows_and_is_reused(idhmc, monkeypatch):
+    """the staging buffers of the draws and records are the context's, grow-only and shared by every path: mcmc(5) (blocks of 5), mcmc(70)
+    (they grow to 64), a tuning stage of 70 and mcmc(5) again (the larger buffers serve) give what one launch per transition gives, and the
+    context then holds exactly the device bytes of one that made the 70 first"""
+    plain, fused = diag_pair(idhmc, monkeypatch)
+    it = 0
+    for call, n in (("mcmc", 5), ("mcmc", 70), ("tuning", 70), ("mcmc", 5)):
+        out = [e.mcmc(n, it) if call == "mcmc" else e.tuning_stage(n, 1, it, store_draws=True, store_stats=True) for e in (plain, fused)]
+        assert_same_output(*out)
+        assert_same_state(plain, fused)
+        it += n
+    other = diag_pair(idhmc, monkeypatch)
+    other[0].close()
+    other = other[1]
+    other.mcmc(70, 0)
+    assert fused.device_bytes() == other.device_bytes()
+    for e in (plain, fused, other):
+        e.close()
+
+
+def test_a_creation_that_fails_late_returns_all_device_memory(idhmc):
+    """a GLM whose observation source does not compile fails after the state, the arenas and the data are on the device: the context is
+    destroyed on that path like on every other one (measured as tests/test_gpu_edges.py::test_create_destroy_returns_all_device_memory)"""
+    import gc
+    import torch
+    rng = np.random.default_rng(3)
+    X, Y = rng.standard_normal((50, 6)), rng.poisson(2.0, 50).astype(float)
+    bad = "__device__ void glm_observation(double z, const GlmObs &o, double &r, double &v) { r = z +; v = 0.0; }"
+
+    def cycle():
+        with pytest.raises(idhmc.IdhmcError) as e:
+            idhmc.Engine(idhmc.GLM(X, Y, bad), 4)
+        assert e.value.code == idhmc.ERR_BAD_ARG and "did not compile" in str(e.value)
+    cycle()                                    # first use: the runtime's own pools (streams, events, code objects) are up
+    gc.collect()                               # (engines of earlier tests that wait in reference cycles give their memory back now, not below)
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info()
+    for _ in range(5):
+        cycle()
+    gc.collect()
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info()
+    print("free device bytes before / after five failed creations: %d / %d" % (free0, free1))
+    assert free0 == free1, "device memory changed by %d bytes over 5 failed creations" % (free0 - free1)
