@@ -301,6 +301,7 @@ static int leaf(orc_chain *c, int z, subtree *t, acc_stat *v)
 {
     double delta = c->zpi[z] - c->pi0;                                  /* :179 */
     int isdiv = delta < c->opt.min_delta;                               /* :180 */
+    note_margin(c, delta - c->opt.min_delta);                           /* a decision like the others: with a tight min_delta it can be the closest */
     v->log_sum_a = delta < 0.0 ? delta : 0.0; v->steps = 1;             /* :76-78 */
     if (isdiv) return 1;
     int ps = pool_alloc(&c->vpool);                                     /* leaf_turn_statistic :113-116 */

@@ -104,7 +104,8 @@ int orc_find_local_optimum(orc_chain *c, double magnitude_penalty, int iteration
  * if refresh_p == 0, the momentum already in the chain */
 int orc_sample_tree_ex(orc_chain *c, double eps, uint32_t iter, int use_directions,
                        uint32_t directions, int refresh_p, orc_tree_stats *stats);
-/* smallest decision margin met inside the last transition (for parity tests) */
+/* smallest decision margin met inside the last transition (for parity tests): the turn tests' dot products, the
+ * proposal draws, and each leaf's delta - min_delta */
 double orc_chain_last_margin(const orc_chain *c);
 
 void orc_da_init(orc_da_state *s, double eps);

@@ -55,7 +55,13 @@ def find_initial_stepsize(par, A):                          # src/stepsize.jl:11
 def local_acceptance_ratio(H, z):                           # src/stepsize.jl:150-164
     target = H.logdensity(z)
     assert math.isfinite(target), "Starting point has non-finite density."
-    return lambda eps: math.exp(H.logdensity(H.leapfrog(z, eps)) - target)
+
+    def ratio(eps):
+        try:
+            return math.exp(H.logdensity(H.leapfrog(z, eps)) - target)
+        except OverflowError:                                # a start far out in the tails: Julia's exp gives Inf, math.exp raises
+            return math.inf
+    return ratio
 
 
 # ---- DualAveraging, src/stepsize.jl:173-241 -------------------------------------------------------------------------------
