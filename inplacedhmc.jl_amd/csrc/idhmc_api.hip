@@ -305,14 +305,10 @@ int idhmc::nuts_launch(idhmc_ctx *c, uint32_t iter, uint32_t flags, uint32_t n_i
     if ((flags & IDHMC_T_ACCUM_DIAG) && !c->s.diag.n) {
         if (int rc = idhmc_diag_reset(c)) return rc;
     }
-    // Two wavefronts per SIMD are the faster form at every tree depth since the far edge and the whole-tree
-    // statistic stopped travelling through the arena (round 2: 3.4e8 / 5.0e8 leapfrog/s at depth 4 / 7 against
-    // 2.9e8 / 3.6e8 with one); IDHMC_NUTS_WIDE=0 still selects the one-wavefront form (experiments, tests).
-    const int wide = nuts_wide_waves_per_block(c->s.nch, c->s.model) > 0 ? (c->force_wide >= 0 ? c->force_wide : 1) : 0;
     volatile unsigned long long *slot = c->ring + (c->launches % idhmc_ctx::kRing) * idhmc_ctx::kPulseWords;
     if (slot[0] == ~0ull && c->launches >= (uint64_t)idhmc_ctx::kRing) HIPCHK(hipStreamSynchronize(c->stream));   // slot still in flight
     slot[0] = ~0ull;
-    HIPCHK(launch_nuts(c->s, iter, flags, wide, c->stream, n_iter, fz_q, fz_st));
+    HIPCHK(launch_nuts(c->s, iter, flags, c->stream, n_iter, fz_q, fz_st));
     // the transition of a separable density leaves grad l of the new state unwritten (8 KB per chain and transition that nothing on
     // the sampling path reads: the kernel re-derives the gradient from q); whoever needs the array re-evaluates first (ensure_grad)
     if (c->s.model == IDHMC_MODEL_ISO_GAUSSIAN || c->s.model == IDHMC_MODEL_DIAG_GAUSSIAN) c->grad_stale = true;

@@ -207,7 +207,6 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
 // create one; nothing reads the environment on the launch path)
 static void read_environment(idhmc_ctx *c)
 {
-    if (const char *w = getenv("IDHMC_NUTS_WIDE")) c->force_wide = atoi(w) != 0;
     if (const char *w = getenv("IDHMC_FUSE")) c->fuse = atoi(w) != 0;
     if (const char *w = getenv("IDHMC_TEST_XCC_MISMATCH")) c->test_xcc = atoi(w) != 0;
     if (const char *w = getenv("IDHMC_DENSE_MFMA")) c->dense_mfma = w[0] != '0';
@@ -405,15 +404,13 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
     }
     // persistent NUTS waves and their tree arenas
     {
-        // one workgroup of W wavefronts per CU (W = 4: one wavefront per SIMD with the full 512-register
-        // budget; its LDS footprint and registers allow no more); slots in multiples of W
-        const int W0 = nuts_waves_per_block(s.nch, s.model, opt.metric_mode != IDHMC_METRIC_PER_CHAIN, s.lr_a), W1 = nuts_wide_waves_per_block(s.nch, s.model);
-        const int W = W1 > W0 ? W1 : W0;
+        // one workgroup of W wavefronts per CU (nuts_waves); slots in multiples of W
+        const int W = nuts_waves_per_block(s.nch, s.model, opt.metric_mode != IDHMC_METRIC_PER_CHAIN, s.lr_a);
         int64_t nslots = (int64_t)prop.multiProcessorCount * W;
         const int64_t need = (nchains + W - 1) / W * W;
         if (nslots > need) nslots = need;
         s.nslots = (int32_t)nslots;
-        s.arena_stride = (int64_t)arena_vectors(opt.max_depth, s.model, s.L) * s.L;
+        s.arena_stride = (int64_t)arena_vectors(opt.max_depth, s.model == IDHMC_MODEL_ISO_GAUSSIAN || s.model == IDHMC_MODEL_DIAG_GAUSSIAN, s.L) * s.L;
         DALLOC(s.arena, s.arena_stride * nslots);
     }
     // a user-supplied density: upload its parameters ...

@@ -16,9 +16,6 @@
 #include "idhmc_xchg.hpp"
 
 namespace idhmc {
-int arena_vectors(int max_depth, int model, int L);
-int nuts_waves_per_block(int nch, int model, int shared_metric, int glm_aux);
-int nuts_wide_waves_per_block(int nch, int model);
 // sets the text of idhmc_last_error (one per thread) and returns `code`
 int fail(int code, const char *fmt, ...);
 }
@@ -64,12 +61,11 @@ struct idhmc_ctx {
     // copied asynchronously into a pinned ring, one slot per launch.  The drivers read it without ever synchronising
     // the stream: (1) the reference aborts the moment a chain's stepsize falls below 1e-10 (src/warmup.jl:291-296) --
     // the drivers keep at most kLag launches in flight and stop at the first slot that carries the code; (2)
-    // measurement / choice of the kernel form.
+    // measurement.
     static constexpr int kRing = 64, kLag = 8, kPulseWords = 2;
     unsigned long long *ring = nullptr;   // pinned host memory, kRing x kPulseWords; word 0 == ~0: not yet written
     uint64_t launches = 0;
     // switches from the environment, read once in idhmc_create
-    int force_wide = -1;                  // IDHMC_NUTS_WIDE = 0 / 1 forces one form (tests, experiments)
     int fuse = -1;                        // IDHMC_FUSE = 0 / 1: the drivers never / always make several transitions per launch (-1: yes)
     bool fuse_ok = false;                 // workgroups b and b + 8 share an XCD on this device (probed at creation): fused launches are possible
     bool test_xcc = false;                // IDHMC_TEST_XCC_MISMATCH=1: the transition flags may carry kTestXccFlag (test suite only)

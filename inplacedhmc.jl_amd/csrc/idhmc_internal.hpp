@@ -98,6 +98,7 @@ __device__ __forceinline__ void bind_chain(Model &mdl, const DevState &s, uint32
     if constexpr (BindsChain<Model>::value) mdl.bind_chain(s, global_chain);
 }
 constexpr int kPulseAt = 0;
+constexpr int kLdsBytes = 160 * 1024;   // LDS of a CU
 // transition flag of the test suite only (see the XCD check in k_nuts); idhmc_nuts_transition(s) accept it on a context created
 // with IDHMC_TEST_XCC_MISMATCH=1 in the environment, and refuse it, like every other bit outside the IDHMC_T_* set, otherwise
 constexpr uint32_t kTestXccFlag = 1u << 30;
@@ -175,7 +176,11 @@ hipError_t launch_spin(long long ticks_100MHz, hipStream_t st);   // an idle wav
 hipError_t launch_placement_probe(double *const *v, int nvec, int64_t C, int L, hipStream_t st);   // reads and rewrites v[k][0 .. C L)
 hipError_t launch_pack_draw(const DevState &s, double *q_out, idhmc_tree_stats *st_out, hipStream_t st);
 hipError_t launch_broadcast_row(double *a, int L, int64_t C, hipStream_t st);
-hipError_t launch_nuts(const DevState &s, uint32_t iter, uint32_t flags, int wide, hipStream_t st, uint32_t n_iter = 1,
+// the NUTS kernel's shape decisions (idhmc_nuts.hip): arena vectors per wavefront, wavefronts per workgroup, dynamic LDS of a custom density
+int arena_vectors(int max_depth, bool separable, int L);
+int nuts_waves_per_block(int nch, int model, int shared_metric, int glm_aux);
+size_t nuts_lds_bytes(int nch, bool shared_metric);
+hipError_t launch_nuts(const DevState &s, uint32_t iter, uint32_t flags, hipStream_t st, uint32_t n_iter = 1,
                        double *fz_q = nullptr, idhmc_tree_stats *fz_st = nullptr);
 hipError_t launch_stepsize_search(const DevState &s, hipStream_t st);
 hipError_t launch_local_optimum(const DevState &s, double penalty, int iterations, hipStream_t st);

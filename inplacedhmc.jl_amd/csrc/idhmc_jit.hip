@@ -20,9 +20,6 @@
 
 namespace idhmc {
 
-int nuts_waves_per_block(int nch, int model, int shared_metric, int glm_aux);
-size_t nuts_lds_bytes(int L, bool lds_params, bool shared_metric, bool separable);
-
 struct JitModule {
     hipModule_t mod = nullptr;
     hipFunction_t f_eval = nullptr, f_leapfrog = nullptr, f_stepsize = nullptr, f_nuts = nullptr, f_optimum = nullptr;
@@ -138,11 +135,11 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
     }
     hiprtcDestroyProgram(&prog);
     // a GLM's NUTS kernel may be the cooperative form: its tiles are sized by the density (kLdsDoubles), not by the general rule
-    m->nuts_lds = glm ? glm_nuts_lds_bytes(s.nch, shared, glm_a) : nuts_lds_bytes(s.L, false, shared, false);
+    m->nuts_lds = glm ? glm_nuts_lds_bytes(s.nch, shared, glm_a) : nuts_lds_bytes(s.nch, shared);
     // glm_coop's table keeps the cooperative form inside a CU's LDS; a kernel whose static part outgrew it is refused here, not at its launch
     int static_lds = 0;
     if (glm && hipFuncGetAttribute(&static_lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, m->f_nuts) == hipSuccess &&
-        m->nuts_lds + (size_t)static_lds > 160 * 1024) {
+        m->nuts_lds + (size_t)static_lds > (size_t)kLdsBytes) {
         put_log(log, log_cap, "the NUTS kernel needs " + std::to_string(m->nuts_lds + (size_t)static_lds) + " bytes of LDS, a CU has 163840");
         (void)hipModuleUnload(m->mod);
         delete m;

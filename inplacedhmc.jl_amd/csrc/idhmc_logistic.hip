@@ -30,8 +30,7 @@ static size_t glm_nuts_lds_t(bool shared)
 {
     const bool coop = glm_coop(NCH, AUX, shared);
     const int tiles = coop ? GlmCoop<NCH, GlmShapeObs<AUX>>::kLdsDoubles : 0;
-    const int waves = nuts_waves(NCH, false, coop, shared);
-    return sizeof(double) * nuts_lds_doubles(128 * NCH, false, shared, false, tiles, waves);
+    return sizeof(double) * nuts_lds(NCH, false, false, tiles, shared, nuts_waves(NCH, false, coop, shared)).total;
 }
 template <int NCH>
 static size_t glm_nuts_lds_a(bool shared, int aux)

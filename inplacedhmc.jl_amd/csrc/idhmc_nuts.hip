@@ -6,10 +6,9 @@
 namespace idhmc {
 
 // the tree arena also serves as the L-BFGS history of the FindLocalOptimum stage (2 * kLbfgsR vectors)
-int arena_vectors(int max_depth, int model, int L)
+int arena_vectors(int max_depth, bool separable, int L)
 {
-    const bool separable = model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN;     // dense, logistic, GLM, custom: not
-    const int n = ArenaMap{max_depth, nuts_regenerate(separable), nuts_defer(separable) ? nuts_dl_vectors(max_depth, L) : 0}.count();
+    const int n = arena_map(max_depth, separable, L).count();
     return n > 2 * kLbfgsR ? n : 2 * kLbfgsR;
 }
 // the dense MVN runs the workgroup-cooperative matrix-core gradient (DenseMvnCoop) when one 16-column tile per
@@ -21,26 +20,21 @@ int nuts_waves_per_block(int nch, int model, int shared_metric, int glm_aux)
                       (model == IDHMC_MODEL_DENSE_MVN && dense_coop(nch)) || ((model == IDHMC_MODEL_LOGISTIC_REGRESSION || model == IDHMC_MODEL_GLM) && glm_coop(nch, glm_aux, shared_metric != 0)),
                       shared_metric != 0);
 }
-// wavefronts per workgroup of the wide form of the kernel (0: the model/shape has none); the arena is sized for it
-int nuts_wide_waves_per_block(int nch, int model)
+// dynamic LDS of a custom density's kernel (the general form; a GLM's: glm_nuts_lds_bytes)
+size_t nuts_lds_bytes(int nch, bool shared_metric)
 {
-    return nuts_wide_waves(nch, model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN, false);
-}
-size_t nuts_lds_bytes(int L, bool lds_params, bool shared_metric, bool separable)
-{
-    return sizeof(double) * nuts_lds_doubles(L, lds_params, shared_metric, separable) ;
+    return sizeof(double) * nuts_lds(nch, false, false, 0, shared_metric, nuts_waves(nch, false, false, shared_metric)).total;
 }
 
-hipError_t launch_nuts_sep_from1(const DevState &s, uint32_t iter, uint32_t flags, int wide, int grid, hipStream_t st);
-hipError_t launch_nuts_sep_from5(const DevState &s, uint32_t iter, uint32_t flags, int wide, int grid, hipStream_t st);
-hipError_t launch_nuts_sep_from9(const DevState &s, uint32_t iter, uint32_t flags, int wide, int grid, hipStream_t st);
-hipError_t launch_nuts_sep_from13(const DevState &s, uint32_t iter, uint32_t flags, int wide, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from1(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from5(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from9(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from13(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
 hipError_t launch_stepsize_search_dense(const DevState &s, hipStream_t st);
 hipError_t launch_nuts_jit(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
 hipError_t launch_stepsize_search_jit(const DevState &s, hipStream_t st);
 
-// wide != 0 selects the wide form of the kernel where one exists (same arithmetic, same results)
-hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wide, hipStream_t st, uint32_t n_iter, double *fz_q, idhmc_tree_stats *fz_st)
+hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, hipStream_t st, uint32_t n_iter, double *fz_q, idhmc_tree_stats *fz_st)
 {
     if (s0.max_depth < 1 || s0.max_depth > kMaxDepth - 1) return hipErrorInvalidValue;
     if (n_iter < 1 || (uint64_t)s0.C * n_iter >= (1ull << 31)) return hipErrorInvalidValue;
@@ -55,9 +49,7 @@ hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wi
         e = hipMemsetAsync(s.iters_done, 0, sizeof(uint32_t) * (size_t)s.C, st);
         if (e != hipSuccess) return e;
     }
-    const int WW = nuts_wide_waves_per_block(s.nch, s.model);
-    wide = wide && WW > 0;
-    const int W = wide ? WW : nuts_waves_per_block(s.nch, s.model, s.minv_stride == 0, s.lr_a);
+    const int W = nuts_waves_per_block(s.nch, s.model, s.minv_stride == 0, s.lr_a);
     int64_t need = (s.C + W - 1) / W;
     const int64_t have = s.nslots / W;
     const int grid = (int)(need < have ? need : have);
@@ -76,10 +68,10 @@ hipError_t launch_nuts(const DevState &s0, uint32_t iter, uint32_t flags, int wi
         return hipErrorInvalidValue;
     }
     // separable densities: one translation unit per four padded lengths (idhmc_nuts_sep.inc)
-    if (s.nch <= 4) return launch_nuts_sep_from1(s, iter, flags, wide, grid, st);
-    if (s.nch <= 8) return launch_nuts_sep_from5(s, iter, flags, wide, grid, st);
-    if (s.nch <= 12) return launch_nuts_sep_from9(s, iter, flags, wide, grid, st);
-    return launch_nuts_sep_from13(s, iter, flags, wide, grid, st);
+    if (s.nch <= 4) return launch_nuts_sep_from1(s, iter, flags, grid, st);
+    if (s.nch <= 8) return launch_nuts_sep_from5(s, iter, flags, grid, st);
+    if (s.nch <= 12) return launch_nuts_sep_from9(s, iter, flags, grid, st);
+    return launch_nuts_sep_from13(s, iter, flags, grid, st);
 }
 
 hipError_t launch_local_optimum_dense(const DevState &s, double penalty, int iterations, hipStream_t st);

@@ -9,19 +9,24 @@
 // trailing 1 bit of n) are merged bottom-up, exactly the post-order of the recursion, so turn checks,
 // early exits, log-sum-exp association and RNG consumption are the same as the reference's.
 //
+// The kernel exists in three families, told apart by two facts of the density (DESIGN.md 3.3 has the counters behind every choice):
+//   separable (Model::kSeparable: the Gaussians)  the gradient is recomputed from q, so a proposal candidate is a position on the
+//           trajectory: the winner is regenerated at the end and the tree's scalar bookkeeping is deferred (nuts_replay);
+//   general (neither)  carries grad l, stores its candidates' q in the arena and does the bookkeeping merge by merge;
+//   cooperative (Model::kCooperative)  a general density whose gradients the 16 wavefronts of a workgroup compute together on the
+//           matrix cores; otherwise the general form, with the separable forms' level-0 / level-1 placement.
+//
 // Where the state lives (D = 1024: one vector = 8 KiB):
 //   VGPRs   q, p of the trajectory's moving end (64 regs) for the whole transition -- the separable
 //           Gaussian gradients are recomputed from q (2 flops per element) instead of being carried;
-//           rho of the sub-tree being merged (32 regs) during a merge cascade; in the one-wavefront-per-SIMD
-//           form also the whole-tree rho and the level-2 p#_first (the compiler parks them in AGPRs).
-//   LDS     mu, tau (and a shared M^-1) once per workgroup; per wavefront: the level-0 summary (momentum of
-//           the previous leaf: rho and, times M^-1, p#), the level-1 summary as far as it fits (nuts_l1_lds),
-//           level-2 rho in the one-wavefront form, a per-chain M^-1, and the per-level scalars.
+//           rho of the sub-tree being merged (32 regs) during a merge cascade.
+//   LDS     mu, tau (and a shared M^-1) once per workgroup; per wavefront: the level-0 summary where it is not in registers
+//           (momentum of the previous leaf), the level-1 summary as far as it fits (NutsLds), a per-chain M^-1, and the
+//           per-level scalars.
 //   HBM/L2  per-wavefront arena: deeper summaries (rho, p#_first), the far edge once it has left the starting
-//           point (until then the state arrays s.q, s.p, s.g ARE the far edge), the whole-tree rho where it is
+//           point (until then the state arrays s.q, s.p, s.g ARE the far edge), the whole-tree rho while it is
 //           not on chip, regeneration checkpoints; proposal candidates only for general densities.
-// Workgroups are persistent (one per CU) and pull chains from a device-wide queue; 512 < L <= 1024 runs two wavefronts per
-// SIMD by default and has a one-per-SIMD form as well (DESIGN.md 3.3 has the counters behind every choice here).
+// Workgroups are persistent (one per CU) and pull chains from a device-wide queue.
 #pragma once
 #include "idhmc_device.hpp"
 #include "idhmc_internal.hpp"
@@ -30,32 +35,26 @@
 namespace idhmc {
 
 constexpr int kMaxDepth = 16;
-// Proposal candidates are not stored: a candidate is (position on the trajectory, l(q), pi), and the winner's q is
+// Separable densities do not store proposal candidates: a candidate is (position on the trajectory, l(q), pi), and the winner's q is
 // REGENERATED at the end by |position| leapfrog steps from the starting point (bit-identical: the trajectory is one
 // deterministic leapfrog chain in each direction).  Storing every candidate's q was 2/3 of the kernel's HBM writes
 // (rocprofv3 PMC at D = 1024, depth 7: 9 KB written per leaf, 3.2 TB/s); the regeneration costs ~25 % more leapfrogs.
 // Separable densities only: a general density's leapfrog is expensive (the cooperative dense gradient would also
 // wait for the longest regeneration of its 16-chain group: measured 2.5e8 -> 1.7e8), so it stores its candidates.
-__host__ __device__ constexpr bool nuts_regenerate(bool separable) { return separable; }
-// Round 3: with regeneration a proposal candidate is a position on the trajectory, so NOTHING the tree's scalar bookkeeping
-// computes (the log-sum-exps of the weights and of the acceptance statistic, the multinomial picks and their exponential draws)
-// feeds back into the trajectory: tree shape, turn tests and divergences depend on the vectors alone.  The kernel therefore
+// With regeneration NOTHING the tree's scalar bookkeeping computes (the log-sum-exps of the weights and of the acceptance
+// statistic, the multinomial picks and their exponential draws) feeds back into the trajectory: tree shape, turn tests and
+// divergences depend on the vectors alone.  A separable density's kernel therefore
 // only LOGS every leaf's Delta (8 bytes) while it builds the tree and evaluates the bookkeeping afterwards, in the order the
 // reference prescribes but 64 leaves per pass -- one lane per leaf (nuts_replay below).  Sequentially it was ~176 vector
 // instructions per merge, i.e. per leaf, executed identically by all 64 lanes: a quarter of the kernel's instructions.
-__host__ __device__ constexpr bool nuts_defer(bool separable) { return nuts_regenerate(separable); }
+
 // vectors of L doubles that hold one double per possible leaf of a transition (2^max_depth - 1 of them)
 __host__ __device__ constexpr int nuts_dl_vectors(int max_depth, int L) { return ((1 << max_depth) + L - 1) / L; }
 // Wavefronts per workgroup (one workgroup per CU): the phase point of a chain lives in VGPRs, so the register
-// budget decides.  This function gives the BASE form; 512 < L <= 1024 also has the two-per-SIMD form of nuts_wide_waves,
-// which the host prefers since round 2.  L > 512: 4 wavefronts, one per SIMD with 256 VGPRs + 256 AGPRs (beyond L = 1024
-// two per SIMD spill 176-576 B and lose 25-75 %).  L <= 512: 8 wavefronts, two per
-// SIMD -- they fit in 256 registers (8 spilled dwords at L = 512), and a single wavefront can only issue an fp64
-// instruction every ~7 cycles.  Measured, separable, 8 vs 4 wavefronts: D = 256 1.0e9 vs 0.6e9 leapfrog/s; D = 512
-// 4.6e8 vs 3.8e8 at depth 4, 6.9e8 vs 5.0e8 at depth 7.  L <= 256: 16 wavefronts, four per SIMD (121 registers at
-// L = 256): D = 128 1.05e9 / 1.53e9 (depth 4 / 7) vs 0.89e9 / 1.09e9 with 8; D = 256 0.81e9 / 1.22e9 vs 0.74e9 / 1.00e9;
-// L = 384 (round 2): 7.0e8 / 1.05e9 vs 6.4e8 / 9.1e8 with 8 (128 registers, 16 B of scratch); L = 512 does not fit four per
-// SIMD (112 B of scratch: 4.6e8 / 6.6e8 vs 5.6e8 / 8.4e8 with two).
+// budget decides.  Separable densities: L <= 384 runs 16 (four per SIMD, 128 registers), L = 512 runs 12 (three per SIMD, 167
+// registers), 512 < L <= 1024 runs 8 (two per SIMD, 256 registers) and L > 1024 runs 4, one per SIMD with 256 VGPRs + 256 AGPRs
+// (two per SIMD spill there).  A single wavefront can only issue an fp64 instruction every ~7 cycles, so every form takes the most
+// wavefronts its registers allow; the measurements behind each threshold are in DESIGN.md 3.3.
 // A general density keeps 4:
 // the dense MVN streams its 512 KiB matrix through L1 per gradient, and 8 concurrent streams per CU thrash it
 // (63 M/s with 4 wavefronts, 36 M/s with 8).  A cooperative density (DenseMvnCoop, idhmc_device.hpp) runs 16: one per
@@ -65,72 +64,98 @@ __host__ __device__ constexpr int nuts_waves(int nch, bool separable, bool coope
 {
     if (cooperative) return 16;
     if (nch > 8 && !shared_metric && 10 * nch > 152) return 3;     // mu, tau + 4 x (p_prev, M^-1) must fit 152 KB
-    return separable ? (nch <= 3 ? 16 : (nch <= 4 ? 12 : 4)) : 4;      // L = 512: three per SIMD since round 3 (167 registers): +6 % over two
+    return separable ? (nch <= 3 ? 16 : (nch <= 4 ? 12 : (nch <= 8 ? 8 : 4))) : 4;
 }
 
-// Separable densities keep the level-1 sub-tree summary (rho and p#_first) in LDS next to the level-0 one: at
-// L = 1024 the kernel is bound by the arena's traffic to the Infinity Cache (the live arena of the 128 wavefronts
-// of an XCD is ~28 MB, its L2 4 MB; ~21 KB per leaf at 3.5e8 leaves/s), and half of the level >= 1 merges are
-// level-1 merges.
-// (when the workgroup's LDS allows: 2 more vectors per wavefront).
-// Returns how many of the two level-1 vectors fit per wavefront: 2 = rho and p#_first, 1 = rho only, 0 = none.
-// Budget: the CU's 160 KB less the per-level scalars (LevelScalars, 848 B per wavefront) and the kernel's other statics.
-// Round 3: the level-0 summary (the previous leaf's momentum) is no longer staged in LDS by the separable forms: the momentum a
-// leapfrog starts from IS the previous leaf's, so the odd leaves simply keep their input momentum in registers until the level-0
-// merge (32 VGPRs at L = 1024, live only while rho / p#_first of a merge are not).  The vector this frees per wavefront holds
-// the level-1 p#_first, which was the largest single source of arena traffic (one 8 KB store and one 8 KB load per four leaves:
-// profiles/r03_nuts_bytes_by_source.json).  The register-rich form keeps its own layout.
-// The cooperative dense density takes both over (round 3): its merges of level >= 1 fetched rho and p#_first from the arena one level after
-// the other -- the slowest of a workgroup's 16 wavefronts sets the pace of every gradient round -- and a CU has the LDS for the level-1 pair.
-__host__ __device__ constexpr bool nuts_prev_regs(bool separable, bool cooperative, bool rich)
+// per-wavefront scalars of the live sub-tree summaries; every lane reads/writes the same address with
+// the same value
+struct LevelScalars {
+    double omega[kMaxDepth];
+    double lsa[kMaxDepth];
+    int steps[kMaxDepth];
+    int zeta[kMaxDepth];
+    int pf[kMaxDepth];
+    double z_lq[kMaxDepth + 4];
+    double z_pi[kMaxDepth + 4];
+    int z_idx[kMaxDepth + 4];     // separable: where the doubling of depth d started (signed position on the trajectory)
+    int ck_pos[kMaxDepth];        // separable: signed position of the checkpoint of the doubling of depth d
+};
+constexpr int kWgAcc = 40;            // the workgroup's counters (k_nuts): [0..38] diagnostics counters, [39] leapfrog steps
+// static LDS of k_nuts: LevelScalars per wavefront, coop_ctl[2], wg_acc[kWgAcc], up to the dynamic part's alignment (an upper bound:
+// the compiler drops coop_ctl where nothing is cooperative)
+__host__ __device__ constexpr int nuts_static_lds(int waves)
 {
-    return !rich && (separable || cooperative);
+    return (waves * (int)sizeof(LevelScalars) + 2 * (int)sizeof(int) + kWgAcc * (int)sizeof(unsigned long long) + 15) / 16 * 16;
 }
-// coop_lds: doubles of LDS the cooperative density's gradient rounds use (Model::kLdsDoubles), 0 for every other density
-__host__ __device__ constexpr int nuts_l1_lds(int nch, bool separable, int waves, bool lds_params = true, bool shared_metric = true,
-                                              bool prev_regs = false, int coop_lds = 0)
+
+// ---- the dynamic LDS of k_nuts, for the kernel (which carves it) and the host (which sizes the launch) -------------------------------
+// In vectors of L doubles: [mu][tau] if a separable density has parameters (a general one keeps them in L2), [M^-1] if the metric is
+// shared, then per wavefront [scratch | p_prev] [per-chain M^-1] [general density: staging] [level-1 rho] [level-1 p#_first]; after
+// the wavefronts the tiles of a cooperative density's gradient rounds (coop_lds doubles, Model::kLdsDoubles; 0: not cooperative).
+//   Level 0.  Separable and cooperative densities keep the level-0 summary (the previous leaf's momentum) in registers: the momentum a
+// leapfrog starts from IS the previous leaf's, so the odd leaves keep their input momentum until the level-0 merge (32 VGPRs at
+// L = 1024, live only while rho / p#_first of a merge are not).  A general density stages it in LDS (p_prev).
+//   Level 1.  The same densities keep the level-1 summary (rho and p#_first of the parked two-leaf sub-tree) in LDS as far as the CU's
+// LDS allows: at L = 1024 the kernel is bound by the arena's traffic to the Infinity Cache (the live arena of the 128 wavefronts of an
+// XCD is ~28 MB, its L2 4 MB), half of the level >= 1 merges are level-1 merges, and the level-1 p#_first was the largest single source
+// of arena traffic (profiles/r03_nuts_bytes_by_source.json).  For the cooperative density the slowest of a workgroup's 16 wavefronts
+// sets the pace of every gradient round, and its merges fetched rho and p#_first from the arena one after the other.
+//   l1n = how many of the two fit: 2 = rho and p#_first, 1 = rho only, 0 = none.  The momentum refresh needs one scratch vector per
+// wavefront: the level-1 rho slot, or a vector of its own where there is none.
+struct NutsLds {
+    bool prev_regs;                 // level-0 summary in registers, not LDS
+    int l1n;
+    int mu, tau, minv;              // workgroup vectors (where present)
+    int waves, per_wave;            // wavefront w's block starts at vector waves + w * per_wave; within it:
+    int scratch, minv_w, stage, l1rho, l1pf;
+    int coop;                       // in doubles: the cooperative density's tiles
+    int total;                      // in doubles
+};
+__host__ __device__ constexpr NutsLds nuts_lds(int nch, bool separable, bool has_params, int coop_lds, bool shared_metric, int waves)
 {
-    if (coop_lds > 0) {     // no parameters in LDS, a shared metric is read from L2; the tiles of the gradient rounds
-        if (!prev_regs) return 0;
-        const int base = (shared_metric ? 1 : 0) + waves * (shared_metric ? 0 : 1);
-        const int budget = (163840 - 912 * waves - 256 - coop_lds * 8) / (1024 * nch);
-        return base + 2 * waves <= budget ? 2 : (base + waves <= budget ? 1 : 0);
+    const bool cooperative = coop_lds > 0;
+    const int group = ((has_params && separable) ? 2 : 0) + (shared_metric ? 1 : 0);
+    const int metric_w = shared_metric ? 0 : 1, stage = (separable || cooperative) ? 0 : 1;
+    NutsLds o{};
+    o.prev_regs = separable || cooperative;
+    if (o.prev_regs) {
+        // vectors the CU has beyond the kernel's static arrays and the tiles; `base` of them are taken in any case
+        const int budget = (kLdsBytes - nuts_static_lds(waves) - coop_lds * 8) / (1024 * nch);
+        const int base = group + waves * metric_w;
+        o.l1n = base + 2 * waves <= budget ? 2 : (base + waves <= budget ? 1 : 0);
     }
-    if (!separable) return 0;
-    const int base = (lds_params ? 2 : 0) + (shared_metric ? 1 : 0) + waves * ((prev_regs ? 0 : 1) + (shared_metric ? 0 : 1));
-    const int budget = (163840 - 848 * waves - 256) / (1024 * nch);     // vectors of L doubles
-    return base + 2 * waves <= budget ? 2 : (base + waves <= budget ? 1 : 0);
+    const int first = o.prev_regs ? (o.l1n == 0 ? 1 : 0) : 1;
+    o.mu = 0; o.tau = 1; o.minv = group - 1;
+    o.waves = group;
+    o.minv_w = first;
+    o.stage = first + metric_w;
+    o.l1rho = first + metric_w + stage;
+    o.l1pf = o.l1rho + 1;
+    o.scratch = first ? 0 : o.l1rho;
+    o.per_wave = o.l1rho + o.l1n;
+    o.coop = 128 * nch * (group + waves * o.per_wave);
+    o.total = o.coop + coop_lds;
+    return o;
 }
-// L = 1024, separable: the kernel exists in two forms and the host picks one per launch (launch_nuts): the default
-// one wavefront per SIMD (level-1 summary in LDS, inlined merge scalars; best for adapted chains, depth ~4) and a
-// WIDE one with two per SIMD (256 registers, level-1 summary in the arena; 11-18 % faster on deep trees, 3-12 %
-// slower on shallow ones).
-__host__ __device__ constexpr int nuts_wide_waves(int nch, bool separable, bool cooperative = false)
+// LDS doubles of a density's cooperative gradient rounds (0: not cooperative)
+template <class Model>
+__host__ __device__ constexpr int coop_lds_doubles()
 {
-    return (separable && !cooperative && nch > 4 && nch <= 8) ? 8 : 0;     // 0: no wide form
+    if constexpr (Model::kCooperative) return Model::kLdsDoubles;
+    else return 0;
 }
-
-// "Register-rich" form: separable density, one wavefront per SIMD (4 per workgroup), L <= 1024.  Each wavefront owns
-// the SIMD's whole 512-register file, so the whole-tree rho and the level-2 p#_first live in registers (the compiler
-// parks them in AGPRs) and the level-1 summary and level-2 rho in LDS; mu, tau and M^-1 are staged in LDS as in the
-// other forms.
-__host__ __device__ constexpr bool nuts_rich(int nch, bool separable, bool cooperative, int waves)
+template <int NCH, class Model, bool SHARED_METRIC, int WAVES>
+__host__ __device__ constexpr NutsLds nuts_lds_of()
 {
-    return separable && !cooperative && waves == 4 && nch <= 8;
-}
-// register-rich form: does rho of the level-2 summary fit in LDS next to the rest (else it stays in registers like the
-// level-2 p#_first)?  Budget: 152 KB of the CU's 160 (the per-level scalars and the compiler's own use take the rest).
-__host__ __device__ constexpr bool nuts_l2_lds(int nch, bool lds_params, bool shared_metric)
-{
-    return ((lds_params ? 2 : 0) + (shared_metric ? 1 : 0) + 4 * (4 + (shared_metric ? 0 : 1))) * nch <= 152;
+    return nuts_lds(NCH, Model::kSeparable, Model::kHasParams, coop_lds_doubles<Model>(), SHARED_METRIC, WAVES);
 }
 template <bool B> struct BoolC { static constexpr bool value = B; };
 
 // arena vector indices (each vector = L doubles); MD = max_depth
 struct ArenaMap {
     int md;
-    bool regen;   // no candidate vectors
-    int dlv = 0;  // vectors at the end that hold the log of the leaves' Delta (deferred tree bookkeeping, nuts_defer)
+    bool separable;   // no candidate vectors
+    int dlv = 0;      // vectors at the end that hold the log of the leaves' Delta (separable: the deferred tree bookkeeping)
     // the trajectory edge that is not in registers (p, q and, for general densities, grad); while that edge is
     // still the starting point it is read from the state arrays (s.p, s.q, s.g) instead and these stay unwritten
     __host__ __device__ int edge_p() const { return 0; }
@@ -139,14 +164,18 @@ struct ArenaMap {
     __host__ __device__ int top_rho() const { return 3; }                         // forms that do not keep it in registers
     __host__ __device__ int stk_rho(int k) const { return 4 + k; }                // 1 <= k < md
     __host__ __device__ int pf(int s) const { return 4 + md + s; }                // s < md + 1
-    __host__ __device__ int zq(int s) const { return 4 + 2 * md + 1 + (s - 1); }  // s in [1, md + 2]; !regen only
-    // regen only: the phase point at which the doubling of depth d >= kCheckpointDepth started (regeneration of the
+    __host__ __device__ int zq(int s) const { return 4 + 2 * md + 1 + (s - 1); }  // s in [1, md + 2]; !separable only
+    // separable only: the phase point at which the doubling of depth d >= kCheckpointDepth started (regeneration of the
     // proposal walks from the nearest of these instead of from the starting point)
     __host__ __device__ int ck_q(int d) const { return 4 + 2 * md + 1 + 2 * d; }
     __host__ __device__ int ck_p(int d) const { return 4 + 2 * md + 2 + 2 * d; }
-    __host__ __device__ int dl_at() const { return 4 + 2 * md + 1 + (regen ? 2 * md : md + 2); }
+    __host__ __device__ int dl_at() const { return 4 + 2 * md + 1 + (separable ? 2 * md : md + 2); }
     __host__ __device__ int count() const { return dl_at() + dlv; }
 };
+__host__ __device__ constexpr ArenaMap arena_map(int max_depth, bool separable, int L)
+{
+    return ArenaMap{max_depth, separable, separable ? nuts_dl_vectors(max_depth, L) : 0};
+}
 
 // Doublings of at least 2^kCheckpointDepth leaves (16: measured 2..5, within 2 % of each other) leave their starting phase point in the arena (2 vector stores): the
 // winner of the multinomial sampling lies in the last doubling with probability >= 1/2, and regenerating it from there
@@ -188,8 +217,10 @@ IDHMC_DEV AccStat combine_acc(AccStat a, AccStat b)  // src/NUTS.jl:68-70
 // randexp for its own operands (one shared dexp, one shared dlog, one shared division), so the three results
 // are bit-identical to the sequential form; they are read back with v_readlane.  The draw is speculative
 // (a pure function of its address): the caller consumes it only if the reference would have drawn.
+// Out of line like the rest of the scalar bookkeeping: the tree loop of the general and cooperative forms calls it per merge,
+// nuts_replay (the separable forms) after the tree.
 struct MergeScalars { double lsa, omega; };
-__device__ __forceinline__ MergeScalars nuts_merge_scalars_body(double lsa_a, double lsa_b, double om_a, double om_b)
+__device__ __noinline__ MergeScalars nuts_merge_scalars(double lsa_a, double lsa_b, double om_a, double om_b)
 {
     const bool odd = (threadIdx.x & 1) != 0;
     const double x = odd ? om_a : lsa_a, y = odd ? om_b : lsa_b;
@@ -207,20 +238,6 @@ __device__ __forceinline__ MergeScalars nuts_merge_scalars_body(double lsa_a, do
     o.lsa = read_lane(lae, 0);
     o.omega = read_lane(lae, 1);
     return o;
-}
-__device__ __noinline__ MergeScalars nuts_merge_scalars(double lsa_a, double lsa_b, double om_a, double om_b)
-{
-    return nuts_merge_scalars_body(lsa_a, lsa_b, om_a, om_b);
-}
-// With one wavefront per SIMD (512 registers) the merge cascade inlines it: the scheduler then interleaves this
-// dependent chain (exp, log, divide) with the independent one of the turn test (two fma chains and their DPP
-// reductions), which a call boundary forbids: +3 % at depth 4, +6.5 % at depth 7 at L = 1024.  At two or four
-// wavefronts per SIMD the inlined coefficients cost registers the kernel does not have.
-template <bool INLINE>
-IDHMC_DEV MergeScalars merge_scalars(double lsa_a, double lsa_b, double om_a, double om_b)
-{
-    if constexpr (INLINE) return nuts_merge_scalars_body(lsa_a, lsa_b, om_a, om_b);
-    else return nuts_merge_scalars(lsa_a, lsa_b, om_a, om_b);
 }
 // The exponential draws of a transition are addressed (seed, chain, transition, draw index), so 64
 // consecutive draws are produced by ONE Philox + log pass, lane l holding draw base + l; a merge reads its
@@ -306,54 +323,11 @@ IDHMC_DEV void lds_store(double2 *p, const Vec<NCH> &v)
 IDHMC_DEV bool uni(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0ull; }
 IDHMC_DEV int usi(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
-// per-wavefront scalars of the live sub-tree summaries; every lane reads/writes the same address with
-// the same value
-struct LevelScalars {
-    double omega[kMaxDepth];
-    double lsa[kMaxDepth];
-    int steps[kMaxDepth];
-    int zeta[kMaxDepth];
-    int pf[kMaxDepth];
-    double z_lq[kMaxDepth + 4];
-    double z_pi[kMaxDepth + 4];
-    int z_idx[kMaxDepth + 4];     // signed position of the candidate on the trajectory (kRegenerate)
-    int ck_pos[kMaxDepth];        // signed position of the checkpoint of the doubling of depth d (kRegenerate)
-};
-
-// dynamic LDS layout (doubles): [mu L][tau L] if the density has parameters, [M^-1 L] if the metric is
-// shared, then per wavefront [p_prev L] and, for a per-chain metric, [M^-1 L].
-// A general (non-separable) density adds one staging vector per wavefront and keeps its parameters in L2;
-// a cooperative one has the workgroup's tiles instead (coop_lds doubles, Model::kLdsDoubles; 0: not cooperative).
-__host__ __device__ inline size_t nuts_lds_doubles(int L, bool lds_params, bool shared_metric, bool separable,
-                                                   int coop_lds = 0, int waves = 0)
-{
-    const bool cooperative = coop_lds > 0;
-    if (waves == 0) waves = nuts_waves(L / 128, separable, cooperative, shared_metric);
-    if (nuts_rich(L / 128, separable, cooperative, waves)) {    // per wavefront: p_prev, the level-1 summary, rho of level 2
-        const int l2 = nuts_l2_lds(L / 128, lds_params, shared_metric) ? 1 : 0;
-        return (size_t)L * (waves * (3 + l2 + (shared_metric ? 0 : 1)) + (lds_params ? 2 : 0) + (shared_metric ? 1 : 0));
-    }
-    // per wavefront: [p_prev, or one scratch vector when nothing else is there] [per-chain M^-1] [general: staging] [level-1 rho, p#]
-    const bool pr = nuts_prev_regs(separable, cooperative, false);
-    const int l1n = nuts_l1_lds(L / 128, separable, waves, lds_params, shared_metric, pr, coop_lds);
-    const int first = pr ? (l1n == 0 ? 1 : 0) : 1;
-    return (size_t)L * ((lds_params ? 2 : 0) + (shared_metric ? 1 : 0) +
-                        waves * (first + (shared_metric ? 0 : 1) + ((separable || cooperative) ? 0 : 1) + l1n)) +
-           (size_t)coop_lds;      // the cooperative density's tiles
-}
-// LDS doubles of a density's cooperative gradient rounds (0: not cooperative)
-template <class Model>
-__host__ __device__ constexpr int coop_lds_doubles()
-{
-    if constexpr (Model::kCooperative) return Model::kLdsDoubles;
-    else return 0;
-}
-
 }  // namespace idhmc
 #include "idhmc_nuts_replay.hpp"     // nuts_replay: the deferred bookkeeping (separable densities)
 namespace idhmc {
 
-enum : int { kPfLeaf = -1, kPfLevel0 = -2, kPfLevel1 = -3, kPfLevel2 = -4 };
+enum : int { kPfLeaf = -1, kPfLevel0 = -2, kPfLevel1 = -3 };
 
 // diagnostic build only: per-phase shader-cycle sums (never in the shipped library)
 // diagnostic build only (-DIDHMC_BYTES, tools/nuts_bytes.sh): vectors moved between the wavefront and memory, by source, summed over the
@@ -446,57 +420,40 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
     // Counters every chain adds to (leapfrog steps; the 39 scalar diagnostics counters) are summed per workgroup here and reach the global
     // words once, when the workgroup leaves: 65 536 atomics per launch on ONE address cost ~0.2 ms each hot address (3.5 -> 2.5 ms per
     // transition with IDHMC_T_ACCUM_DIAG at configs[2], tools/bench_accum.py).  Integers: the order of the additions is immaterial.
-    constexpr int kWgAcc = 40;            // [0..38] diagnostics counters, [39] leapfrog steps
     __shared__ unsigned long long wg_acc[kWgAcc];
     constexpr int L = 128 * NCH;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // scalar: branches on it stay wave-uniform
     LevelScalars &S = Sall[wv];
-    constexpr bool kRegenerate = nuts_regenerate(Model::kSeparable);
-    constexpr bool kDefer = nuts_defer(Model::kSeparable);       // the tree's scalar bookkeeping is evaluated after the tree (nuts_replay)
-    const ArenaMap am{s.max_depth, kRegenerate, kDefer ? nuts_dl_vectors(s.max_depth, 128 * NCH) : 0};
+    const ArenaMap am = arena_map(s.max_depth, Model::kSeparable, 128 * NCH);
     double *const arena = s.arena + ((int64_t)blockIdx.x * kNutsWaves + wv) * s.arena_stride;
 
-    // ---- stage the shared read-only vectors in LDS, once per workgroup (register-rich form: in VGPRs) ----------
-    double *cursor = lds;
+    // ---- carve the dynamic LDS (NutsLds) and stage the shared read-only vectors in it, once per workgroup ----------
     Model mdl;
-    constexpr bool kRich = nuts_rich(NCH, Model::kSeparable, kCoop, kNutsWaves);
-    constexpr bool kPrevRegs = nuts_prev_regs(Model::kSeparable, kCoop, kRich);     // level-0 summary in registers, not LDS
-    constexpr int kL1N = kRich ? 2 : nuts_l1_lds(NCH, Model::kSeparable, kNutsWaves, Model::kHasParams && Model::kSeparable, SHARED_METRIC, kPrevRegs,
-                                                    coop_lds_doubles<Model>());
-    constexpr bool kL1Rho = kL1N >= 1, kL1Pf = kL1N >= 2;     // level-1 summary in LDS: rho / p#_first
-    constexpr bool kL2 = kRich;    // level-2 summary on chip as well: rho in LDS, p#_first in registers
-    // LDS vectors per wavefront: [p_prev | scratch], [per-chain M^-1], [general density: staging], [level-1 rho, p#], [level-2 rho];
-    // kPrevRegs: no p_prev vector; the momentum refresh's scratch is then the level-1 rho slot (or one vector of its own)
-    constexpr int kMetricVec = SHARED_METRIC ? 0 : 1;
-    constexpr bool kL2Lds = kL2 && nuts_l2_lds(NCH, Model::kHasParams, SHARED_METRIC);
-    constexpr int kFirstVec = kPrevRegs ? (kL1N == 0 ? 1 : 0) : 1;
-    constexpr int kPerWave = kFirstVec + kMetricVec + ((Model::kSeparable || kCoop) ? 0 : 1) + kL1N + (kL2Lds ? 1 : 0);
+    constexpr NutsLds kLds = nuts_lds_of<NCH, Model, SHARED_METRIC, kNutsWaves>();
+    constexpr bool kPrevRegs = kLds.prev_regs;                          // level-0 summary in registers, not LDS
+    constexpr bool kL1Rho = kLds.l1n >= 1, kL1Pf = kLds.l1n >= 2;     // level-1 summary in LDS: rho / p#_first
     if constexpr (Model::kHasParams && Model::kSeparable) {
-        double *lmu = cursor, *ltau = cursor + L;
-        cursor += 2 * L;
+        double *lmu = lds + kLds.mu * L, *ltau = lds + kLds.tau * L;
         for (int i = threadIdx.x; i < L; i += kNutsWaves * 64) { lmu[i] = s.mu[i]; ltau[i] = s.tau[i]; }
         mdl.m = reinterpret_cast<const double2 *>(lmu) + lane;
         mdl.t = reinterpret_cast<const double2 *>(ltau) + lane;
     }
     LdsVec minv;
     if constexpr (SHARED_METRIC) {
-        double *lm = cursor;
-        cursor += L;
+        double *lm = lds + kLds.minv * L;
         for (int i = threadIdx.x; i < L; i += kNutsWaves * 64) lm[i] = s.minv[i];
         minv.p = reinterpret_cast<const double2 *>(lm) + lane;
     }
-    double *my = cursor + (size_t)wv * (kPerWave * L);
-    if constexpr (kMetricVec) minv.p = reinterpret_cast<const double2 *>(my + kFirstVec * L) + lane;
-    // level-1 summary (kL1Rho, kL1Pf): rho and p#_first of the parked two-leaf sub-tree; level-2 (kL2): rho
-    constexpr int kL1At = kFirstVec + kMetricVec + ((Model::kSeparable || kCoop) ? 0 : 1);
+    double *my = lds + kLds.waves * L + (size_t)wv * (kLds.per_wave * L);
+    if constexpr (!SHARED_METRIC) minv.p = reinterpret_cast<const double2 *>(my + kLds.minv_w * L) + lane;
     // level-0 summary (previous leaf's momentum) where it is staged in LDS; always the momentum refresh's scratch vector
-    double2 *const pprev = reinterpret_cast<double2 *>(my + (kFirstVec ? 0 : kL1At) * L) + lane;
-    double2 *const l1rho = reinterpret_cast<double2 *>(my + kL1At * L) + lane;
-    double2 *const l1pf = reinterpret_cast<double2 *>(my + (kL1At + 1) * L) + lane;
-    double2 *const l2rho = reinterpret_cast<double2 *>(my + (kL1At + 2) * L) + lane;
-    if constexpr (kCoop) mdl.init(s, cursor + (size_t)kNutsWaves * (kPerWave * L), &coop_ctl[1], lane, wv);
-    else if constexpr (!Model::kSeparable) mdl.init(s, my + (kFirstVec + kMetricVec) * L, lane);   // general density: one LDS vector
+    double2 *const pprev = reinterpret_cast<double2 *>(my + kLds.scratch * L) + lane;
+    // level-1 summary (kL1Rho, kL1Pf): rho and p#_first of the parked two-leaf sub-tree
+    double2 *const l1rho = reinterpret_cast<double2 *>(my + kLds.l1rho * L) + lane;
+    double2 *const l1pf = reinterpret_cast<double2 *>(my + kLds.l1pf * L) + lane;
+    if constexpr (kCoop) mdl.init(s, lds + kLds.coop, &coop_ctl[1], lane, wv);
+    else if constexpr (!Model::kSeparable) mdl.init(s, my + kLds.stage * L, lane);   // general density: one LDS vector
     if constexpr (kCoop) { if (threadIdx.x == 0) coop_ctl[1] = kNutsWaves; }
     if (threadIdx.x < kWgAcc) wg_acc[threadIdx.x] = 0ull;
     __syncthreads();
@@ -571,7 +528,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         Vec<NCH> q = bload<NCH, kAuxFresh>(s.q + off, lane);  BYTES(0, 1);
         Vec<NCH> g;                     // carried only for general densities (separable ones recompute it)
         if constexpr (!Model::kSeparable) { g = bload<NCH, kAuxFresh>(s.g + off, lane); BYTES(0, 1); }
-        if constexpr (!SHARED_METRIC) { lds_store<NCH>(reinterpret_cast<double2 *>(my + kFirstVec * L) + lane, bload<NCH>(s.minv + off, lane)); BYTES(0, 1); }
+        if constexpr (!SHARED_METRIC) { lds_store<NCH>(reinterpret_cast<double2 *>(my + kLds.minv_w * L) + lane, bload<NCH>(s.minv + off, lane)); BYTES(0, 1); }
         Vec<NCH> p;
         if (flags & IDHMC_T_KEEP_P) {
             p = bload<NCH, kAuxFresh>(s.p + off, lane);  BYTES(0, 1);
@@ -603,7 +560,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         // randexp draws of this transition, 64 per batch (src/NUTS.jl:33; RNG address = draw index)
         uint32_t draw = 0, ebase = 0;
         double ebatch = 0.0;
-        if constexpr (!kDefer) ebatch = nuts_randexp_batch(key.k0, key.k1, key.chain, iter, 0u);
+        if constexpr (!Model::kSeparable) ebatch = nuts_randexp_batch(key.k0, key.k1, key.chain, iter, 0u);
         auto take_draw = [&]() -> double {
             if (draw >= ebase + 64u) {
                 ebase += 64u;
@@ -615,18 +572,14 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         };
 
         // ---- sample_trajectory initial leaf (src/tree.jl:388-393) ---------------------------------
-        // whole-tree turn statistic: rho in registers (register-rich form) or in the arena; the p# of the two ends
+        // whole-tree turn statistic: rho in LDS or in the arena; the p# of the two ends
         // are not kept -- the tests form them from the momenta of the edges (turn_dots_pp)
-        Vec<NCH> top_rho_r;             // kRich
-        Vec<NCH> l2pf_r;                // kL2: p#_first of the parked level-2 sub-tree
-        Vec<NCH> l2rho_r;               // kL2 && !kL2Lds: its rho
         // Forms with the level-1 rho in LDS park the whole-tree rho in that slot between doublings (nothing is parked
         // there then): a doubling of one or two leaves never needs the slot, a longer one moves the vector to the
         // arena when its first two-leaf sub-tree is parked.
-        constexpr bool kTopLds = !kRich && kL1Rho;
+        constexpr bool kTopLds = kL1Rho;
         bool top_in_lds = kTopLds;
-        if constexpr (kRich) top_rho_r = p;
-        else if constexpr (kTopLds) lds_store<NCH>(l1rho, p);
+        if constexpr (kTopLds) lds_store<NCH>(l1rho, p);
         else { bstore<NCH>(arena + (int64_t)am.top_rho() * L, lane, p); BYTES(5, 1); }
         STAMP(0);                       // prologue
         int top_zeta = 0;               // slot 0 = the starting point itself (lives in s.q / s.g)
@@ -640,7 +593,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         int regs_edge = 1;              // registers hold the '+' edge; the arena holds the '-' edge
         int i_minus = 0, i_plus = 0, depth = 0;
         int term_left = 1, term_right = 0;                        // REACHED_MAX_DEPTH, src/tree.jl:300
-        // kDefer: the record nuts_replay works from -- Delta of every leaf, where each doubling started, where the tree stopped
+        // separable: the record nuts_replay works from -- Delta of every leaf, where each doubling started, where the tree stopped
         double *const dlog = arena + (int64_t)am.dl_at() * L;
         int stop_kind = 0, stop_n = 0, stop_k = 0;
         uint32_t fwdmask = 0;
@@ -673,7 +626,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             }
             const int i_start = fwd ? i_plus : i_minus;
             const int sgn = fwd ? 1 : -1;
-            if constexpr (kRegenerate) {
+            if constexpr (Model::kSeparable) {
                 if (depth >= kCheckpointDepth && i_start != 0) {                  // (position 0 is the state arrays themselves)
                     bstore<NCH>(arena + (int64_t)am.ck_q(depth) * L, lane, q);
                     bstore<NCH>(arena + (int64_t)am.ck_p(depth) * L, lane, p);  BYTES(2, 2);
@@ -683,8 +636,8 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             }
             const double eps_dir = fwd ? eps : -eps;              // move, src/NUTS.jl:18-21
             const int nleaves = 1 << depth;
-            if constexpr (kDefer) {
-                S.z_idx[depth] = i_start;                         // (the candidates' position array is free in this form)
+            if constexpr (Model::kSeparable) {
+                S.z_idx[depth] = i_start;
                 fwdmask |= (uint32_t)fwd << depth;
             }
 
@@ -710,11 +663,11 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                 const double delta = pi - pi0;                                   // leaf, src/NUTS.jl:179
                 i_n = i_start + sgn * (n + 1);
                 cur_v = AccStat{delta < 0.0 ? delta : 0.0, 1};                   // :76-78
-                if constexpr (kDefer) { if (lane == 0) dlog[nleaves - 1 + n] = delta; }
+                if constexpr (Model::kSeparable) { if (lane == 0) dlog[nleaves - 1 + n] = delta; }
                 if (uni(delta < s.min_delta)) {                                  // divergence :180
                     invalid = true;
                     term_left = i_n; term_right = i_n;                           // InvalidTree(i'), tree.jl:332
-                    if constexpr (kDefer) {
+                    if constexpr (Model::kSeparable) {
                         stop_kind = 1; stop_n = n;
                     } else {
                         vres = cur_v;
@@ -748,10 +701,6 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                                 rx = lds_load<NCH>(l1rho);
                                 if constexpr (kL1Pf) pfx = lds_load<NCH>(l1pf);
                                 else { pfx = bload<NCH>(arena + (int64_t)am.pf(usi(S.pf[1])) * L, lane); BYTES(3, 1); }
-                            } else if (kL2 && k == 2) {
-                                if constexpr (kL2Lds) rx = lds_load<NCH>(l2rho);
-                                else rx = l2rho_r;
-                                pfx = l2pf_r;
                             } else {
                                 rx = bload<NCH>(arena + (int64_t)am.stk_rho(k) * L, lane);
                                 pfx = bload<NCH>(arena + (int64_t)am.pf(usi(S.pf[k])) * L, lane);  BYTES(4, 2);
@@ -761,8 +710,8 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                     if constexpr (kNutsWaves == 4 || kCoop) fetch_left();
                     MergeScalars ms{0.0, 0.0};
                     AccStat vk{0.0, 0};
-                    if constexpr (!kDefer) {
-                        ms = merge_scalars<kNutsWaves == 4 && Model::kSeparable>(S.lsa[k], cur_v.lsa, S.omega[k], cur_omega);
+                    if constexpr (!Model::kSeparable) {
+                        ms = nuts_merge_scalars(S.lsa[k], cur_v.lsa, S.omega[k], cur_omega);
                         vk = AccStat{ms.lsa, usi(S.steps[k]) + cur_v.steps};                         // tree.jl:347
                     }
                     if constexpr (kNutsWaves != 4 && !kCoop) fetch_left();
@@ -779,7 +728,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                         invalid = true;
                         term_left = i_start + sgn * (n - (2 << k) + 2);          // first node of this sub-tree
                         term_right = i_n;
-                        if constexpr (kDefer) {
+                        if constexpr (Model::kSeparable) {
                             stop_kind = 2; stop_n = n; stop_k = k;
                         } else {
                             vres = vk;
@@ -788,7 +737,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                         }
                         return false;
                     }
-                    if constexpr (!kDefer) {
+                    if constexpr (!Model::kSeparable) {
                         // combine_proposals_and_logweights(is_doubling = false), tree.jl:238-245, :361-363
                         const double omega = ms.omega;
                         const double logprob2 = cur_omega - omega;               // biased_progressive_logprob2 :261-263
@@ -834,11 +783,10 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                 STAMP(2);                                                        // merge cascade
                 if (invalid) break;
                 // materialise the leaf as a proposal candidate if it survived its merges (write-only until the end)
-                if (!kDefer && cur_zeta < 0) {
+                if (!Model::kSeparable && cur_zeta < 0) {
                     const int zs = __builtin_ctz(zfree);
                     zfree &= ~(1u << zs);
-                    if constexpr (kRegenerate) S.z_idx[zs] = i_n;
-                    else { bstore<NCH>(arena + (int64_t)am.zq(zs) * L, lane, q); BYTES(7, 1); }
+                    bstore<NCH>(arena + (int64_t)am.zq(zs) * L, lane, q); BYTES(7, 1);
                     S.z_lq[zs] = lq;
                     S.z_pi[zs] = pi;
                     cur_zeta = zs;
@@ -849,17 +797,13 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                     // level 0: rho = p, p# = M^-1 p, both from p (kPrevRegs: p is the next leapfrog's input, nothing to store)
                     if constexpr (!kPrevRegs) lds_store<NCH>(pprev, p);
                 } else {
-                    // rho of the parked sub-tree: LDS for level 1 (a two-leaf sub-tree) where it fits, level 2 on chip in
-                    // the register-rich form, else the arena
+                    // rho of the parked sub-tree: LDS for level 1 (a two-leaf sub-tree) where it fits, else the arena
                     if (kL1Rho && k == 1) {
                         if (kTopLds && top_in_lds) {                             // the slot still holds the whole-tree rho
                             bstore<NCH>(arena + (int64_t)am.top_rho() * L, lane, lds_load<NCH>(l1rho));  BYTES(5, 1);
                             top_in_lds = false;
                         }
                         lds_store<NCH>(l1rho, rho);
-                    } else if (kL2 && k == 2) {
-                        if constexpr (kL2Lds) lds_store<NCH>(l2rho, rho);
-                        else l2rho_r = rho;
                     } else {
                         bstore<NCH>(arena + (int64_t)am.stk_rho(k) * L, lane, rho);  BYTES(4, 1);
                     }
@@ -868,25 +812,19 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                         // the first leaf is the level-0 summary just merged: M^-1 p_prev stays in LDS
                         if constexpr (!kPrevRegs) lds_store<NCH>(l1pf, psharp<NCH>(minv, lds_load<NCH>(pprev)));     // (kPrevRegs: stored in the merge)
                         S.pf[1] = kPfLevel1;
-                    } else if (kL2 && k == 2) {
-                        l2pf_r = lds_load<NCH>(l1pf);                            // the level-1 summary's, still in LDS
-                        S.pf[2] = kPfLevel2;
                     } else {
-                        if (cur_pf < kPfLeaf) {                                  // p#_first moves from LDS / registers to an arena slot
+                        if (cur_pf < kPfLeaf) {                                  // p#_first moves from LDS to an arena slot
                             const int ps = __builtin_ctz(pffree);
                             pffree &= ~(1u << ps);
                             BYTES(cur_pf == kPfLevel0 ? 3 : 4, 1);
-                            if (kL2 && cur_pf == kPfLevel2)
-                                bstore<NCH>(arena + (int64_t)am.pf(ps) * L, lane, l2pf_r);
-                            else
-                                bstore<NCH>(arena + (int64_t)am.pf(ps) * L, lane,
-                                            cur_pf == kPfLevel0 ? psharp<NCH>(minv, lds_load<NCH>(pprev)) : lds_load<NCH>(l1pf));
+                            bstore<NCH>(arena + (int64_t)am.pf(ps) * L, lane,
+                                        cur_pf == kPfLevel0 ? psharp<NCH>(minv, lds_load<NCH>(pprev)) : lds_load<NCH>(l1pf));
                             cur_pf = ps;
                         }
                         S.pf[k] = cur_pf;
                     }
                 }
-                if constexpr (!kDefer) {
+                if constexpr (!Model::kSeparable) {
                     S.omega[k] = cur_omega;
                     S.lsa[k] = cur_v.lsa;
                     S.steps[k] = cur_v.steps;
@@ -896,7 +834,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             }
 
             if (invalid) {
-                if constexpr (!kDefer) v = combine_acc(v, vres);                 // tree.jl:414, :417
+                if constexpr (!Model::kSeparable) v = combine_acc(v, vres);                 // tree.jl:414, :417
                 break;
             }
             // request the far edge's momentum (and the whole-tree rho where it lives in the arena) now; the scalar work
@@ -904,14 +842,13 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             const int i_far = fwd ? i_minus : i_plus;
             const Vec<NCH> p_far = bload<NCH, kAuxFresh>(i_far ? arena + (int64_t)am.edge_p() * L : s.p + off, lane);  BYTES(5, 1);
             Vec<NCH> tr;
-            if constexpr (kRich) tr = top_rho_r;
-            else if (kTopLds && top_in_lds) tr = lds_load<NCH>(l1rho);
+            if (kTopLds && top_in_lds) tr = lds_load<NCH>(l1rho);
             else { tr = bload<NCH>(arena + (int64_t)am.top_rho() * L, lane); BYTES(5, 1); }
             if (fwd) i_plus = i_n; else i_minus = i_n;                           // :424-428
             if (cur_pf >= 0) pffree |= 1u << cur_pf;
 
             // combine_proposals_and_logweights(is_doubling = true), tree.jl:431-433
-            if constexpr (!kDefer) {
+            if constexpr (!Model::kSeparable) {
                 const MergeScalars mt = nuts_merge_scalars(v.lsa, cur_v.lsa, top_omega, cur_omega);
                 v = AccStat{mt.lsa, v.steps + cur_v.steps};                      // tree.jl:414
                 const double omega = mt.omega;
@@ -931,8 +868,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             // whole-tree turn statistic and U-turn test, tree.jl:437-438
             {
                 const Vec<NCH> trho = has_rho ? vadd<NCH>(tr, rho) : vadd<NCH>(tr, p);
-                if constexpr (kRich) top_rho_r = trho;
-                else if constexpr (kTopLds) { lds_store<NCH>(l1rho, trho); top_in_lds = true; }
+                if constexpr (kTopLds) { lds_store<NCH>(l1rho, trho); top_in_lds = true; }
                 else { bstore<NCH>(arena + (int64_t)am.top_rho() * L, lane, trho); BYTES(5, 1); }
                 double d_other, d_new;
                 turn_dots_pp<NCH>(trho, p_far, p, minv, d_other, d_new);
@@ -946,8 +882,8 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         STAMP(4);                                                                // doubling bookkeeping
         // ---- epilogue: TreeStatisticsNUTS (src/NUTS.jl:262), next state, adaptation hooks ----------
         double lq_new = lq0, pi_new = pi0;                                       // the state the transition ends in (slot 0: the start)
-        int iw_defer = 0;
-        if constexpr (kDefer) {
+        int iw = 0;                                                              // separable: the winner's position on the trajectory
+        if constexpr (Model::kSeparable) {
             // the tree is built; now its bookkeeping (nuts_replay): acceptance statistic and the winner of the progressive sampling
             ReplayIn ri;
             ri.dl = dlog;
@@ -959,7 +895,7 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
             v = AccStat{ro.lsa, ro.steps};
             if (ro.win_d >= 0) {
                 const int st = usi(S.z_idx[ro.win_d]);
-                iw_defer = ((fwdmask >> ro.win_d) & 1u) ? st + (ro.win_n + 1) : st - (ro.win_n + 1);
+                iw = ((fwdmask >> ro.win_d) & 1u) ? st + (ro.win_n + 1) : st - (ro.win_n + 1);
                 top_zeta = 1;
             }
         } else {
@@ -969,10 +905,9 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         const double a_raw = nuts_dexp(v.lsa) / (double)v.steps;                      // acceptance_rate, NUTS.jl:84
         const double a = a_raw < 1.0 ? a_raw : 1.0;
         if (top_zeta > 0) {
-            if constexpr (kRegenerate) {
+            if constexpr (Model::kSeparable) {
                 // walk to the winner along the same leapfrog chain the tree took: from the nearest checkpoint before it
                 // on its side of the trajectory, else from the starting point
-                const int iw = kDefer ? iw_defer : usi(S.z_idx[top_zeta]);
                 int i_from = 0, d_from = -1;
                 for (int d = kCheckpointDepth; d < depth + 1 && d < s.max_depth; ++d) {
                     if (!((ckmask >> d) & 1u)) continue;
@@ -984,29 +919,22 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
                 const int nw = (iw > 0 ? iw : -iw) - (i_from > 0 ? i_from : -i_from);
                 q = bload<NCH, kAuxFresh>(d_from >= 0 ? arena + (int64_t)am.ck_q(d_from) * L : s.q + off, lane);
                 p = bload<NCH, kAuxFresh>(d_from >= 0 ? arena + (int64_t)am.ck_p(d_from) * L : s.p + off, lane);  BYTES(2, 2);
-                if constexpr (!Model::kSeparable) { g = bload<NCH, kAuxFresh>(s.g + off, lane); BYTES(2, 1); }
                 double lqw, Kw;
-                for (int t = 0; t < nw - (kDefer ? 1 : 0); ++t) {
-                    if constexpr (Model::kSeparable) leapfrog_step_regrad<NCH>(mdl, minv, eps_w, q, p, lqw, Kw);
-                    else leapfrog_step_general<NCH>(mdl, minv, eps_w, q, p, g, lqw, Kw);
-                }
-                if constexpr (kDefer) {
-                    // the last step is the winning leaf itself: its l(q) and pi are the leaf's, bit for bit (the steps before it
-                    // drop their reductions: nothing reads them)
-                    leapfrog_step_regrad<NCH>(mdl, minv, eps_w, q, p, lqw, Kw);
-                    lq_new = lqw;
-                    pi_new = phase_logdensity(lqw, Kw);
-                }
+                for (int t = 0; t < nw - 1; ++t) leapfrog_step_regrad<NCH>(mdl, minv, eps_w, q, p, lqw, Kw);
+                // the last step is the winning leaf itself: its l(q) and pi are the leaf's, bit for bit (the steps before it
+                // drop their reductions: nothing reads them)
+                leapfrog_step_regrad<NCH>(mdl, minv, eps_w, q, p, lqw, Kw);
+                lq_new = lqw;
+                pi_new = phase_logdensity(lqw, Kw);
                 // (separable densities do not write grad l back: the gradient of a separable density is re-derived from q wherever it
                 // is needed -- this kernel never reads the array -- and the host marks it stale, idhmc_api.hip ensure_grad)
             } else {
                 q = bload<NCH>(arena + (int64_t)am.zq(top_zeta) * L, lane);  BYTES(7, 1);
                 // the proposal's gradient, same bits as when it was a leaf
-                if constexpr (Model::kSeparable) (void)eval_density<NCH>(mdl, q, g);
-                else (void)mdl.grad(q, g);
+                (void)mdl.grad(q, g);
             }
             bstore<NCH>(s.q + off, lane, q);  BYTES(6, 1);
-            if constexpr (!(kRegenerate && Model::kSeparable)) { bstore<NCH>(s.g + off, lane, g); BYTES(6, 1); }
+            if constexpr (!Model::kSeparable) { bstore<NCH>(s.g + off, lane, g); BYTES(6, 1); }
         } else if ((flags & (IDHMC_T_ACCUM_METRIC | IDHMC_T_ACCUM_MOMENTS)) || s.fz_q) {
             q = bload<NCH, kAuxFresh>(s.q + off, lane);  BYTES(6, 1);
         }
@@ -1215,8 +1143,9 @@ __global__ __launch_bounds__(256) void k_stepsize_search(DevState s)
 template <int NCH, class Model, bool SHARED, int WAVES = nuts_waves(NCH, Model::kSeparable, Model::kCooperative, SHARED)>
 static hipError_t launch_nuts_t(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
 {
-    const size_t bytes = sizeof(double) * nuts_lds_doubles(128 * NCH, Model::kHasParams && Model::kSeparable, SHARED,
-                                                           Model::kSeparable, coop_lds_doubles<Model>(), WAVES);
+    constexpr NutsLds kLds = nuts_lds_of<NCH, Model, SHARED, WAVES>();
+    constexpr size_t bytes = sizeof(double) * kLds.total;
+    static_assert(bytes + nuts_static_lds(WAVES) <= (size_t)kLdsBytes, "k_nuts: dynamic + static LDS exceed a CU's");
     static bool attr_done[64] = {};  // per instantiation and device (the attribute is per device)
     int dev = 0;
     (void)hipGetDevice(&dev);

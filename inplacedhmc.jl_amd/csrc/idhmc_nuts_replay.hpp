@@ -1,4 +1,4 @@
-// idhmc_nuts_replay.hpp -- the tree's scalar bookkeeping of a NUTS transition, evaluated AFTER the tree (nuts_defer): acceptance statistic
+// idhmc_nuts_replay.hpp -- the tree's scalar bookkeeping of a NUTS transition, evaluated AFTER the tree (separable densities): acceptance statistic
 // and the winner of the biased progressive sampling from the log of the leaves' Delta, one level of up to 64 leaves per pass.
 // Included by idhmc_nuts_kernel.hpp (after AccStat, MergeScalars, nuts_merge_scalars, nuts_logaddexp, nuts_randexp_batch, uni / usi);
 // replaces, for the separable densities, what reference adjacent_tree / sample_trajectory compute on the way
@@ -7,7 +7,7 @@
 
 namespace idhmc {
 
-// ---- deferred tree bookkeeping (nuts_defer) -------------------------------------------------------------------------------
+// ---- deferred tree bookkeeping ------------------------------------------------------------------------------------------------------
 // What the tree loop leaves behind: Delta of every leaf (dl: the leaf n of the doubling of depth d at index 2^d - 1 + n, the order
 // in which the leaves were made), how many doublings completed and were merged into the tree (ndone), and where the doubling after
 // them stopped, if it did: stop_kind 1 = divergent leaf stop_n (src/tree.jl:332), 2 = the sub-tree completed by leaf stop_n turned

@@ -5,19 +5,9 @@
 namespace idhmc {
 
 template <int NCH>
-static hipError_t launch_nuts_sep_nch(const DevState &s, uint32_t iter, uint32_t flags, int wide, int grid, hipStream_t st)
+static hipError_t launch_nuts_sep_nch(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
 {
     const bool shared = s.minv_stride == 0;
-    if constexpr (nuts_wide_waves(NCH, true) > 0) {
-        constexpr int WWV = nuts_wide_waves(NCH, true);
-        if (wide) {
-            if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)
-                return shared ? launch_nuts_t<NCH, IsoGaussian<NCH>, true, WWV>(s, iter, flags, grid, st)
-                              : launch_nuts_t<NCH, IsoGaussian<NCH>, false, WWV>(s, iter, flags, grid, st);
-            return shared ? launch_nuts_t<NCH, DiagGaussianLds<NCH>, true, WWV>(s, iter, flags, grid, st)
-                          : launch_nuts_t<NCH, DiagGaussianLds<NCH>, false, WWV>(s, iter, flags, grid, st);
-        }
-    }
     if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)
         return shared ? launch_nuts_t<NCH, IsoGaussian<NCH>, true>(s, iter, flags, grid, st)
                       : launch_nuts_t<NCH, IsoGaussian<NCH>, false>(s, iter, flags, grid, st);
@@ -27,13 +17,13 @@ static hipError_t launch_nuts_sep_nch(const DevState &s, uint32_t iter, uint32_t
 
 #define IDHMC_NUTS_SEP_NAME2(lo) launch_nuts_sep_from##lo
 #define IDHMC_NUTS_SEP_NAME(lo) IDHMC_NUTS_SEP_NAME2(lo)
-hipError_t IDHMC_NUTS_SEP_NAME(IDHMC_NUTS_LO)(const DevState &s, uint32_t iter, uint32_t flags, int wide, int grid, hipStream_t st)
+hipError_t IDHMC_NUTS_SEP_NAME(IDHMC_NUTS_LO)(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
 {
     switch (s.nch) {
-    case IDHMC_NUTS_LO: return launch_nuts_sep_nch<IDHMC_NUTS_LO>(s, iter, flags, wide, grid, st);
-    case IDHMC_NUTS_LO + 1: return launch_nuts_sep_nch<IDHMC_NUTS_LO + 1>(s, iter, flags, wide, grid, st);
-    case IDHMC_NUTS_LO + 2: return launch_nuts_sep_nch<IDHMC_NUTS_LO + 2>(s, iter, flags, wide, grid, st);
-    case IDHMC_NUTS_LO + 3: return launch_nuts_sep_nch<IDHMC_NUTS_LO + 3>(s, iter, flags, wide, grid, st);
+    case IDHMC_NUTS_LO: return launch_nuts_sep_nch<IDHMC_NUTS_LO>(s, iter, flags, grid, st);
+    case IDHMC_NUTS_LO + 1: return launch_nuts_sep_nch<IDHMC_NUTS_LO + 1>(s, iter, flags, grid, st);
+    case IDHMC_NUTS_LO + 2: return launch_nuts_sep_nch<IDHMC_NUTS_LO + 2>(s, iter, flags, grid, st);
+    case IDHMC_NUTS_LO + 3: return launch_nuts_sep_nch<IDHMC_NUTS_LO + 3>(s, iter, flags, grid, st);
     default: return hipErrorInvalidValue;
     }
 }

@@ -171,15 +171,14 @@ def assert_accumulators_equal(got, want, what=""):
 # ---- the Gaussian cases of tests/test_gpu_accumulators.py ------------------------------------------------------------------------------
 # eps: chain c runs at lo * (hi / lo) ** (c / (C - 1)).  The metric is the target's variance times a factor in [0.5, 2), so a unit-scale
 # leapfrog is stable below eps = 2 / sqrt(2): the first chains stop at max_depth, the middle ones turn at depths 1 to 5, the last ones
-# diverge at once and stay where they are.  wide = 0: created under IDHMC_NUTS_WIDE=0 (the kernel has a second, wide form at L = 640
-# to 1024 only, which is the default there: diag1024_shared runs it, diag640_narrow the other; at D = 300 the switch selects nothing).
+# diverge at once and stay where they are.
 GAUSSIAN_CASES = {
-    "diag40": dict(kind="diag", D=40, C=37, N=30, max_depth=5, shared=False, wide=None, eps=(0.15, 1.8), seed=9),
-    "diag200": dict(kind="diag", D=200, C=300, N=24, max_depth=6, shared=False, wide=None, eps=(0.15, 1.8), seed=9),
-    "diag1024_shared": dict(kind="diag", D=1024, C=24, N=24, max_depth=6, shared=True, wide=None, eps=(0.15, 1.8), seed=9),
-    "iso300_narrow": dict(kind="iso", D=300, C=64, N=30, max_depth=6, shared=False, wide=0, eps=(0.2, 2.6), seed=9),
-    "diag64_few": dict(kind="diag", D=64, C=3, N=60, max_depth=4, shared=False, wide=None, eps=(0.15, 1.8), seed=9),
-    "diag640_narrow": dict(kind="diag", D=640, C=24, N=24, max_depth=6, shared=False, wide=0, eps=(0.15, 1.8), seed=9),
+    "diag40": dict(kind="diag", D=40, C=37, N=30, max_depth=5, shared=False, eps=(0.15, 1.8), seed=9),
+    "diag200": dict(kind="diag", D=200, C=300, N=24, max_depth=6, shared=False, eps=(0.15, 1.8), seed=9),
+    "diag1024_shared": dict(kind="diag", D=1024, C=24, N=24, max_depth=6, shared=True, eps=(0.15, 1.8), seed=9),
+    "iso300_narrow": dict(kind="iso", D=300, C=64, N=30, max_depth=6, shared=False, eps=(0.2, 2.6), seed=9),
+    "diag64_few": dict(kind="diag", D=64, C=3, N=60, max_depth=4, shared=False, eps=(0.15, 1.8), seed=9),
+    "diag640_narrow": dict(kind="diag", D=640, C=24, N=24, max_depth=6, shared=False, eps=(0.15, 1.8), seed=9),
 }
 
 

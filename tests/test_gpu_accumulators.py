@@ -42,7 +42,7 @@ def gaussian_case(idhmc, name):
     D = case["D"]
     model = idhmc.IsoGaussian(D) if case["kind"] == "iso" else idhmc.DiagGaussian(mu, sigma=sig)
     return dict(model=model, C=case["C"], N=case["N"], eps=eps, start=None, minv=minv, seed=case["seed"], shared=case["shared"],
-                opt=dict(max_depth=case["max_depth"]), env={} if case["wide"] is None else {"IDHMC_NUTS_WIDE": str(case["wide"])},
+                opt=dict(max_depth=case["max_depth"]), env={},
                 padded=(D + 127) // 128 * 128, form=-1)
 
 

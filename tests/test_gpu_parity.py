@@ -172,13 +172,10 @@ def test_long_doublings_stop_at_every_level(idhmc, oracle, kind, D, eps):
 
 @pytest.mark.parametrize("D", [1024, 700])
 @pytest.mark.parametrize("shared", [False, True])
-@pytest.mark.parametrize("wide", ["0", "1"])
-def test_both_forms_of_the_l1024_kernel(idhmc, oracle, monkeypatch, wide, shared, D):
-    """512 < L <= 1024 has two forms of k_nuts: two wavefronts per SIMD (the default: level-1 rho in LDS with a shared
-    metric, whole-tree rho parked in that slot between doublings) and one per SIMD (level-2 summary and whole-tree rho on
-    chip); IDHMC_NUTS_WIDE pins one.  Same arithmetic: both equal the oracle bit for bit, with a per-chain and a shared
+def test_the_l1024_kernel_with_both_metric_modes(idhmc, oracle, shared, D):
+    """512 < L <= 1024 runs k_nuts with two wavefronts per SIMD (level-1 rho in LDS with a shared metric, whole-tree rho
+    parked in that slot between doublings).  It equals the oracle bit for bit, with a per-chain and a shared
     metric, deep enough trees (depth 7) for level >= 3 merges, the regeneration checkpoints and every park path."""
-    monkeypatch.setenv("IDHMC_NUTS_WIDE", wide)
     C, T = 9, 6
     kw = dict(metric_mode=idhmc.METRIC_SHARED) if shared else {}
     eng, chains = make_pair(idhmc, oracle, "diag", D, C, seed=11, max_depth=7, **kw)

@@ -49,8 +49,7 @@ CASES = [
     ("diag8-k_nuts-DiagGaussianLds<1>-perchain", "diag", 8, 1 << 18, False, (0.2, 0.6), 10, 3, {}),
     ("diag8-k_nuts-DiagGaussianLds<1>-shared", "diag", 8, 1 << 18, True, (0.2, 0.6), 10, 3, {}),
     ("iso129-k_nuts-IsoGaussian<2>-ragged", "iso", 129, 1 << 16, False, (0.3, 0.8), 10, 2, {}),
-    ("diag1024-k_nuts<8>-wide0", "diag", 1024, 1 << 16, False, (0.15, 0.35), 10, 0, {"IDHMC_NUTS_WIDE": "0"}),
-    ("diag1024-k_nuts<8>-wide1", "diag", 1024, 1 << 16, False, (0.15, 0.35), 10, 0, {"IDHMC_NUTS_WIDE": "1"}),
+    ("diag1024-k_nuts<8>", "diag", 1024, 1 << 16, False, (0.15, 0.35), 10, 0, {}),
     ("diag1500-k_nuts<12>-beyond1024", "diag", 1500, 1 << 14, False, (0.15, 0.35), 10, 2, {}),
     ("dense40-k_nuts-DenseMvnCoop<1>-perchain", "dense", 40, 1 << 16, False, (0.1, 0.2), 10, 2, {}),
     ("dense256-k_nuts-DenseMvnCoop<2>-shared", "dense", 256, 1 << 15, True, (0.1, 0.2), 10, 2, {}),
