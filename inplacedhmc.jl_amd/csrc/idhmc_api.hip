@@ -167,14 +167,14 @@ int idhmc_set_q(idhmc_ctx *c, const double *q)
     CTXCHK(c);
     if (!q) return fail(IDHMC_ERR_BAD_ARG, "null q");
     if (int rc = put_vec(c, c->s.q, q, c->s.C)) return rc;
-    HIPCHK(launch_eval(c->s, c->stream));
+    HIPCHK(launch_eval(c->s, 0, c->stream));
     c->grad_stale = false;
     return IDHMC_OK;
 }
 int idhmc_random_position(idhmc_ctx *c)
 {
     CTXCHK(c);
-    HIPCHK(launch_random_position(c->s, c->stream));
+    HIPCHK(launch_eval(c->s, 1, c->stream));
     c->grad_stale = false;
     return IDHMC_OK;
 }
@@ -265,15 +265,14 @@ int idhmc_refresh_momentum(idhmc_ctx *c, uint32_t iter)
 int idhmc::ensure_grad(idhmc_ctx *c)
 {
     if (c->grad_stale) {
-        HIPCHK(launch_eval(c->s, c->stream));
+        HIPCHK(launch_eval(c->s, 0, c->stream));
         c->grad_stale = false;
     }
     return IDHMC_OK;
 }
 int idhmc::leapfrog_regrad(const idhmc_ctx *c, int32_t n_steps)
 {
-    const bool separable = c->s.model == IDHMC_MODEL_ISO_GAUSSIAN || c->s.model == IDHMC_MODEL_DIAG_GAUSSIAN;
-    return (c->opt.leapfrog_grad_mode == IDHMC_GRAD_RECOMPUTE && separable && n_steps == 1) ? 1 : 0;
+    return (c->opt.leapfrog_grad_mode == IDHMC_GRAD_RECOMPUTE && model_is_separable(c->s.model) && n_steps == 1) ? 1 : 0;
 }
 int idhmc_set_leapfrog_grad_mode(idhmc_ctx *c, int32_t mode)
 {
@@ -311,7 +310,7 @@ int idhmc::nuts_launch(idhmc_ctx *c, uint32_t iter, uint32_t flags, uint32_t n_i
     HIPCHK(launch_nuts(c->s, iter, flags, c->stream, n_iter, fz_q, fz_st));
     // the transition of a separable density leaves grad l of the new state unwritten (8 KB per chain and transition that nothing on
     // the sampling path reads: the kernel re-derives the gradient from q); whoever needs the array re-evaluates first (ensure_grad)
-    if (c->s.model == IDHMC_MODEL_ISO_GAUSSIAN || c->s.model == IDHMC_MODEL_DIAG_GAUSSIAN) c->grad_stale = true;
+    if (model_is_separable(c->s.model)) c->grad_stale = true;
     HIPCHK(hipMemcpyAsync(const_cast<unsigned long long *>(slot), c->s.total_steps + kPulseAt, sizeof(unsigned long long) * idhmc_ctx::kPulseWords,
                           hipMemcpyDeviceToHost, c->stream));
     ++c->launches;

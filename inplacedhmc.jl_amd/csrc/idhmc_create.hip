@@ -410,7 +410,7 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
         const int64_t need = (nchains + W - 1) / W * W;
         if (nslots > need) nslots = need;
         s.nslots = (int32_t)nslots;
-        s.arena_stride = (int64_t)arena_vectors(opt.max_depth, s.model == IDHMC_MODEL_ISO_GAUSSIAN || s.model == IDHMC_MODEL_DIAG_GAUSSIAN, s.L) * s.L;
+        s.arena_stride = (int64_t)arena_vectors(opt.max_depth, model_is_separable(s.model), s.L) * s.L;
         DALLOC(s.arena, s.arena_stride * nslots);
     }
     // a user-supplied density: upload its parameters ...
@@ -442,7 +442,7 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
         if (e != hipSuccess) return fail(IDHMC_ERR_HIP, "init kernels failed: %s", hipGetErrorString(e));
     }
     {
-        hipError_t e = launch_eval(s, c->stream);   // q = 0: consistent (lq, grad)
+        hipError_t e = launch_eval(s, 0, c->stream);   // q = 0: consistent (lq, grad)
         if (e != hipSuccess && e != hipErrorNotSupported) return fail(IDHMC_ERR_HIP, "eval failed: %s", hipGetErrorString(e));
         e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(IDHMC_ERR_HIP, "init sync failed: %s", hipGetErrorString(e));

@@ -98,6 +98,7 @@ __device__ __forceinline__ void bind_chain(Model &mdl, const DevState &s, uint32
     if constexpr (BindsChain<Model>::value) mdl.bind_chain(s, global_chain);
 }
 constexpr int kPulseAt = 0;
+constexpr int kStreamWaves = 4;         // wavefronts, i.e. chains, per workgroup of the streaming kernels (idhmc_stream.hpp, idhmc_optimum.hpp)
 constexpr int kLdsBytes = 160 * 1024;   // LDS of a CU
 // transition flag of the test suite only (see the XCD check in k_nuts); idhmc_nuts_transition(s) accept it on a context created
 // with IDHMC_TEST_XCC_MISMATCH=1 in the environment, and refuse it, like every other bit outside the IDHMC_T_* set, otherwise
@@ -127,15 +128,13 @@ constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
         IDHMC_NCH_CASE(1, __VA_ARGS__) IDHMC_NCH_CASE(2, __VA_ARGS__) IDHMC_NCH_CASE(4, __VA_ARGS__) IDHMC_NCH_CASE(8, __VA_ARGS__)    \
     default: return hipErrorInvalidValue;                                                                          \
     }
-// ---- custom densities through hipRTC (idhmc_jit.hip) -------------------------------------------------
+// ---- custom densities and GLMs through hipRTC (idhmc_jit.hip) -------------------------------------------
 struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
 // K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
-hipError_t launch_eval_jit(const DevState &s, int random_q, hipStream_t st);
-hipError_t launch_leapfrog_jit(const DevState &s, double eps, int own, int n_steps, hipStream_t st);
 
 // ---- RCCL communicator for the global-eps exchange (idhmc_comm.hip; RCCL bound with dlopen) ----------
 struct Comm;
@@ -145,20 +144,61 @@ int comm_allreduce_sum(Comm *c, double *dev_buf, int n, hipStream_t st, char *er
 void comm_destroy(Comm *c);
 void comm_info(const Comm *c, int *nranks, int *rank, long long *allreduces);
 
-// ---- Bayesian logistic regression (idhmc_logistic.hip) ---------------------------------------------
-hipError_t launch_eval_logistic(const DevState &s, int random_q, hipStream_t st);
-hipError_t launch_leapfrog_logistic(const DevState &s, double eps, int own, int n_steps, hipStream_t st);
-hipError_t launch_stepsize_search_logistic(const DevState &s, hipStream_t st);
-hipError_t launch_local_optimum_logistic(const DevState &s, double penalty, int iterations, hipStream_t st);
-hipError_t launch_nuts_logistic(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+// ---- the backends: who evaluates a density -------------------------------------------------------------
+// One row per backend, defined by the translation unit that owns it; the launchers below go through backend(model).
+struct Backend {
+    hipError_t (*eval)(const DevState &s, int random_q, hipStream_t st);
+    // regrad, dense_mfma: as for launch_leapfrog; a backend they do not concern ignores them
+    hipError_t (*leapfrog)(const DevState &s, double eps, int own, int n_steps, int regrad, int dense_mfma, hipStream_t st);
+    hipError_t (*stepsize_search)(const DevState &s, hipStream_t st);
+    hipError_t (*local_optimum)(const DevState &s, double penalty, int iterations, hipStream_t st);
+    hipError_t (*nuts)(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+};
+// (functions, not variables: a constant at namespace scope would be emitted for the device as well, host pointers and all)
+const Backend &separable_backend();   // idhmc_kernels.hip: the Gaussians
+const Backend &dense_backend();       // idhmc_dense.hip
+const Backend &logistic_backend();    // idhmc_logistic.hip
+const Backend &jit_backend();         // idhmc_jit.hip: a custom density or a GLM, compiled at run time
+inline bool model_is_separable(int model) { return model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN; }
+inline const Backend *backend(int model)
+{
+    if (model_is_separable(model)) return &separable_backend();
+    if (model == IDHMC_MODEL_DENSE_MVN) return &dense_backend();
+    if (model == IDHMC_MODEL_LOGISTIC_REGRESSION) return &logistic_backend();
+    if (model == IDHMC_MODEL_CUSTOM || model == IDHMC_MODEL_GLM) return &jit_backend();
+    return nullptr;
+}
+// entries of a row that another translation unit defines, so that the parallel build stays as it is: the separable densities'
+// search and optimum stage and every k_nuts of the separable and dense rows (idhmc_nuts.hip, idhmc_nuts_sep{1,2,3,4}.hip), the
+// dense density's matrix-core leapfrog (idhmc_dense_mfma.hip)
+hipError_t launch_stepsize_search_separable(const DevState &s, hipStream_t st);
+hipError_t launch_local_optimum_separable(const DevState &s, double penalty, int iterations, hipStream_t st);
+hipError_t launch_nuts_separable(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from1(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from5(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from9(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_sep_from13(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_nuts_dense(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st);
+hipError_t launch_leapfrog_dense_mfma(const DevState &s, double eps, int own, int n_steps, hipStream_t st);
+// The grid of a streaming kernel: kStreamWaves chains per workgroup, capped so that every CU keeps several workgroups
+// (k_leapfrog1 is uncapped, the optimum stage bounded by the arena slots: every launched wavefront owns one, >= 2 kLbfgsR vectors)
+constexpr int kSeparableBlocks = 256 * 16, kGeneralBlocks = 256 * 8;
+inline int stream_grid(int64_t C, int64_t max_blocks)
+{
+    int64_t b = (C + kStreamWaves - 1) / kStreamWaves;
+    if (b > max_blocks) b = max_blocks;
+    return (int)(b < 1 ? 1 : b);
+}
+inline int optimum_grid(const DevState &s) { return stream_grid(s.C, s.nslots / kStreamWaves); }
+
+// ---- GLM shapes (idhmc_logistic.hip) ---------------------------------------------------------------
 // NUTS gradients on the matrix cores (GlmCoop: logistic regression, GLM) at this padded length, with `aux` auxiliary coordinates
 // and a shared (or pooled) metric or a per-chain one
 bool glm_coop(int nch, int aux, bool shared);
 size_t glm_nuts_lds_bytes(int nch, bool shared, int aux);   // dynamic LDS of a GLM's NUTS kernel
 
 // ---- launchers (idhmc_kernels.hip / idhmc_nuts.hip) ------------------------------------------------
-hipError_t launch_eval(const DevState &s, hipStream_t st);                 // lq, grad from q
-hipError_t launch_random_position(const DevState &s, hipStream_t st);
+hipError_t launch_eval(const DevState &s, int random_q, hipStream_t st);   // lq, grad from q; random_q: q ~ U[-2,2)^D first
 hipError_t launch_refresh(const DevState &s, uint32_t iter, hipStream_t st);   // p = W randn; pi
 hipError_t launch_logdensity(const DevState &s, hipStream_t st);               // pi from (lq, p)
 // regrad != 0 (separable densities, single step): the gradient array is neither read nor written and goes stale;

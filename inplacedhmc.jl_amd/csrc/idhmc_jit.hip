@@ -1,5 +1,5 @@
 // idhmc_jit.hip -- user-supplied densities (IDHMC_MODEL_CUSTOM): the user's HIP source is compiled with hipRTC
-// against the engine's own kernel templates (idhmc_general.hpp, idhmc_nuts_kernel.hpp), so a custom density
+// against the engine's own kernel templates (idhmc_stream.hpp, idhmc_optimum.hpp, idhmc_nuts_kernel.hpp), so a custom density
 // runs through exactly the code paths of the built-in general density (dense MVN): evaluation, fused
 // leapfrog, initial-stepsize search and the NUTS transition.  This is the device form of the reference's
 // downward boundary, logdensity_and_gradient!(grad, model, q, sptr) (src/kinetic_energy.jl:73).
@@ -54,13 +54,13 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
     const bool glm = s.model == IDHMC_MODEL_GLM;
     std::string src;
     if (!glm) {
-        src = "#define IDHMC_JIT_USER_DENSITY 1\n#include \"idhmc_general.hpp\"\n#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n"
+        src = "#define IDHMC_JIT_USER_DENSITY 1\n#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n"
               "namespace idhmc {\n#line 1 \"user_density.hip\"\n";
         src += source;
         src += "\n}\n";
     } else {
         // the user's glm_observation as the observation policy of idhmc_glm.hpp, K data columns
-        src = "#include \"idhmc_general.hpp\"\n#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n#include \"idhmc_glm.hpp\"\n"
+        src = "#include \"idhmc_nuts_kernel.hpp\"\n#include \"idhmc_optimum.hpp\"\n#include \"idhmc_glm.hpp\"\n"
               "namespace idhmc {\n#line 1 \"user_glm.hip\"\n";
         src += source;
         src += "\n#line 1 \"idhmc_glm_policy\"\nstruct UserGlmObs {\n    static constexpr int K = " + std::to_string(glm_k) +
@@ -80,11 +80,11 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
     const std::string model = glm ? "idhmc::GlmWave<" + n + ", idhmc::UserGlmObs>" : "idhmc::JitModel<" + n + ">";
     const std::string nuts_model = glm && glm_coop(s.nch, glm_a, shared) ? "idhmc::GlmCoop<" + n + ", idhmc::UserGlmObs>" : model;
     constexpr int kKernels = 5;
-    const std::string names[kKernels] = {"idhmc::k_eval_general<" + n + ", " + model + ">",
-                                  "idhmc::k_leapfrog_general<" + n + ", " + model + ">",
-                                  "idhmc::k_stepsize_general<" + n + ", " + model + ">",
+    const std::string names[kKernels] = {"idhmc::k_eval<" + n + ", " + model + ">",
+                                  "idhmc::k_leapfrog<" + n + ", " + model + ">",
+                                  "idhmc::k_stepsize_search<" + n + ", " + model + ">",
                                   "idhmc::k_nuts<" + n + ", " + nuts_model + ", " + (shared ? "true" : "false") + ">",
-                                  "idhmc::k_local_optimum_general<" + n + ", " + model + ">"};
+                                  "idhmc::k_local_optimum<" + n + ", " + model + ">"};
     for (const std::string &nm : names) hiprtcAddNameExpression(prog, nm.c_str());
 
     hipDeviceProp_t prop;
@@ -170,47 +170,46 @@ static hipError_t launch_packed(hipFunction_t f, int grid, int block, size_t lds
     return hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, (unsigned)lds, st, nullptr, extra);
 }
 
-static int general_grid_host(int64_t C)
-{
-    int64_t b = (C + 3) / 4;
-    if (b > 256 * 8) b = 256 * 8;
-    return (int)(b < 1 ? 1 : b);
-}
-
-hipError_t launch_eval_jit(const DevState &s, int random_q, hipStream_t st)
+static hipError_t launch_eval_jit(const DevState &s, int random_q, hipStream_t st)
 {
     const JitModule *m = static_cast<const JitModule *>(s.jit);
     if (!m) return hipErrorInvalidValue;
     struct { DevState s; int r; } a{s, random_q};
-    return launch_packed(m->f_eval, general_grid_host(s.C), 256, 0, st, a);
+    return launch_packed(m->f_eval, stream_grid(s.C, kGeneralBlocks), kStreamWaves * 64, 0, st, a);
 }
-hipError_t launch_leapfrog_jit(const DevState &s, double eps, int own, int n_steps, hipStream_t st)
+static hipError_t launch_leapfrog_jit(const DevState &s, double eps, int own, int n_steps, int, int, hipStream_t st)
 {
     const JitModule *m = static_cast<const JitModule *>(s.jit);
     if (!m) return hipErrorInvalidValue;
     struct { DevState s; double eps; int own; int n; } a{s, eps, own, n_steps};
-    return launch_packed(m->f_leapfrog, general_grid_host(s.C), 256, 0, st, a);
+    return launch_packed(m->f_leapfrog, stream_grid(s.C, kGeneralBlocks), kStreamWaves * 64, 0, st, a);
 }
-hipError_t launch_stepsize_search_jit(const DevState &s, hipStream_t st)
+static hipError_t launch_stepsize_search_jit(const DevState &s, hipStream_t st)
 {
     const JitModule *m = static_cast<const JitModule *>(s.jit);
     if (!m) return hipErrorInvalidValue;
     struct { DevState s; } a{s};
-    return launch_packed(m->f_stepsize, general_grid_host(s.C), 256, 0, st, a);
+    return launch_packed(m->f_stepsize, stream_grid(s.C, kGeneralBlocks), kStreamWaves * 64, 0, st, a);
 }
-hipError_t launch_local_optimum_jit(const DevState &s, double penalty, int iterations, int grid, hipStream_t st)
+static hipError_t launch_local_optimum_jit(const DevState &s, double penalty, int iterations, hipStream_t st)
 {
     const JitModule *m = static_cast<const JitModule *>(s.jit);
     if (!m) return hipErrorInvalidValue;
     struct { DevState s; double penalty; int iterations; } a{s, penalty, iterations};
-    return launch_packed(m->f_optimum, grid, 256, 0, st, a);
+    return launch_packed(m->f_optimum, optimum_grid(s), kStreamWaves * 64, 0, st, a);
 }
-hipError_t launch_nuts_jit(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
+static hipError_t launch_nuts_jit(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
 {
     const JitModule *m = static_cast<const JitModule *>(s.jit);
     if (!m) return hipErrorInvalidValue;
     struct { DevState s; uint32_t iter; uint32_t flags; } a{s, iter, flags};
     return launch_packed(m->f_nuts, grid, nuts_waves_per_block(s.nch, s.model, s.minv_stride == 0, s.lr_a) * 64, m->nuts_lds, st, a);
+}
+const Backend &jit_backend()
+{
+    static const Backend row = {launch_eval_jit, launch_leapfrog_jit, launch_stepsize_search_jit, launch_local_optimum_jit,
+                                launch_nuts_jit};
+    return row;
 }
 
 }  // namespace idhmc

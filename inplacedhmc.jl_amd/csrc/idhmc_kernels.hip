@@ -1,64 +1,10 @@
-// idhmc_kernels.hip -- streaming kernels: density evaluation, momentum refresh, fused leapfrog,
-// dual-averaging / metric / moment bookkeeping.  One chain per wavefront (see idhmc_device.hpp).
-#include "idhmc_device.hpp"
-#include "idhmc_internal.hpp"
+// idhmc_kernels.hip -- the separable densities' streaming kernels (idhmc_stream.hpp) and their single-step leapfrog, the momentum
+// refresh, dual-averaging / metric / moment bookkeeping, and the launchers that go through the table of backends.  One chain per
+// wavefront (see idhmc_device.hpp).
+#include "idhmc_stream.hpp"
 #include "idhmc_xchg.hpp"
 
 namespace idhmc {
-
-static inline int blocks_for(int64_t C, int waves_per_block, int max_blocks)
-{
-    int64_t b = (C + waves_per_block - 1) / waves_per_block;
-    if (b > max_blocks) b = max_blocks;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// evaluate_l! for every chain (reference src/kinetic_energy.jl:72-85)
-template <int NCH, class Model>
-__global__ __launch_bounds__(256) void k_eval(DevState s)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    Model mdl;
-    mdl.load(s.mu, s.tau, lane);
-    for (int64_t c = wave; c < s.C; c += nw) {
-        const Vec<NCH> q = vload<NCH>(s.q + c * s.L, lane);
-        Vec<NCH> g;
-        const double lq = eval_density<NCH>(mdl, q, g);
-        vstore<NCH>(s.g + c * s.L, lane, g);
-        if (lane == 0) s.lq[c] = lq;
-    }
-}
-
-// random_position! (reference src/warmup.jl:73): q ~ U[-2,2)^D, then evaluate
-template <int NCH, class Model>
-__global__ __launch_bounds__(256) void k_random_position(DevState s)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    Model mdl;
-    mdl.load(s.mu, s.tau, lane);
-    for (int64_t c = wave; c < s.C; c += nw) {
-        const RngKey key{s.k0, s.k1, s.first_chain + (uint32_t)c};
-        Vec<NCH> q, g;
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            const int pair = j * 64 + lane;
-            const u32x4 x = rng_draw(key, 0u, kStreamInitQ, (uint32_t)pair);
-            const double u0 = u01(x.x, x.y), u1 = u01(x.z, x.w);
-            q.c[j].x = (2 * pair < s.D) ? dfma(4.0, u0, -2.0) : 0.0;
-            q.c[j].y = (2 * pair + 1 < s.D) ? dfma(4.0, u1, -2.0) : 0.0;
-        }
-        const double lq = eval_density<NCH>(mdl, q, g);
-        vstore<NCH>(s.q + c * s.L, lane, q);
-        vstore<NCH>(s.g + c * s.L, lane, g);
-        if (lane == 0) s.lq[c] = lq;
-    }
-}
 
 // rand_p! (reference src/kinetic_energy.jl:63) + pi = logdensity(H, z) (:107-112)
 template <int NCH>
@@ -83,37 +29,7 @@ __global__ __launch_bounds__(256) void k_refresh(DevState s, uint32_t iter, int 
     }
 }
 
-// Fused leapfrog (reference src/kinetic_energy.jl:126-163), n_steps steps per launch.
-// HBM traffic per chain and launch: read q, p, grad, write q', p', grad' = 6*L*8 bytes
-// (M^-1, mu, tau are L2-resident: 3*L*8 bytes shared by all chains).
-template <int NCH, class Model>
-__global__ __launch_bounds__(256) void k_leapfrog(DevState s, double eps_arg, int own_eps, int n_steps)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    Model mdl;
-    mdl.load(s.mu, s.tau, lane);
-    for (int64_t c = wave; c < s.C; c += nw) {
-        const int64_t off = c * s.L;
-        Vec<NCH> q = vload<NCH>(s.q + off, lane);
-        Vec<NCH> p = vload<NCH>(s.p + off, lane);
-        Vec<NCH> g = vload<NCH>(s.g + off, lane);
-        const Vec<NCH> minv = vload<NCH>(s.minv + c * s.minv_stride, lane);
-        const double eps = own_eps ? s.eps[c] : eps_arg;
-        double lq = 0.0, K = 0.0;
-        for (int it = 0; it < n_steps; ++it) leapfrog_step<NCH>(mdl, minv, eps, q, p, g, lq, K);
-        vstore<NCH>(s.q + off, lane, q);
-        vstore<NCH>(s.p + off, lane, p);
-        vstore<NCH>(s.g + off, lane, g);
-        if (lane == 0) {
-            s.lq[c] = lq;
-            s.pi[c] = phase_logdensity(lq, K);
-        }
-    }
-}
-
-// Single-step form of the same kernel, the HBM-bound headline path (BASELINE.json configs[1]).
+// Single-step form of k_leapfrog (idhmc_stream.hpp), the HBM-bound headline path (BASELINE.json configs[1]).
 // VAR bit 0: issue every load of the chain (q, p, grad: 3 KiB per chunk from HBM; M^-1, mu, tau from L2)
 //            before the first store, so one wave keeps 24 KiB of HBM reads in flight (2 waves/SIMD);
 //            otherwise chunk-by-chunk at 4 waves/SIMD.
@@ -490,60 +406,15 @@ __global__ void k_status_max(DevState s, int32_t *out)
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------
-#define IDHMC_LAUNCH_SEPARABLE(KERNEL, GRID, ...)                                                     \
-    IDHMC_DISPATCH_NCH(s.nch, {                                                                       \
-        if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)                                                      \
-            hipLaunchKernelGGL((KERNEL<NCH, IsoGaussian<NCH>>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__); \
-        else if (s.model == IDHMC_MODEL_DIAG_GAUSSIAN)                                                \
-            hipLaunchKernelGGL((KERNEL<NCH, DiagGaussian<NCH>>), dim3(GRID), dim3(256), 0, st, __VA_ARGS__); \
-        else                                                                                          \
-            return hipErrorNotSupported;                                                              \
-    })
 
-// streaming kernels: 4 chains per 256-thread block, capped so that every CU keeps several blocks
-static constexpr int kMaxStreamBlocks = 256 * 16;
-
-hipError_t launch_eval_dense(const DevState &s, hipStream_t st);
-hipError_t launch_leapfrog_dense(const DevState &s, double eps, int own, int n_steps, int mfma, hipStream_t st);
-hipError_t launch_random_position_dense(const DevState &s, hipStream_t st);
-
-hipError_t launch_eval(const DevState &s, hipStream_t st)
+static hipError_t launch_eval_separable(const DevState &s, int random_q, hipStream_t st)
 {
-    if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_eval_dense(s, st);
-    if (s.model == IDHMC_MODEL_CUSTOM || s.model == IDHMC_MODEL_GLM) return launch_eval_jit(s, 0, st);
-    if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_eval_logistic(s, 0, st);
-    const int grid = blocks_for(s.C, 4, kMaxStreamBlocks);
-    IDHMC_LAUNCH_SEPARABLE(k_eval, grid, s);
-    return hipGetLastError();
+    return IDHMC_SEPARABLE(launch_eval_t, s, random_q, st);
 }
-hipError_t launch_random_position(const DevState &s, hipStream_t st)
+static hipError_t launch_leapfrog_separable(const DevState &s, double eps, int own, int n_steps, int regrad, int, hipStream_t st)
 {
-    if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_random_position_dense(s, st);
-    if (s.model == IDHMC_MODEL_CUSTOM || s.model == IDHMC_MODEL_GLM) return launch_eval_jit(s, 1, st);
-    if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_eval_logistic(s, 1, st);
-    const int grid = blocks_for(s.C, 4, kMaxStreamBlocks);
-    IDHMC_LAUNCH_SEPARABLE(k_random_position, grid, s);
-    return hipGetLastError();
-}
-hipError_t launch_refresh(const DevState &s, uint32_t iter, hipStream_t st)
-{
-    const int grid = blocks_for(s.C, 4, kMaxStreamBlocks);
-    IDHMC_DISPATCH_NCH(s.nch, hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(256), 0, st, s, iter, 1));
-    return hipGetLastError();
-}
-hipError_t launch_logdensity(const DevState &s, hipStream_t st)
-{
-    const int grid = blocks_for(s.C, 4, kMaxStreamBlocks);
-    IDHMC_DISPATCH_NCH(s.nch, hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(256), 0, st, s, 0u, 0));
-    return hipGetLastError();
-}
-hipError_t launch_leapfrog(const DevState &s, double eps, int own, int n_steps, int regrad, int dense_mfma, hipStream_t st)
-{
-    if (s.model == IDHMC_MODEL_DENSE_MVN) return launch_leapfrog_dense(s, eps, own, n_steps, dense_mfma, st);
-    if (s.model == IDHMC_MODEL_CUSTOM || s.model == IDHMC_MODEL_GLM) return launch_leapfrog_jit(s, eps, own, n_steps, st);
-    if (s.model == IDHMC_MODEL_LOGISTIC_REGRESSION) return launch_leapfrog_logistic(s, eps, own, n_steps, st);
     if (n_steps == 1) {
-        const int grid = blocks_for(s.C, 4, 1 << 30);     // one block per four chains, uncapped
+        const int grid = stream_grid(s.C, 1 << 30);       // one block per four chains, uncapped
         // measured on MI355X (65 536 chains x 1024): diag 6.03 TB/s with 3, iso 5.89 TB/s with 2
         int var = (s.model == IDHMC_MODEL_ISO_GAUSSIAN) ? 2 : 3;
         if (regrad) var = 7;
@@ -563,8 +434,47 @@ hipError_t launch_leapfrog(const DevState &s, double eps, int own, int n_steps, 
         }
         return hipGetLastError();
     }
-    const int grid = blocks_for(s.C, 4, kMaxStreamBlocks);
-    IDHMC_LAUNCH_SEPARABLE(k_leapfrog, grid, s, eps, own, n_steps);
+    return IDHMC_SEPARABLE(launch_leapfrog_t, s, eps, own, n_steps, st);
+}
+const Backend &separable_backend()
+{
+    static const Backend row = {launch_eval_separable, launch_leapfrog_separable, launch_stepsize_search_separable,
+                                launch_local_optimum_separable, launch_nuts_separable};
+    return row;
+}
+
+// each: the common prologue, then the model's backend
+hipError_t launch_eval(const DevState &s, int random_q, hipStream_t st)
+{
+    const Backend *b = backend(s.model);
+    return b ? b->eval(s, random_q, st) : hipErrorNotSupported;
+}
+hipError_t launch_leapfrog(const DevState &s, double eps, int own, int n_steps, int regrad, int dense_mfma, hipStream_t st)
+{
+    const Backend *b = backend(s.model);
+    return b ? b->leapfrog(s, eps, own, n_steps, regrad, dense_mfma, st) : hipErrorNotSupported;
+}
+hipError_t launch_stepsize_search(const DevState &s, hipStream_t st)
+{
+    const Backend *b = backend(s.model);
+    return b ? b->stepsize_search(s, st) : hipErrorNotSupported;
+}
+// FindLocalOptimum (src/warmup.jl:137-187), idhmc_optimum.hpp
+hipError_t launch_local_optimum(const DevState &s, double penalty, int iterations, hipStream_t st)
+{
+    const Backend *b = backend(s.model);
+    return b ? b->local_optimum(s, penalty, iterations, st) : hipErrorNotSupported;
+}
+hipError_t launch_refresh(const DevState &s, uint32_t iter, hipStream_t st)
+{
+    const int grid = stream_grid(s.C, kSeparableBlocks);
+    IDHMC_DISPATCH_NCH(s.nch, hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(256), 0, st, s, iter, 1));
+    return hipGetLastError();
+}
+hipError_t launch_logdensity(const DevState &s, hipStream_t st)
+{
+    const int grid = stream_grid(s.C, kSeparableBlocks);
+    IDHMC_DISPATCH_NCH(s.nch, hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(256), 0, st, s, 0u, 0));
     return hipGetLastError();
 }
 hipError_t launch_set_w(const DevState &s, hipStream_t st)
@@ -636,7 +546,6 @@ hipError_t launch_fill(double *p, double v, int64_t n, hipStream_t st)
     hipLaunchKernelGGL(k_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, v, n);
     return hipGetLastError();
 }
-__global__ void k_eps_from_global(DevState s);
 hipError_t launch_da_init(const DevState &s, hipStream_t st)
 {
     if (s.eps_mode == IDHMC_EPS_GLOBAL) {

@@ -1,10 +1,9 @@
 // idhmc_logistic.hip -- Bayesian logistic regression (IDHMC_MODEL_LOGISTIC_REGRESSION, idhmc_glm.hpp with Obs = LogisticObs):
-// ahead-of-time instantiation of the general-density kernels (idhmc_general.hpp, idhmc_optimum.hpp) with the per-wave form, and
+// ahead-of-time instantiation of the streaming kernels (idhmc_stream.hpp, idhmc_optimum.hpp) with the per-wave form, and
 // of the NUTS transition with the matrix-core form where it applies (L <= 256) and the per-wave form beyond.  A user's GLM
 // (IDHMC_MODEL_GLM) instantiates the same templates through hipRTC (idhmc_jit.hip) and takes its shape decisions from here.  The padded length is a power
 // of two (L = 128, 256, 512, 1024), as for the dense density.
 #include <type_traits>
-#include "idhmc_general.hpp"
 #include "idhmc_nuts_kernel.hpp"
 #include "idhmc_optimum.hpp"
 #include "idhmc_glm.hpp"
@@ -55,31 +54,7 @@ size_t glm_nuts_lds_bytes(int nch, bool shared, int aux)
     }
 }
 
-hipError_t launch_eval_logistic(const DevState &s, int random_q, hipStream_t st)
-{
-    IDHMC_DISPATCH_NCH_POW2(s.nch, hipLaunchKernelGGL((k_eval_general<NCH, LogisticRegression<NCH>>), dim3(general_grid(s.C)),
-                                                      dim3(kGeneralWaves * 64), 0, st, s, random_q));
-    return hipGetLastError();
-}
-hipError_t launch_leapfrog_logistic(const DevState &s, double eps, int own, int n_steps, hipStream_t st)
-{
-    IDHMC_DISPATCH_NCH_POW2(s.nch, hipLaunchKernelGGL((k_leapfrog_general<NCH, LogisticRegression<NCH>>), dim3(general_grid(s.C)),
-                                                      dim3(kGeneralWaves * 64), 0, st, s, eps, own, n_steps));
-    return hipGetLastError();
-}
-hipError_t launch_stepsize_search_logistic(const DevState &s, hipStream_t st)
-{
-    IDHMC_DISPATCH_NCH_POW2(s.nch, hipLaunchKernelGGL((k_stepsize_general<NCH, LogisticRegression<NCH>>), dim3(general_grid(s.C)),
-                                                      dim3(kGeneralWaves * 64), 0, st, s));
-    return hipGetLastError();
-}
-hipError_t launch_local_optimum_logistic(const DevState &s, double penalty, int iterations, hipStream_t st)
-{
-    IDHMC_DISPATCH_NCH_POW2(s.nch, hipLaunchKernelGGL((k_local_optimum_general<NCH, LogisticRegression<NCH>>), dim3(optimum_grid(s)),
-                                                      dim3(kOptimumWaves * 64), 0, st, s, penalty, iterations));
-    return hipGetLastError();
-}
-hipError_t launch_nuts_logistic(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
+static hipError_t launch_nuts_logistic(const DevState &s, uint32_t iter, uint32_t flags, int grid, hipStream_t st)
 {
     const bool shared = s.minv_stride == 0;
     IDHMC_DISPATCH_NCH_POW2(s.nch, {
@@ -92,6 +67,17 @@ hipError_t launch_nuts_logistic(const DevState &s, uint32_t iter, uint32_t flags
         }
     });
     return hipErrorInvalidValue;
+}
+static hipError_t launch_leapfrog_logistic(const DevState &s, double eps, int own, int n_steps, int, int, hipStream_t st)
+{
+    return launch_leapfrog_t<LogisticRegression>(s, eps, own, n_steps, st);
+}
+const Backend &logistic_backend()
+{
+    static const Backend row = {launch_eval_t<LogisticRegression>, launch_leapfrog_logistic,
+                                launch_stepsize_search_t<LogisticRegression>, launch_local_optimum_t<LogisticRegression>,
+                                launch_nuts_logistic};
+    return row;
 }
 
 }  // namespace idhmc

@@ -1,7 +1,7 @@
-// idhmc_nuts_kernel.hpp -- one NUTS transition per chain, one chain per wavefront, and the initial-stepsize
-// search (kernel templates; instantiated ahead of time for the built-in densities in idhmc_nuts.hip and at
+// idhmc_nuts_kernel.hpp -- one NUTS transition per chain, one chain per wavefront (kernel template; instantiated ahead of time
+// for the built-in densities in idhmc_nuts.hip, idhmc_nuts_sep.inc and idhmc_logistic.hip and at
 // run time, through hipRTC, for a user-supplied density).  Replaces reference sample_tree / sample_trajectory / adjacent_tree / leaf / is_turning /
-// combine_* (src/NUTS.jl:18-264, src/tree.jl:131-444) and find_initial_stepsize (src/stepsize.jl:51-164).
+// combine_* (src/NUTS.jl:18-264, src/tree.jl:131-444).
 //
 // The reference builds each doubling by recursion (adjacent_tree calls itself for the left and right
 // half, src/tree.jl:335-346) with a bitmask arena for the live vectors (src/tree.jl:16-121).  Here each
@@ -1061,78 +1061,6 @@ void k_nuts(DevState s, uint32_t iter0, uint32_t flags)
         if (x) {
             if (threadIdx.x == 39) atomicAdd(s.total_steps, x);
             else if (s.diag.counters) atomicAdd(s.diag.counters + threadIdx.x, x);
-        }
-    }
-}
-
-// ---- find_initial_stepsize (src/stepsize.jl:111-126,150-164) per chain ------------------------------
-// A(eps) = exp(logdensity(H, leapfrog(z, eps)) - logdensity(H, z)); only scalars leave the registers.
-template <int NCH, class Model>
-IDHMC_DEV double local_ratio(const Model &mdl, const Vec<NCH> &minv, const Vec<NCH> &q, const Vec<NCH> &p,
-                             const Vec<NCH> &g, double eps, double target)
-{
-    Vec<NCH> q1 = q, p1 = p, g1 = g;
-    double lq, K;
-    leapfrog_step<NCH>(mdl, minv, eps, q1, p1, g1, lq, K);
-    return dexp(phase_logdensity(lq, K) - target);
-}
-
-template <int NCH, class Model>
-__global__ __launch_bounds__(256) void k_stepsize_search(DevState s)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    Model mdl;
-    mdl.load(s.mu, s.tau, lane);
-    for (int64_t c = wave; c < s.C; c += nw) {
-        const int64_t off = c * s.L;
-        const Vec<NCH> q = vload<NCH>(s.q + off, lane);
-        const Vec<NCH> p = vload<NCH>(s.p + off, lane);
-        const Vec<NCH> g = vload<NCH>(s.g + off, lane);
-        const Vec<NCH> minv = vload<NCH>(s.minv + c * s.minv_stride, lane);
-        const double target = phase_logdensity(s.lq[c], kinetic_energy<NCH>(minv, p));   // :151
-        int rc = 0;
-        double e0 = s.ss_eps0, result = s.ss_eps0;
-        if (!dfinite(target)) {
-            rc = IDHMC_ERR_NONFINITE_START;                                              // :152-153
-        } else {
-            double A0 = local_ratio<NCH>(mdl, minv, q, p, g, e0, target);                // :113
-            if (!(s.ss_a_min <= A0 && A0 <= s.ss_a_max)) {                               // :114
-                // find_crossing_stepsize :51-72
-                const double sg = A0 > s.ss_a_max ? 1.0 : -1.0;
-                const double a = A0 > s.ss_a_max ? s.ss_a_max : s.ss_a_min;
-                const double Cf = sg < 0.0 ? 1.0 / s.ss_C : s.ss_C;
-                double e1 = e0, A1 = A0;
-                bool found = false;
-                for (int it = 0; it < s.ss_maxiter_crossing; ++it) {
-                    const double e = e0 * Cf;
-                    const double Ae = local_ratio<NCH>(mdl, minv, q, p, g, e, target);
-                    if (sg * (Ae - a) <= 0.0) { e1 = e; A1 = Ae; found = true; break; }
-                    e0 = e; A0 = Ae;
-                }
-                if (!found) {
-                    rc = IDHMC_ERR_STEPSIZE_SEARCH;                                      // :71
-                } else if (s.ss_a_min <= A1 && A1 <= s.ss_a_max) {
-                    result = e1;                                                         // :118
-                } else {
-                    double lo = e0, hi = e1;                                             // :120-124
-                    if (!(e0 < e1)) { lo = e1; hi = e0; }
-                    found = false;
-                    for (int it = 0; it < s.ss_maxiter_bisect; ++it) {                   // bisect_stepsize :83-102
-                        const double em = 0.5 * (lo + hi);
-                        const double Am = local_ratio<NCH>(mdl, minv, q, p, g, em, target);
-                        if (s.ss_a_min <= Am && Am <= s.ss_a_max) { result = em; found = true; break; }
-                        else if (Am < s.ss_a_min) hi = em;
-                        else lo = em;
-                    }
-                    if (!found) rc = IDHMC_ERR_STEPSIZE_SEARCH;                          // :101
-                }
-            }
-        }
-        if (lane == 0) {
-            s.eps[c] = result;
-            if (rc) s.status[c] = rc;
         }
     }
 }

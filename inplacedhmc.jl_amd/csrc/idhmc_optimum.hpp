@@ -14,13 +14,11 @@
 // one slot is always free, so a new pair is formed in place and simply not committed when it fails the
 // curvature test; rho, alpha and the loop state in SGPR-uniform scalars.
 #pragma once
-#include "idhmc_device.hpp"
-#include "idhmc_internal.hpp"
+#include "idhmc_stream.hpp"
 
 namespace idhmc {
 
 constexpr int kLbfgsM = 5, kLbfgsR = kLbfgsM + 1;
-constexpr int kOptimumWaves = 4;
 
 template <int NCH>
 IDHMC_DEV double vdot(const Vec<NCH> &a, const Vec<NCH> &b)
@@ -71,14 +69,6 @@ IDHMC_DEV void ring_set(double (&a)[kLbfgsR], int i, double v)
 {
 #pragma unroll
     for (int u = 0; u < kLbfgsR; ++u) a[u] = (i == u) ? v : a[u];
-}
-template <int NCH, class Model>
-IDHMC_DEV double density_eval(const Model &mdl, const Vec<NCH> &q, Vec<NCH> &g)
-{
-    double lq;
-    if constexpr (Model::kSeparable) lq = eval_density<NCH>(mdl, q, g);
-    else lq = mdl.grad(q, g);
-    return dfinite(lq) ? lq : -kInf;                    // evaluate_l!, src/kinetic_energy.jl:80-84
 }
 
 template <int NCH, class Model>
@@ -164,14 +154,7 @@ IDHMC_DEV void local_optimum_body(const DevState &s, Model &mdl, double penalty,
             }
             if (dfinite(lq)) { rc = 0; break; }                                       // :168
             // random_position! with this attempt's draws, evaluate, double the penalty (:169-171)
-#pragma unroll
-            for (int j = 0; j < NCH; ++j) {
-                const int pair = j * 64 + lane;
-                const u32x4 u = rng_draw(key, attempt + 1u, kStreamInitQ, (uint32_t)pair);
-                const double u0 = u01(u.x, u.y), u1 = u01(u.z, u.w);
-                x.c[j].x = (2 * pair < s.D) ? dfma(4.0, u0, -2.0) : 0.0;
-                x.c[j].y = (2 * pair + 1 < s.D) ? dfma(4.0, u1, -2.0) : 0.0;
-            }
+            x = uniform_position<NCH>(key, attempt + 1u, lane, s.D);
             lq = density_eval<NCH>(mdl, x, gl);
             lam += lam;
         }
@@ -184,33 +167,28 @@ IDHMC_DEV void local_optimum_body(const DevState &s, Model &mdl, double penalty,
     }
 }
 
-// separable densities: parameters in registers
+// a separable density's parameters in registers, a general density's LDS vector per wavefront (idhmc_stream.hpp)
 template <int NCH, class Model>
-__global__ __launch_bounds__(kOptimumWaves * 64) void k_local_optimum(DevState s, double penalty, int iterations)
+__global__ __launch_bounds__(kStreamWaves * 64) void k_local_optimum(DevState s, double penalty, int iterations)
 {
+    IDHMC_WAVE_LDS_VECTOR(lds_vec);
     Model mdl;
-    mdl.load(s.mu, s.tau, threadIdx.x & 63);
-    double *hist = s.arena + ((int64_t)blockIdx.x * kOptimumWaves + (threadIdx.x >> 6)) * s.arena_stride;
-    local_optimum_body<NCH, Model>(s, mdl, penalty, iterations, hist);
-}
-// general densities: one LDS vector per wavefront
-template <int NCH, class Model>
-__global__ __launch_bounds__(kOptimumWaves * 64) void k_local_optimum_general(DevState s, double penalty, int iterations)
-{
-    __shared__ __attribute__((aligned(16))) double dshare[kOptimumWaves][128 * NCH];
-    Model mdl;
-    mdl.init(s, dshare[threadIdx.x >> 6], threadIdx.x & 63);
-    double *hist = s.arena + ((int64_t)blockIdx.x * kOptimumWaves + (threadIdx.x >> 6)) * s.arena_stride;
+    density_setup(mdl, s, lds_vec, threadIdx.x & 63);
+    double *hist = s.arena + ((int64_t)blockIdx.x * kStreamWaves + (threadIdx.x >> 6)) * s.arena_stride;
     local_optimum_body<NCH, Model>(s, mdl, penalty, iterations, hist);
 }
 
-// every launched wavefront owns one arena slot (>= 2 kLbfgsR vectors: the arena holds at least 12)
-inline int optimum_grid(const DevState &s)
+#ifndef __HIPCC_RTC__
+template <template <int> class Model>
+static hipError_t launch_local_optimum_t(const DevState &s, double penalty, int iterations, hipStream_t st)
 {
-    int64_t b = (s.C + kOptimumWaves - 1) / kOptimumWaves;
-    const int64_t have = s.nslots / kOptimumWaves;
-    if (b > have) b = have;
-    return (int)(b < 1 ? 1 : b);
+    return dispatch_nch<Model>(s.nch, [&](auto n) {
+        constexpr int NCH = decltype(n)::value;
+        hipLaunchKernelGGL((k_local_optimum<NCH, Model<NCH>>), dim3(optimum_grid(s)), dim3(kStreamWaves * 64), 0, st, s, penalty,
+                           iterations);
+        return hipGetLastError();
+    });
 }
+#endif
 
 }  // namespace idhmc

@@ -1,6 +1,6 @@
 """Every option reaches every kernel that reads it: the option sets of tests/test_options_cpu.py on the device, against the CPU oracle
 under the same options -- which that module holds against the numpy restatement, and shows to differ from the oracle under the default
-options.  The stepsize search (k_stepsize_search for the separable Gaussians, stepsize_general_body for every other model) with
+options.  The stepsize search (k_stepsize_search: the separable Gaussians' instantiations and those of every other model) with
 non-default a_min, a_max, eps0 and C and with both of its failures; dual averaging with non-default delta, gamma, kappa and t0 in the
 NUTS kernel's epilogue (per-chain stepsizes, one launch per transition and fused) and in k_da_adapt_global; stepsize_search = 0,
 eps_init and adapt_metric = 0 in mcmc_with_warmup.  min_delta is tests/test_gpu_deep_trees.py's.  Every comparison is of bits."""

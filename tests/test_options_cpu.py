@@ -37,9 +37,9 @@ FAILURE_SETS = {
 SEARCH_C = 16
 # model -> (problem of tests/test_deep_trees_cpu.py or a Gaussian, the decades over which the 16 starts are scaled)
 SEARCH_MODELS = {
-    "iso8": ("iso", 8, (-2.0, 4.0)),                       # k_stepsize_search
-    "diag130": ("diag", 130, (-2.0, 4.0)),                 # k_stepsize_search, two chunks
-    "custom128": ("problem", "custom128", (-2.0, 1.0)),    # stepsize_general_body from here on
+    "iso8": ("iso", 8, (-2.0, 4.0)),                       # k_stepsize_search of a separable density
+    "diag130": ("diag", 130, (-2.0, 4.0)),                 # the same, two chunks
+    "custom128": ("problem", "custom128", (-2.0, 1.0)),    # k_stepsize_search of a general density from here on
     "logistic_mc128": ("problem", "logistic_mc128", (-2.0, 2.0)),
     "glm_responses": ("problem", "glm_responses", (-2.0, 2.0)),
     "dense_coop128": ("problem", "dense_coop128", (-2.0, 4.0)),

@@ -5,12 +5,13 @@ usage: isa_diff.py DIR_A DIR_B     (each holds NAME.s made with the Makefile's f
 
 For every function that both sides define, the instruction text (label to .Lfunc_end) and, for a kernel, its .amdhsa_kernel descriptor
 block and the compiler's resource figures must be equal after the numbers of local labels are taken out (.LBB<n>_ -- also where a loop comment names it as BB<n>_ --, .Ltmp<n>, and the per-expansion suffix of the
-inline-assembly labels .Lnwi_*<n>): those number the functions and inline-assembly expansions of a translation unit, nothing else.
+inline-assembly labels .Lnwi_*<n>; the padding between such a label and its comment): those number the functions and inline-assembly expansions of a translation unit, nothing else.
 Prints one line per file and the functions that differ or exist on one side only; exit status 1 if a common function differs."""
 import os, re, subprocess, sys
 
 def normal(line):
     line = re.sub(r"(\.L|\b)BB\d+_", r"\1BB_", line.rstrip())      # .LBB<n>_<k>, and BB<n>_<k> in the compiler's loop comments
+    line = re.sub(r"^(\.LBB_\d+:) +;", r"\1 ;", line)              # the comment's column moves with the digits taken out
     line = re.sub(r"\.Ltmp\d+", ".Ltmp", line)
     return re.sub(r"(\.Lnwi_[a-z]+)\d+", r"\1", line)
 
@@ -63,7 +64,7 @@ def main(a, b):
         gone, new = [n for n in fa if n not in fb], [n for n in fb if n not in fa]
         lines = [len(fa[n]) for n in common if " " not in n]
         print("%s: %d functions, descriptors and resource blocks compared (functions of %d to %d lines), %d identical, %d differ, %d only in A, %d only in B" % (
-            f, len(common), min(lines), max(lines), len(common) - len(differ), len(differ), len(gone), len(new)))
+            f, len(common), min(lines, default=0), max(lines, default=0), len(common) - len(differ), len(differ), len(gone), len(new)))
         for tag, names in (("differs", differ), ("only in A", gone), ("only in B", new)):
             for d in demangle([n for n in names if tag == "differs" or " " not in n]):     # a missing function: one line, not three
                 print("    %s: %s" % (tag, d))
