@@ -137,8 +137,9 @@ enum {
  * bits.  For one chain every operation is the one a single-response context with Y[g / chains_per_response] performs: the draws are
  * bit-identical to that context's.  The matrix-core form takes 16 chains of any responses per tile and needs no further LDS:
  * idhmc_glm_form is what it is for the same (L, A, metric) with one response.  Stepsize and metric are per chain (or the fixed
- * SHARED metric); the statistics pooled over chains (IDHMC_EPS_GLOBAL, IDHMC_METRIC_POOLED) would mix posteriors and are refused
- * with M > 1.  The diagnostics counters stay context-wide. */
+ * SHARED metric) or pooled over the chains_per_response chains of each response (IDHMC_EPS_PER_RESPONSE,
+ * IDHMC_METRIC_PER_RESPONSE, below); the statistics pooled over every chain of the context (IDHMC_EPS_GLOBAL, IDHMC_METRIC_POOLED)
+ * would mix posteriors and are refused with M > 1.  The diagnostics counters stay context-wide. */
 enum {
     IDHMC_MODEL_ISO_GAUSSIAN = 0,   /* l(q) = -1/2 |q|^2                       */
     IDHMC_MODEL_DIAG_GAUSSIAN = 1,  /* l(q) = -1/2 sum tau_d (q_d - mu_d)^2    */
@@ -166,8 +167,8 @@ typedef struct {
  * DualAveraging(d, g, k, t0)        src/stepsize.jl:191-193
  * InitialStepsizeSearch(...)        src/stepsize.jl:29-37
  * default_warmup_stages(...)        src/warmup.jl:361-372                    */
-enum { IDHMC_EPS_PER_CHAIN = 0, IDHMC_EPS_GLOBAL = 1 };
-enum { IDHMC_METRIC_PER_CHAIN = 0, IDHMC_METRIC_SHARED = 1, IDHMC_METRIC_POOLED = 2 };
+enum { IDHMC_EPS_PER_CHAIN = 0, IDHMC_EPS_GLOBAL = 1, IDHMC_EPS_PER_RESPONSE = 2 };
+enum { IDHMC_METRIC_PER_CHAIN = 0, IDHMC_METRIC_SHARED = 1, IDHMC_METRIC_POOLED = 2, IDHMC_METRIC_PER_RESPONSE = 3 };
 typedef struct {
     int32_t max_depth;               /* 10 */
     double  min_delta;               /* -1000.0 */
@@ -181,7 +182,11 @@ typedef struct {
     double  eps_init;                /* initialization = (eps = ...), src/warmup.jl:87-92 */
     int32_t eps_mode;                /* IDHMC_EPS_PER_CHAIN = reference semantics (src/warmup.jl:284-303);
                                         IDHMC_EPS_GLOBAL = one dual-averaging state fed by the mean
-                                        acceptance of all chains of all ranks (the RCCL all-reduce hook) */
+                                        acceptance of all chains of all ranks (the RCCL all-reduce hook);
+                                        IDHMC_EPS_PER_RESPONSE (idhmc_create_glm_responses only) = one dual-averaging state per
+                                        response, fed by the mean acceptance of that response's chains_per_response chains: for
+                                        every response the bits of a single-response context in IDHMC_EPS_GLOBAL on the same
+                                        chains.  A context in this mode holds whole responses, so nothing is exchanged */
     int32_t metric_mode;             /* IDHMC_METRIC_PER_CHAIN = reference semantics (src/warmup.jl:309);
                                         IDHMC_METRIC_SHARED = one fixed M^-1 for all chains, never adapted;
                                         IDHMC_METRIC_POOLED = one M^-1 for all chains, adapted from the pooled windows of
@@ -189,7 +194,11 @@ typedef struct {
                                         of D + 1 doubles per window) -- an addition for the many-chain regime, like the
                                         global stepsize; not reference semantics.  Rank-count-invariant like the stepsize:
                                         partial sums are formed per segment of IDHMC_POOL_SEGMENT GLOBAL chain ids and
-                                        added in segment order on every rank (see idhmc_pool_partials) */
+                                        added in segment order on every rank (see idhmc_pool_partials);
+                                        IDHMC_METRIC_PER_RESPONSE (idhmc_create_glm_responses only) = one M^-1 per response,
+                                        adapted from the pooled windows of its chains with IDHMC_METRIC_POOLED's sums (the
+                                        same segments of global chain ids, the same order), stored in the per-chain layout:
+                                        D <= 512, whole responses per context, the bits of a single-response POOLED context */
     int32_t local_opt_iterations;    /* FindLocalOptimum stage of idhmc_mcmc_with_warmup (src/warmup.jl:137-150,
                                         362): 0 = skipped (default at this level), reference default 50 */
     int32_t leapfrog_grad_mode;      /* IDHMC_GRAD_RECOMPUTE (what idhmc_default_options sets): in idhmc_leapfrog(eps, 1) a
@@ -247,8 +256,10 @@ int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first
  * chain of global id g samples response g / chains_per_response.  With M = 1 the context is bit for bit the one idhmc_create_glm
  * makes.  Refused with IDHMC_ERR_BAD_ARG before the device is touched: everything idhmc_create_glm refuses (a non-finite value in any
  * of the M planes of Y), M < 1, chains_per_response < 1, first_chain_id + nchains > M * chains_per_response (a chain without a
- * response), M * K * n_pad > 2^27 (Y on the device takes at most 1 GiB, as X does), and M > 1 together with IDHMC_EPS_GLOBAL or
- * IDHMC_METRIC_POOLED. */
+ * response), M * K * n_pad > 2^27 (Y on the device takes at most 1 GiB, as X does), M > 1 together with IDHMC_EPS_GLOBAL or
+ * IDHMC_METRIC_POOLED, and, in IDHMC_EPS_PER_RESPONSE or IDHMC_METRIC_PER_RESPONSE, a first_chain_id or an nchains that is not a
+ * multiple of chains_per_response (a context in these modes holds whole responses; every other mode takes any shard) and, for the
+ * metric, D > 512.  Every other creation function refuses the two modes. */
 int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
                                const idhmc_glm_desc *glm, int64_t M, int64_t chains_per_response,
                                const idhmc_options *opt, uint64_t seed);
@@ -344,7 +355,8 @@ enum {
     IDHMC_T_USE_DIRECTIONS = 16,/* use injected directions (reference kwarg directions=...) */
     IDHMC_T_ACCUM_DIAG = 32     /* add the transition to the device-side diagnostics (idhmc_diag_reset first) */
 };
-/* Any other bit of `flags` is refused with IDHMC_ERR_BAD_ARG before anything is launched (by idhmc_nuts_transitions too).
+/* Any other bit of `flags` is refused with IDHMC_ERR_BAD_ARG before anything is launched (by idhmc_nuts_transitions too), and so
+ * is IDHMC_T_ADAPT_EPS on a context in IDHMC_EPS_PER_RESPONSE (the per-response stepsize adapts between transitions, in the drivers).
  * (Bit 30 is the test suite's: accepted only on a context created with IDHMC_TEST_XCC_MISMATCH=1 in the environment.) */
 int idhmc_nuts_transition(idhmc_ctx *ctx, uint32_t iter, uint32_t flags);
 /* n transitions of every chain, numbered iter, iter + 1, ..., iter + n - 1, in ONE launch (src/warmup.jl:288-305 and :324-330 run
@@ -353,7 +365,7 @@ int idhmc_nuts_transition(idhmc_ctx *ctx, uint32_t iter, uint32_t flags);
  * (transition, chain) pairs from one queue, so a chain's next transition starts as soon as its previous one is done and a
  * wavefront is free, instead of when the slowest tree of the whole launch is: with few chains per resident wavefront (configs[3]:
  * four) the end of every single-transition launch is a quarter of its time.  Only the records of the last transition are kept
- * (idhmc_get_tree_stats); IDHMC_T_USE_DIRECTIONS and IDHMC_T_KEEP_P are not allowed, nor IDHMC_T_ADAPT_EPS with the global stepsize (its exchange
+ * (idhmc_get_tree_stats); IDHMC_T_USE_DIRECTIONS and IDHMC_T_KEEP_P are not allowed, nor IDHMC_T_ADAPT_EPS with the global or the per-response stepsize (its exchange
  * sits between transitions).  If a chain raises the abort code no further transitions are started (nor any at all while the code
  * of an earlier launch is still set: the next driver call reports and clears it).
  * The library's own drivers (idhmc_tuning_stage, idhmc_mcmc) use it where no per-transition record leaves the device and the
@@ -518,6 +530,12 @@ int idhmc_total_steps(idhmc_ctx *ctx, int64_t *steps);
 int idhmc_time_leapfrog(idhmc_ctx *ctx, double eps, int32_t sweeps, float *ms_per_sweep);
 int idhmc_time_transitions(idhmc_ctx *ctx, int32_t n, uint32_t iter0, float *ms_total);      /* n idhmc_nuts_transition launches */
 int idhmc_time_transitions_fused(idhmc_ctx *ctx, int32_t n, uint32_t iter0, float *ms_total); /* one idhmc_nuts_transitions(n) launch */
+/* n times what the drivers enqueue between two adapting transitions to pool the acceptance and adapt the stepsize, bracketed by HIP
+ * events: in IDHMC_EPS_GLOBAL the exchange sum, the all-reduce (hook or communicator, if any), the adaptation and the broadcast (three
+ * launches), in IDHMC_EPS_PER_RESPONSE the one launch that does all of it per response; refused in IDHMC_EPS_PER_CHAIN, which adapts
+ * inside the transition kernel.  It feeds the acceptance rates of the last transition n times: the stepsizes and the dual-averaging
+ * state move as after n such transitions (call idhmc_da_init first; a measurement, not a step of any algorithm). */
+int idhmc_time_eps_adapt(idhmc_ctx *ctx, int32_t n, float *ms_total);
 /* 32 device counters: [0] = total leapfrog steps; [1] = pending abort code; [2..] = per-phase shader-cycle sums of the
  * NUTS kernel, filled only by the diagnostic build (-DIDHMC_STAMPS, tools/stamps.sh), zero otherwise. */
 int idhmc_debug_counters(idhmc_ctx *ctx, uint64_t *out32);

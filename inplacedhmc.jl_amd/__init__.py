@@ -7,7 +7,8 @@ computes on the CPU and nothing falls back to a CPU path.
 from ._lib import IdhmcError, LIB_PATH, load as load_library  # noqa: F401
 from .engine import (Engine, Model, IsoGaussian, DiagGaussian, DenseMVN, CustomDensity, LogisticRegression, GLM, default_options,  # noqa: F401
                      MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION, MODEL_GLM, MODEL_GLM_AUX,
-                     TREE_STATS_DTYPE, EPS_PER_CHAIN, EPS_GLOBAL, METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED, GRAD_STORE, GRAD_RECOMPUTE,
+                     TREE_STATS_DTYPE, EPS_PER_CHAIN, EPS_GLOBAL, EPS_PER_RESPONSE, METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED, METRIC_PER_RESPONSE,
+                     GRAD_STORE, GRAD_RECOMPUTE,
                      T_ADAPT_EPS, T_ACCUM_METRIC, T_ACCUM_MOMENTS, T_KEEP_P, T_USE_DIRECTIONS, T_ACCUM_DIAG,
                      XCHG_DOUBLES, XCHG_ACCEPT, XCHG_LOGEPS, POOL_SEGMENT, xchg_accumulate, xchg_mean,
                      ERR_BAD_ARG, ERR_HIP, ERR_EPS_UNDERFLOW, ERR_STEPSIZE_SEARCH, ERR_NONFINITE_START, ERR_NO_DEVICE, ERR_ALLOC,

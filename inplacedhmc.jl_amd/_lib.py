@@ -130,6 +130,7 @@ SYMBOLS = {
     "idhmc_time_leapfrog": (C.c_int, [_vp, _dbl, _i32, C.POINTER(C.c_float)]),
     "idhmc_time_transitions": (C.c_int, [_vp, _i32, _u32, C.POINTER(C.c_float)]),
     "idhmc_time_transitions_fused": (C.c_int, [_vp, _i32, _u32, C.POINTER(C.c_float)]),
+    "idhmc_time_eps_adapt": (C.c_int, [_vp, _i32, C.POINTER(C.c_float)]),
     "idhmc_debug_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 

@@ -329,6 +329,7 @@ int idhmc_nuts_transition(idhmc_ctx *c, uint32_t iter, uint32_t flags)
 {
     CTXCHK(c);
     if (int rc = check_flags(c, flags)) return rc;
+    if ((flags & IDHMC_T_ADAPT_EPS) && c->s.eps_mode == IDHMC_EPS_PER_RESPONSE) return fail(IDHMC_ERR_BAD_ARG, "the per-response stepsize adapts between transitions");
     return nuts_launch(c, iter, flags, 1);
 }
 int idhmc_nuts_transitions(idhmc_ctx *c, uint32_t iter, int32_t n, uint32_t flags)
@@ -339,6 +340,7 @@ int idhmc_nuts_transitions(idhmc_ctx *c, uint32_t iter, int32_t n, uint32_t flag
     if ((uint64_t)c->s.C * (uint64_t)n >= (1ull << 31)) return fail(IDHMC_ERR_BAD_ARG, "nchains * n must be below 2^31");
     if (flags & (IDHMC_T_USE_DIRECTIONS | IDHMC_T_KEEP_P)) return fail(IDHMC_ERR_BAD_ARG, "injected directions / a kept momentum are one transition's");
     if ((flags & IDHMC_T_ADAPT_EPS) && c->s.eps_mode == IDHMC_EPS_GLOBAL) return fail(IDHMC_ERR_BAD_ARG, "the global stepsize adapts between transitions");
+    if ((flags & IDHMC_T_ADAPT_EPS) && c->s.eps_mode == IDHMC_EPS_PER_RESPONSE) return fail(IDHMC_ERR_BAD_ARG, "the per-response stepsize adapts between transitions");
     if (!c->fuse_ok) {       // (a device whose workgroups b and b + 8 do not share an XCD: the same result from n launches)
         for (int32_t i = 0; i < n; ++i) { if (int rc = nuts_launch(c, iter + (uint32_t)i, flags, 1)) return rc; }
         return IDHMC_OK;
@@ -465,6 +467,14 @@ int idhmc::status_exchange(idhmc_ctx *c, const char *what)
 int idhmc_find_initial_stepsize(idhmc_ctx *c)
 {
     CTXCHK(c);
+    if (c->s.eps_mode == IDHMC_EPS_PER_RESPONSE) {
+        // one eps per response: exp(mean log eps) over its searches.  The context holds whole responses, so nothing is exchanged but
+        // the outcome, as for per-chain stepsizes
+        if (int rc = ensure_grad(c)) return rc;
+        HIPCHK(launch_stepsize_search(c->s, c->stream));
+        HIPCHK(launch_resp_eps(c->s, IDHMC_XCHG_LOGEPS, c->resp_da, c->glm_r, c->resp_n, c->stream));
+        return status_exchange(c, "find_initial_stepsize");
+    }
     if (c->s.eps_mode != IDHMC_EPS_GLOBAL && !sharded(c)) return idhmc_find_initial_stepsize_per_chain(c);
     if (int rc = ensure_grad(c)) return rc;
     HIPCHK(launch_stepsize_search(c->s, c->stream));
@@ -483,8 +493,20 @@ int idhmc_find_initial_stepsize(idhmc_ctx *c)
     if (int rc = get_scalar(c, rec, buf, sizeof rec)) return rc;
     return status_agreed(c, "find_initial_stepsize", rec[3]);
 }
-int idhmc_da_init(idhmc_ctx *c) { CTXCHK(c); HIPCHK(launch_da_init(c->s, c->stream)); return IDHMC_OK; }
-int idhmc_da_finalize(idhmc_ctx *c) { CTXCHK(c); HIPCHK(launch_da_finalize(c->s, c->stream)); return IDHMC_OK; }
+int idhmc_da_init(idhmc_ctx *c)
+{
+    CTXCHK(c);
+    if (c->s.eps_mode == IDHMC_EPS_PER_RESPONSE) HIPCHK(launch_resp_da_init(c->s, c->resp_da, c->glm_r, c->resp_n, c->stream));
+    else HIPCHK(launch_da_init(c->s, c->stream));
+    return IDHMC_OK;
+}
+int idhmc_da_finalize(idhmc_ctx *c)
+{
+    CTXCHK(c);
+    if (c->s.eps_mode == IDHMC_EPS_PER_RESPONSE) HIPCHK(launch_resp_da_finalize(c->s, c->resp_da, c->glm_r, c->stream));
+    else HIPCHK(launch_da_finalize(c->s, c->stream));
+    return IDHMC_OK;
+}
 static int xchg_sum(idhmc_ctx *c, int32_t kind, double *dev_xchg)
 {
     CTXCHK(c);
@@ -621,6 +643,10 @@ int idhmc_metric_update(idhmc_ctx *c, double lambda)
     CTXCHK(c);
     if (!c->s.mw_x1) return fail(IDHMC_ERR_BAD_ARG, "shared-metric context has no metric window");
     if (!(lambda >= 0.0)) return fail(IDHMC_ERR_BAD_ARG, "lambda must be >= 0");
+    if (c->opt.metric_mode == IDHMC_METRIC_PER_RESPONSE) {      // the pooled sums with one instance per response, no collective
+        HIPCHK(launch_resp_metric(c->s, lambda, c->glm_r, c->resp_n, c->stream));
+        return IDHMC_OK;
+    }
     if (c->s.minv_stride == 0) {
         // pooled: every chain's window, on every rank when the context has a communicator.  The table of per-segment
         // partials covers the global segments [0, ceil(total / IDHMC_POOL_SEGMENT)); the total comes from an exact all-reduce

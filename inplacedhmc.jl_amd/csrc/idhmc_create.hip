@@ -122,6 +122,16 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
         if (M > 1 && opt.metric_mode == IDHMC_METRIC_POOLED)
             return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses with metric_mode = POOLED: the pooled metric pools the windows of chains "
                         "that sample different posteriors (use PER_CHAIN or SHARED)", what, (long long)M);
+        // pooled per response: rank-local and free of collectives because a context holds whole responses
+        if (opt.eps_mode == IDHMC_EPS_PER_RESPONSE || opt.metric_mode == IDHMC_METRIC_PER_RESPONSE) {
+            const char *mode = opt.eps_mode == IDHMC_EPS_PER_RESPONSE ? "eps_mode" : "metric_mode";
+            if (first_chain_id % R != 0)
+                return fail(IDHMC_ERR_BAD_ARG, "%s: first_chain_id = %lld is not a multiple of chains_per_response = %lld: a context with %s = "
+                            "PER_RESPONSE holds whole responses", what, (long long)first_chain_id, (long long)R, mode);
+            if (nchains % R != 0)
+                return fail(IDHMC_ERR_BAD_ARG, "%s: nchains = %lld is not a multiple of chains_per_response = %lld: a context with %s = "
+                            "PER_RESPONSE holds whole responses", what, (long long)nchains, (long long)R, mode);
+        }
     }
     const int64_t n = g.n, K = g.K, M = g.M;
     const int64_t Dx = D - g.A - g.H;      // the columns of X
@@ -156,6 +166,9 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
     }
     if (D > 512 && opt.metric_mode == IDHMC_METRIC_PER_CHAIN)
         return fail(IDHMC_ERR_BAD_ARG, "%s with D > 512 needs metric_mode = SHARED (LDS budget of the NUTS kernel)", what);
+    if (D > 512 && opt.metric_mode == IDHMC_METRIC_PER_RESPONSE)
+        return fail(IDHMC_ERR_BAD_ARG, "%s with D = %d > 512 and metric_mode = PER_RESPONSE: the per-response metric is stored per chain and "
+                    "shares the per-chain metric's LDS budget of the NUTS kernel (use SHARED)", what, D);
     return IDHMC_OK;
 }
 // X, X' and the K planes of Y zero-padded to [n_pad][L], [L][n_pad], [K][n_pad] (one set of planes per response, [M][K][n_pad]);
@@ -243,7 +256,12 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
         if (kind == IDHMC_MODEL_GLM)
             return fail(IDHMC_ERR_BAD_ARG, "D = %d: a GLM is limited to D <= 1024", model->D);
     }
-    if (opt_in && (opt_in->metric_mode < 0 || opt_in->metric_mode > IDHMC_METRIC_POOLED)) return fail(IDHMC_ERR_BAD_ARG, "unknown metric_mode %d", opt_in->metric_mode);
+    if (opt_in && (opt_in->metric_mode < 0 || opt_in->metric_mode > IDHMC_METRIC_PER_RESPONSE)) return fail(IDHMC_ERR_BAD_ARG, "unknown metric_mode %d", opt_in->metric_mode);
+    // one stepsize / one metric per response: only a context with responses has any
+    if (opt.eps_mode == IDHMC_EPS_PER_RESPONSE && !(parts && parts->responses))
+        return fail(IDHMC_ERR_BAD_ARG, "eps_mode = %d (PER_RESPONSE) needs a context made by idhmc_create_glm_responses", opt.eps_mode);
+    if (opt.metric_mode == IDHMC_METRIC_PER_RESPONSE && !(parts && parts->responses))
+        return fail(IDHMC_ERR_BAD_ARG, "metric_mode = %d (PER_RESPONSE) needs a context made by idhmc_create_glm_responses", opt.metric_mode);
     if (kind < 0 || kind > IDHMC_MODEL_GLM_AUX) return fail(IDHMC_ERR_BAD_ARG, "unknown model kind %d", model->kind);
     if (kind == IDHMC_MODEL_CUSTOM) {
         if (!model->source || !model->source[0]) return fail(IDHMC_ERR_BAD_ARG, "custom model needs HIP source");
@@ -329,7 +347,8 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
     const int64_t CL = nchains * s.L;
     // the dense leapfrog's matrix-core kernel reads whole 32-chain tiles: rows past the last chain exist (zeros), see kRowPad
     const int64_t CLp = CL + (kind == IDHMC_MODEL_DENSE_MVN ? (int64_t)kRowPad * s.L : 0);
-    const bool own_minv = opt.metric_mode == IDHMC_METRIC_PER_CHAIN;
+    // (the per-response metric lives in the per-chain layout: the R rows of a response hold the same values)
+    const bool own_minv = opt.metric_mode == IDHMC_METRIC_PER_CHAIN || opt.metric_mode == IDHMC_METRIC_PER_RESPONSE;
     {
         double *sv[4] = {nullptr, nullptr, nullptr, nullptr};
         if (int rc = place_state(c, sv, own_minv ? 4 : 3, CLp, nchains, s.L)) return rc;
@@ -361,6 +380,8 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
     DALLOC(s.da.mu, nchains); DALLOC(s.da.Hbar, nchains); DALLOC(s.da.logeps, nchains);
     DALLOC(s.da.logeps_bar, nchains); DALLOC(s.da.m, nchains);
     DALLOC(s.da_global, 8);
+    if (opt.eps_mode == IDHMC_EPS_PER_RESPONSE || opt.metric_mode == IDHMC_METRIC_PER_RESPONSE) c->resp_n = nchains / g.R;
+    if (opt.eps_mode == IDHMC_EPS_PER_RESPONSE) DALLOC(c->resp_da, 6 * c->resp_n);
     DALLOC(s.xchg_acc, 3 * kXchgBlocks + 1);
     DALLOC(s.status, nchains);
     DALLOC(s.total_steps, 32);
@@ -405,7 +426,7 @@ static int create_context(idhmc_ctx **out, int device, int64_t nchains, int64_t 
     // persistent NUTS waves and their tree arenas
     {
         // one workgroup of W wavefronts per CU (nuts_waves); slots in multiples of W
-        const int W = nuts_waves_per_block(s.nch, s.model, opt.metric_mode != IDHMC_METRIC_PER_CHAIN, s.lr_a);
+        const int W = nuts_waves_per_block(s.nch, s.model, !own_minv, s.lr_a);
         int64_t nslots = (int64_t)prop.multiProcessorCount * W;
         const int64_t need = (nchains + W - 1) / W * W;
         if (nslots > need) nslots = need;

@@ -5,17 +5,25 @@
 
 
 // ---- the reference's caller loops --------------------------------------------------------------------
-// one transition by a launch of its own; `adapt` with a global stepsize: the acceptance is pooled and the stepsize adapted behind it
-static int one_transition(idhmc_ctx *c, uint32_t iter, uint32_t flags, bool adapt)
+// what sits between two adapting transitions where the stepsize is not a chain's own: the acceptance is pooled and the stepsize adapted
+// behind the transition (global: the exchange record, the ranks' all-reduce, the adaptation; per response: one launch, nothing to exchange)
+static int adapt_pooled_eps(idhmc_ctx *c)
 {
-    if (int rc = idhmc_nuts_transition(c, iter, flags)) return rc;
-    if (adapt && c->s.eps_mode == IDHMC_EPS_GLOBAL) {
+    if (c->s.eps_mode == IDHMC_EPS_GLOBAL) {
         double *buf = xchg_buf(c);
         HIPCHK(launch_xchg_sum(c->s, IDHMC_XCHG_ACCEPT, buf, c->stream));
         if (int rc = exchange(c, buf)) return rc;
         HIPCHK(launch_da_adapt_global(c->s, buf, c->stream));
+    } else if (c->s.eps_mode == IDHMC_EPS_PER_RESPONSE) {
+        HIPCHK(launch_resp_eps(c->s, IDHMC_XCHG_ACCEPT, c->resp_da, c->glm_r, c->resp_n, c->stream));
     }
     return IDHMC_OK;
+}
+// one transition by a launch of its own; `adapt` with a global or per-response stepsize: adapt_pooled_eps behind it
+static int one_transition(idhmc_ctx *c, uint32_t iter, uint32_t flags, bool adapt)
+{
+    if (int rc = idhmc_nuts_transition(c, iter, flags)) return rc;
+    return adapt ? adapt_pooled_eps(c) : IDHMC_OK;
 }
 // ---- draws and records to the host, overlapped with the next transition ------------------------------------------------
 // fetch_pack(n) is enqueued right behind transition n: the device packs the draw (padded rows -> contiguous) and the records
@@ -103,8 +111,8 @@ static int run_transitions(idhmc_ctx *c, uint32_t iter_first, int32_t N, uint32_
                            double *draws, idhmc_tree_stats *stats)
 {
     const bool any = draws || stats;
-    // the global stepsize adapts between transitions: one launch each
-    const bool fusable = fuse_transitions(c) && !(adapt && c->s.eps_mode == IDHMC_EPS_GLOBAL);
+    // the global and the per-response stepsize adapt between transitions: one launch each
+    const bool fusable = fuse_transitions(c) && !(adapt && (c->s.eps_mode == IDHMC_EPS_GLOBAL || c->s.eps_mode == IDHMC_EPS_PER_RESPONSE));
     const int32_t K = any && fusable ? block_transitions(c, N) : 0;
     if (any) { if (int rc = stage_reserve(c, K ? K : 1, draws != nullptr, stats != nullptr)) return rc; }
     if (adapt && c->s.eps_mode == IDHMC_EPS_PER_CHAIN) flags |= IDHMC_T_ADAPT_EPS;
@@ -222,4 +230,15 @@ int idhmc_time_transitions_fused(idhmc_ctx *c, int32_t n, uint32_t iter0, float 
     CTXCHK(c);
     if (n < 1 || !ms_total) return fail(IDHMC_ERR_BAD_ARG, "bad arguments");
     return time_bracket(c, ms_total, [&]() -> int { return idhmc_nuts_transitions(c, iter0 + 1u, n, 0u); });
+}
+int idhmc_time_eps_adapt(idhmc_ctx *c, int32_t n, float *ms_total)
+{
+    CTXCHK(c);
+    if (n < 1 || !ms_total) return fail(IDHMC_ERR_BAD_ARG, "bad arguments");
+    if (c->s.eps_mode != IDHMC_EPS_GLOBAL && c->s.eps_mode != IDHMC_EPS_PER_RESPONSE)
+        return fail(IDHMC_ERR_BAD_ARG, "the per-chain stepsize adapts inside the transition kernel");
+    return time_bracket(c, ms_total, [&]() -> int {
+        for (int i = 0; i < n; ++i) { if (int rc = adapt_pooled_eps(c)) return rc; }
+        return IDHMC_OK;
+    });
 }

@@ -48,6 +48,9 @@ struct idhmc_ctx {
     std::vector<void *> allocs;
     int64_t bytes = 0;
     int64_t glm_r = 0;             // idhmc_create_glm_responses: chains per response as given (0: any other context)
+    // IDHMC_EPS_PER_RESPONSE / IDHMC_METRIC_PER_RESPONSE: the context holds resp_n = C / glm_r whole responses (0 in every other mode)
+    int64_t resp_n = 0;
+    double *resp_da = nullptr;     // [resp_n][6] dual-averaging states of IDHMC_EPS_PER_RESPONSE: mu, m, Hbar, logeps, logeps_bar, eps
     double *xchg = nullptr;        // library-owned exchange record (IDHMC_XCHG_DOUBLES)
     int32_t *status_out = nullptr; // device scalar
     double *scratch = nullptr;     // [C][L] staging for broadcasts / moments

@@ -103,6 +103,7 @@ constexpr int kLdsBytes = 160 * 1024;   // LDS of a CU
 // transition flag of the test suite only (see the XCD check in k_nuts); idhmc_nuts_transition(s) accept it on a context created
 // with IDHMC_TEST_XCC_MISMATCH=1 in the environment, and refuse it, like every other bit outside the IDHMC_T_* set, otherwise
 constexpr uint32_t kTestXccFlag = 1u << 30;
+constexpr int kRespBlocks = 1024;   // most workgroups of k_resp_eps / k_resp_da_init (four wavefronts each, strided beyond)
 constexpr int kXchgBlocks = 64;   // workgroups of k_xchg_sum; DevState::xchg_acc holds 3 * kXchgBlocks partials + 1 ticket
 // the most q, p, grad bytes the single-step leapfrog keeps in the 256 MiB Infinity Cache across sweeps: every lf_stride-th chain, with
 // lf_stride = ceil(C L 3 8 / kIcSliceBytes), 1 when the whole state fits (tools/ubench/ic_slice.hip: 192 MiB stays resident behind a
@@ -237,6 +238,12 @@ hipError_t launch_pool_partials(const DevState &s, int pass, const double *scrat
                                 hipStream_t st);
 hipError_t launch_pool_consume(const DevState &s, int pass, double *scratch, const double *table, long long nseg, double lambda,
                                hipStream_t st);
+// per-response stepsize and metric (IDHMC_EPS_PER_RESPONSE, IDHMC_METRIC_PER_RESPONSE): the context's chains are nresp whole responses
+// of R chains; resp_da is the context's [nresp][6] dual-averaging states (idhmc_kernels.hip)
+hipError_t launch_resp_eps(const DevState &s, int kind, double *resp_da, long long R, long long nresp, hipStream_t st);
+hipError_t launch_resp_da_init(const DevState &s, double *resp_da, long long R, long long nresp, hipStream_t st);
+hipError_t launch_resp_da_finalize(const DevState &s, const double *resp_da, long long R, hipStream_t st);
+hipError_t launch_resp_metric(const DevState &s, double lambda, long long R, long long nresp, hipStream_t st);
 hipError_t launch_status_max(const DevState &s, int32_t *dev_out, hipStream_t st);
 hipError_t launch_ebfmi(const DevState &s, double *out, hipStream_t st);
 #endif  // !__HIPCC_RTC__

@@ -372,6 +372,172 @@ __global__ void k_pool_apply(DevState s, const double *acc0, const double *acc1,
     s.minv[d] = mv;
     s.w[d] = wv;
 }
+// ---- per-response stepsize and metric (IDHMC_EPS_PER_RESPONSE, IDHMC_METRIC_PER_RESPONSE) -----------------
+// A context of a GLM with several responses holds whole responses: response r of the context is its chains [r R, (r + 1) R).  What
+// follows is the global stepsize and the pooled metric with one instance per response, and for every response bit for bit what a
+// single-response context on the same chains computes with k_xchg_sum / k_da_adapt_global / k_eps_from_global and k_pool_*: the
+// same integer record, the same expression sequences.  resp_da is [responses][6]: mu, m, Hbar, logeps, logeps_bar, eps.
+// Lanes by response: a response of R <= 32 chains takes the smallest power of two of lanes that holds it, so a wavefront serves
+// 64 / resp_lanes(R) responses side by side (at R = 16 four: k_resp_eps over 4096 responses takes 10.4-11.0 us where one response per
+// wavefront took 13.7-14.6, profiles/r10_glm_pooling.log); a larger one has the wavefront to itself
+__host__ __device__ inline int resp_lanes(long long R)
+{
+    int g = 64;
+    while (g > 1 && (g >> 1) >= R) g >>= 1;
+    return g;
+}
+// eps of every chain of a response (lane l of its `lanes`), k_eps_from_global's underflow rule for that response
+__device__ __forceinline__ void resp_set_eps(const DevState &s, long long c0, long long c1, int l, int lanes, double e)
+{
+    for (long long c = c0 + l; c < c1; c += lanes) {
+        s.eps[c] = e;
+        if (e < 1e-10) s.status[c] = IDHMC_ERR_EPS_UNDERFLOW;
+    }
+    if (e < 1e-10 && l == 0) atomicMax(s.total_steps + 1, (unsigned long long)IDHMC_ERR_EPS_UNDERFLOW);   // the host's pulse
+}
+// One launch per call.  A response is reduced inside one wavefront, its lanes striding over its chains (any R), the grid striding
+// over the responses: the limbs are integers, so the order of the reduction cannot change a bit, and nothing needs LDS, an atomic or
+// a ticket.  KIND = IDHMC_XCHG_ACCEPT: adapt_stepsize on the response's mean acceptance, then its eps to its chains;
+// IDHMC_XCHG_LOGEPS: eps = exp(mean log eps).
+template <int KIND>
+__global__ __launch_bounds__(256) void k_resp_eps(DevState s, double *resp_da, long long R, long long nresp)
+{
+    const int lane = threadIdx.x & 63;
+    const int lanes = resp_lanes(R), per = 64 / lanes, sub = lane / lanes, l = lane - sub * lanes;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
+    const long long nunits = (nresp + per - 1) / per;            // wavefronts' worth of responses
+    for (long long u = wave; u < nunits; u += nw) {
+        const long long r = u * per + sub;
+        const bool live = r < nresp;                             // (the last wavefront may have lanes without a response: they add zeros)
+        const long long c0 = r * R, c1 = live ? c0 + R : c0;
+        long long hi = 0, lo = 0;
+        for (long long c = c0 + l; c < c1; c += lanes) {
+            const double x = (KIND == IDHMC_XCHG_ACCEPT) ? s.stats[c].acceptance_rate : dlog(s.eps[c]);
+            long long h, w;
+            xchg_limbs(KIND, x, h, w);
+            hi += h; lo += w;
+        }
+        for (int o = lanes >> 1; o > 0; o >>= 1) {               // (xor with o < lanes stays inside the response's lanes)
+            hi += __shfl_xor(hi, o);
+            lo += __shfl_xor(lo, o);
+        }
+        if (!live) continue;
+        const double mean = xchg_mean(KIND, (double)hi, (double)lo, (double)R);
+        double e;
+        if (KIND == IDHMC_XCHG_ACCEPT) {             // k_da_adapt_global's sequence (every lane computes, lane 0 of the response keeps the state)
+            double *da = resp_da + 6 * r;
+            double mu = da[0], m = da[1], Hbar = da[2], lb = da[4];
+            m += 1.0;
+            Hbar += (s.da_delta - mean - Hbar) / (m + (double)s.da_t0);
+            const double le = mu - __builtin_sqrt(m) / s.da_gamma * Hbar;
+            lb += dexp(-s.da_kappa * dlog(m)) * (le - lb);
+            e = dexp(le);
+            if (l == 0) {
+                da[1] = m;
+                da[2] = Hbar;
+                da[3] = le;
+                da[4] = lb;
+                da[5] = e;
+            }
+        } else {
+            e = dexp(mean);
+        }
+        resp_set_eps(s, c0, c1, l, lanes, e);
+    }
+}
+// k_da_init_global per response: the state starts from the eps of the response's first chain (all of them hold the same value)
+__global__ __launch_bounds__(256) void k_resp_da_init(DevState s, double *resp_da, long long R, long long nresp)
+{
+    const int lane = threadIdx.x & 63;
+    const int lanes = resp_lanes(R), per = 64 / lanes, sub = lane / lanes, l = lane - sub * lanes;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
+    const long long nunits = (nresp + per - 1) / per;
+    for (long long u = wave; u < nunits; u += nw) {
+        const long long r = u * per + sub;
+        if (r >= nresp) continue;
+        const double le = dlog(s.eps[r * R]);
+        const double e = dexp(le);
+        if (l == 0) {
+            double *da = resp_da + 6 * r;
+            da[0] = dlog(10.0) + le;
+            da[1] = 0.0;
+            da[2] = 0.0;
+            da[3] = le;
+            da[4] = 0.0;
+            da[5] = e;
+        }
+        resp_set_eps(s, r * R, r * R + R, l, lanes, e);
+    }
+}
+// final_eps = exp(logeps_bar) of the chain's response (k_da_finalize's global branch)
+__global__ void k_resp_da_finalize(DevState s, const double *resp_da, long long R)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= s.C) return;
+    s.eps[c] = dexp(resp_da[6 * (c / R) + 4]);
+}
+// The pooled metric of every response: one thread per (response, d), d fastest, so the loads of the windows and the stores of the
+// rows are coalesced.  The sums are k_pool_partial's and k_pool_finish's restricted to the response: a partial per
+// IDHMC_POOL_SEGMENT-aligned segment of GLOBAL chain ids in ascending id, chains with an empty window skipped, the partials added to
+// 0.0 in ascending segment order (a response that straddles a multiple of the segment size has two); then k_pool_mean, the second
+// pass and k_pool_apply.  M^-1 and W go to the rows of all R chains; pads stay 1.
+__global__ __launch_bounds__(256) void k_resp_metric(DevState s, double lambda, long long R, long long nresp)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nresp * s.L) return;
+    const long long r = i / s.L;
+    const int d = (int)(i - r * s.L);
+    const long long c0 = r * R, c1 = c0 + R;
+    double mv = 1.0, wv = 1.0;
+    if (d < s.D) {
+        const long long first = (long long)s.first_chain;
+        const long long g0 = first + c0, g1 = first + c1;
+        const long long seg_lo = g0 / IDHMC_POOL_SEGMENT, seg_hi = (g1 + IDHMC_POOL_SEGMENT - 1) / IDHMC_POOL_SEGMENT;
+        double N = 0.0, A = 0.0;                      // pass 0: the count column and sum_c (n_c x1 + s1)
+        for (long long seg = seg_lo; seg < seg_hi; ++seg) {
+            long long a = seg * IDHMC_POOL_SEGMENT, b = a + IDHMC_POOL_SEGMENT;
+            a = (a < g0 ? g0 : a) - first;
+            b = (b > g1 ? g1 : b) - first;
+            double pn = 0.0, pa = 0.0;
+            for (long long c = a; c < b; ++c) {
+                const double n = (double)s.mw_n[c];
+                pn += n;
+                if (!(n > 0.0)) continue;
+                const int64_t k = c * s.L + d;
+                pa += dfma(n, s.mw_x1[k], s.mw_s1[k]);
+            }
+            N += pn;
+            A += pa;
+        }
+        const double mu = A / N;                      // k_pool_mean
+        double S = 0.0;                               // pass 1
+        for (long long seg = seg_lo; seg < seg_hi; ++seg) {
+            long long a = seg * IDHMC_POOL_SEGMENT, b = a + IDHMC_POOL_SEGMENT;
+            a = (a < g0 ? g0 : a) - first;
+            b = (b > g1 ? g1 : b) - first;
+            double ps = 0.0;
+            for (long long c = a; c < b; ++c) {
+                const double n = (double)s.mw_n[c];
+                if (!(n > 0.0)) continue;
+                const int64_t k = c * s.L + d;
+                const double x1 = s.mw_x1[k], s1 = s.mw_s1[k], s2 = s.mw_s2[k];
+                const double m = x1 + s1 / n, dm = m - mu;
+                ps += dfma(-(s1 * s1), 1.0 / n, s2) + n * (dm * dm);
+            }
+            S += ps;
+        }
+        const double mulreg = N / ((N + lambda) * (N - 1.0));         // src/hamiltonian.jl:157
+        const double addreg = 1e-3 * lambda / (N + lambda);           // :158
+        mv = dfma(S, mulreg, addreg);                                 // :96
+        wv = 1.0 / __builtin_sqrt(mv);                                // :97
+    }
+    for (long long c = c0; c < c1; ++c) {
+        s.minv[c * s.L + d] = mv;
+        s.w[c * s.L + d] = wv;
+    }
+}
 __global__ void k_moments_get(DevState s, double *mean, double *var)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -607,6 +773,35 @@ hipError_t launch_pool_consume(const DevState &s, int pass, double *scratch, con
     hipLaunchKernelGGL(k_pool_finish, dim3(g1), dim3(256), 0, st, s, table, nseg, pass ? acc1 : acc0);
     if (pass == 0) hipLaunchKernelGGL(k_pool_mean, dim3(g0), dim3(256), 0, st, s, acc0, mean);
     else hipLaunchKernelGGL(k_pool_apply, dim3(g0), dim3(256), 0, st, s, acc0, acc1, lambda);
+    return hipGetLastError();
+}
+// per-response stepsize and metric: R chains per response, nresp = C / R responses in this context
+static dim3 resp_grid(long long R, long long nresp)
+{
+    const long long per = 64 / resp_lanes(R);         // responses per wavefront, four wavefronts per workgroup
+    const long long b = ((nresp + per - 1) / per + 3) / 4;
+    return dim3((unsigned)(b > kRespBlocks ? kRespBlocks : b));
+}
+hipError_t launch_resp_eps(const DevState &s, int kind, double *resp_da, long long R, long long nresp, hipStream_t st)
+{
+    if (kind == IDHMC_XCHG_ACCEPT) hipLaunchKernelGGL(k_resp_eps<IDHMC_XCHG_ACCEPT>, resp_grid(R, nresp), dim3(256), 0, st, s, resp_da, R, nresp);
+    else hipLaunchKernelGGL(k_resp_eps<IDHMC_XCHG_LOGEPS>, resp_grid(R, nresp), dim3(256), 0, st, s, resp_da, R, nresp);
+    return hipGetLastError();
+}
+hipError_t launch_resp_da_init(const DevState &s, double *resp_da, long long R, long long nresp, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_resp_da_init, resp_grid(R, nresp), dim3(256), 0, st, s, resp_da, R, nresp);
+    return hipGetLastError();
+}
+hipError_t launch_resp_da_finalize(const DevState &s, const double *resp_da, long long R, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_resp_da_finalize, dim3((unsigned)((s.C + 255) / 256)), dim3(256), 0, st, s, resp_da, R);
+    return hipGetLastError();
+}
+hipError_t launch_resp_metric(const DevState &s, double lambda, long long R, long long nresp, hipStream_t st)
+{
+    const long long n = nresp * s.L;
+    hipLaunchKernelGGL(k_resp_metric, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s, lambda, R, nresp);
     return hipGetLastError();
 }
 hipError_t launch_moments_get(const DevState &s, double *mean_out, double *var_out, hipStream_t st)

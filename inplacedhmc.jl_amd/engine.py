@@ -13,8 +13,8 @@ assert TREE_STATS_DTYPE.itemsize == 32
 
 MODEL_ISO_GAUSSIAN, MODEL_DIAG_GAUSSIAN, MODEL_DENSE_MVN, MODEL_CUSTOM, MODEL_LOGISTIC_REGRESSION, MODEL_GLM = 0, 1, 2, 3, 4, 5
 MODEL_GLM_AUX = 6
-EPS_PER_CHAIN, EPS_GLOBAL = 0, 1
-METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED = 0, 1, 2
+EPS_PER_CHAIN, EPS_GLOBAL, EPS_PER_RESPONSE = 0, 1, 2
+METRIC_PER_CHAIN, METRIC_SHARED, METRIC_POOLED, METRIC_PER_RESPONSE = 0, 1, 2, 3
 GRAD_STORE, GRAD_RECOMPUTE = 0, 1
 T_ADAPT_EPS, T_ACCUM_METRIC, T_ACCUM_MOMENTS, T_KEEP_P, T_USE_DIRECTIONS, T_ACCUM_DIAG = 1, 2, 4, 8, 16, 32
 XCHG_DOUBLES, XCHG_ACCEPT, XCHG_LOGEPS = 4, 0, 1
@@ -187,6 +187,9 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     (M, n, K), and the chain of global id g samples the posterior of Y[g // R]; X, the prior, the constants, the source and the groups
     are shared.  An Engine (or the shards of a run, through first_chain) holds at most M * R chains, with a per-chain stepsize and a
     per-chain or SHARED metric (EPS_GLOBAL and METRIC_POOLED pool over chains of different posteriors and are refused with M > 1).
+    EPS_PER_RESPONSE and METRIC_PER_RESPONSE pool over the R chains of each response instead: one dual-averaging stepsize, one adapted
+    diagonal metric per response (D <= 512), bit-identical to a single-response model in EPS_GLOBAL / METRIC_POOLED on those chains;
+    an Engine in either mode holds whole responses (first_chain and the number of chains are multiples of R).
     Each chain's draws are bit-identical to those of a single-response model on its Y.  glm.response_of_chain, glm.by_response and
     diagnostics.rhat_by_response sort chains and draws by response.  The Model exposes M and R (1 and None without the keyword)."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
@@ -603,4 +606,11 @@ class Engine:
         """the same n transitions as one idhmc_nuts_transitions launch"""
         ms = C.c_float()
         check(self.lib.idhmc_time_transitions_fused(self.h, n, iter0, C.byref(ms)))
+        return ms.value
+
+    def time_eps_adapt(self, n):
+        """n times what the drivers enqueue between two adapting transitions in EPS_GLOBAL (three launches) or EPS_PER_RESPONSE (one):
+        milliseconds in all (include/idhmc.h); moves the stepsizes, call da_init first"""
+        ms = C.c_float()
+        check(self.lib.idhmc_time_eps_adapt(self.h, int(n), C.byref(ms)))
         return ms.value

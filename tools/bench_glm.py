@@ -27,9 +27,16 @@ model, each with its own seed; every chain starts from the first response's Lapl
 existing entry point, the poisson pair's glm_poisson.  --chains-per-response R,... names the same rows by R (M = C / R).  --repeats K
 makes K engines per row, for the run-to-run spread.
 
+--adapt per-chain|per-response times, for every row of --responses, ONE ADAPTING TUNING STAGE with an adapted metric
+window (tuning_stage(--stage-steps, adapt_metric=True), nothing stored) instead of the fixed-eps transitions: per-chain is EPS_PER_CHAIN +
+METRIC_PER_CHAIN (the stage is one fused launch), per-response EPS_PER_RESPONSE + METRIC_PER_RESPONSE (one transition and one pooling
+launch per transition; on the plain GLM of M = 1 the context-wide EPS_GLOBAL + METRIC_POOLED, which are the same thing there).  With a
+pooled stepsize it also reports what sits between two transitions alone, by HIP events: idhmc_time_eps_adapt, and for the global
+stepsize the same three launches enqueued by hand (accept_sum, da_adapt_global) between two torch events.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
-                              [--responses 1,4096] [--chains-per-response 16] [--repeats 1]
+                              [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
 """
 import argparse
 import json
@@ -436,6 +443,74 @@ def run(form, X, y, q_map, cov, C, T, seed=1, metric=None, mdl=None):
     return out, head, tail
 
 
+def global_adapt_by_hand(eng, n):
+    """n times (accept_sum, da_adapt_global) -- the global stepsize's three launches -- between two torch events: milliseconds"""
+    import torch
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        buf = torch.zeros(pkg.XCHG_DOUBLES, dtype=torch.float64, device="cuda")
+    st.synchronize()
+    eng.synchronize()
+    eng.set_stream(st.cuda_stream)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(st)
+    for _ in range(n):
+        eng.accept_sum(buf.data_ptr())
+        eng.da_adapt_global(buf.data_ptr())
+    e1.record(st)
+    e1.synchronize()
+    eng.set_stream(None)
+    return e0.elapsed_time(e1)
+
+
+def run_adapt(X, y, q_map, cov, C, N, adapt, seed=1, mdl=None):
+    """one adapting tuning stage of N transitions with a metric window, from the start `run` uses; wall time, the stream idle at both ends"""
+    if adapt == "per-chain":
+        eps_mode, metric = pkg.EPS_PER_CHAIN, pkg.METRIC_PER_CHAIN
+    elif mdl is None:
+        eps_mode, metric = pkg.EPS_GLOBAL, pkg.METRIC_POOLED
+    else:
+        eps_mode, metric = pkg.EPS_PER_RESPONSE, pkg.METRIC_PER_RESPONSE
+    t0 = time.perf_counter()
+    eng = pkg.Engine(model("glm_poisson", X, y, q_map) if mdl is None else mdl, C,
+                     pkg.default_options(eps_mode=eps_mode, metric_mode=metric, max_depth=10), seed=seed)
+    create_s = time.perf_counter() - t0
+    q0 = q_map + np.random.default_rng(seed).standard_normal((C, q_map.size)) @ np.linalg.cholesky(cov).T
+    eps = 0.5 * np.sqrt(np.linalg.eigvalsh(cov)[0])
+
+    def start():
+        eng.set_q(q0)
+        eng.set_eps(eps)
+        eng.set_minv(np.ones(q_map.size))
+        eng.synchronize()
+    start()
+    eng.tuning_stage(2, True, 0, store_draws=False, store_stats=False)      # warm-up (and the module's first launches)
+    start()
+    s0 = eng.total_steps()
+    t0 = time.perf_counter()
+    eng.tuning_stage(N, True, 0, store_draws=False, store_stats=False)
+    eng.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3
+    steps = eng.total_steps() - s0
+    e = eng.eps
+    out = dict(create_s=create_s, adapt=adapt, eps_mode=int(eps_mode), metric_mode=int(metric), stage_transitions=N, stage_ms=ms,
+               ms_per_transition=ms / N, steps=int(steps), leapfrog_steps_per_s=steps / ms * 1e3, eps_start=float(eps),
+               eps_final_mean=float(e.mean()), eps_final_distinct=int(len(set(e))), minv_mean=float(eng.minv[:64].mean()),
+               fused=bool(eng.fused_launch_info()[1] and adapt == "per-chain"), glm_form=eng.glm_form())
+    if adapt == "per-response":
+        n = 400
+        eng.da_init()
+        if hasattr(eng, "time_eps_adapt"):
+            eng.time_eps_adapt(20)
+            out["eps_adapt_us_per_transition"] = eng.time_eps_adapt(n) / n * 1e3
+            out["eps_adapt_launches"] = 3 if eps_mode == pkg.EPS_GLOBAL else 1
+        if eps_mode == pkg.EPS_GLOBAL:
+            global_adapt_by_hand(eng, 20)
+            out["eps_adapt_by_hand_us_per_transition"] = global_adapt_by_hand(eng, n) / n * 1e3
+    eng.close()
+    return out
+
+
 PAIRS = {"poisson": ("glm_poisson", "custom_poisson", poisson_problem),
          "logistic": ("glm_logistic", "builtin_logistic", logistic_problem),
          "gaussian": ("glm_gaussian", "custom_gaussian", gaussian_problem),
@@ -457,12 +532,18 @@ def main():
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
     ap.add_argument("--repeats", type=int, default=1, help="engines per row of --responses (the run-to-run spread)")
+    ap.add_argument("--adapt", default="", choices=["", "per-chain", "per-response"], help="the rows of --responses time one adapting tuning "
+                    "stage with a metric window, stepsize and metric per chain or pooled per response (DESIGN section 16)")
+    ap.add_argument("--stage-steps", type=int, default=25, help="transitions of the stage that --adapt times")
     ap.add_argument("--metric", default="shared", choices=["shared", "per_chain"])
     ap.add_argument("--lockstep", action="store_true", help="eps / 1000 and max_depth = 6: every tree of every density takes the same 63 "
                     "steps, so steps/s compares the cost per gradient and not the trees")
     a = ap.parse_args()
     global LOCKSTEP
     LOCKSTEP = a.lockstep
+    if a.adapt == "per-response":
+        import torch
+        torch.zeros(1, device="cuda")      # (torch's device start-up before the first context: the hand-made launches are timed with its events)
     metric = pkg.METRIC_SHARED if a.metric == "shared" else pkg.METRIC_PER_CHAIN
     res = dict(device_peak_fp64_mfma_flops=PEAK_FP64_MFMA, transitions_per_launch=a.transitions, results=[])
     for shape in a.shapes.split(","):
@@ -509,6 +590,14 @@ def main():
                     row = dict(pair="responses", D=D, n=n, chains=C, M=M, chains_per_response=C // M, metric=a.metric, runs=[])
                     for _ in range(a.repeats):
                         mdl = None if M == 1 else responses_model(X, y, q_map, M, C)
+                        if a.adapt:
+                            r = run_adapt(X, y, q_map, cov, C, a.stage_steps, a.adapt, mdl=mdl)
+                            row["runs"].append(r)
+                            print("# D=%d n=%d C=%d M=%d adapt %s: stage of %d transitions %.2f ms, %.3f ms/transition, %.4e leapfrog steps/s%s" %
+                                  (D, n, C, M, a.adapt, a.stage_steps, r["stage_ms"], r["ms_per_transition"], r["leapfrog_steps_per_s"],
+                                   "".join(", %s %.2f" % (k, v) for k, v in r.items() if k.startswith("eps_adapt") and k.endswith("transition"))),
+                                  file=sys.stderr, flush=True)
+                            continue
                         row["runs"].append(run("glm_poisson", X, y, q_map, cov, C, a.transitions, metric=metric, mdl=mdl)[0])
                         r = row["runs"][-1]
                         print("# D=%d n=%d C=%d M=%d (form %d): %.4e leapfrog steps/s, %.2f ms/transition, depth %.2f, create %.2f s" %
