@@ -506,6 +506,59 @@ int idhmc_tree_summary_from_counters(const uint64_t *counters, idhmc_tree_summar
  * fewer than two of them (0 / 0, as the reference's formula gives on one record) */
 int idhmc_get_ebfmi(idhmc_ctx *ctx, double *ebfmi);                          /* nchains */
 
+/* ---- posterior summaries reduced on the device ------------------------------------------
+ * With the draws kept, idhmc_mcmc is bound by the copy into the caller's array; a summary reduces the staged draws where they lie:
+ * per group of chains and per reported parameter the pooled mean, variance, minimum, maximum, the number of positive values and a
+ * histogram from which idhmc_summary_quantiles reads quantiles.
+ *
+ * Groups.  Chains are pooled in groups of chains_per_group consecutive GLOBAL chain ids; 0 means the default: chains_per_response of a
+ * context of idhmc_create_glm_responses, nchains otherwise.  The context must hold whole groups: first_chain_id and nchains must be
+ * multiples of chains_per_group.  Summaries are local to the context: nothing is exchanged between ranks.
+ *
+ * The reported vector theta has length D.  theta = q, except for a GLM with coefficient groups (H > 0), where
+ * theta = [beta (Dx) | a (A, raw) | sigma (H)], sigma_g = exp(omega_g) and beta_c = u_c sigma_grp[c] (u_c itself for an ungrouped
+ * column): the bits the density's own evaluation multiplies with X.
+ *
+ * Running statistics.  Each group's chains are cut into segments of IDHMC_SUMMARY_SEGMENT chains, counted from the group's first
+ * chain.  Per (segment, d) the state (n, mean, m2, min, max, pos) starts at (0, 0, 0, +inf, -inf, 0); values are visited transition
+ * by transition in the order the transitions happened, ascending chain id inside a transition, across blocks and calls:
+ *   n += 1; inv = 1.0 / (double)n; dx = theta - mean; mean = fma(dx, inv, mean); m2 = fma(dx, theta - mean, m2)
+ *   min = theta < min ? theta : min (likewise max); pos += theta > 0.0
+ * The segments are folded in ascending order from segment 0; for the next segment b with nb > 0:
+ *   n = na + nb; delta = mean_b - mean_a; f = (double)nb / (double)n; mean = fma(delta, f, mean_a)
+ *   m2 = (m2_a + m2_b) + (delta delta) ((double)na f)
+ * and var = m2 / (n - 1), 0.0 when n <= 1.  The bits depend on the segment size, which is why it is public.
+ *
+ * Histogram (bins > 0 interior bins, at most IDHMC_SUMMARY_BINS_MAX).  Values reduced while no range is set are not binned.
+ * idhmc_summary_set_range takes host arrays lo, hi [groups][D] (finite, lo <= hi), or both NULL for the range of what has been
+ * accumulated: sd = sqrt(var), lo = fma(-span, sd, mean), hi = fma(span, sd, mean) (needs two values in every group).
+ * inv_w = hi > lo ? (double)bins / (hi - lo) : 0.0 is computed once and stored.  The call zeroes the histogram and its count; the moments
+ * stay.  A binned value goes to bin 0 if theta < lo, to bin bins + 1 if theta >= hi, to 1 + min((int)((theta - lo) inv_w), bins - 1)
+ * otherwise.  Counts are uint32: a call that could take a group's binned count past 2^32 - 1 is refused before it launches.
+ *
+ * Feeding.  While a summary is open idhmc_mcmc reduces every draw it makes, whether or not draws / stats are NULL; idhmc_tuning_stage
+ * (and so the warm-up of idhmc_mcmc_with_warmup) never does.  When idhmc_mcmc fails the summary is invalid: idhmc_get_summary and
+ * idhmc_summary_set_range refuse it until idhmc_summary_begin is called again.  idhmc_summary_add_draws reduces cnt host draws
+ * [cnt][nchains][D] (draws saved earlier, or a test's) through the same staging buffers and the same kernel.
+ *
+ * Every refusal is IDHMC_ERR_BAD_ARG with the offending value in idhmc_last_error. */
+#define IDHMC_SUMMARY_SEGMENT 256
+#define IDHMC_SUMMARY_BINS_MAX 256
+int idhmc_summary_begin(idhmc_ctx *ctx, int64_t chains_per_group, int32_t bins);   /* (re)opens: an open summary is discarded */
+int idhmc_summary_set_range(idhmc_ctx *ctx, const double *lo, const double *hi, double span);
+int idhmc_summary_add_draws(idhmc_ctx *ctx, const double *draws, int64_t cnt);
+int idhmc_summary_dims(idhmc_ctx *ctx, int64_t *groups, int64_t *chains_per_group, int32_t *dim, int32_t *bins);
+/* n, binned: [groups] values taken / binned per (group, parameter); mean ... inv_w: [groups][D]; counts: [groups][D][bins + 2] (untouched
+ * when bins = 0).  lo, hi, inv_w are zero until a range is set.  Any pointer may be NULL. */
+int idhmc_get_summary(idhmc_ctx *ctx, int64_t *n, int64_t *binned, double *mean, double *var, double *min, double *max, int64_t *pos,
+                      double *lo, double *hi, double *inv_w, uint32_t *counts);
+int idhmc_summary_end(idhmc_ctx *ctx);                                             /* frees everything; no summary open: nothing */
+/* host only, no context: quantiles of one (group, parameter) from its bins + 2 counts.  With n_h = sum counts, k = clamp(ceil(p n_h), 1, n_h)
+ * and j the smallest bin whose cumulative count reaches k: lo if j = 0, hi if j = bins + 1,
+ * lo + (j - 1 + (k - cum_{j-1} - 0.5) / c_j) (hi - lo) / bins otherwise; NaN if n_h = 0.  The estimate lies in the bin that holds the
+ * k-th order statistic: unless that is an end bin, its error is below one bin width. */
+int idhmc_summary_quantiles(const uint32_t *counts, int32_t bins, double lo, double hi, const double *probs, int32_t nprobs, double *out);
+
 /* ---- drivers: the reference's caller loops, run by the library -------------- */
 /* warmup!(TuningNUTS) (src/warmup.jl:269-314): N transitions with dual averaging, optional
  * metric update at the end.  draws (host, N*nchains*D) / stats (host, N*nchains) may be NULL.

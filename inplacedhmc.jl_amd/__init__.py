@@ -18,7 +18,7 @@ from .api import (NUTS, DualAveraging, FixedStepsize, InitialStepsizeSearch, Fin
                   fixed_stepsize_warmup_stages, mcmc_with_warmup, threaded_mcmc, run_stages, num_stored)
 from . import diagnostics as Diagnostics  # noqa: F401,E402
 from .diagnostics import (EBFMI, summarize_tree_statistics, summary_from_counters, ess, rhat_from_moments,  # noqa: F401,E402
-                          ess_from_moments, rhat_by_response)
+                          ess_from_moments, rhat_by_response, PosteriorSummary)
 from . import distributed  # noqa: F401,E402
 from . import glm  # noqa: F401,E402
 

@@ -47,6 +47,8 @@ class TreeSummary(C.Structure):
 
 
 DIAG_COUNTERS = 39 + 1024
+SUMMARY_SEGMENT = 256       # IDHMC_SUMMARY_SEGMENT
+SUMMARY_BINS_MAX = 256      # IDHMC_SUMMARY_BINS_MAX
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
 # every symbol include/idhmc.h declares: name -> (restype, argtypes)
@@ -123,6 +125,14 @@ SYMBOLS = {
     "idhmc_get_diag_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "idhmc_tree_summary_from_counters": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(TreeSummary)]),
     "idhmc_get_ebfmi": (C.c_int, [_vp, _dp]),
+    "idhmc_summary_begin": (C.c_int, [_vp, _i64, _i32]),
+    "idhmc_summary_set_range": (C.c_int, [_vp, _dp, _dp, _dbl]),
+    "idhmc_summary_add_draws": (C.c_int, [_vp, _dp, _i64]),
+    "idhmc_summary_dims": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
+    "idhmc_get_summary": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), _dp, _dp, _dp, _dp, C.POINTER(_i64), _dp, _dp, _dp,
+                                    C.POINTER(_u32)]),
+    "idhmc_summary_end": (C.c_int, [_vp]),
+    "idhmc_summary_quantiles": (C.c_int, [C.POINTER(_u32), _i32, _dbl, _dbl, _dp, _i32, _dp]),
     "idhmc_tuning_stage": (C.c_int, [_vp, _i32, _i32, _u32, _dp, _vp]),
     "idhmc_mcmc": (C.c_int, [_vp, _i32, _u32, _dp, _vp]),
     "idhmc_mcmc_with_warmup": (C.c_int, [_vp, _i32, _dp, _vp]),

@@ -31,7 +31,7 @@ static int one_transition(idhmc_ctx *c, uint32_t iter, uint32_t flags, bool adap
 // copies to the caller's (pageable) arrays on a second stream -- the host blocks in that copy while the device computes.
 // Buffer n & 1 is reused by pack(n + 2), which is enqueued after the copy of n has returned.
 // stage_reserve: the staging buffers hold K transitions (grow-only; every path uses the same buffers)
-static int stage_reserve(idhmc_ctx *c, int32_t K, bool draws, bool stats)
+int idhmc::stage_reserve(idhmc_ctx *c, int32_t K, bool draws, bool stats)
 {
     const DevState &s = c->s;
     if (!c->copy_stream) {
@@ -54,13 +54,14 @@ static int stage_reserve(idhmc_ctx *c, int32_t K, bool draws, bool stats)
     if (stats && c->stage_kst < K) c->stage_kst = K;
     return IDHMC_OK;
 }
-static int fetch_pack(idhmc_ctx *c, int32_t n, bool draws, bool stats)
+// `sum`: an open summary reduces the packed draw where it lies, right behind the pack (the host copy needs the pack alone)
+static int fetch_pack(idhmc_ctx *c, int32_t n, bool draws, bool stats, bool sum)
 {
     if (!draws && !stats) return IDHMC_OK;
     const int b = n & 1;
     HIPCHK(launch_pack_draw(c->s, draws ? c->stage_q[b] : nullptr, stats ? c->stage_st[b] : nullptr, c->stream));
     HIPCHK(hipEventRecord(c->ev_packed[b], c->stream));
-    return IDHMC_OK;
+    return sum ? summary_feed(c, c->stage_q[b], 1) : IDHMC_OK;
 }
 // transitions n0 .. n0 + cnt - 1 from staging buffer b to the caller's arrays
 static int stage_copy(idhmc_ctx *c, int32_t n0, int32_t cnt, int b, double *draws, idhmc_tree_stats *stats)
@@ -89,15 +90,17 @@ static int32_t block_transitions(const idhmc_ctx *c, int32_t N)
     if (K < 2 || (uint64_t)c->s.C * (uint64_t)K >= (1ull << 31)) K = 0;
     return K;
 }
-static int run_blocks(idhmc_ctx *c, uint32_t iter_first, int32_t N, uint32_t fl, int32_t K, double *draws, idhmc_tree_stats *stats)
+// `sum`: the draws are staged for an open summary too (also when the host wants none), and each block is reduced behind its launch
+static int run_blocks(idhmc_ctx *c, uint32_t iter_first, int32_t N, uint32_t fl, int32_t K, double *draws, idhmc_tree_stats *stats, bool sum)
 {
     int32_t prev_n0 = -1, prev_cnt = 0;
     int blk = 0;
     for (int32_t n0 = 0; n0 < N; n0 += K, ++blk) {
         const int32_t cnt = N - n0 < K ? N - n0 : K;
         const int b = blk & 1;
-        if (int rc = nuts_launch(c, iter_first + (uint32_t)n0, fl, (uint32_t)cnt, draws ? c->stage_q[b] : nullptr, stats ? c->stage_st[b] : nullptr)) return rc;
+        if (int rc = nuts_launch(c, iter_first + (uint32_t)n0, fl, (uint32_t)cnt, draws || sum ? c->stage_q[b] : nullptr, stats ? c->stage_st[b] : nullptr)) return rc;
         HIPCHK(hipEventRecord(c->ev_packed[b], c->stream));
+        if (sum) { if (int rc = summary_feed(c, c->stage_q[b], cnt)) return rc; }
         if (prev_n0 >= 0) { if (int rc = stage_copy(c, prev_n0, prev_cnt, b ^ 1, draws, stats)) return rc; }      // ... while block blk computes
         prev_n0 = n0; prev_cnt = cnt;
     }
@@ -106,17 +109,20 @@ static int run_blocks(idhmc_ctx *c, uint32_t iter_first, int32_t N, uint32_t fl,
     return IDHMC_OK;
 }
 // N transitions, the first one `iter_first`, for idhmc_tuning_stage (`adapt`: the stepsize adapts; `stop_on_abort`) and idhmc_mcmc:
-// in blocks of K transitions, in one launch, or one launch per transition
+// in blocks of K transitions, in one launch, or one launch per transition.  `feed` (idhmc_mcmc): an open summary takes every draw, so
+// the draws are staged on the device whether or not the host wants them; the host copies stay the non-null pointers' alone
 static int run_transitions(idhmc_ctx *c, uint32_t iter_first, int32_t N, uint32_t flags, bool adapt, bool stop_on_abort,
-                           double *draws, idhmc_tree_stats *stats)
+                           double *draws, idhmc_tree_stats *stats, bool feed)
 {
-    const bool any = draws || stats;
+    const bool sum = feed && c->sum.open;
+    const bool stage_q = draws || sum;
+    const bool any = stage_q || stats;
     // the global and the per-response stepsize adapt between transitions: one launch each
     const bool fusable = fuse_transitions(c) && !(adapt && (c->s.eps_mode == IDHMC_EPS_GLOBAL || c->s.eps_mode == IDHMC_EPS_PER_RESPONSE));
     const int32_t K = any && fusable ? block_transitions(c, N) : 0;
-    if (any) { if (int rc = stage_reserve(c, K ? K : 1, draws != nullptr, stats != nullptr)) return rc; }
+    if (any) { if (int rc = stage_reserve(c, K ? K : 1, stage_q, stats != nullptr)) return rc; }
     if (adapt && c->s.eps_mode == IDHMC_EPS_PER_CHAIN) flags |= IDHMC_T_ADAPT_EPS;
-    if (K) return run_blocks(c, iter_first, N, flags, K, draws, stats);     // the draws / records leave in blocks of K transitions
+    if (K) return run_blocks(c, iter_first, N, flags, K, draws, stats, sum);     // the draws / records leave in blocks of K transitions
     if (!any && fusable && N > 1) {
         // nothing leaves the device per transition: one launch (the kernel itself stops handing out
         // transitions once a chain has raised the abort code)
@@ -129,7 +135,7 @@ static int run_transitions(idhmc_ctx *c, uint32_t iter_first, int32_t N, uint32_
         // the reference throws as soon as eps < 1e-10 (:291-296): stop within kLag transitions of the one that set it
         if (stop_on_abort && pulse_abort(c, idhmc_ctx::kLag)) break;
         if (int rc = one_transition(c, iter_first + (uint32_t)n, flags, adapt)) return rc;
-        if (int rc = fetch_pack(c, n, draws != nullptr, stats != nullptr)) return rc;
+        if (int rc = fetch_pack(c, n, stage_q, stats != nullptr, sum)) return rc;
         if (n > 0) { if (int rc = stage_copy(c, n - 1, 1, (n - 1) & 1, draws, stats)) return rc; }   // ... while transition n computes
         done = n + 1;
     }
@@ -145,7 +151,7 @@ int idhmc_tuning_stage(idhmc_ctx *c, int32_t N, int32_t adapt_metric, uint32_t i
     if (int rc = idhmc_da_init(c)) return rc;                                    // src/warmup.jl:284
     if (adapt_metric) { if (int rc = idhmc_metric_begin(c)) return rc; }
     const double lambda = 5.0 / (double)N;                                       // src/warmup.jl:229
-    if (int rc = run_transitions(c, iter0 + 1u, N, adapt_metric ? IDHMC_T_ACCUM_METRIC : 0u, true, true, draws, stats)) return rc;
+    if (int rc = run_transitions(c, iter0 + 1u, N, adapt_metric ? IDHMC_T_ACCUM_METRIC : 0u, true, true, draws, stats, false)) return rc;
     // sharded: agree on the outcome first -- a rank that failed alone would leave the others in the pooled metric's all-reduces
     if (int rc = status_exchange(c, "warmup")) return rc;
     if (adapt_metric) { if (int rc = idhmc_metric_update(c, lambda)) return rc; } // :308-311
@@ -156,11 +162,15 @@ int idhmc_mcmc(idhmc_ctx *c, int32_t N, uint32_t iter0, double *draws, idhmc_tre
     CTXCHK(c);
     if (N < 0) return fail(IDHMC_ERR_BAD_ARG, "N must be >= 0");
     const uint32_t fl = (c->s.mom_mean ? IDHMC_T_ACCUM_MOMENTS : 0u) | (c->s.diag.n ? IDHMC_T_ACCUM_DIAG : 0u);
-    if (int rc = run_transitions(c, iter0 + 1u, N, fl, false, false, draws, stats)) return rc;
+    if (int rc = summary_admit(c, N)) return rc;
+    int rc = run_transitions(c, iter0 + 1u, N, fl, false, false, draws, stats, true);
     // A status still pending (a refused launch, a caller's own transition that underflowed) must not pass as success: a launch of
     // several transitions hands out none while the abort word is set, and the staging blocks are not zeroed.  A local check (it
     // also waits for the stream): sampling has no collective that a rank failing alone could leave the others waiting in.
-    return check_status(c, "mcmc");
+    // An open summary has then reduced staging rows that may never have been written: it is invalid until idhmc_summary_begin.
+    if (!rc) rc = check_status(c, "mcmc");
+    if (rc && c->sum.open) c->sum.valid = false;
+    return rc;
 }
 int idhmc_mcmc_with_warmup(idhmc_ctx *c, int32_t N, double *draws, idhmc_tree_stats *stats)
 {

@@ -39,6 +39,22 @@ using namespace idhmc;
         if (int rc_lanes_ = lanes_join(ctx)) return rc_lanes_;               \
     } while (0)
 
+// an open posterior summary (idhmc_summary_begin; idhmc_summary.hip): the tables are the reduction's own arguments,
+// DevState knows nothing of them
+struct Summary {
+    bool open = false, valid = false;     // valid: no idhmc_mcmc that fed it has failed
+    bool ranged = false;                  // a histogram range is set: values reduced from now on are binned
+    int64_t G = 0, groups = 0;            // chains per group, groups of this context
+    int32_t spg = 0, bins = 0;            // segments of IDHMC_SUMMARY_SEGMENT chains per group, interior bins
+    double *part = nullptr;               // [6][groups spg D] per-segment running state
+    double *fin = nullptr;                // [6][groups D] the fold of the segments (k_summary_finish)
+    double *rng = nullptr;                // [3][groups D] lo, hi, inv_w
+    uint32_t *hist = nullptr;             // [groups][D][bins + 2]
+    double *scales = nullptr;             // [scales_rows][H] group scales of a staged block's rows (GLM with coefficient groups)
+    int64_t scales_rows = 0;
+    uint64_t fed_t = 0, binned_t = 0;     // transitions reduced / binned since begin / set_range: times G, a group's counts
+};
+
 struct idhmc_ctx {
     int device = 0;
     DevState s{};
@@ -97,6 +113,7 @@ struct idhmc_ctx {
     int32_t stage_kq = 1, stage_kst = 1;  // transitions the staging buffers hold (idhmc_mcmc's launches of several transitions: more than one)
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_packed[2] = {nullptr, nullptr};
+    Summary sum;                          // fed by idhmc_mcmc and idhmc_summary_add_draws while open
     // Lanes of the dense single-step leapfrog (configs[3]).  One sweep of its matrix-core kernel is a load phase, a matrix
     // phase and a store phase that every CU goes through at the same time, so HBM idles while the matrix cores work and vice
     // versa.  Chains are independent, so the context cuts them into up to kLanes contiguous ranges of tiles, each
@@ -148,5 +165,9 @@ int pulse_abort(idhmc_ctx *c, int lag);
 int check_status(idhmc_ctx *c, const char *what);
 int status_exchange(idhmc_ctx *c, const char *what);
 double *xchg_buf(idhmc_ctx *c);
+int stage_reserve(idhmc_ctx *c, int32_t K, bool draws, bool stats);                        // idhmc_drivers.hip
+// idhmc_summary.hip, for idhmc_mcmc: may cnt more transitions be reduced; reduce the staged block [cnt][C][D] on the context's stream
+int summary_admit(idhmc_ctx *c, int64_t cnt);
+int summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt);
 int exchange(idhmc_ctx *c, double *buf);
 }

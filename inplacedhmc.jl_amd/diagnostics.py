@@ -138,3 +138,65 @@ def ess_from_moments(mean, var, n, cap=False):
     V = (n - 1.0) / n * W + Bn
     e = C * V / Bn
     return np.minimum(e, C * n) if cap else e
+
+
+# ---- posterior summaries reduced on the device (include/idhmc.h) -----------------------------------------------
+@dataclass
+class PosteriorSummary:
+    """What Engine.summary() returns: per group of chains and per reported parameter the pooled moments, extremes, sign counts and the
+    histogram.  n, binned: [groups]; mean, var, min, max, pos, lo, hi, inv_w: [groups][D]; counts: [groups][D][bins + 2] (bin 0 below lo,
+    bin bins + 1 from hi on), None without a histogram."""
+    chains_per_group: int
+    bins: int
+    n: np.ndarray
+    binned: np.ndarray
+    mean: np.ndarray
+    var: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    pos: np.ndarray
+    lo: np.ndarray
+    hi: np.ndarray
+    inv_w: np.ndarray
+    counts: object = None
+
+    @property
+    def sd(self):
+        return np.sqrt(self.var)
+
+    @property
+    def p_positive(self):
+        """P(theta > 0) = pos / n (NaN where nothing has been reduced)"""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.pos / self.n[:, None].astype(np.float64)
+
+    def quantiles(self, probs):
+        """[groups][D][len(probs)] from the histogram (idhmc_summary_quantiles): within one bin width (hi - lo) / bins of the sample's
+        order statistic unless it lies in an end bin -- then the estimate is the range's end, and a warning says so."""
+        import ctypes as C
+        import warnings
+        from . import _lib
+        if self.counts is None or self.bins < 1:
+            raise ValueError("the summary has no histogram (bins = 0)")
+        lib = _lib.load()
+        probs = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+        counts = np.ascontiguousarray(self.counts, dtype=np.uint32)
+        G, D = self.mean.shape
+        out = np.empty((G, D, len(probs)))
+        one = np.empty(len(probs))
+        dp = C.POINTER(C.c_double)
+        ends = 0
+        for g in range(G):
+            for d in range(D):
+                row = counts[g, d]
+                _lib.check(lib.idhmc_summary_quantiles(row.ctypes.data_as(C.POINTER(C.c_uint32)), int(self.bins), float(self.lo[g, d]),
+                                                       float(self.hi[g, d]), probs.ctypes.data_as(dp), len(probs), one.ctypes.data_as(dp)))
+                out[g, d] = one
+                nh = int(row.sum(dtype=np.uint64))
+                if nh:
+                    k = np.clip(np.ceil(probs * nh), 1, nh)
+                    ends += int(np.count_nonzero((k <= row[0]) | (k > nh - int(row[-1]))))
+        if ends:
+            warnings.warn("%d requested quantiles lie in an end bin of their histogram: the range's end is reported, not an estimate "
+                          "(set a wider range)" % ends, RuntimeWarning, stacklevel=2)
+        return out

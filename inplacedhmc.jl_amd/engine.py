@@ -570,6 +570,81 @@ class Engine:
         check(self.lib.idhmc_get_ebfmi(self.h, _dp(out)))
         return out
 
+    # ---- posterior summaries reduced on the device (include/idhmc.h) ----------------
+    def summary_begin(self, chains_per_group=None, bins=128):
+        """open a summary: mcmc() then reduces every draw on the device, pooled over groups of chains_per_group consecutive global chain
+        ids (None: the chains of a response of a many-response GLM, all chains otherwise); bins interior histogram bins, 0 for none"""
+        check(self.lib.idhmc_summary_begin(self.h, 0 if chains_per_group is None else int(chains_per_group), int(bins)))
+
+    def summary_dims(self):
+        g, cpg, d, b = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(self.lib.idhmc_summary_dims(self.h, C.byref(g), C.byref(cpg), C.byref(d), C.byref(b)))
+        return g.value, cpg.value, d.value, b.value
+
+    def summary_set_range(self, lo=None, hi=None, span=6.0):
+        """the histogram's range: arrays [groups][D], or (both None) mean -+ span sd of what has been accumulated; zeroes the histogram"""
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        if lo is None:
+            check(self.lib.idhmc_summary_set_range(self.h, None, None, float(span)))
+            return
+        try:
+            groups, _, D, _ = self.summary_dims()
+        except _lib.IdhmcError:
+            groups, D = 1, np.size(lo)      # (no summary open: let the library refuse)
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.size != groups * D or hi.size != groups * D:
+            raise ValueError("expected lo, hi of shape (%d, %d)" % (groups, D))
+        check(self.lib.idhmc_summary_set_range(self.h, _dp(lo), _dp(hi), float(span)))
+
+    def summary_add_draws(self, draws):
+        """reduce host draws [cnt][nchains][D] (saved earlier, or a test's) through the staging buffers and the reduction kernel"""
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim != 3 or draws.shape[1:] != (self.C, self.D):
+            raise ValueError("expected shape (cnt, %d, %d), got %s" % (self.C, self.D, draws.shape))
+        check(self.lib.idhmc_summary_add_draws(self.h, _dp(draws), draws.shape[0]))
+
+    def summary(self):
+        from .diagnostics import PosteriorSummary
+        groups, cpg, D, bins = self.summary_dims()
+        f = {k: np.empty((groups, D)) for k in ("mean", "var", "min", "max", "lo", "hi", "inv_w")}
+        n, binned = np.empty(groups, dtype=np.int64), np.empty(groups, dtype=np.int64)
+        pos = np.empty((groups, D), dtype=np.int64)
+        counts = np.zeros((groups, D, bins + 2), dtype=np.uint32) if bins > 0 else None
+        ip = C.POINTER(C.c_int64)
+        check(self.lib.idhmc_get_summary(self.h, n.ctypes.data_as(ip), binned.ctypes.data_as(ip), _dp(f["mean"]), _dp(f["var"]),
+                                         _dp(f["min"]), _dp(f["max"]), pos.ctypes.data_as(ip), _dp(f["lo"]), _dp(f["hi"]), _dp(f["inv_w"]),
+                                         counts.ctypes.data_as(C.POINTER(C.c_uint32)) if bins > 0 else None))
+        return PosteriorSummary(chains_per_group=cpg, bins=bins, n=n, binned=binned, pos=pos, counts=counts, **f)
+
+    def summary_end(self):
+        check(self.lib.idhmc_summary_end(self.h))
+
+    def mcmc_summary(self, N, iter0, pilot=None, chains_per_group=None, bins=128, span=6.0):
+        """N transitions reduced on the device, nothing stored: begin, `pilot` transitions, the range from their moments, the other
+        N - pilot, summary, end.  The pilot draws count in the moments, sign counts, min and max, not in the histogram.  The default
+        pilot is the smallest count with pilot * chains_per_group >= 256, at least 2 and at most N // 2: a heuristic that nobody has
+        measured -- a range from few values can put tail quantiles in an end bin (quantiles() warns)."""
+        N = int(N)
+        self.summary_begin(chains_per_group, bins)
+        try:
+            if bins > 0:
+                if pilot is None:
+                    cpg = self.summary_dims()[1]
+                    pilot = min(max(2, -(-256 // cpg)), N // 2)
+                pilot = int(pilot)
+                if not 1 <= pilot < N:
+                    raise ValueError("pilot = %d must be at least 1 and below N = %d" % (pilot, N))
+                self.mcmc(pilot, iter0, store_draws=False, store_stats=False)
+                self.summary_set_range(span=span)
+                self.mcmc(N - pilot, iter0 + pilot, store_draws=False, store_stats=False)
+            else:
+                self.mcmc(N, iter0, store_draws=False, store_stats=False)
+            return self.summary()
+        finally:
+            self.summary_end()
+
     # ---- drivers -----------------------------------------------------------------------------------
     def _bufs(self, N, store_draws, store_stats):
         draws = np.empty((N, self.C, self.D)) if store_draws else None
