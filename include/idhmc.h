@@ -265,6 +265,41 @@ int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int
                                const idhmc_options *opt, uint64_t seed);
 /* M and chains_per_response of a context made by idhmc_create_glm_responses; 1 and 0 for every other context */
 int idhmc_glm_responses(const idhmc_ctx *ctx, int64_t *M, int64_t *chains_per_response);
+/* Priors beyond the Gaussian.  Each sampled coordinate c < D = Dx + A + H carries mu_c and tau_c (idhmc_glm_desc) and
+ * here a kind_c and a nu_c.  With d = q_c - mu_c, T the partial that accumulates -2 log prior (up to a constant) and G_c the
+ * likelihood's part of the gradient -- the kernels and the tests' C restatement follow this bit for bit: plain operations in the
+ * association written, dfma, dexp and dlog1p those of idhmc_math.hpp --
+ *
+ *   kind                    meaning                                      contribution to T                         g_c
+ *   0 NORMAL                q_c ~ N(mu, 1 / tau)                         T = dfma(tau d, d, T)                     dfma(-tau, d, G_c)
+ *   1 STUDENT_T             q_c = mu + t_nu / sqrt(tau)                  a = tau d; s = a d;
+ *                                                                        T = T + (nu + 1) dlog1p(s / nu)           G_c + (-((nu + 1) a) / (nu + s))
+ *   2 LOG_HALF_NORMAL       exp(q_c) half-normal, scale exp(mu)          e = dexp(2 d);  T = T + (e - 2 d)         G_c + (1 - e)
+ *   3 LOG_HALF_STUDENT_T    exp(q_c) half-t_nu, scale exp(mu)            e = dexp(2 d);
+ *                           (half-Cauchy: nu = 1)                        T = T + ((nu + 1) dlog1p(e / nu) - 2 d)   G_c + (1 - ((nu + 1) e) / (nu + e))
+ *   4 LOG_EXPONENTIAL       exp(q_c) exponential, mean exp(mu)           e = dexp(d);  T = T + 2 (e - d)           G_c + (1 - e)
+ *
+ * Everything behind T is unchanged: l(q) = -sum_i v_i - T_total / 2.  The log kinds are priors on sigma = exp(q_c) -- a group's
+ * standard deviation exp(omega_g), a dispersion exp(a_j) -- and include the Jacobian of exp: the coordinate stays unconstrained.
+ * Each kind is finite wherever its log density is, and that ends at: kind 1, tau d^2 finite (|d| < 1.3e154 / sqrt(tau)); kinds 2 and 3,
+ * 2 d < 709.78 (dexp finite; every more negative d is fine: e = 0, T = -2 d); kind 4, d < 709.08 (2 exp(d) finite).  Past those ends T is +inf, which
+ * the engine reads as l(q) = -inf: the ordinary rejected point.
+ *
+ * idhmc_create_glm_priors makes the context of idhmc_create_glm (M = 1, chains_per_response = 0) or of idhmc_create_glm_responses
+ * (anything else) with these priors; kind and nu have Dx + A + H entries each, nu may be NULL if no kind takes one.  priors == NULL,
+ * priors->kind == NULL or every kind 0 gives the existing context: the same kernels, the same bits.  Otherwise the GLM's kernels are
+ * compiled with the table above in their last loop (no LDS is added: idhmc_glm_form is what it is for the same (L, A, metric) with
+ * Gaussian priors).  Refused with IDHMC_ERR_BAD_ARG before the device is touched: a kind outside 0..4; nu not finite or <= 0 for
+ * kinds 1 and 3 (or nu NULL with such a kind); nu != 0 for kinds 0, 2 and 4; tau != 1 for kinds 2..4 (their one scale is exp(mu));
+ * kinds 2..4 on a coordinate c < Dx (a coefficient is not a logarithm); and everything the other two functions refuse. */
+enum { IDHMC_PRIOR_NORMAL = 0, IDHMC_PRIOR_STUDENT_T = 1, IDHMC_PRIOR_LOG_HALF_NORMAL = 2, IDHMC_PRIOR_LOG_HALF_STUDENT_T = 3,
+       IDHMC_PRIOR_LOG_EXPONENTIAL = 4 };
+typedef struct { const int32_t *kind; const double *nu; } idhmc_glm_priors;   /* Dx + A + H entries each; nu may be NULL if no kind takes one */
+int idhmc_create_glm_priors(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                            const idhmc_glm_desc *glm, const idhmc_glm_priors *priors,
+                            int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
+/* kind and nu as the context was given them, D entries each; all 0 for every other context */
+int idhmc_glm_priors_get(const idhmc_ctx *ctx, int32_t *kind, double *nu);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

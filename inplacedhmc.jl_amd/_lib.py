@@ -26,6 +26,10 @@ class GlmDesc(C.Structure):
                 ("source", C.c_char_p)]
 
 
+class GlmPriors(C.Structure):
+    _fields_ = [("kind", C.POINTER(C.c_int32)), ("nu", C.POINTER(C.c_double))]
+
+
 class Options(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("min_delta", C.c_double),
                 ("da_delta", C.c_double), ("da_gamma", C.c_double), ("da_kappa", C.c_double),
@@ -63,6 +67,9 @@ SYMBOLS = {
     "idhmc_create_glm": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(Options), _u64]),
     "idhmc_create_glm_responses": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), _i64, _i64, C.POINTER(Options), _u64]),
     "idhmc_glm_responses": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "idhmc_create_glm_priors": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), _i64, _i64,
+                                          C.POINTER(Options), _u64]),
+    "idhmc_glm_priors_get": (C.c_int, [_vp, C.POINTER(_i32), _dp]),
     "idhmc_destroy": (C.c_int, [_vp]),
     "idhmc_set_stream": (C.c_int, [_vp, _vp]),
     "idhmc_synchronize": (C.c_int, [_vp]),

@@ -1,4 +1,4 @@
-// idhmc_create.hip -- a context's life: the argument checks of the three creation entry points (every one answers before the
+// idhmc_create.hip -- a context's life: the argument checks of the creation entry points (every one answers before the
 // device is looked for), set-up, idhmc_destroy, the default options and what a context can be asked about itself.
 #include "idhmc_host.hpp"
 
@@ -59,6 +59,8 @@ struct GlmParts {
     const int32_t *grp = nullptr;        // [Dx], H > 0
     bool responses = false;    // idhmc_create_glm_responses: Y is [M][n][K], global chain g samples response g / R
     int64_t M = 1, R = 0;      // (1, 0 otherwise)
+    const int32_t *pkind = nullptr;      // [D] idhmc_create_glm_priors with some kind != 0: the priors' kinds and their nu (never null then)
+    const double *pnu = nullptr;
 };
 // The head of a packed params array into *g: `head` = 0 (a logistic regression's [X | y]), 2 ([K, nc, c | X | Y]) or 3
 // ([K, nc, A, c | X | Y]) doubles in front of the constants.  The entries are checked as doubles (integral, hence finite, and in
@@ -210,6 +212,25 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         if (int rc = dalloc(c, &dg, L)) return rc;
         HIPCHK(hipMemcpyAsync(dg, hg.data(), sizeof(int32_t) * hg.size(), hipMemcpyHostToDevice, c->stream));
         s.lr_grp = dg;
+    }
+    std::vector<int32_t> hk;
+    std::vector<double> hnu;
+    if (g.pkind) {
+        // the prior of every coordinate: kind 0 (and nu 0) past the sampled ones
+        const int64_t Dall = s.D;
+        hk.assign((size_t)L, 0);
+        hnu.assign((size_t)L, 0.0);
+        for (int64_t k = 0; k < Dall; ++k) { hk[(size_t)k] = g.pkind[k]; hnu[(size_t)k] = g.pnu[k]; }
+        int32_t *dk = nullptr;
+        double *dnu = nullptr;
+        if (int rc = dalloc(c, &dk, L)) return rc;
+        if (int rc = dalloc(c, &dnu, L)) return rc;
+        HIPCHK(hipMemcpyAsync(dk, hk.data(), sizeof(int32_t) * hk.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dnu, hnu.data(), sizeof(double) * hnu.size(), hipMemcpyHostToDevice, c->stream));
+        s.lr_pkind = dk;
+        s.lr_pnu = dnu;
+        c->prior_kind.assign(g.pkind, g.pkind + Dall);
+        c->prior_nu.assign(g.pnu, g.pnu + Dall);
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
     s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
@@ -479,9 +500,44 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     return create_context(out, device, nchains, first_chain_id, model, opt_in, seed, nullptr);
 }
 
-// idhmc_create_glm and idhmc_create_glm_responses
+// The priors of idhmc_create_glm_priors: every check of kind and nu.  *any: some kind is not 0 (none is: the context is the one
+// without priors).  nu_out: nu with 0 wherever the caller passed none.
+static int validate_priors(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, std::vector<double> *nu_out, bool *any)
+{
+    *any = false;
+    if (!pr || !pr->kind) {
+        if (pr && pr->nu) return fail(IDHMC_ERR_BAD_ARG, "GLM: priors->nu without priors->kind");
+        return IDHMC_OK;
+    }
+    const int D = glm->Dx + glm->A + glm->H;
+    nu_out->assign((size_t)D, 0.0);
+    for (int c = 0; c < D; ++c) {
+        const int32_t k = pr->kind[c];
+        const double nu = pr->nu ? pr->nu[c] : 0.0;
+        if (k < IDHMC_PRIOR_NORMAL || k > IDHMC_PRIOR_LOG_EXPONENTIAL)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: prior kind[%d] = %d is outside 0..4", c, k);
+        const bool takes_nu = k == IDHMC_PRIOR_STUDENT_T || k == IDHMC_PRIOR_LOG_HALF_STUDENT_T;
+        if (takes_nu && !pr->nu) return fail(IDHMC_ERR_BAD_ARG, "GLM: prior kind[%d] = %d needs nu (priors->nu is NULL)", c, k);
+        if (takes_nu && !(std::isfinite(nu) && nu > 0.0))
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: prior nu[%d] = %g must be finite and > 0 (kind %d)", c, nu, k);
+        if (!takes_nu && nu != 0.0) return fail(IDHMC_ERR_BAD_ARG, "GLM: prior nu[%d] = %g must be 0 (kind %d takes no nu)", c, nu, k);
+        if (k >= IDHMC_PRIOR_LOG_HALF_NORMAL) {
+            if (c < glm->Dx)
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: prior kind[%d] = %d is a prior on exp(q): coordinate %d is a coefficient, not a logarithm "
+                            "(kinds 2..4 are for the A + H coordinates behind the Dx = %d coefficients)", c, k, c, glm->Dx);
+            if (glm->tau && glm->tau[c] != 1.0)
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: prior tau[%d] = %g must be 1 (kind %d: its one scale is exp(mu))", c, glm->tau[c], k);
+        }
+        (*nu_out)[(size_t)c] = nu;
+        if (k != IDHMC_PRIOR_NORMAL) *any = true;
+    }
+    return IDHMC_OK;
+}
+
+// idhmc_create_glm, idhmc_create_glm_responses and idhmc_create_glm_priors
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
-                      bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed)
+                      bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
+                      const idhmc_glm_priors *priors = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
@@ -508,7 +564,11 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     m.mu = glm->mu;
     m.tau = glm->tau;
     m.source = glm->source;
-    const GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
+    std::vector<double> nu;
+    bool any = false;
+    if (int rc = validate_priors(glm, priors, &nu, &any)) return rc;
+    GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
+    if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
     return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
 }
 
@@ -525,6 +585,26 @@ int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_responses: null argument");
     return create_glm(out, device, nchains, first_chain_id, glm, true, M, chains_per_response, opt_in, seed);
+}
+
+int idhmc_create_glm_priors(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                            const idhmc_glm_desc *glm, const idhmc_glm_priors *priors,
+                            int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_priors: null argument");
+    // (1, 0): the context of idhmc_create_glm; anything else: the one of idhmc_create_glm_responses, which refuses what it refuses
+    const bool responses = !(M == 1 && chains_per_response == 0);
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors);
+}
+
+int idhmc_glm_priors_get(const idhmc_ctx *c, int32_t *kind, double *nu)
+{
+    if (!c || !kind || !nu) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_priors_get: null argument");
+    for (int k = 0; k < c->s.D; ++k) {
+        kind[k] = c->prior_kind.empty() ? 0 : c->prior_kind[(size_t)k];
+        nu[k] = c->prior_nu.empty() ? 0.0 : c->prior_nu[(size_t)k];
+    }
+    return IDHMC_OK;
 }
 
 int idhmc_glm_responses(const idhmc_ctx *c, int64_t *M, int64_t *chains_per_response)

@@ -54,6 +54,23 @@
 // Y; in the matrix-core form the 16 rows of a tile are 16 chains of any responses, so the requester publishes its offset in
 // column L of its Q row (padding: zphase, gphase and both row accesses of the requester touch columns < L only) and the Z wavefronts
 // read y per accumulator row instead of once per lane.  No LDS, no tile, no barrier is added.
+//
+// Priors beyond the Gaussian (idhmc_create_glm_priors): Obs::kPriors, a compile-time flag of the policy (false for the
+// policies above and for every model whose kinds are all 0: none of their instructions changes).  Every coordinate c carries kind_c
+// (DevState::lr_pkind) and nu_c (lr_pnu) next to mu_c and tau_c; d = q_c - mu_c, and the last loop of both forms becomes, per coordinate
+// (glm_prior; plain operations in the association written, dfma where written):
+//   0 NORMAL               T = dfma(tau d, d, T)                                        g = dfma(-tau, d, G)          (as above)
+//   1 STUDENT_T            a = tau d; s = a d;   T = T + (nu + 1) dlog1p(s / nu)          g = G + (-((nu + 1) a) / (nu + s))
+//   2 LOG_HALF_NORMAL      e = dexp(2 d);        T = T + (e - 2 d)                        g = G + (1 - e)
+//   3 LOG_HALF_STUDENT_T   e = dexp(2 d);        T = T + ((nu + 1) dlog1p(e / nu) - 2 d)  g = G + (1 - ((nu + 1) e) / (nu + e))
+//   4 LOG_EXPONENTIAL      e = dexp(d);          T = T + 2 (e - d)                        g = G + (1 - e)
+// T is -2 log prior up to a constant; the log kinds are priors on exp(q_c) with scale exp(mu_c) and carry the Jacobian of exp.  The
+// order of accumulation is unchanged (chunks ascending per lane component), padded coordinates are kind 0, and everything behind T
+// is as above.  The two components of a lane, and neighbouring chunks, may be of different kinds: the kinds are branches of one
+// function, evaluated after barrier C in the matrix-core form, with nothing of theirs alive across multiply().  No LDS is added.
+// Each kind is finite wherever its log density is, and that ends at: kind 1, tau d^2 finite (|d| < 1.3e154 / sqrt(tau)); kinds 2
+// and 3, 2 d < 709.78 (every more negative d is fine: e = 0 and T = -2 d); kind 4, d < 709.08 (2 exp(d) finite).  Past those ends T is +inf (g may be
+// NaN), which the engine reads as l(q) = -inf: the ordinary rejected point.
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -161,6 +178,33 @@ IDHMC_DEV void glm_group_chain(Vec<NCH> &G, const Vec<NCH> &q, const int2 *grp2,
     }
 }
 
+// The prior of one coordinate (the table of the header comment): kind and nu select the row, d = q_c - mu_c, G the likelihood's part
+// of the gradient.  Adds the coordinate's -2 log prior to T and returns g_c.
+IDHMC_DEV double glm_prior(int kind, double nu, double tau, double d, double G, double &T)
+{
+    if (kind == 0) {
+        T = dfma(tau * d, d, T);
+        return dfma(-tau, d, G);
+    }
+    if (kind == 1) {
+        const double a = tau * d, s = a * d;
+        T = T + (nu + 1.0) * dlog1p(s / nu);
+        return G + (-((nu + 1.0) * a) / (nu + s));
+    }
+    if (kind == 4) {
+        const double e = dexp(d);
+        T = T + 2.0 * (e - d);
+        return G + (1.0 - e);
+    }
+    const double e = dexp(2.0 * d);
+    if (kind == 2) {
+        T = T + (e - 2.0 * d);
+        return G + (1.0 - e);
+    }
+    T = T + ((nu + 1.0) * dlog1p(e / nu) - 2.0 * d);
+    return G + (1.0 - ((nu + 1.0) * e) / (nu + e));
+}
+
 // v_i and r_i of one observation (y is 0 or 1)
 IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 {
@@ -174,7 +218,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false;
+    static constexpr bool kResponses = false, kPriors = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -194,6 +238,8 @@ struct GlmWave {
     const double2 *mu2, *tau2;   // lane-offset, device
     const double *cst;       // the constants, device
     const int2 *grp2;        // the group ids, lane-offset, device (Obs::H > 0)
+    const int2 *kind2;       // the priors' kinds and their nu, lane-offset, device (Obs::kPriors)
+    const double2 *nu2;
     double *buf;             // this wavefront's LDS vector, L doubles
     int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, then Obs::H log scales)
     template <class State>
@@ -206,6 +252,10 @@ struct GlmWave {
         tau2 = reinterpret_cast<const double2 *>(s.tau) + lane_;
         cst = s.user_params;
         if constexpr (Obs::H > 0) grp2 = reinterpret_cast<const int2 *>(s.lr_grp) + lane_;
+        if constexpr (Obs::kPriors) {
+            kind2 = reinterpret_cast<const int2 *>(s.lr_pkind) + lane_;
+            nu2 = reinterpret_cast<const double2 *>(s.lr_pnu) + lane_;
+        }
         buf = lds_vec;
         D = s.D - Obs::A - Obs::H;
         n = s.lr_n;
@@ -310,9 +360,16 @@ struct GlmWave {
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
             const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
-            t0 = dfma(t.x * dx, dx, t0);
-            t1 = dfma(t.y * dy, dy, t1);
-            g.c[j] = make_double2(dfma(-t.x, dx, G.c[j].x), dfma(-t.y, dy, G.c[j].y));
+            if constexpr (Obs::kPriors) {
+                const int2 k = kind2[j * 64];
+                const double2 nu = nu2[j * 64];
+                g.c[j].x = glm_prior(k.x, nu.x, t.x, dx, G.c[j].x, t0);
+                g.c[j].y = glm_prior(k.y, nu.y, t.y, dy, G.c[j].y, t1);
+            } else {
+                t0 = dfma(t.x * dx, dx, t0);
+                t1 = dfma(t.y * dy, dy, t1);
+                g.c[j] = make_double2(dfma(-t.x, dx, G.c[j].x), dfma(-t.y, dy, G.c[j].y));
+            }
         }
         const double lq = -0.5 * wave_sum(dfma(2.0, a0, t0), dfma(2.0, a1, t1));
         return dfinite(lq) ? lq : -kInf;
@@ -359,6 +416,8 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     const double2 *mu2, *tau2;   // lane-offset, device
     const double *cst;           // the constants, device
     const int2 *grp2;            // the group ids, lane-offset, device (Obs::H > 0)
+    const int2 *kind2;           // the priors' kinds and their nu, lane-offset, device (Obs::kPriors)
+    const double2 *nu2;
     double *tile;
     int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, then Obs::H log scales)
     template <class State>
@@ -366,6 +425,10 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     {
         dx = s.D - Obs::A - Obs::H;
         if constexpr (Obs::H > 0) grp2 = reinterpret_cast<const int2 *>(s.lr_grp) + lane_;
+        if constexpr (Obs::kPriors) {
+            kind2 = reinterpret_cast<const int2 *>(s.lr_pkind) + lane_;
+            nu2 = reinterpret_cast<const double2 *>(s.lr_pnu) + lane_;
+        }
         x = s.lr_x;
         xt = s.lr_xt;
         y = s.lr_y;
@@ -575,9 +638,17 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 }
             }
             const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
-            t0 = dfma(t.x * dx, dx, t0);
-            t1 = dfma(t.y * dy, dy, t1);
-            g.c[j] = make_double2(dfma(-t.x, dx, G.x), dfma(-t.y, dy, G.y));
+            if constexpr (Obs::kPriors) {
+                // kinds and nu are read here, after barrier C: nothing of the prior is alive across multiply()
+                const int2 k = kind2[j * 64];
+                const double2 nu = nu2[j * 64];
+                g.c[j].x = glm_prior(k.x, nu.x, t.x, dx, G.x, t0);
+                g.c[j].y = glm_prior(k.y, nu.y, t.y, dy, G.y, t1);
+            } else {
+                t0 = dfma(t.x * dx, dx, t0);
+                t1 = dfma(t.y * dy, dy, t1);
+                g.c[j] = make_double2(dfma(-t.x, dx, G.x), dfma(-t.y, dy, G.y));
+            }
         }
         l0 = dfma(2.0, A.x, t0);
         l1 = dfma(2.0, A.y, t1);

@@ -85,6 +85,9 @@ struct DevState {
     unsigned long long *total_steps;  // [32]: the pulse the host polls = {[0] leapfrog steps, [1] abort code (an IDHMC_ERR_* a
                                       // chain raised: eps underflow)}; [2..9] cycle stamps of the diagnostic build (-DIDHMC_STAMPS)
     const int32_t *lr_grp;    // [L] a GLM with lr_h > 0: the group of every coordinate, -1 for ungrouped and padded ones (null otherwise)
+    // a GLM with a non-Gaussian prior on some coordinate (idhmc_create_glm_priors; both null otherwise)
+    const int32_t *lr_pkind;  // [L] IDHMC_PRIOR_* of every coordinate, 0 for padded ones
+    const double *lr_pnu;     // [L] degrees of freedom of the kinds that take them, 0 elsewhere
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -133,7 +136,7 @@ constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
 struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
-// K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses)
+// K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

@@ -4,7 +4,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import GlmDesc, ModelDesc, Options, check
+from . import glm as _glm
+from ._lib import GlmDesc, GlmPriors, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -161,7 +162,8 @@ def _prior(D, prior_mu, prior_tau):
     return mu, tau
 
 
-def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None):
+def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None, prior_kind=None,
+        prior_nu=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -191,7 +193,15 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     diagonal metric per response (D <= 512), bit-identical to a single-response model in EPS_GLOBAL / METRIC_POOLED on those chains;
     an Engine in either mode holds whole responses (first_chain and the number of chains are multiples of R).
     Each chain's draws are bit-identical to those of a single-response model on its Y.  glm.response_of_chain, glm.by_response and
-    diagnostics.rhat_by_response sort chains and draws by response.  The Model exposes M and R (1 and None without the keyword)."""
+    diagnostics.rhat_by_response sort chains and draws by response.  The Model exposes M and R (1 and None without the keyword).
+
+    prior_kind, prior_nu: scalars or length Dx + A + H -- priors beyond the Gaussian (idhmc_create_glm_priors).  A kind is one of
+    glm.PRIOR_NORMAL (the default), PRIOR_STUDENT_T, PRIOR_LOG_HALF_NORMAL, PRIOR_LOG_HALF_STUDENT_T, PRIOR_LOG_EXPONENTIAL or its name;
+    prior_mu and prior_tau keep their places as location and precision (Student-t: q = mu + t_nu / sqrt(tau)), the log kinds put a
+    half-normal, half-t or exponential prior with scale exp(mu) on exp(q) for an auxiliary coordinate or a group scale (tau = 1 there,
+    never on a coefficient), prior_nu is the degrees of freedom of the two t kinds and 0 elsewhere.  glm.priors() assembles all four
+    from glm.normal, glm.student_t, glm.half_normal, glm.half_student_t and glm.exponential.  With every kind PRIOR_NORMAL the model is
+    the one without the keywords.  The Model exposes prior_kind and prior_nu (None without the keywords); Engine.glm_priors() reads them back."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -248,9 +258,12 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     if not isinstance(source, str) or not source.strip():
         raise ValueError("a GLM needs HIP source defining glm_observation")
     mu, tau = _prior(D, prior_mu, prior_tau)
+    kind, nu = _glm.prior_kinds(prior_kind, prior_nu, D, Dx, tau)
+    priors = kind is not None and bool(kind.any())
     K = Y.shape[-1]
-    if H > 0 or R is not None:
-        # handed over in parts (idhmc_create_glm, idhmc_create_glm_responses): the packed params are not stretched for the groups or the responses
+    if H > 0 or R is not None or priors:
+        # handed over in parts (idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors): the packed params are not stretched
+        # for the groups, the responses or the priors
         m = Model(MODEL_GLM_AUX if A else MODEL_GLM, D, mu=mu, tau=tau, source=source)
         m.X, m.Y, m.constants = np.ascontiguousarray(X), np.ascontiguousarray(Y), np.ascontiguousarray(c)
     elif A == 0:
@@ -261,6 +274,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
                   params=np.concatenate([[float(K), float(c.size), float(A)], c, X.ravel(), Y.ravel()]))
     m.n, m.K, m.nc, m.Dx, m.A, m.H, m.groups = n, K, c.size, Dx, A, H, grp
     m.M, m.R = M, R
+    m.prior_kind, m.prior_nu = kind, nu
     return m
 
 
@@ -283,7 +297,14 @@ class Engine:
         self.opt = options if options is not None else default_options()
         self.C, self.D = int(nchains), model.D
         h = C.c_void_p()
-        if getattr(model, "R", None) is not None:
+        kind = getattr(model, "prior_kind", None)
+        if kind is not None and kind.any():
+            desc = model.glm_desc()
+            pr = GlmPriors(kind=kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=_dp(model.prior_nu))
+            R = getattr(model, "R", None)
+            check(self.lib.idhmc_create_glm_priors(C.byref(h), device, self.C, first_chain, C.byref(desc), C.byref(pr),
+                                                   model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
+        elif getattr(model, "R", None) is not None:
             desc = model.glm_desc()
             check(self.lib.idhmc_create_glm_responses(C.byref(h), device, self.C, first_chain, C.byref(desc), model.M, model.R,
                                                       C.byref(self.opt), seed))
@@ -397,6 +418,12 @@ class Engine:
         m, r = C.c_int64(0), C.c_int64(0)
         check(self.lib.idhmc_glm_responses(self.h, C.byref(m), C.byref(r)))
         return int(m.value), int(r.value)
+
+    def glm_priors(self):
+        """(kind, nu) of every sampled coordinate as the context holds them (GLM(..., prior_kind=, prior_nu=)); zeros for every other model"""
+        kind, nu = np.zeros(self.D, np.int32), np.zeros(self.D)
+        check(self.lib.idhmc_glm_priors_get(self.h, kind.ctypes.data_as(C.POINTER(C.c_int32)), _dp(nu)))
+        return kind, nu
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -55,8 +55,33 @@ sigma = exp(omega).
 Every source above also works unchanged with several responses, GLM(..., chains_per_response=R): Y is (M, n, K)
 and the chain of global id g samples the posterior of Y[g // R].  response_of_chain(model, nchains, first_chain) names each chain's
 response and by_response(model, draws, first_chain) sorts draws (or any per-chain array) by it.
+
+Priors beyond the Gaussian, GLM(..., prior_kind=..., prior_nu=...) (idhmc_create_glm_priors): every sampled
+coordinate has a kind next to its prior_mu and prior_tau, and every source above works unchanged with them.  d = q - mu:
+
+  PRIOR_NORMAL              q ~ N(mu, 1 / tau)                                          (the default, on every coordinate)
+  PRIOR_STUDENT_T           q = mu + t_nu / sqrt(tau)                                   (Cauchy: nu = 1)
+  PRIOR_LOG_HALF_NORMAL     exp(q) is half-normal with scale exp(mu)
+  PRIOR_LOG_HALF_STUDENT_T  exp(q) is half-t_nu with scale exp(mu)                      (half-Cauchy: nu = 1)
+  PRIOR_LOG_EXPONENTIAL     exp(q) is exponential with mean exp(mu)
+
+The log kinds are for the coordinates that are logarithms -- a (the A auxiliary coordinates of the sources above) and omega (the H
+group scales) -- and include the Jacobian of exp; they take tau = 1.  priors(Dx, A, H, coefficients=, aux=, scales=) assembles the
+four keyword arguments from normal(), student_t(), half_normal(), half_student_t() and exponential().
+
+Each is finite wherever the log density itself is, and that ends at the arguments of dexp and at the square of d:
+  PRIOR_STUDENT_T           tau d^2 finite: |d| < 1.3e154 / sqrt(tau).
+  PRIOR_LOG_HALF_NORMAL     2 d < 709.78 (exp(2 d) finite); every more negative d is fine (exp(2 d) is 0 and -2 log p = -2 d).
+  PRIOR_LOG_HALF_STUDENT_T  2 d < 709.78, as above.
+  PRIOR_LOG_EXPONENTIAL     d < 709.08 (2 exp(d) finite); every more negative d is fine.
+Past those ends -2 log p is +inf, which the engine reads as l(q) = -inf: the ordinary rejected point.
 """
+import collections
+
 import numpy as np
+
+PRIOR_NORMAL, PRIOR_STUDENT_T, PRIOR_LOG_HALF_NORMAL, PRIOR_LOG_HALF_STUDENT_T, PRIOR_LOG_EXPONENTIAL = range(5)
+PRIOR_NAMES = ("NORMAL", "STUDENT_T", "LOG_HALF_NORMAL", "LOG_HALF_STUDENT_T", "LOG_EXPONENTIAL")
 
 POISSON_LOG = r"""
 __device__ void glm_observation(double z, const GlmObs &o, double &r, double &v)
@@ -318,3 +343,118 @@ def coefficients(model, draws):
     grp = np.asarray(model.groups)
     s = np.where(grp >= 0, sigma[..., np.maximum(grp, 0)], 1.0)
     return s * u
+
+
+# ---- priors ---------------------------------------------------------------------------------------------------------------------------
+def prior_kinds(prior_kind, prior_nu, D, Dx, tau):
+    """GLM()'s validation of prior_kind and prior_nu (scalars or length D; kinds as integers or names): (kind int32 (D,), nu (D,)),
+    or (None, None) when neither is given.  The checks are idhmc_create_glm_priors'."""
+    if prior_kind is None:
+        if prior_nu is not None:
+            raise ValueError("prior_nu needs prior_kind (only PRIOR_STUDENT_T and PRIOR_LOG_HALF_STUDENT_T take a nu)")
+        return None, None
+    raw = prior_kind if isinstance(prior_kind, np.ndarray) else np.asarray(prior_kind, dtype=object)      # (names and integers may mix)
+    if raw.ndim > 1 or (raw.ndim == 1 and raw.shape[0] != D):
+        raise ValueError("prior_kind must be a scalar or have one entry per sampled coordinate (%d), got shape %s" % (D, raw.shape))
+    kind = np.empty(D, np.int32)
+    for c, k in enumerate(np.broadcast_to(raw, (D,)).tolist()):
+        if isinstance(k, str):
+            name = k[6:] if k.startswith("PRIOR_") else k
+            if name not in PRIOR_NAMES:
+                raise ValueError("prior_kind[%d] = %r is not one of %s" % (c, k, ", ".join(PRIOR_NAMES)))
+            k = PRIOR_NAMES.index(name)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k <= 4:
+            raise ValueError("prior_kind[%d] = %r must be an integer in 0..4 or one of %s" % (c, k, ", ".join(PRIOR_NAMES)))
+        kind[c] = k
+    if prior_nu is None:
+        nu = np.zeros(D)
+    else:
+        nu = np.asarray(prior_nu, dtype=np.float64)
+        if nu.ndim > 1 or (nu.ndim == 1 and nu.shape[0] != D):
+            raise ValueError("prior_nu must be a scalar or have one entry per sampled coordinate (%d), got shape %s" % (D, nu.shape))
+        nu = np.array(np.broadcast_to(nu, (D,)))
+    for c in range(D):
+        k = int(kind[c])
+        if k in (PRIOR_STUDENT_T, PRIOR_LOG_HALF_STUDENT_T):
+            if not (np.isfinite(nu[c]) and nu[c] > 0.0):
+                raise ValueError("prior_nu[%d] = %r must be finite and > 0 (PRIOR_%s)" % (c, float(nu[c]), PRIOR_NAMES[k]))
+        elif nu[c] != 0.0:
+            raise ValueError("prior_nu[%d] = %r must be 0 (PRIOR_%s takes no nu)" % (c, float(nu[c]), PRIOR_NAMES[k]))
+        if k >= PRIOR_LOG_HALF_NORMAL:
+            if c < Dx:
+                raise ValueError("prior_kind[%d] = PRIOR_%s is a prior on exp(q): coordinate %d is a coefficient, not a logarithm (the log "
+                                 "kinds are for the auxiliary coordinates and the group scales behind the %d coefficients)"
+                                 % (c, PRIOR_NAMES[k], c, Dx))
+            if tau is not None and tau[c] != 1.0:
+                raise ValueError("prior_tau[%d] = %r must be 1 (PRIOR_%s: its one scale is exp(prior_mu))" % (c, float(tau[c]), PRIOR_NAMES[k]))
+    return kind, nu
+
+
+# one coordinate's prior as priors() takes it: the kind and the three numbers that go with it
+PriorSpec = collections.namedtuple("PriorSpec", "kind mu tau nu")
+
+
+def _positive(what, x):
+    x = float(x)
+    if not (np.isfinite(x) and x > 0.0):
+        raise ValueError("%s = %r must be finite and > 0" % (what, x))
+    return x
+
+
+def _finite(what, x):
+    x = float(x)
+    if not np.isfinite(x):
+        raise ValueError("%s = %r must be finite" % (what, x))
+    return x
+
+
+def normal(mean=0.0, sd=1.0):
+    """q ~ N(mean, sd^2)"""
+    return PriorSpec(PRIOR_NORMAL, _finite("mean", mean), 1.0 / _positive("sd", sd) ** 2, 0.0)
+
+
+def student_t(nu, mean=0.0, scale=1.0):
+    """q = mean + scale t_nu (Cauchy: nu = 1)"""
+    return PriorSpec(PRIOR_STUDENT_T, _finite("mean", mean), 1.0 / _positive("scale", scale) ** 2, _positive("nu", nu))
+
+
+def half_normal(scale=1.0):
+    """sigma = exp(q) is half-normal with this scale"""
+    return PriorSpec(PRIOR_LOG_HALF_NORMAL, float(np.log(_positive("scale", scale))), 1.0, 0.0)
+
+
+def half_student_t(nu, scale=1.0):
+    """sigma = exp(q) is half-t_nu with this scale (half-Cauchy: nu = 1)"""
+    return PriorSpec(PRIOR_LOG_HALF_STUDENT_T, float(np.log(_positive("scale", scale))), 1.0, _positive("nu", nu))
+
+
+def exponential(mean=1.0):
+    """sigma = exp(q) is exponential with this mean"""
+    return PriorSpec(PRIOR_LOG_EXPONENTIAL, float(np.log(_positive("mean", mean))), 1.0, 0.0)
+
+
+def priors(Dx, A=0, H=0, coefficients=None, aux=None, scales=None):
+    """the keyword arguments prior_mu, prior_tau, prior_kind and prior_nu of GLM() for Dx coefficients, A auxiliary coordinates and H
+    group scales: GLM(X, Y, source, aux=A, groups=g, **glm.priors(Dx, A, H, coefficients=glm.student_t(3), scales=glm.half_student_t(4))).
+    Each role takes one spec (for every coordinate of the role) or a sequence of one spec per coordinate; None is normal(0, 1), today's
+    prior (on a and omega: a standard normal on the logarithm).  The specs of sigma = exp(q) -- half_normal, half_student_t,
+    exponential -- are for aux and scales only."""
+    out = []
+    for role, count, spec in (("coefficients", int(Dx), coefficients), ("aux", int(A), aux), ("scales", int(H), scales)):
+        if count < 0:
+            raise ValueError("%s: a count of %d" % (role, count))
+        if spec is None:
+            spec = normal()
+        if isinstance(spec, PriorSpec):
+            spec = [spec] * count
+        spec = list(spec)
+        if len(spec) != count or not all(isinstance(p, PriorSpec) for p in spec):
+            raise ValueError("%s must be one prior spec or a sequence of %d (glm.normal, glm.student_t, glm.half_normal, glm.half_student_t, "
+                             "glm.exponential)" % (role, count))
+        if role == "coefficients":
+            for c, p in enumerate(spec):
+                if p.kind >= PRIOR_LOG_HALF_NORMAL:
+                    raise ValueError("coefficients[%d]: PRIOR_%s is a prior on exp(q); a coefficient is not a logarithm" % (c, PRIOR_NAMES[p.kind]))
+        out += spec
+    return {"prior_mu": np.array([p.mu for p in out], np.float64), "prior_tau": np.array([p.tau for p in out], np.float64),
+            "prior_kind": np.array([p.kind for p in out], np.int32), "prior_nu": np.array([p.nu for p in out], np.float64)}

@@ -34,9 +34,15 @@ launch per transition; on the plain GLM of M = 1 the context-wide EPS_GLOBAL + M
 pooled stepsize it also reports what sits between two transitions alone, by HIP events: idhmc_time_eps_adapt, and for the global
 stepsize the same three launches enqueued by hand (accept_sum, da_adapt_global) between two torch events.
 
+--prior-cost (GLM(..., prior_kind=, prior_nu=)) adds, per shape and chain count, what the priors' table costs: the
+poisson pair's GLM with Gaussian priors, the same with a Student-t prior (nu = 3) on every coefficient, and the --hier-cost design
+with H = 4 groups under Gaussian priors and with a half-t (nu = 4) on the four scales, each from the Gaussian model's Laplace
+approximation.  Meant to run under --lockstep, so that every tree has the same length and ms per transition compares the gradients.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
+                              [--prior-cost]
 """
 import argparse
 import json
@@ -366,6 +372,10 @@ def hier_problem(n, D, seed, H=1):
 
 def model(form, X, y, q_map=None):
     D = X.shape[1]
+    if form == "glm_hier_h4_halft":                   # glm_hier_h4 with a half-t (nu = 4) on the four scales
+        return pkg.GLM(X, y, pkg.glm.BERNOULLI_LOGIT, groups=hier_groups(D, 4), **pkg.glm.priors(D, 0, 4, scales=pkg.glm.half_student_t(4.0)))
+    if form == "glm_poisson_t":                       # glm_poisson with a Student-t (nu = 3) on every coefficient
+        return pkg.GLM(X, y, pkg.glm.POISSON_LOG, **pkg.glm.priors(D, coefficients=pkg.glm.student_t(3.0)))
     if form.startswith("glm_hier"):                   # glm_hier (H = 1), glm_hier_h0, glm_hier_h4
         H = int(form[-1]) if form[-2:-1] == "h" else 1
         return pkg.GLM(X, y, pkg.glm.BERNOULLI_LOGIT, groups=hier_groups(D, H) if H else None)
@@ -528,6 +538,8 @@ def main():
     ap.add_argument("--hier-cost", action="store_true", help="the hier pair's design with H = 0, 1 and 4 groups per shape (DESIGN section 13)")
     ap.add_argument("--dispersion-cost", action="store_true", help="the negative binomial next to POISSON_LOG on the same design and counts, "
                     "and a beta regression, per shape (DESIGN section 14)")
+    ap.add_argument("--prior-cost", action="store_true", help="the Poisson GLM with Gaussian and with Student-t priors on the coefficients, and "
+                    "the hier design (H = 4) with Gaussian and with half-t priors on the scales, per shape (DESIGN section 18); use --lockstep")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -580,6 +592,19 @@ def main():
                     print("# D=%d n=%d C=%d %s (form %d): %.3e leapfrog steps/s, depth %.2f" %
                           (D, n, C, f, row[f]["glm_form"], row[f]["leapfrog_steps_per_s"], row[f]["mean_depth"]), file=sys.stderr, flush=True)
                 row["negbin_over_poisson"] = row["glm_negbin"]["leapfrog_steps_per_s"] / row["glm_poisson"]["leapfrog_steps_per_s"]
+                res["results"].append(row)
+        if a.prior_cost:
+            po = poisson_problem(n, D, seed=D * 7919 + n)
+            hi = hier_problem(n, D, seed=D * 7919 + n, H=4)
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="prior_cost", D=D, n=n, chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                for f, args in (("glm_poisson", po), ("glm_poisson_t", po), ("glm_hier_h4", hi), ("glm_hier_h4_halft", hi)):
+                    row[f] = run(f, *args, C, a.transitions, metric=metric)[0]
+                    print("# D=%d n=%d C=%d %s (form %d): %.3f ms/transition, %.3e leapfrog steps/s, depth %.2f" %
+                          (D, n, C, f, row[f]["glm_form"], row[f]["ms_per_transition"], row[f]["leapfrog_steps_per_s"], row[f]["mean_depth"]),
+                          file=sys.stderr, flush=True)
+                row["student_t_over_gaussian_ms"] = row["glm_poisson_t"]["ms_per_transition"] / row["glm_poisson"]["ms_per_transition"]
+                row["half_t_over_gaussian_ms"] = row["glm_hier_h4_halft"]["ms_per_transition"] / row["glm_hier_h4"]["ms_per_transition"]
                 res["results"].append(row)
         if a.responses or a.chains_per_response:
             X, y, q_map, cov = poisson_problem(n, D, seed=D * 7919 + n)
