@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void k_refresh(DevState s, uint32_t iter, int 
 }
 
 // Single-step form of k_leapfrog (idhmc_stream.hpp), the HBM-bound headline path (BASELINE.json configs[1]).
-// VAR bit 0: issue every load of the chain (q, p, grad: 3 KiB per chunk from HBM; M^-1, mu, tau from L2)
+// VAR bit 0: issue every load of the chain (q, p, grad: 3 KiB per chunk from HBM; a per-chain M^-1 likewise)
 //            before the first store, so one wave keeps 24 KiB of HBM reads in flight (2 waves/SIMD);
 //            otherwise chunk-by-chunk at 4 waves/SIMD.
 // VAR bit 1: non-temporal loads/stores for the streamed state.
@@ -42,12 +42,56 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 template <bool NT> IDHMC_DEV v2d ld2(const v2d *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
 template <bool NT> IDHMC_DEV void st2(v2d *p, v2d v) { if (NT) __builtin_nontemporal_store(v, p); else *p = v; }
 
-// one chain of k_leapfrog1; NT: the policy of this chain's q, p, grad loads and stores
-template <int NCH, class Model, bool PRE, bool NT, bool REGRAD>
-IDHMC_DEV void leapfrog1_chain(const DevState &s, int64_t c, int lane, double eps_arg, int own_eps)
+// The parameters every chain of a launch shares -- M^-1 of a shared metric, mu and tau of the density -- live in LDS: rows kLf1M, kLf1Mu,
+// kLf1Tau of NCH chunks, one v2d per lane per chunk (one ds_read_b128 per read), staged by the workgroup's four waves in every launch
+// (nothing outlives a launch: set_minv, a metric update or new model parameters are seen by the next one).  Read from global memory by
+// every chain they were 24 KiB of L2 requests per 32 KiB of state.
+constexpr int kLf1M = 0, kLf1Mu = 1, kLf1Tau = 2;
+template <class Model> constexpr int lf1_param_rows() { return Model::kHasParams ? 3 : 1; }
+
+// this wave's share of the staging (chunks wv, wv + 4, ... of every staged row), then the workgroup's barrier: every wave of the
+// workgroup comes here exactly once, with or without a chain.  The call is inlined into each form of the chain body and into the
+// kernel's tail, so the waves of one workgroup may arrive at different s_barrier instructions (one per policy branch, one for a wave
+// without a chain): this relies on the hardware barrier counting the workgroup's arrivals wherever their program counters are.
+template <int NCH, class Model>
+IDHMC_DEV void leapfrog1_stage(const DevState &s, v2d *prm, int lane)
 {
-    const v2d *__restrict__ mu2 = reinterpret_cast<const v2d *>(s.mu) + lane;
-    const v2d *__restrict__ tau2 = reinterpret_cast<const v2d *>(s.tau) + lane;
+    constexpr int kPer = (NCH + kStreamWaves - 1) / kStreamWaves;
+    const int wv = (int)(threadIdx.x >> 6);
+    const bool shared_m = s.minv_stride == 0;
+    const v2d *src[3] = {reinterpret_cast<const v2d *>(s.minv) + lane, reinterpret_cast<const v2d *>(s.mu) + lane,
+                         reinterpret_cast<const v2d *>(s.tau) + lane};
+    v2d t[3][kPer];
+    // every load before the first LDS store; a chunk index past the row is clamped for the load and not stored
+#pragma unroll
+    for (int k = 0; k < lf1_param_rows<Model>(); ++k) {
+        if (k == kLf1M && !shared_m) continue;
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const int j = wv + i * kStreamWaves;
+            t[k][i] = src[k][(j < NCH ? j : NCH - 1) * 64];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < lf1_param_rows<Model>(); ++k) {
+        if (k == kLf1M && !shared_m) continue;
+#pragma unroll
+        for (int i = 0; i < kPer; ++i) {
+            const int j = wv + i * kStreamWaves;
+            if (j < NCH) prm[(k * NCH + j) * 64 + lane] = t[k][i];
+        }
+    }
+    __syncthreads();
+}
+
+// one chain of k_leapfrog1; NT: the policy of this chain's q, p, grad loads and stores; MSH: the metric is shared (M^-1 from LDS),
+// otherwise this chain's own row streams from global memory.  stage: the wave's first chain, which fills the LDS rows once its own
+// q, p (grad) loads are on their way, so the fill's L2 latency runs under their HBM latency.
+template <int NCH, class Model, bool PRE, bool NT, bool REGRAD, bool MSH>
+IDHMC_DEV void leapfrog1_chain(const DevState &s, v2d *prm, bool stage, int64_t c, int lane, double eps_arg, int own_eps)
+{
+    const v2d *mL = prm + kLf1M * NCH * 64 + lane, *muL = nullptr, *tauL = nullptr;
+    if constexpr (Model::kHasParams) { muL = prm + kLf1Mu * NCH * 64 + lane; tauL = prm + kLf1Tau * NCH * 64 + lane; }
     const int64_t off = c * s.L;
     v2d *__restrict__ q2 = reinterpret_cast<v2d *>(s.q + off) + lane;
     v2d *__restrict__ p2 = reinterpret_cast<v2d *>(s.p + off) + lane;
@@ -56,33 +100,34 @@ IDHMC_DEV void leapfrog1_chain(const DevState &s, int64_t c, int lane, double ep
     const double eps = own_eps ? s.eps[c] : eps_arg;
     const double eh = 0.5 * eps;
     double l0 = 0.0, l1 = 0.0, k0 = 0.0, k1 = 0.0;
-    v2d qv[NCH], pv[NCH], gv[NCH], mvv[NCH], muv[NCH], tav[NCH];
-    if (PRE) {
+    // PRE: the whole chain; otherwise chunk 0 only, the rest chunk by chunk below
+    constexpr int NPRE = PRE ? NCH : 1;
+    v2d qv[NPRE], pv[NPRE], gv[NPRE], mvv[NPRE];
 #pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            qv[j] = ld2<NT>(q2 + j * 64);
-            pv[j] = ld2<NT>(p2 + j * 64);
-            if (!REGRAD) gv[j] = ld2<NT>(g2 + j * 64);
-        }
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            mvv[j] = m2[j * 64];
-            if (Model::kHasParams) { muv[j] = mu2[j * 64]; tav[j] = tau2[j * 64]; }
-        }
+    for (int j = 0; j < NPRE; ++j) {
+        qv[j] = ld2<NT>(q2 + j * 64);
+        pv[j] = ld2<NT>(p2 + j * 64);
+        if (!REGRAD) gv[j] = ld2<NT>(g2 + j * 64);
     }
+    if (!MSH) {
+#pragma unroll
+        for (int j = 0; j < NPRE; ++j) mvv[j] = m2[j * 64];
+    }
+    if (stage) leapfrog1_stage<NCH, Model>(s, prm, lane);
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
         v2d q, p, g, mv, mu = {0.0, 0.0}, tau = {1.0, 1.0};
-        if (PRE) {
-            q = qv[j]; p = pv[j]; mv = mvv[j];
+        if (j < NPRE) {
+            q = qv[j]; p = pv[j];
             if (!REGRAD) g = gv[j];
-            if (Model::kHasParams) { mu = muv[j]; tau = tav[j]; }
+            if (!MSH) mv = mvv[j];
         } else {
             q = ld2<NT>(q2 + j * 64); p = ld2<NT>(p2 + j * 64);
             if (!REGRAD) g = ld2<NT>(g2 + j * 64);
-            mv = m2[j * 64];
-            if (Model::kHasParams) { mu = mu2[j * 64]; tau = tau2[j * 64]; }
+            if (!MSH) mv = m2[j * 64];
         }
+        if (MSH) mv = mL[j * 64];
+        if (Model::kHasParams) { mu = muL[j * 64]; tau = tauL[j * 64]; }
         if (REGRAD) g = v2d{-(tau.x * (q.x - mu.x)), -(tau.y * (q.y - mu.y))};
         const double pmx = dfma(eh, g.x, p.x), pmy = dfma(eh, g.y, p.y);
         const double qx = dfma(eps * mv.x, pmx, q.x), qy = dfma(eps * mv.y, pmy, q.y);
@@ -96,6 +141,7 @@ IDHMC_DEV void leapfrog1_chain(const DevState &s, int64_t c, int lane, double ep
         st2<NT>(q2 + j * 64, v2d{qx, qy});
         st2<NT>(p2 + j * 64, v2d{px, py});
         if (!REGRAD) st2<NT>(g2 + j * 64, v2d{-tx, -ty});
+        if (!PRE) sched_fence();      // chunk by chunk: the LDS reads of all chunks, hoisted to the top, would spill at 4 waves/SIMD
     }
     double sl, sk;
     wave_sum2(l0, l1, k0, k1, sl, sk);
@@ -107,8 +153,17 @@ IDHMC_DEV void leapfrog1_chain(const DevState &s, int64_t c, int lane, double ep
     }
 }
 
+// waves per SIMD, at least: 2 with the whole chain preloaded; chunk by chunk 4 -- 3 where four workgroups' staged rows (42 KiB and up)
+// exceed a CU's LDS.  At most: what the registers admit, as ever, except for the preload variants at NCH = 8, which stay at the two
+// they have always run: without the preloaded parameters the registers would admit a third, which measured slower.
 template <int NCH, class Model, int VAR>
-__global__ __launch_bounds__(256, (VAR & 1) ? 2 : 4) void k_leapfrog1(DevState s, double eps_arg, int own_eps)
+constexpr int lf1_waves() { return (VAR & 1) ? 2 : (4 * lf1_param_rows<Model>() * NCH * 1024 > kLdsBytes ? 3 : 4); }
+template <int NCH, int VAR>
+constexpr int lf1_max_waves() { return ((VAR & 1) && NCH == 8) ? 2 : 8; }
+
+template <int NCH, class Model, int VAR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lf1_waves<NCH, Model, VAR>(), lf1_max_waves<NCH, VAR>())))
+void k_leapfrog1(DevState s, double eps_arg, int own_eps)
 {
     // VAR bit 2 (REGRAD): the gradient stream is dropped -- grad l(q) is re-derived from q (2 flops per element, the
     // very bits the previous step would have stored) and grad l(q') is not written: 4 D 8 bytes per step instead of 6 D 8
@@ -117,10 +172,20 @@ __global__ __launch_bounds__(256, (VAR & 1) ? 2 : 4) void k_leapfrog1(DevState s
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int64_t stride = REGRAD ? s.lf_stride2 : s.lf_stride;
-    for (int64_t c = wave; c < s.C; c += nw) {
-        if (PRE && NT && c % stride == 0) leapfrog1_chain<NCH, Model, PRE, false, REGRAD>(s, c, lane, eps_arg, own_eps);
-        else leapfrog1_chain<NCH, Model, PRE, NT, REGRAD>(s, c, lane, eps_arg, own_eps);
+    __shared__ v2d prm[lf1_param_rows<Model>() * NCH * 64];
+    bool stage = true;
+    if (s.minv_stride == 0) {
+        for (int64_t c = wave; c < s.C; c += nw, stage = false) {
+            if (PRE && NT && c % stride == 0) leapfrog1_chain<NCH, Model, PRE, false, REGRAD, true>(s, prm, stage, c, lane, eps_arg, own_eps);
+            else leapfrog1_chain<NCH, Model, PRE, NT, REGRAD, true>(s, prm, stage, c, lane, eps_arg, own_eps);
+        }
+    } else {
+        for (int64_t c = wave; c < s.C; c += nw, stage = false) {
+            if (PRE && NT && c % stride == 0) leapfrog1_chain<NCH, Model, PRE, false, REGRAD, false>(s, prm, stage, c, lane, eps_arg, own_eps);
+            else leapfrog1_chain<NCH, Model, PRE, NT, REGRAD, false>(s, prm, stage, c, lane, eps_arg, own_eps);
+        }
     }
+    if (stage) leapfrog1_stage<NCH, Model>(s, prm, lane);      // a wave without a chain: its share of the fill, and the barrier
 }
 
 // W = 1/sqrt(M^-1) (GaussianKineticEnergy, reference src/hamiltonian.jl:50-57)
@@ -585,12 +650,17 @@ static hipError_t launch_leapfrog_separable(const DevState &s, double eps, int o
         int var = (s.model == IDHMC_MODEL_ISO_GAUSSIAN) ? 2 : 3;
         if (regrad) var = 7;
         if (s.nch > 8) var = regrad ? 6 : 2;      // L = 2048: preloading the whole chain would spill, chunk by chunk instead
+        // only the forms the choice above can reach are built: the preload variants up to NCH 8, variant 6 past it
 #define IDHMC_LF1(V)                                                                                          \
     IDHMC_DISPATCH_NCH(s.nch, {                                                                               \
-        if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)                                                              \
-            hipLaunchKernelGGL((k_leapfrog1<NCH, IsoGaussian<NCH>, V>), dim3(grid), dim3(256), 0, st, s, eps, own); \
-        else                                                                                                  \
-            hipLaunchKernelGGL((k_leapfrog1<NCH, DiagGaussian<NCH>, V>), dim3(grid), dim3(256), 0, st, s, eps, own); \
+        if constexpr (((V) & 1) ? NCH <= 8 : ((V) == 2 || NCH > 8)) {                                         \
+            if (s.model == IDHMC_MODEL_ISO_GAUSSIAN)                                                          \
+                hipLaunchKernelGGL((k_leapfrog1<NCH, IsoGaussian<NCH>, V>), dim3(grid), dim3(256), 0, st, s, eps, own); \
+            else                                                                                              \
+                hipLaunchKernelGGL((k_leapfrog1<NCH, DiagGaussian<NCH>, V>), dim3(grid), dim3(256), 0, st, s, eps, own); \
+        } else {                                                                                              \
+            return hipErrorInvalidValue;                                                                      \
+        }                                                                                                     \
     })
         switch (var) {      // (variants 0 and 1, temporal loads, lost the round-1 sweep and are no longer built)
         case 2: IDHMC_LF1(2); break;

@@ -15,4 +15,10 @@ timeout -k 10 540 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/prof_${
 echo "fetch pass done"
 timeout -k 10 540 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/prof_${TAG}_write -- python3 $R/bench.py $ARGS > $OUT/prof_${TAG}_write.json 2> $OUT/prof_${TAG}_write.log
 echo "write pass done"
+# L2 requests of the headline kernel (how many reads the CUs send to L2, and what L2 sees and hits): one counter per run, plain bench
+LEAN="--steps 200 --warmup 20"
+for CTR in TCP_TCC_READ_REQ_sum TCC_REQ_sum TCC_HIT_sum; do
+    timeout -k 10 300 rocprofv3 --pmc $CTR --output-format csv -d $OUT/prof_${TAG}_$CTR -- python3 $R/bench.py $LEAN > $OUT/prof_${TAG}_$CTR.json 2> $OUT/prof_${TAG}_$CTR.log
+    echo "$CTR pass done"
+done
 cd $R && python3 tools/summarize_prof.py $TAG --stage-only

@@ -36,6 +36,13 @@ for cname in ("fetch", "write"):
             acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
     for k, v in acc.items():
         vals[k] = sum(v) / len(v)
+l2 = {}        # the L2 request passes of profile_bench.sh, where they were taken: mean per launch
+for cname in ("TCP_TCC_READ_REQ_sum", "TCC_REQ_sum", "TCC_HIT_sum"):
+    found = glob.glob(f"{src}/prof_{tag}_{cname}/*/*_counter_collection.csv")
+    if found:
+        v = [float(r["Counter_Value"]) for r in csv.DictReader(open(found[0])) if kernel in r["Kernel_Name"] and r["Counter_Name"] == cname]
+        if v:
+            l2[cname] = sum(v) / len(v)
 fetch_b = vals["FETCH_SIZE"] * 1024 * 2
 write_b = vals["WRITE_SIZE"] * 1024
 line = json.loads(open(f"{src}/prof_{tag}_trace.json").read().strip().splitlines()[-1])
@@ -51,7 +58,9 @@ out = {"kernel": name, "calls": calls, "avg_duration_ns": avg_ns,
        "hbm_read_bytes_per_launch": fetch_b, "hbm_write_bytes_per_launch": write_b,
        "hbm_bytes_per_launch": fetch_b + write_b, "hbm_over_algorithmic": (fetch_b + write_b) / alg,
        "correction": "FETCH_SIZE x2 (gfx950 wide coalesced reads), WRITE_SIZE x1",
+       "l2_requests_per_launch": l2,
        "other_kernels": other,
-       "command": "rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu --no-cfg3"}
+       "command": "rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu --no-cfg3"
+                  + ("; l2_requests_per_launch: rocprofv3 --pmc <one counter per run> -- python3 bench.py --steps 200 --warmup 20" if l2 else "")}
 json.dump(out, open(f"{dst}/{tag}_leapfrog_pmc.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
