@@ -300,6 +300,41 @@ int idhmc_create_glm_priors(idhmc_ctx **out, int device, int64_t nchains, int64_
                             int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
 /* kind and nu as the context was given them, D entries each; all 0 for every other context */
 int idhmc_glm_priors_get(const idhmc_ctx *ctx, int32_t *kind, double *nu);
+/* Per-coefficient local scales: the horseshoe and its regularised form.  local[c] in {0, 1} per column of X; the J
+ * flagged columns, in ascending column order, get local coordinates k = 0 .. J-1, and a chain's position is
+ *   q = [u (Dx) | a (A) | omega (H) | lambda (J)],   D = Dx + A + H + J <= 1024,
+ * lambda_k the LOGARITHM of the local scale of its column col(k).  slab_scale S > 0 is fixed, not sampled, inv2 = 1.0 / (S * S) computed
+ * once on the host; S = 0: no slab.  Per gradient -- the kernels and the tests' C restatement follow this bit for bit: plain IEEE
+ * operations in the association written, dfma and dexp those of idhmc_math.hpp, sqrt correctly rounded -- e_g = dexp(omega_g), and for a
+ * column c < Dx with id = groups[c]:
+ *   not flagged: b_c = id >= 0 ? u_c * e_id : u_c, as without local scales
+ *   flagged, local coordinate k:
+ *     f = dexp(lambda_k);  s = id >= 0 ? e_id * f : f
+ *     without slab: st = s (h unused)
+ *     with slab:    i = 1.0 / s;  nn = dfma(i, i, inv2);  st = 1.0 / sqrt(nn);  h = 1.0 - inv2 / nn
+ *                   (st = s / sqrt(1 + s^2 / S^2), h = d log st / d log s; s = inf gives st = S, h = 0; s = 0 gives st = 0, h = 1)
+ *     b_c = u_c * st
+ * z_i, (r_i, v_i, s_ij), G_c, S_j and A[rho] are as without local scales, over the columns < Dx.  Then, for a flagged column,
+ *   w_c = G_c * b_c;  wl_c = slab ? w_c * h : w_c;  G_{Dx+A+H+k} = wl_c (no reduction: one column feeds one coordinate);
+ *   W_id[c & 127] takes wl_c where it took w_c (grouped);  G_c <- G_c * st (an unflagged grouped column: G_c * e_id)
+ * W_g goes into G_{Dx+A+g} by the canonical tree and the prior runs over all D coordinates, unchanged: the lambdas are coordinates >= Dx, so
+ * kinds 2..4 apply to them.  The horseshoe: u ~ N(0, 1), IDHMC_PRIOR_LOG_HALF_STUDENT_T with nu = 1 on every lambda, the same kind with
+ * mu = log tau0 on the omega of the group that holds the shrunk columns, and optionally S.
+ * Finite: with a slab at every finite q; without one s = inf (omega_g + lambda_k past 709.78) makes b_c infinite or NaN, l is not
+ * finite and reads as -inf, the ordinary rejected point.  With a slab and s below about 1.5e-154, i * i overflows and st is 0 where it
+ * should be s: an absolute error below 1.5e-154 |u_c| in b_c, not engineered around.
+ *
+ * idhmc_create_glm_local is idhmc_create_glm_priors with these; mu, tau, kind and nu have Dx + A + H + J entries.  local == NULL,
+ * local->local == NULL or all zeros, with slab_scale == 0, gives the context of idhmc_create_glm_priors: the same kernels, the same bits.
+ * No LDS is added: idhmc_glm_form is what it is for the same (L, A, metric), L counting the J lambdas.  Refused with
+ * IDHMC_ERR_BAD_ARG before the device is touched: an entry of local other than 0 or 1; slab_scale negative or not finite; slab_scale > 0
+ * with J = 0; D > 1024; and everything the other creation functions refuse (IDHMC_METRIC_PER_RESPONSE still needs D <= 512). */
+typedef struct { const int32_t *local; double slab_scale; } idhmc_glm_local;   /* local: Dx entries, 0 or 1 */
+int idhmc_create_glm_local(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                           int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
+/* local (Dx entries) and slab_scale as the context was given them; zeros and 0 for every other context */
+int idhmc_glm_local_get(const idhmc_ctx *ctx, int32_t *local, double *slab_scale);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

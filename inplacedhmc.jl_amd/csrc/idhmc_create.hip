@@ -61,6 +61,9 @@ struct GlmParts {
     int64_t M = 1, R = 0;      // (1, 0 otherwise)
     const int32_t *pkind = nullptr;      // [D] idhmc_create_glm_priors with some kind != 0: the priors' kinds and their nu (never null then)
     const double *pnu = nullptr;
+    int32_t J = 0;             // idhmc_create_glm_local: flagged columns; the last J coordinates are the logarithms of their local scales
+    const int32_t *local = nullptr;      // [Dx] 0 or 1, J > 0 (never null then)
+    double slab = 0.0;         // the slab scale (0: none)
 };
 // The head of a packed params array into *g: `head` = 0 (a logistic regression's [X | y]), 2 ([K, nc, c | X | Y]) or 3
 // ([K, nc, A, c | X | Y]) doubles in front of the constants.  The entries are checked as doubles (integral, hence finite, and in
@@ -136,7 +139,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
         }
     }
     const int64_t n = g.n, K = g.K, M = g.M;
-    const int64_t Dx = D - g.A - g.H;      // the columns of X
+    const int64_t Dx = D - g.A - g.H - g.J;      // the columns of X
     int L = 128;
     while (L < D) L *= 2;
     const int64_t npad = (n + 127) / 128 * 128;
@@ -178,7 +181,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
 static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
 {
     DevState &s = c->s;
-    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - g.A - g.H, K = g.K, M = g.M;     // D: the columns of X
+    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - g.A - g.H - g.J, K = g.K, M = g.M;     // D: the columns of X
     std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(M * K * npad), 0.0);
     for (int64_t i = 0; i < n; ++i)
         for (int64_t k = 0; k < D; ++k) {
@@ -231,6 +234,22 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         s.lr_pnu = dnu;
         c->prior_kind.assign(g.pkind, g.pkind + Dall);
         c->prior_nu.assign(g.pnu, g.pnu + Dall);
+    }
+    std::vector<int32_t> hp;
+    if (g.J > 0) {
+        // the partner of every coordinate: the k-th flagged column (ascending) and coordinate Dx + A + H + k name each other
+        hp.assign((size_t)L, -1);
+        int64_t k = s.D - g.J;
+        for (int64_t col = 0; col < D; ++col)
+            if (g.local[col]) { hp[(size_t)col] = (int32_t)k; hp[(size_t)k] = (int32_t)col; ++k; }
+        int32_t *dp = nullptr;
+        if (int rc = dalloc(c, &dp, L)) return rc;
+        HIPCHK(hipMemcpyAsync(dp, hp.data(), sizeof(int32_t) * hp.size(), hipMemcpyHostToDevice, c->stream));
+        s.lr_lpart = dp;
+        s.lr_j = g.J;
+        s.lr_inv2 = g.slab > 0.0 ? 1.0 / (g.slab * g.slab) : 0.0;
+        c->glm_local.assign(g.local, g.local + D);
+        c->slab_scale = g.slab;
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
     s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
@@ -502,14 +521,14 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
 
 // The priors of idhmc_create_glm_priors: every check of kind and nu.  *any: some kind is not 0 (none is: the context is the one
 // without priors).  nu_out: nu with 0 wherever the caller passed none.
-static int validate_priors(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, std::vector<double> *nu_out, bool *any)
+static int validate_priors(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, int J, std::vector<double> *nu_out, bool *any)
 {
     *any = false;
     if (!pr || !pr->kind) {
         if (pr && pr->nu) return fail(IDHMC_ERR_BAD_ARG, "GLM: priors->nu without priors->kind");
         return IDHMC_OK;
     }
-    const int D = glm->Dx + glm->A + glm->H;
+    const int D = glm->Dx + glm->A + glm->H + J;
     nu_out->assign((size_t)D, 0.0);
     for (int c = 0; c < D; ++c) {
         const int32_t k = pr->kind[c];
@@ -524,7 +543,7 @@ static int validate_priors(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr
         if (k >= IDHMC_PRIOR_LOG_HALF_NORMAL) {
             if (c < glm->Dx)
                 return fail(IDHMC_ERR_BAD_ARG, "GLM: prior kind[%d] = %d is a prior on exp(q): coordinate %d is a coefficient, not a logarithm "
-                            "(kinds 2..4 are for the A + H coordinates behind the Dx = %d coefficients)", c, k, c, glm->Dx);
+                            "(kinds 2..4 are for the coordinates behind the Dx = %d coefficients)", c, k, c, glm->Dx);
             if (glm->tau && glm->tau[c] != 1.0)
                 return fail(IDHMC_ERR_BAD_ARG, "GLM: prior tau[%d] = %g must be 1 (kind %d: its one scale is exp(mu))", c, glm->tau[c], k);
         }
@@ -534,10 +553,28 @@ static int validate_priors(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr
     return IDHMC_OK;
 }
 
-// idhmc_create_glm, idhmc_create_glm_responses and idhmc_create_glm_priors
+// The local scales of idhmc_create_glm_local: every check of local and slab_scale.  *J: the flagged columns (0: the context is the one
+// without local scales)
+static int validate_local(const idhmc_glm_desc *glm, const idhmc_glm_local *lc, int *J)
+{
+    *J = 0;
+    if (!lc) return IDHMC_OK;
+    if (!(std::isfinite(lc->slab_scale) && lc->slab_scale >= 0.0))
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: slab_scale = %g must be finite and >= 0 (0: no slab)", lc->slab_scale);
+    if (lc->local)
+        for (int c = 0; c < glm->Dx; ++c) {
+            if (lc->local[c] != 0 && lc->local[c] != 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: local[%d] = %d is neither 0 nor 1", c, lc->local[c]);
+            *J += lc->local[c];
+        }
+    if (lc->slab_scale > 0.0 && *J == 0)
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: slab_scale = %g without a column that has a local scale (local is NULL or all zeros)", lc->slab_scale);
+    return IDHMC_OK;
+}
+
+// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors and idhmc_create_glm_local
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
-                      const idhmc_glm_priors *priors = nullptr)
+                      const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
@@ -545,6 +582,11 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (glm->H < 0 || glm->H > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d must be an integer in 0..4", glm->H);
     if (glm->Dx > 1024 - glm->A - glm->H)
         return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H = %lld: a GLM is limited to D <= 1024", (long long)glm->Dx + glm->A + glm->H);
+    int J = 0;
+    if (int rc = validate_local(glm, local, &J)) return rc;
+    if (glm->Dx + J > 1024 - glm->A - glm->H)
+        return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J = %lld: a GLM is limited to D <= 1024 (J = %d local scales)",
+                    (long long)glm->Dx + glm->A + glm->H + J, J);
     if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
     if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
     if (glm->H > 0) {
@@ -560,15 +602,16 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     idhmc_model_desc m;
     memset(&m, 0, sizeof m);
     m.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM;
-    m.D = glm->Dx + glm->A + glm->H;
+    m.D = glm->Dx + glm->A + glm->H + J;
     m.mu = glm->mu;
     m.tau = glm->tau;
     m.source = glm->source;
     std::vector<double> nu;
     bool any = false;
-    if (int rc = validate_priors(glm, priors, &nu, &any)) return rc;
+    if (int rc = validate_priors(glm, priors, J, &nu, &any)) return rc;
     GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
     if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
+    if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
     return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
 }
 
@@ -595,6 +638,24 @@ int idhmc_create_glm_priors(idhmc_ctx **out, int device, int64_t nchains, int64_
     // (1, 0): the context of idhmc_create_glm; anything else: the one of idhmc_create_glm_responses, which refuses what it refuses
     const bool responses = !(M == 1 && chains_per_response == 0);
     return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors);
+}
+
+int idhmc_create_glm_local(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                           int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_local: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local);
+}
+
+int idhmc_glm_local_get(const idhmc_ctx *c, int32_t *local, double *slab_scale)
+{
+    if (!c || !local || !slab_scale) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_local_get: null argument");
+    const int Dx = c->s.D - c->s.lr_a - c->s.lr_h - c->s.lr_j;
+    for (int k = 0; k < Dx; ++k) local[k] = c->glm_local.empty() ? 0 : c->glm_local[(size_t)k];
+    *slab_scale = c->slab_scale;
+    return IDHMC_OK;
 }
 
 int idhmc_glm_priors_get(const idhmc_ctx *c, int32_t *kind, double *nu)

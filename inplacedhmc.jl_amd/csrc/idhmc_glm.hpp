@@ -71,6 +71,29 @@
 // Each kind is finite wherever its log density is, and that ends at: kind 1, tau d^2 finite (|d| < 1.3e154 / sqrt(tau)); kinds 2
 // and 3, 2 d < 709.78 (every more negative d is fine: e = 0 and T = -2 d); kind 4, d < 709.08 (2 exp(d) finite).  Past those ends T is +inf (g may be
 // NaN), which the engine reads as l(q) = -inf: the ordinary rejected point.
+//
+// Per-coefficient local scales (idhmc_create_glm_local): Obs::kLocal, a compile-time flag of the policy (false for the
+// policies above and for every model without a flagged column: none of their instructions changes).  local[c] in {0, 1} per column of
+// X; the J flagged columns, ascending, get local coordinates k = 0 .. J-1 and q = [u (Dx) | a (A) | omega (H) | lambda (J)], lambda_k the
+// LOGARITHM of the local scale of its column col(k).  inv2 = 1 / (S S) for a fixed slab scale S > 0 (DevState::lr_inv2; 0: no slab).
+// DevState::lr_lpart holds the partner of every coordinate: for a flagged column its lambda, for a lambda its column, -1 elsewhere.
+//   flagged column c, local coordinate k, id = grp[c]:
+//     f = dexp(lambda_k);  s = id >= 0 ? e_id * f : f
+//     no slab: st = s (h unused);  slab: i = 1 / s;  nn = dfma(i, i, inv2);  st = 1 / sqrt(nn);  h = 1 - inv2 / nn
+//       (st = s / sqrt(1 + s^2 / S^2), h = d log st / d log s; s = inf gives st = S, h = 0; s = 0 gives st = 0, h = 1; with s below
+//        about 1.5e-154 i i overflows and st is 0 where it should be s: an absolute error below 1.5e-154 |u| in b_c)
+//     b_c = u_c * st
+//   every other column: as above.  z, (r, v, s), G_c, S_j, A[rho] as above, over the columns < Dx.  Then, for a flagged column:
+//     w_c = G_c * b_c;  wl_c = slab ? w_c * h : w_c;  G_{Dx+A+H+k} = wl_c (no reduction: one column feeds one coordinate);
+//     W_id takes wl_c where it took w_c (grouped);  G_c <- G_c * st.
+//   W_g into G_{Dx+A+g} by the canonical tree and the prior loop over all D coordinates are unchanged (lambda is a coordinate >= Dx:
+//   the log kinds apply to it).
+// A column and its lambda live in different lanes, chunks and components in general.  Both forms read the partner through the
+// wavefront-private LDS vector they already have, written and read by the same wavefront in program order (no workgroup barrier):
+// GlmWave through buf -- q is staged, b is computed ONCE per gradient and kept in registers across the observation blocks (staged
+// again per block as before), and st, h are computed again from q after the loop, as GlmCoop does, rather than held (two more
+// vectors of registers); GlmCoop through the requester's Q row -- q, then b in its place before barrier A; after barrier C the G
+// row is taken into registers, then q, then wl go through the row.  Nothing of the local scales is alive across multiply().
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -178,6 +201,102 @@ IDHMC_DEV void glm_group_chain(Vec<NCH> &G, const Vec<NCH> &q, const int2 *grp2,
     }
 }
 
+// Local scales (Obs::kLocal).  st and h of a flagged column: lam its lambda, id its group; inv2 = 0: no slab (st = s, h = 1 unused)
+template <int H>
+IDHMC_DEV void glm_local_scale(double lam, int id, double e0, double e1, double e2, double e3, double inv2, double &st, double &h)
+{
+    const double s = glm_scaled<H>(dexp(lam), id, e0, e1, e2, e3);
+    st = s;
+    h = 1.0;
+    if (inv2 != 0.0) {
+        const double i = 1.0 / s;
+        const double nn = dfma(i, i, inv2);
+        st = 1.0 / __builtin_sqrt(nn);
+        h = 1.0 - inv2 / nn;
+    }
+}
+// the group ids of chunk j (H = 0: none)
+template <int H>
+IDHMC_DEV int2 glm_ids(const int2 *grp2, int j)
+{
+    if constexpr (H > 0) return grp2[j * 64];
+    else return make_int2(-1, -1);
+}
+// b of every coordinate of the lane: u st for a flagged column, as glm_scaled elsewhere (coordinates >= dx raw).  vec is the
+// wavefront's own LDS vector (>= 128 NCH doubles, indexed by coordinate): q is staged there and each lane reads its columns' lambdas.
+template <int NCH, int H>
+IDHMC_DEV void glm_local_b(Vec<NCH> &b, const Vec<NCH> &q, const int2 *grp2, const int32_t *part, double *vec, int dx, int lane,
+                           double e0, double e1, double e2, double e3, double inv2)
+{
+    constexpr int HN = H > 0 ? H : 1;
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(part) + lane;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = q.c[j];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c0 = 128 * j + 2 * lane;
+        const int2 id = glm_ids<H>(grp2, j), p = part2[j * 64];
+        const bool fx = p.x >= 0 && c0 < dx, fy = p.y >= 0 && c0 + 1 < dx;
+        double sx, hx, sy, hy;
+        glm_local_scale<HN>(vec[fx ? p.x : 0], id.x, e0, e1, e2, e3, inv2, sx, hx);
+        glm_local_scale<HN>(vec[fy ? p.y : 0], id.y, e0, e1, e2, e3, inv2, sy, hy);
+        b.c[j].x = fx ? q.c[j].x * sx : glm_scaled<HN>(q.c[j].x, id.x, e0, e1, e2, e3);
+        b.c[j].y = fy ? q.c[j].y * sy : glm_scaled<HN>(q.c[j].y, id.y, e0, e1, e2, e3);
+    }
+}
+// glm_group_chain with local scales: st, h and b again from q (staged in vec), wl_c to its lambda's coordinate through vec, W_g of
+// the members' wl_c into coordinate c0 + g, G_c st for the flagged columns and G_c e_grp[c] for the other members
+template <int NCH, int H>
+IDHMC_DEV void glm_local_chain(Vec<NCH> &G, const Vec<NCH> &q, const int2 *grp2, const int32_t *part, double *vec, int dx, int c0g,
+                               int lane, double e0, double e1, double e2, double e3, double inv2)
+{
+    constexpr int HN = H > 0 ? H : 1;
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(part) + lane;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = q.c[j];
+    Vec<NCH> wl;
+    double2 W0 = make_double2(0.0, 0.0), W1 = W0, W2 = W0, W3 = W0;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c0 = 128 * j + 2 * lane;
+        const int2 id = glm_ids<H>(grp2, j), p = part2[j * 64];
+        const bool fx = p.x >= 0 && c0 < dx, fy = p.y >= 0 && c0 + 1 < dx;
+        double sx, hx, sy, hy;
+        glm_local_scale<HN>(vec[fx ? p.x : 0], id.x, e0, e1, e2, e3, inv2, sx, hx);
+        glm_local_scale<HN>(vec[fy ? p.y : 0], id.y, e0, e1, e2, e3, inv2, sy, hy);
+        const double bx = fx ? q.c[j].x * sx : glm_scaled<HN>(q.c[j].x, id.x, e0, e1, e2, e3);
+        const double by = fy ? q.c[j].y * sy : glm_scaled<HN>(q.c[j].y, id.y, e0, e1, e2, e3);
+        double wx = G.c[j].x * bx, wy = G.c[j].y * by;
+        wx = fx && inv2 != 0.0 ? wx * hx : wx;
+        wy = fy && inv2 != 0.0 ? wy * hy : wy;
+        if constexpr (H > 0) glm_group_add<0>(W0, id, wx, wy);
+        if constexpr (H > 1) glm_group_add<1>(W1, id, wx, wy);
+        if constexpr (H > 2) glm_group_add<2>(W2, id, wx, wy);
+        if constexpr (H > 3) glm_group_add<3>(W3, id, wx, wy);
+        wl.c[j] = make_double2(wx, wy);
+        G.c[j].x = fx ? G.c[j].x * sx : glm_scaled<HN>(G.c[j].x, id.x, e0, e1, e2, e3);
+        G.c[j].y = fy ? G.c[j].y * sy : glm_scaled<HN>(G.c[j].y, id.y, e0, e1, e2, e3);
+    }
+    // every lambda has been read: wl takes q's place, and each lambda's lane reads its column's
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = wl.c[j];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c0 = 128 * j + 2 * lane;
+        const int2 p = part2[j * 64];
+        const bool lx = p.x >= 0 && c0 >= dx, ly = p.y >= 0 && c0 + 1 >= dx;
+        const double tx = vec[lx ? p.x : 0], ty = vec[ly ? p.y : 0];
+        G.c[j].x = lx ? tx : G.c[j].x;
+        G.c[j].y = ly ? ty : G.c[j].y;
+    }
+    if constexpr (H > 0) glm_group_place<NCH>(G, W0, c0g, lane);
+    if constexpr (H > 1) glm_group_place<NCH>(G, W1, c0g + 1, lane);
+    if constexpr (H > 2) glm_group_place<NCH>(G, W2, c0g + 2, lane);
+    if constexpr (H > 3) glm_group_place<NCH>(G, W3, c0g + 3, lane);
+}
+
 // The prior of one coordinate (the table of the header comment): kind and nu select the row, d = q_c - mu_c, G the likelihood's part
 // of the gradient.  Adds the coordinate's -2 log prior to T and returns g_c.
 IDHMC_DEV double glm_prior(int kind, double nu, double tau, double d, double G, double &T)
@@ -218,7 +337,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -240,8 +359,10 @@ struct GlmWave {
     const int2 *grp2;        // the group ids, lane-offset, device (Obs::H > 0)
     const int2 *kind2;       // the priors' kinds and their nu, lane-offset, device (Obs::kPriors)
     const double2 *nu2;
+    const int32_t *part;     // the partner of every coordinate, device (Obs::kLocal)
+    double inv2;             // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     double *buf;             // this wavefront's LDS vector, L doubles
-    int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, then Obs::H log scales)
+    int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
     IDHMC_DEV void init(const State &s, double *lds_vec, int lane_)
     {
@@ -258,6 +379,11 @@ struct GlmWave {
         }
         buf = lds_vec;
         D = s.D - Obs::A - Obs::H;
+        if constexpr (Obs::kLocal) {
+            part = s.lr_lpart;
+            inv2 = s.lr_inv2;
+            D -= s.lr_j;
+        }
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -282,6 +408,8 @@ struct GlmWave {
         }
         double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;         // the groups' scales
         if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, D + Obs::A, e0, e1, e2, e3);
+        Vec<NCH> bq;                                           // Obs::kLocal: b, once per gradient
+        if constexpr (Obs::kLocal) glm_local_b<NCH, Obs::H>(bq, q, grp2, part, buf, D, lane, e0, e1, e2, e3, inv2);
         double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;
         const int nb = npad >> 7;
         for (int b = 0; b < nb; ++b) {
@@ -289,7 +417,9 @@ struct GlmWave {
             // (with groups b = u e is staged, computed again per block rather than kept: ids -1 past the columns of X leave a raw)
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
-                if constexpr (Obs::H > 0) {
+                if constexpr (Obs::kLocal) {
+                    b2[j * 64] = bq.c[j];
+                } else if constexpr (Obs::H > 0) {
                     const int2 id = grp2[j * 64];
                     b2[j * 64] = make_double2(glm_scaled<HN>(q.c[j].x, id.x, e0, e1, e2, e3), glm_scaled<HN>(q.c[j].y, id.y, e0, e1, e2, e3));
                 } else {
@@ -354,7 +484,8 @@ struct GlmWave {
                 for (int j = 0; j < NCH; ++j) glm_place(G.c[j], j, D + jx, lane, S);
             }
         }
-        if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, q, grp2, D + Obs::A, lane, e0, e1, e2, e3);
+        if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(G, q, grp2, part, buf, D, D + Obs::A, lane, e0, e1, e2, e3, inv2);
+        else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, q, grp2, D + Obs::A, lane, e0, e1, e2, e3);
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
@@ -418,12 +549,19 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     const int2 *grp2;            // the group ids, lane-offset, device (Obs::H > 0)
     const int2 *kind2;           // the priors' kinds and their nu, lane-offset, device (Obs::kPriors)
     const double2 *nu2;
+    const int32_t *part;         // the partner of every coordinate, device (Obs::kLocal)
+    double inv2;                 // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     double *tile;
-    int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, then Obs::H log scales)
+    int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
     IDHMC_DEV void init(const State &s, double *tile_, int *alive_, int lane_, int wv_)
     {
         dx = s.D - Obs::A - Obs::H;
+        if constexpr (Obs::kLocal) {
+            part = s.lr_lpart;
+            inv2 = s.lr_inv2;
+            dx -= s.lr_j;
+        }
         if constexpr (Obs::H > 0) grp2 = reinterpret_cast<const int2 *>(s.lr_grp) + lane_;
         if constexpr (Obs::kPriors) {
             kind2 = reinterpret_cast<const int2 *>(s.lr_pkind) + lane_;
@@ -570,7 +708,17 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         Prefetch pf;
         double2 *row = reinterpret_cast<double2 *>(tile + kQ + wv * DS) + lane;
         double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;        // the groups' scales
-        if constexpr (Obs::H > 0) {
+        if constexpr (Obs::kLocal) {
+            // q goes through the row first (each column reads its lambda there), then b takes its place, +0 in every column >= dx
+            if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, dx + Obs::A, e0, e1, e2, e3);
+            Vec<NCH> bq;
+            glm_local_b<NCH, Obs::H>(bq, q, grp2, part, tile + kQ + wv * DS, dx, lane, e0, e1, e2, e3, inv2);
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                const int c0 = 128 * j + 2 * lane;
+                row[j * 64] = make_double2(c0 >= dx ? 0.0 : bq.c[j].x, c0 + 1 >= dx ? 0.0 : bq.c[j].y);
+            }
+        } else if constexpr (Obs::H > 0) {
             // the Q row is b = u e, +0 in every column that is not one of X (the auxiliary ones and the log scales)
             glm_group_scales<NCH, HN>(q, dx + Obs::A, e0, e1, e2, e3);
 #pragma unroll
@@ -607,8 +755,8 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 S[jx] = wave_sum(sp[0], sp[1]);
             }
         }
-        Vec<NCH> Gh;                                          // with groups: the whole G row, for the chain rule
-        if constexpr (Obs::H > 0) {
+        Vec<NCH> Gh;                                          // with groups or local scales: the whole G row, for the chain rule
+        if constexpr (Obs::H > 0 || Obs::kLocal) {
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 Gh.c[j] = row[j * 64];
@@ -620,15 +768,17 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             // the scales again, from q: eight registers held across the round made the matrix loops of multiply() spill
             int c0 = dx + Obs::A;
             asm volatile("" : "+s"(c0));                      // (not the value of before barrier A kept alive)
-            glm_group_scales<NCH, HN>(q, c0, e0, e1, e2, e3);
-            glm_group_chain<NCH, HN>(Gh, q, grp2, c0, lane, e0, e1, e2, e3);
+            if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, c0, e0, e1, e2, e3);
+            // (local scales: the G row is in registers now, so q and then wl go through the row, which is the requester's own until barrier A)
+            if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(Gh, q, grp2, part, tile + kQ + wv * DS, dx, c0, lane, e0, e1, e2, e3, inv2);
+            else glm_group_chain<NCH, HN>(Gh, q, grp2, c0, lane, e0, e1, e2, e3);
         }
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
             double2 G;
-            if constexpr (Obs::H > 0) {
+            if constexpr (Obs::H > 0 || Obs::kLocal) {
                 G = Gh.c[j];
             } else {
                 G = row[j * 64];

@@ -66,6 +66,8 @@ struct idhmc_ctx {
     int64_t glm_r = 0;             // idhmc_create_glm_responses: chains per response as given (0: any other context)
     std::vector<int32_t> prior_kind;   // idhmc_create_glm_priors with some kind != 0: kind and nu as given, D entries each (empty otherwise)
     std::vector<double> prior_nu;
+    std::vector<int32_t> glm_local;    // idhmc_create_glm_local with some column flagged: local as given, Dx entries (empty otherwise)
+    double slab_scale = 0.0;           // and its slab scale (0: none)
     // IDHMC_EPS_PER_RESPONSE / IDHMC_METRIC_PER_RESPONSE: the context holds resp_n = C / glm_r whole responses (0 in every other mode)
     int64_t resp_n = 0;
     double *resp_da = nullptr;     // [resp_n][6] dual-averaging states of IDHMC_EPS_PER_RESPONSE: mu, m, Hbar, logeps, logeps_bar, eps

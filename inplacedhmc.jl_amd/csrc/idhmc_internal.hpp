@@ -88,6 +88,11 @@ struct DevState {
     // a GLM with a non-Gaussian prior on some coordinate (idhmc_create_glm_priors; both null otherwise)
     const int32_t *lr_pkind;  // [L] IDHMC_PRIOR_* of every coordinate, 0 for padded ones
     const double *lr_pnu;     // [L] degrees of freedom of the kinds that take them, 0 elsewhere
+    // a GLM with per-coefficient local scales (idhmc_create_glm_local; null, 0, 0 otherwise): the last lr_j coordinates
+    // are their logarithms, X has D - lr_a - lr_h - lr_j columns
+    const int32_t *lr_lpart;  // [L] the partner of every coordinate: a flagged column's lambda, a lambda's column, -1 elsewhere
+    double lr_inv2;           // 1 / slab_scale^2 (0: no slab)
+    int32_t lr_j;
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -136,7 +141,8 @@ constexpr int64_t kIcSliceBytes = (int64_t)192 << 20;
 struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
-// K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors)
+// K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors),
+// s.lr_lpart one with local scales (kLocal)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

@@ -24,6 +24,9 @@ struct SumArgs {
     int64_t C, G, lanes;     // chains, chains per group, (segment, d) pairs = groups spg D
     int32_t D, cnt, spg;     // dimension, transitions of the block, segments per group
     int32_t bins, Dx, A, H;
+    // a GLM with local scales: theta = [beta | a raw | sigma | exp(lambda)], a row of scales is [e (H) | f (J) | st (J)]
+    const int32_t *lpart;    // DevState::lr_lpart
+    int32_t J, W;            // local scales; doubles per row of scales = H + 2 J
 };
 
 // one value into a lane's running state: the expressions of k_nuts at IDHMC_T_ACCUM_MOMENTS, then min / max / sign
@@ -63,13 +66,45 @@ __global__ void k_summary_scales(const double *stage, double *scales, int64_t ro
     scales[i] = dexp(stage[r * D + (D - H) + g]);
 }
 
+// The same for a GLM with local scales, one thread per (row, group or local coordinate): e_g = dexp(omega_g) as above; for local
+// coordinate k, column col(k) with id = grp[col(k)], f = dexp(lambda_k) and st by the expressions of idhmc_glm.hpp (glm_local_scale):
+//   s = id >= 0 ? e_id * f : f;  no slab: st = s;  slab: i = 1 / s, nn = dfma(i, i, inv2), st = 1 / sqrt(nn)
+// A row of scales is [e (H) | f (J) | st (J)].
+__global__ void k_summary_local_scales(const double *stage, double *scales, int64_t rows, int32_t D, int32_t H, int32_t J, const int32_t *grp,
+                                       const int32_t *lpart, double inv2)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t T = H + J, W = H + 2 * J;
+    if (i >= rows * T) return;
+    const int64_t r = i / T;
+    const int32_t t = (int32_t)(i - r * T);
+    const double *q = stage + r * D;
+    if (t < H) {
+        scales[r * W + t] = dexp(q[(D - J - H) + t]);
+        return;
+    }
+    const int32_t k = t - H;
+    const double f = dexp(q[(D - J) + k]);
+    const int32_t id = H > 0 ? grp[lpart[(D - J) + k]] : -1;
+    const double s = id >= 0 ? dexp(q[(D - J - H) + id]) * f : f;
+    double st = s;
+    if (inv2 != 0.0) {
+        const double iv = 1.0 / s;
+        const double nn = dfma(iv, iv, inv2);
+        st = 1.0 / __builtin_sqrt(nn);
+    }
+    scales[r * W + H + k] = f;
+    scales[r * W + H + J + k] = st;
+}
+
 // The reduction.  Lane i owns (segment, d) = (i / D, i % D): consecutive lanes take consecutive d, so a wavefront reads contiguous
 // runs of a row.  The lane visits its segment's chains transition by transition, ascending chain id inside, with its state in
 // registers; HIST: it counts its values' bins in its own LDS row and the workgroup adds the rows to the table at the end.
-template <bool HIST, bool SCALED>
-__global__ __launch_bounds__(kSumBlock) void k_summary(SumArgs a)
+// MODE: 0 theta = q; 1 coefficient groups; 2 local scales (with or without groups)
+template <bool HIST, int MODE>
+IDHMC_DEV void summary_body(const SumArgs &a, uint16_t *lds_cnt)
 {
-    extern __shared__ __align__(16) uint16_t lds_cnt[];   // [bins + 2][kSumRow]
+    constexpr bool SCALED = MODE == 1;
     const int tid = threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * kSumBlock + tid;
     if constexpr (HIST) {
@@ -104,8 +139,22 @@ __global__ __launch_bounds__(kSumBlock) void k_summary(SumArgs a)
             if (d < a.Dx) sidx = a.grp[d];
             else if (d >= a.Dx + a.A) { sidx = d - a.Dx - a.A; sigma = true; }
         }
+        // with local scales: the column of the row of scales this lane's coordinate takes (-1: raw), and whether the value is the scale itself
+        if constexpr (MODE == 2) {
+            if (d < a.Dx) {
+                const int32_t p = a.lpart[d];
+                sidx = p >= 0 ? a.H + a.J + (p - (a.D - a.J)) : (a.H > 0 ? a.grp[d] : -1);
+            } else if (d >= a.Dx + a.A) {
+                sidx = d - a.Dx - a.A;          // e_g, then f_k: the row of scales continues as theta does
+                sigma = true;
+            }
+        }
         auto value = [&](double u, int64_t row) -> double {
-            if constexpr (SCALED) {
+            if constexpr (MODE == 2) {
+                if (sidx < 0) return u;
+                const double e = a.scales[row * a.W + sidx];
+                return sigma ? e : u * e;
+            } else if constexpr (SCALED) {
                 if (sidx < 0) return u;
                 const double e = a.scales[row * a.H + sidx];
                 return sigma ? e : u * e;
@@ -161,6 +210,19 @@ __global__ __launch_bounds__(kSumBlock) void k_summary(SumArgs a)
             }
         }
     }
+}
+
+template <bool HIST, bool SCALED>
+__global__ __launch_bounds__(kSumBlock) void k_summary(SumArgs a)
+{
+    extern __shared__ __align__(16) uint16_t lds_cnt[];   // [bins + 2][kSumRow]
+    summary_body<HIST, SCALED ? 1 : 0>(a, lds_cnt);
+}
+template <bool HIST>
+__global__ __launch_bounds__(kSumBlock) void k_summary_local(SumArgs a)
+{
+    extern __shared__ __align__(16) uint16_t lds_cnt[];
+    summary_body<HIST, 2>(a, lds_cnt);
 }
 
 __global__ void k_summary_init(double *part, int64_t lanes)
@@ -227,29 +289,36 @@ __global__ void k_summary_range(const double *fin, double *rng, int64_t GD, int3
 
 static unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-template <bool HIST, bool SCALED>
+// MODE as summary_body's
+template <bool HIST, int MODE>
 static hipError_t launch_summary(const SumArgs &a, hipStream_t st)
 {
+    void (*const kernel)(SumArgs) = [] {
+        if constexpr (MODE == 2) return &k_summary_local<HIST>;
+        else return &k_summary<HIST, MODE == 1>;
+    }();
     const size_t lds = HIST ? (size_t)(a.bins + 2) * kSumRow * sizeof(uint16_t) : 0;
     if constexpr (HIST) {
         static bool attr_done[64] = {};  // per instantiation and device (the attribute is per device), as launch_nuts_t does
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_summary<HIST, SCALED>), hipFuncAttributeMaxDynamicSharedMemorySize,
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (IDHMC_SUMMARY_BINS_MAX + 2) * kSumRow * (int)sizeof(uint16_t));
             if (e != hipSuccess) return e;
             attr_done[dev & 63] = true;
         }
     }
-    hipLaunchKernelGGL((k_summary<HIST, SCALED>), dim3(blocks_for(a.lanes, kSumBlock)), dim3(kSumBlock), lds, st, a);
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(a.lanes, kSumBlock)), dim3(kSumBlock), lds, st, a);
     return hipGetLastError();
 }
 
 }  // namespace idhmc
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && c->s.lr_h > 0; }
+static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && (c->s.lr_h > 0 || c->s.lr_j > 0); }
+// doubles per row of Summary::scales: e_g, and with local scales f_k and st_k
+static int64_t scales_width(const idhmc_ctx *c) { return c->s.lr_h + 2 * (int64_t)c->s.lr_j; }
 static int64_t sum_gd(const idhmc_ctx *c) { return c->sum.groups * (int64_t)c->s.D; }
 
 static void summary_release(idhmc_ctx *c)
@@ -260,7 +329,7 @@ static void summary_release(idhmc_ctx *c)
     dfree(c, m.fin, (int64_t)sizeof(double) * kSumFields * GD);
     dfree(c, m.rng, (int64_t)sizeof(double) * 3 * GD);
     dfree(c, m.hist, (int64_t)sizeof(uint32_t) * (m.bins > 0 ? GD * (m.bins + 2) : 1));
-    dfree(c, m.scales, (int64_t)sizeof(double) * (m.scales_rows > 0 ? m.scales_rows * c->s.lr_h : 1));
+    dfree(c, m.scales, (int64_t)sizeof(double) * (m.scales_rows > 0 ? m.scales_rows * scales_width(c) : 1));
     m = Summary{};
 }
 
@@ -326,26 +395,31 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
 {
     Summary &m = c->sum;
     const DevState &s = c->s;
-    const bool scaled = scaled_theta(c);
+    const bool scaled = scaled_theta(c), local = s.lr_j > 0;
     if (scaled) {
         const int64_t rows = (int64_t)cnt * s.C;
         if (m.scales_rows < rows) {
-            dfree(c, m.scales, (int64_t)sizeof(double) * m.scales_rows * s.lr_h);
+            dfree(c, m.scales, (int64_t)sizeof(double) * m.scales_rows * scales_width(c));
             m.scales = nullptr; m.scales_rows = 0;
-            if (int rc = dalloc(c, &m.scales, rows * s.lr_h, false)) return rc;
+            if (int rc = dalloc(c, &m.scales, rows * scales_width(c), false)) return rc;
             m.scales_rows = rows;
         }
-        hipLaunchKernelGGL(k_summary_scales, dim3(blocks_for(rows * s.lr_h, 256)), dim3(256), 0, c->stream, stage, m.scales, rows, s.D, s.lr_h);
+        if (local)
+            hipLaunchKernelGGL(k_summary_local_scales, dim3(blocks_for(rows * (s.lr_h + s.lr_j), 256)), dim3(256), 0, c->stream, stage, m.scales, rows,
+                               s.D, s.lr_h, s.lr_j, s.lr_grp, s.lr_lpart, s.lr_inv2);
+        else
+            hipLaunchKernelGGL(k_summary_scales, dim3(blocks_for(rows * s.lr_h, 256)), dim3(256), 0, c->stream, stage, m.scales, rows, s.D, s.lr_h);
         HIPCHK(hipGetLastError());
     }
     SumArgs a{};
     a.stage = stage; a.scales = m.scales; a.grp = s.lr_grp; a.part = m.part; a.rng = m.rng; a.hist = m.hist;
     a.C = s.C; a.G = m.G; a.lanes = sum_gd(c) * m.spg;
     a.D = s.D; a.cnt = cnt; a.spg = m.spg;
-    a.bins = m.bins; a.Dx = s.D - s.lr_a - s.lr_h; a.A = s.lr_a; a.H = s.lr_h;
+    a.bins = m.bins; a.Dx = s.D - s.lr_a - s.lr_h - s.lr_j; a.A = s.lr_a; a.H = s.lr_h;
+    a.lpart = s.lr_lpart; a.J = s.lr_j; a.W = (int32_t)scales_width(c);
     const bool hist = m.ranged && m.bins > 0;
-    hipError_t e = hist ? (scaled ? launch_summary<true, true>(a, c->stream) : launch_summary<true, false>(a, c->stream))
-                        : (scaled ? launch_summary<false, true>(a, c->stream) : launch_summary<false, false>(a, c->stream));
+    hipError_t e = hist ? (local ? launch_summary<true, 2>(a, c->stream) : scaled ? launch_summary<true, 1>(a, c->stream) : launch_summary<true, 0>(a, c->stream))
+                        : (local ? launch_summary<false, 2>(a, c->stream) : scaled ? launch_summary<false, 1>(a, c->stream) : launch_summary<false, 0>(a, c->stream));
     HIPCHK(e);
     m.fed_t += (uint64_t)cnt;
     if (hist) m.binned_t += (uint64_t)cnt;

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmDesc, GlmPriors, ModelDesc, Options, check
+from ._lib import GlmDesc, GlmLocal, GlmPriors, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -163,7 +163,7 @@ def _prior(D, prior_mu, prior_tau):
 
 
 def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None, prior_kind=None,
-        prior_nu=None):
+        prior_nu=None, local=None, slab_scale=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -201,7 +201,17 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     half-normal, half-t or exponential prior with scale exp(mu) on exp(q) for an auxiliary coordinate or a group scale (tau = 1 there,
     never on a coefficient), prior_nu is the degrees of freedom of the two t kinds and 0 elsewhere.  glm.priors() assembles all four
     from glm.normal, glm.student_t, glm.half_normal, glm.half_student_t and glm.exponential.  With every kind PRIOR_NORMAL the model is
-    the one without the keywords.  The Model exposes prior_kind and prior_nu (None without the keywords); Engine.glm_priors() reads them back."""
+    the one without the keywords.  The Model exposes prior_kind and prior_nu (None without the keywords); Engine.glm_priors() reads them back.
+
+    local, slab_scale: per-coefficient local scales (idhmc_create_glm_local) -- the horseshoe and, with a slab, its regularised form.
+    local is a length-Dx boolean or 0/1 sequence, or True for every column; the J flagged columns, in ascending column order, each get
+    one more sampled coordinate lambda_k, the logarithm of the column's local scale: a chain's position is
+    [u (Dx) | a (A) | omega (H) | lambda (J)], the model's D is Dx + A + H + J, and prior_mu, prior_tau, prior_kind, prior_nu are scalars
+    or of that length (the log kinds apply to lambda).  A flagged column of group g has beta_c = u_c st with s = exp(omega_g)
+    exp(lambda_k) (exp(lambda_k) in no group), st = s without a slab and s / sqrt(1 + s^2 / S^2) with slab_scale = S > 0 (fixed, not
+    sampled; None or 0: no slab; it needs a flagged column).  glm.horseshoe() assembles groups, local, slab_scale and the priors;
+    glm.coefficients, glm.group_scales and glm.local_scales read draws.  With no column flagged the model is the one without the
+    keywords.  The Model exposes J, local (int32, or None) and slab_scale (None without a slab); Engine.glm_local() reads them back."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -227,7 +237,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
         grp = np.ascontiguousarray(grp, dtype=np.int32)
         if H == 0:
             grp = None                                          # every column ungrouped: the model without groups
-    D = Dx + A + H
+    loc, J, S = _glm.local_flags(local, slab_scale, Dx)
+    D = Dx + A + H + J
     if D > 1024:
         raise ValueError("a GLM is limited to D <= 1024 (D = %d)" % D)
     if not np.isfinite(X).all():
@@ -261,9 +272,9 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     kind, nu = _glm.prior_kinds(prior_kind, prior_nu, D, Dx, tau)
     priors = kind is not None and bool(kind.any())
     K = Y.shape[-1]
-    if H > 0 or R is not None or priors:
-        # handed over in parts (idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors): the packed params are not stretched
-        # for the groups, the responses or the priors
+    if H > 0 or R is not None or priors or J > 0:
+        # handed over in parts (idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local): the packed
+        # params are not stretched for the groups, the responses, the priors or the local scales
         m = Model(MODEL_GLM_AUX if A else MODEL_GLM, D, mu=mu, tau=tau, source=source)
         m.X, m.Y, m.constants = np.ascontiguousarray(X), np.ascontiguousarray(Y), np.ascontiguousarray(c)
     elif A == 0:
@@ -275,6 +286,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.n, m.K, m.nc, m.Dx, m.A, m.H, m.groups = n, K, c.size, Dx, A, H, grp
     m.M, m.R = M, R
     m.prior_kind, m.prior_nu = kind, nu
+    m.J, m.local, m.slab_scale = J, loc, S
     return m
 
 
@@ -298,7 +310,16 @@ class Engine:
         self.C, self.D = int(nchains), model.D
         h = C.c_void_p()
         kind = getattr(model, "prior_kind", None)
-        if kind is not None and kind.any():
+        if getattr(model, "J", 0) > 0:
+            desc = model.glm_desc()
+            pr = None
+            if kind is not None:
+                pr = C.byref(GlmPriors(kind=kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=_dp(model.prior_nu)))
+            lc = GlmLocal(local=model.local.ctypes.data_as(C.POINTER(C.c_int32)), slab_scale=model.slab_scale or 0.0)
+            R = getattr(model, "R", None)
+            check(self.lib.idhmc_create_glm_local(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, C.byref(lc),
+                                                  model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
+        elif kind is not None and kind.any():
             desc = model.glm_desc()
             pr = GlmPriors(kind=kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=_dp(model.prior_nu))
             R = getattr(model, "R", None)
@@ -424,6 +445,16 @@ class Engine:
         kind, nu = np.zeros(self.D, np.int32), np.zeros(self.D)
         check(self.lib.idhmc_glm_priors_get(self.h, kind.ctypes.data_as(C.POINTER(C.c_int32)), _dp(nu)))
         return kind, nu
+
+    def glm_local(self):
+        """(local int32 (Dx,), slab_scale) as the context holds them (GLM(..., local=, slab_scale=)); (None, 0.0) for a model that is not a
+        GLM handed over in parts, zeros and 0.0 for one without local scales"""
+        Dx = getattr(self.model, "Dx", None)
+        if Dx is None:
+            return None, 0.0
+        loc, S = np.zeros(Dx, np.int32), C.c_double(0.0)
+        check(self.lib.idhmc_glm_local_get(self.h, loc.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(S)))
+        return loc, float(S.value)
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -75,6 +75,18 @@ Each is finite wherever the log density itself is, and that ends at the argument
   PRIOR_LOG_HALF_STUDENT_T  2 d < 709.78, as above.
   PRIOR_LOG_EXPONENTIAL     d < 709.08 (2 exp(d) finite); every more negative d is fine.
 Past those ends -2 log p is +inf, which the engine reads as l(q) = -inf: the ordinary rejected point.
+
+Per-coefficient local scales, GLM(..., local=..., slab_scale=...) (idhmc_create_glm_local): the horseshoe and its
+regularised form, and every source above works unchanged with them.  The J flagged columns of X, in ascending column order, each get
+a sampled coordinate lambda_k, the LOGARITHM of the column's local scale: q = [u (Dx) | a (A) | omega (H) | lambda (J)].  A flagged
+column of group g has s = exp(omega_g) exp(lambda_k) (exp(lambda_k) alone in no group) and beta_c = u_c st, with st = s without a
+slab and st = s / sqrt(1 + s^2 / S^2) with the fixed slab scale S (evaluated as 1 / sqrt(1 / s^2 + 1 / S^2): st -> S as s grows).
+local_scales(model, draws) gives exp(lambda), coefficients() and group_scales() take the longer vector, priors(Dx, A, H, J,
+local_scales=...) has the fourth role, and horseshoe(Dx, columns, global_scale, ...) assembles the whole model: u ~ N(0, 1),
+half-t(nu_local) on every local scale, half-t(nu_global, global_scale) on the scale of the group the columns form.
+With a slab every finite q is finite.  Without one, omega_g + lambda_k past 709.78 makes s infinite and the coefficient infinite or
+NaN: l reads as -inf, the ordinary rejected point.  With a slab and s below about 1.5e-154 the square of 1 / s overflows and st is 0
+where it should be s: an absolute error below 1.5e-154 |u| in the coefficient, stated and not engineered around.
 """
 import collections
 
@@ -321,28 +333,94 @@ def by_response(model, draws, first_chain=0):
     return np.moveaxis(out, -3, 0)
 
 
+def _sampled(model, draws):
+    """draws as float64, checked against the model's D = Dx + A + H + J"""
+    draws = np.asarray(draws, dtype=np.float64)
+    D = model.Dx + model.A + getattr(model, "H", 0) + getattr(model, "J", 0)
+    if draws.shape[-1] != D:
+        raise ValueError("draws must have %d coordinates along the last axis, got %d" % (D, draws.shape[-1]))
+    return draws
+
+
 def group_scales(model, draws):
     """sigma_g = exp(omega_g) of a GLM with coefficient groups, shape draws.shape[:-1] + (H,) (H = 0: an empty last axis).  Any
     leading axes: (M, ..., R, D) from by_response works as (..., C, D) does."""
-    draws = np.asarray(draws, dtype=np.float64)
+    draws = _sampled(model, draws)
     Dx, A, H = model.Dx, model.A, getattr(model, "H", 0)
-    if draws.shape[-1] != Dx + A + H:
-        raise ValueError("draws must have %d coordinates along the last axis, got %d" % (Dx + A + H, draws.shape[-1]))
-    return np.exp(draws[..., Dx + A:])
+    return np.exp(draws[..., Dx + A:Dx + A + H])
+
+
+def local_scales(model, draws):
+    """exp(lambda_k) of a GLM with local scales, shape draws.shape[:-1] + (J,) (J = 0: an empty last axis): the local scale of the k-th
+    flagged column, in ascending column order.  Any leading axes, as group_scales."""
+    draws = _sampled(model, draws)
+    with np.errstate(over="ignore"):                            # (a local scale of inf is a value, not an error: the slab bounds its column)
+        return np.exp(draws[..., model.Dx + model.A + getattr(model, "H", 0):])
 
 
 def coefficients(model, draws):
     """the coefficients beta = s * u of a GLM from draws in the sampled coordinates, shape draws.shape[:-1] + (Dx,):
     beta_c = exp(omega_g) u_c for a column of group g, u_c for a column in no group (and for a model without groups).  Any leading
-    axes: (M, ..., R, D) from by_response works as (..., C, D) does."""
-    draws = np.asarray(draws, dtype=np.float64)
+    axes: (M, ..., R, D) from by_response works as (..., C, D) does.  With local scales a flagged column has beta_c = u_c st, st from
+    s = exp(omega_g) exp(lambda_k) (exp(lambda_k) in no group) by the kernels' operations: s itself without a slab, and with
+    slab_scale S  i = 1 / s, nn = i i + 1 / S^2, st = 1 / sqrt(nn)."""
+    draws = _sampled(model, draws)
     sigma = group_scales(model, draws)
     u = draws[..., :model.Dx]
-    if sigma.shape[-1] == 0:
+    J = getattr(model, "J", 0)
+    if sigma.shape[-1] == 0 and J == 0:
         return u.copy()
-    grp = np.asarray(model.groups)
-    s = np.where(grp >= 0, sigma[..., np.maximum(grp, 0)], 1.0)
+    if sigma.shape[-1] == 0:
+        s = np.ones_like(u)
+        grouped = np.zeros(model.Dx, bool)
+    else:
+        grp = np.asarray(model.groups)
+        grouped = grp >= 0
+        s = np.where(grouped, sigma[..., np.maximum(grp, 0)], 1.0)
+    if J == 0:
+        return s * u
+    cols = np.flatnonzero(model.local)
+    f = local_scales(model, draws)
+    sl = np.where(grouped[cols], s[..., cols] * f, f)
+    S = getattr(model, "slab_scale", None)
+    if S:
+        with np.errstate(divide="ignore", over="ignore"):
+            i = 1.0 / sl
+            sl = 1.0 / np.sqrt(i * i + 1.0 / (S * S))
+    s = s.copy()
+    s[..., cols] = sl
     return s * u
+
+
+def local_flags(local, slab_scale, Dx):
+    """GLM()'s validation of local and slab_scale: (local int32 (Dx,) or None, J, slab_scale float or None).  The checks are
+    idhmc_create_glm_local's; all flags zero without a slab is the model without the keywords."""
+    loc = None
+    if local is not None:
+        if local is True:
+            loc = np.ones(Dx, np.int32)
+        else:
+            raw = np.asarray(local)
+            if raw.ndim != 1 or raw.shape[0] != Dx:
+                raise ValueError("local must be True or have one entry per column of X (%d), got shape %s" % (Dx, raw.shape))
+            if raw.dtype != np.bool_ and not (np.issubdtype(raw.dtype, np.number) and np.isin(raw, (0, 1)).all()):
+                raise ValueError("every entry of local must be 0 or 1 (or a boolean)")
+            loc = np.ascontiguousarray(raw != 0, dtype=np.int32)
+    J = int(loc.sum()) if loc is not None else 0
+    S = None
+    if slab_scale is not None:
+        if isinstance(slab_scale, bool) or not isinstance(slab_scale, (int, float, np.integer, np.floating)):
+            raise ValueError("slab_scale must be a number (got %r)" % (slab_scale,))
+        S = float(slab_scale)
+        if not (np.isfinite(S) and S >= 0.0):
+            raise ValueError("slab_scale = %r must be finite and >= 0 (0 or None: no slab)" % S)
+        if S > 0.0 and J == 0:
+            raise ValueError("slab_scale = %r needs a column with a local scale (local is None or all zeros)" % S)
+        if S == 0.0:
+            S = None
+    if J == 0:
+        loc = None
+    return loc, J, S
 
 
 # ---- priors ---------------------------------------------------------------------------------------------------------------------------
@@ -433,14 +511,15 @@ def exponential(mean=1.0):
     return PriorSpec(PRIOR_LOG_EXPONENTIAL, float(np.log(_positive("mean", mean))), 1.0, 0.0)
 
 
-def priors(Dx, A=0, H=0, coefficients=None, aux=None, scales=None):
-    """the keyword arguments prior_mu, prior_tau, prior_kind and prior_nu of GLM() for Dx coefficients, A auxiliary coordinates and H
-    group scales: GLM(X, Y, source, aux=A, groups=g, **glm.priors(Dx, A, H, coefficients=glm.student_t(3), scales=glm.half_student_t(4))).
+def priors(Dx, A=0, H=0, J=0, coefficients=None, aux=None, scales=None, local_scales=None):
+    """the keyword arguments prior_mu, prior_tau, prior_kind and prior_nu of GLM() for Dx coefficients, A auxiliary coordinates, H
+    group scales and J local scales (GLM(..., local=)): GLM(X, Y, source, aux=A, groups=g, **glm.priors(Dx, A, H, coefficients=glm.student_t(3), scales=glm.half_student_t(4))).
     Each role takes one spec (for every coordinate of the role) or a sequence of one spec per coordinate; None is normal(0, 1), today's
     prior (on a and omega: a standard normal on the logarithm).  The specs of sigma = exp(q) -- half_normal, half_student_t,
-    exponential -- are for aux and scales only."""
+    exponential -- are for aux, scales and local_scales only."""
     out = []
-    for role, count, spec in (("coefficients", int(Dx), coefficients), ("aux", int(A), aux), ("scales", int(H), scales)):
+    for role, count, spec in (("coefficients", int(Dx), coefficients), ("aux", int(A), aux), ("scales", int(H), scales),
+                              ("local_scales", int(J), local_scales)):
         if count < 0:
             raise ValueError("%s: a count of %d" % (role, count))
         if spec is None:
@@ -458,3 +537,32 @@ def priors(Dx, A=0, H=0, coefficients=None, aux=None, scales=None):
         out += spec
     return {"prior_mu": np.array([p.mu for p in out], np.float64), "prior_tau": np.array([p.tau for p in out], np.float64),
             "prior_kind": np.array([p.kind for p in out], np.int32), "prior_nu": np.array([p.nu for p in out], np.float64)}
+
+
+def horseshoe(Dx, columns, global_scale, A=0, nu_local=1.0, nu_global=1.0, slab_scale=None, aux=None):
+    """the keyword arguments groups, local, slab_scale, prior_mu, prior_tau, prior_kind and prior_nu of GLM() for a (regularised)
+    horseshoe on `columns` (column indices or a length-Dx boolean mask) of Dx coefficients, with A auxiliary coordinates:
+    GLM(X, Y, source, aux=A, **glm.horseshoe(Dx, columns, tau0, slab_scale=2.0)).  The columns form group 0, whose sigma = exp(omega_0) is
+    the global scale with a half-t(nu_global, global_scale) prior; each has a local scale exp(lambda_k) with a half-t(nu_local) prior
+    (half-Cauchy on both by default); u ~ N(0, 1) on every column, so an unshrunk column keeps beta_c ~ N(0, 1).  slab_scale: the fixed
+    slab of the regularised horseshoe (None: the plain one).  aux: the spec(s) of the auxiliary coordinates, as priors() takes them."""
+    Dx = int(Dx)
+    cols = np.asarray(columns)
+    if cols.dtype == np.bool_:
+        if cols.shape != (Dx,):
+            raise ValueError("a boolean columns must have one entry per column of X (%d), got shape %s" % (Dx, cols.shape))
+        mask = cols.copy()
+    else:
+        if cols.ndim != 1 or not np.issubdtype(cols.dtype, np.integer) or cols.size == 0 or cols.min() < 0 or cols.max() >= Dx \
+                or np.unique(cols).size != cols.size:
+            raise ValueError("columns must be distinct column indices in 0..%d (or a boolean mask)" % (Dx - 1))
+        mask = np.zeros(Dx, bool)
+        mask[cols] = True
+    J = int(mask.sum())
+    if J == 0:
+        raise ValueError("the horseshoe needs at least one column")
+    kw = priors(Dx, A, 1, J, aux=aux, scales=half_student_t(nu_global, global_scale), local_scales=half_student_t(nu_local))
+    kw["groups"] = np.where(mask, 0, -1).astype(np.int32)
+    kw["local"] = mask.astype(np.int32)
+    kw["slab_scale"] = None if slab_scale is None else _positive("slab_scale", slab_scale)
+    return kw

@@ -39,10 +39,16 @@ poisson pair's GLM with Gaussian priors, the same with a Student-t prior (nu = 3
 with H = 4 groups under Gaussian priors and with a half-t (nu = 4) on the four scales, each from the Gaussian model's Laplace
 approximation.  Meant to run under --lockstep, so that every tree has the same length and ms per transition compares the gradients.
 
+--local-cost (GLM(..., local=, slab_scale=)) adds, per shape DxN and chain count, what the per-coefficient local scales
+cost, on the --hier-cost design with H = 1 and the Poisson likelihood (its 0 / 1 responses as counts): (i) without local scales; (ii)
+every column with a local scale, no slab -- D lambdas more, so L doubles at D = 100; (iii) the same with slab_scale = 2; (iv) a control
+without local scales on 2 D columns, which has the padded length of (ii) and (iii) and so does the same matrix work.  --local-rows picks
+rows (i and iv run on a build without the keywords as well).  Meant to run under --lockstep.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
-                              [--prior-cost]
+                              [--prior-cost] [--local-cost] [--local-rows i,ii,iii,iv]
 """
 import argparse
 import json
@@ -376,6 +382,9 @@ def model(form, X, y, q_map=None):
         return pkg.GLM(X, y, pkg.glm.BERNOULLI_LOGIT, groups=hier_groups(D, 4), **pkg.glm.priors(D, 0, 4, scales=pkg.glm.half_student_t(4.0)))
     if form == "glm_poisson_t":                       # glm_poisson with a Student-t (nu = 3) on every coefficient
         return pkg.GLM(X, y, pkg.glm.POISSON_LOG, **pkg.glm.priors(D, coefficients=pkg.glm.student_t(3.0)))
+    if form.startswith("glm_local"):                  # the hier design (H = 1) with Poisson counts: _base (and the control), _all, _all_slab
+        kw = {} if form == "glm_local_base" else {"local": True, "slab_scale": 2.0 if form.endswith("slab") else None}
+        return pkg.GLM(X, y, pkg.glm.POISSON_LOG, groups=hier_groups(D, 1), **kw)
     if form.startswith("glm_hier"):                   # glm_hier (H = 1), glm_hier_h0, glm_hier_h4
         H = int(form[-1]) if form[-2:-1] == "h" else 1
         return pkg.GLM(X, y, pkg.glm.BERNOULLI_LOGIT, groups=hier_groups(D, H) if H else None)
@@ -430,6 +439,11 @@ def run(form, X, y, q_map, cov, C, T, seed=1, metric=None, mdl=None):
     elif form == "glm_gaussian_a4":                   # three more coordinates, near 0 and narrow
         q_map = np.r_[q_map, np.zeros(3)]
         big = np.eye(Dx + 4) * 1e-4
+        big[:Dx + 1, :Dx + 1] = cov
+        cov = big
+    elif form.startswith("glm_local_all"):            # one log local scale per column more, near 0 and narrow
+        q_map = np.r_[q_map, np.zeros(Dx)]
+        big = np.eye(2 * Dx + 1) * 1e-4
         big[:Dx + 1, :Dx + 1] = cov
         cov = big
     D = q_map.size
@@ -540,6 +554,9 @@ def main():
                     "and a beta regression, per shape (DESIGN section 14)")
     ap.add_argument("--prior-cost", action="store_true", help="the Poisson GLM with Gaussian and with Student-t priors on the coefficients, and "
                     "the hier design (H = 4) with Gaussian and with half-t priors on the scales, per shape (DESIGN section 18); use --lockstep")
+    ap.add_argument("--local-cost", action="store_true", help="the hier design (H = 1, Poisson) without local scales, with one on every "
+                    "column, the same with a slab, and a control of twice the columns without any (DESIGN section 19); use --lockstep")
+    ap.add_argument("--local-rows", default="i,ii,iii,iv", help="the rows of --local-cost to run")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -605,6 +622,23 @@ def main():
                           file=sys.stderr, flush=True)
                 row["student_t_over_gaussian_ms"] = row["glm_poisson_t"]["ms_per_transition"] / row["glm_poisson"]["ms_per_transition"]
                 row["half_t_over_gaussian_ms"] = row["glm_hier_h4_halft"]["ms_per_transition"] / row["glm_hier_h4"]["ms_per_transition"]
+                res["results"].append(row)
+        if a.local_cost:
+            rows = a.local_rows.split(",")
+            small = hier_problem(n, D, seed=D * 7919 + n, H=1)
+            wide = hier_problem(n, 2 * D, seed=D * 7919 + n, H=1) if "iv" in rows else None
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="local_cost", D=D, n=n, chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                for tag, f, args in (("i", "glm_local_base", small), ("ii", "glm_local_all", small), ("iii", "glm_local_all_slab", small),
+                                     ("iv", "glm_local_base", wide)):
+                    if tag not in rows:
+                        continue
+                    r = run(f, *args, C, a.transitions, metric=metric)[0]
+                    r["ms_per_gradient"] = r["ms_per_transition"] * a.transitions / r["steps"] * C
+                    row[tag + "_" + f] = r
+                    print("# D=%d n=%d C=%d %s %s (Dx = %d, form %d): %.3f ms/transition, %.5f ms/gradient sweep, %.3e leapfrog steps/s, depth %.2f" %
+                          (D, n, C, tag, f, args[0].shape[1], r["glm_form"], r["ms_per_transition"], r["ms_per_gradient"], r["leapfrog_steps_per_s"],
+                           r["mean_depth"]), file=sys.stderr, flush=True)
                 res["results"].append(row)
         if a.responses or a.chains_per_response:
             X, y, q_map, cov = poisson_problem(n, D, seed=D * 7919 + n)

@@ -1,18 +1,17 @@
-// jit_rehearsal_priors.hip -- tools/jit_rehearsal.hip for DESIGN section 18: the NUTS kernels hipRTC builds for a GLM, compiled ahead of
-// time once with Gaussian priors (kPriors = false: the parent's kernels) and once with the priors' table in the last loop (kPriors =
-// true), so that tools/kres.py shows both sets of resource figures side by side:
-//     tools/kres.py tools/jit_rehearsal_priors.hip k_nuts -Iinplacedhmc.jl_amd/csrc
-// Poisson (A = 0, H = 0) and the hierarchical Gaussian with a sampled scale (A = 1, H = 4), per-chain and shared metric: the
-// matrix-core form at NCH = 1 and NCH = 2, the per-wave form at NCH = 4.  Not part of the library.
+// jit_rehearsal_local.hip -- tools/jit_rehearsal.hip for DESIGN section 19: the kernels hipRTC builds for a GLM with per-coefficient
+// local scales (kLocal = true), compiled ahead of time so that tools/kres.py shows their resource figures:
+//     tools/kres.py tools/jit_rehearsal_local.hip k_ -Iinplacedhmc.jl_amd/csrc
+// Poisson (A = 0) without a group and with one, with and without the priors' table, and the hierarchical Gaussian with a sampled
+// scale (A = 1, H = 4): the matrix-core form at NCH = 1 and NCH = 2, the per-wave form at NCH = 4 and NCH = 8.  Not part of the library.
 #include "idhmc_nuts_kernel.hpp"
 #include "idhmc_optimum.hpp"
 #include "idhmc_glm.hpp"
 namespace idhmc {
 
-template <bool PRIORS>
-struct PoissonObs {
-    static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = false;
+template <int GROUPS, bool PRIORS>
+struct PoissonLocalObs {
+    static constexpr int K = 1, A = 0, H = GROUPS;
+    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = true;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -20,10 +19,9 @@ struct PoissonObs {
         r = o.y[0] - e;
     }
 };
-template <bool PRIORS>
-struct HierGaussObs {
+struct HierGaussLocalObs {
     static constexpr int K = 1, A = 1, H = 4;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = false;
+    static constexpr bool kResponses = false, kPriors = true, kLocal = true;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);
@@ -42,10 +40,12 @@ struct HierGaussObs {
     IDHMC_REHEARSE_NUTS(1, GlmCoop<1 IDHMC_COMMA OBS>)           \
     IDHMC_REHEARSE_NUTS(2, GlmCoop<2 IDHMC_COMMA OBS>)           \
     IDHMC_REHEARSE_NUTS(4, GlmWave<4 IDHMC_COMMA OBS>)           \
+    template __global__ void k_nuts<8, GlmWave<8 IDHMC_COMMA OBS>, true>(DevState, uint32_t, uint32_t);    \
     template __global__ void k_leapfrog<2, GlmWave<2 IDHMC_COMMA OBS>>(DevState, double, int, int);
-IDHMC_REHEARSE_OBS(PoissonObs<false>)
-IDHMC_REHEARSE_OBS(PoissonObs<true>)
-IDHMC_REHEARSE_OBS(HierGaussObs<false>)
-IDHMC_REHEARSE_OBS(HierGaussObs<true>)
+using PoissonLocal = PoissonLocalObs<0, false>;
+using PoissonLocalGroupPriors = PoissonLocalObs<1, true>;
+IDHMC_REHEARSE_OBS(PoissonLocal)
+IDHMC_REHEARSE_OBS(PoissonLocalGroupPriors)
+IDHMC_REHEARSE_OBS(HierGaussLocalObs)
 
 }  // namespace idhmc
