@@ -335,6 +335,37 @@ int idhmc_create_glm_local(idhmc_ctx **out, int device, int64_t nchains, int64_t
                            int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
 /* local (Dx entries) and slab_scale as the context was given them; zeros and 0 for every other context */
 int idhmc_glm_local_get(const idhmc_ctx *ctx, int32_t *local, double *slab_scale);
+/* Factor terms by level index instead of indicator columns: a random intercept per subject, site or item,
+ * (1 | subject), without a dense column of X per level.  F factors, 0 <= F <= 4; factor f has N_f >= 1 levels and an index
+ * lvl_f[i] in 0 .. N_f-1 per observation.  With Dd >= 1 dense columns, the columns of the model are
+ *   c < Dd: dense, X[i][c] stored      off_f = Dd + N_0 + .. + N_{f-1}      c = off_f + k: level k of factor f, not stored
+ *   Dx = Dd + sum N_f,   q = [u (Dx) | a (A) | omega (H) | lambda (J)],   D = Dx + A + H + J <= 1024   (unchanged)
+ * b_c is as today for every c < Dx (group scale, local scale).  The arithmetic -- the kernels follow this bit for bit --
+ *   z_i  = the dfma chain over c < Dd ascending of X[i][c] * b_c from +0,  then  z_i = z_i + b[off_f + lvl_f[i]]  for f = 0 .. F-1
+ *          ascending (plain additions)
+ *   (r_i, v_i, s_ij) as today; observations i >= n overwritten with 0 as today (the padding carries lvl = -1 and adds nothing to z)
+ *   G_c, c < Dd: as today.   G_{off_f + k} = plain additions, from +0, of r_i over the observations i < n with lvl_f[i] = k, i ascending
+ * and everything after G is untouched: auxiliary scores, group chain rule, local scales, prior loop, T, A[rho], P, l.
+ * For finite b and r this is bit for bit the arithmetic of the same model with its factors written out as indicator columns of X
+ * (n x Dx, column off_f + k holding 1.0 where lvl_f[i] = k and 0.0 elsewhere): adding +-0 changes nothing, because a chain from +0
+ * never holds -0, and fma(1, x, y) is y + x rounded once.  The equivalence ends at the non-finite: a non-finite b of one level poisons
+ * every z of the expanded model (0 * inf) and here only that level's observations; both are rejected points.  A level with no
+ * observation is allowed: its G is +0 and the prior alone moves it.
+ *
+ * idhmc_create_glm_factors is idhmc_create_glm_local with these: glm->Dx counts dense and level columns (Dd = Dx - sum N_f), glm->X is
+ * n x Dd, and groups, local, mu, tau, kind and nu have the lengths they have today.  factors == NULL or F == 0 gives the context of
+ * idhmc_create_glm_local: the same kernels, the same bits.  On the device X is stored Lx = 128 ceil(Dd / 128) wide, not L, and the
+ * limit on the observations is n_pad * Lx <= 2^27.  No LDS is added: idhmc_glm_form is what it is for the same (L, A, metric).
+ * Refused with IDHMC_ERR_BAD_ARG before the device is touched: F outside 0..4; levels or index NULL with F > 0; N_f < 1; an index
+ * outside 0 .. N_f-1; Dd < 1; and everything the other creation functions refuse. */
+typedef struct { int32_t F; const int32_t *levels; const int32_t *index; } idhmc_glm_factors;   /* levels: F entries; index: F x n, row-major */
+int idhmc_create_glm_factors(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                             const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                             const idhmc_glm_factors *factors, int64_t M, int64_t chains_per_response,
+                             const idhmc_options *opt, uint64_t seed);
+/* F, the levels (F entries; room for 4) and the indices (F x n, row-major) as the context was given them; F = 0 for every other
+ * context.  levels and index may be NULL (F alone is wanted) */
+int idhmc_glm_factors_get(const idhmc_ctx *ctx, int32_t *F, int32_t *levels, int32_t *index);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

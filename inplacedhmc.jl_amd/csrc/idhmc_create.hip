@@ -64,7 +64,18 @@ struct GlmParts {
     int32_t J = 0;             // idhmc_create_glm_local: flagged columns; the last J coordinates are the logarithms of their local scales
     const int32_t *local = nullptr;      // [Dx] 0 or 1, J > 0 (never null then)
     double slab = 0.0;         // the slab scale (0: none)
+    int32_t F = 0;             // idhmc_create_glm_factors: factors; X holds the Dd = D - A - H - J - fcols dense columns only
+    int32_t fcols = 0;         // their level columns, sum N_f
+    const int32_t *levels = nullptr, *findex = nullptr;   // [F], [F][n], F > 0 (never null then; every index checked)
 };
+// the padded width of the stored columns of X: L of the model, and with factors Lx = 128 ceil(Dd / 128)
+static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
+{
+    int64_t L = 128;
+    while (L < D) L *= 2;
+    if (L_out) *L_out = L;
+    return g.F > 0 ? ((int64_t)D - g.A - g.H - g.J - g.fcols + 127) / 128 * 128 : L;
+}
 // The head of a packed params array into *g: `head` = 0 (a logistic regression's [X | y]), 2 ([K, nc, c | X | Y]) or 3
 // ([K, nc, A, c | X | Y]) doubles in front of the constants.  The entries are checked as doubles (integral, hence finite, and in
 // range) before they are converted, and nothing at or past nparams is read: X, Y and c point at exactly the nparams - head doubles
@@ -139,13 +150,12 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
         }
     }
     const int64_t n = g.n, K = g.K, M = g.M;
-    const int64_t Dx = D - g.A - g.H - g.J;      // the columns of X
-    int L = 128;
-    while (L < D) L *= 2;
+    const int64_t Dx = D - g.A - g.H - g.J - g.fcols;      // the columns of X (with factors: the dense ones)
+    const int64_t L = stored_width(g, D);
     const int64_t npad = (n + 127) / 128 * 128;
     if (npad * L > ((int64_t)1 << 27))
-        return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld observations at D = %d exceed n_pad * L <= 2^27 (at most %lld)",
-                    what, (long long)n, D, (long long)((((int64_t)1 << 27) / L) / 128 * 128));
+        return fail(IDHMC_ERR_BAD_ARG, "%s: n = %lld observations at D = %d exceed n_pad * %s <= 2^27 (at most %lld)",
+                    what, (long long)n, D, g.F > 0 ? "Lx" : "L", (long long)((((int64_t)1 << 27) / L) / 128 * 128));
     if (M > ((int64_t)1 << 27) || M * K * npad > ((int64_t)1 << 27))
         return fail(IDHMC_ERR_BAD_ARG, "%s: M = %lld responses of K = %lld columns and n = %lld observations exceed M * K * n_pad <= 2^27",
                     what, (long long)M, (long long)K, (long long)n);
@@ -181,20 +191,46 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
 static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
 {
     DevState &s = c->s;
-    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, D = s.D - g.A - g.H - g.J, K = g.K, M = g.M;     // D: the columns of X
-    std::vector<double> hx((size_t)(npad * L), 0.0), hxt((size_t)(npad * L), 0.0), hy((size_t)(M * K * npad), 0.0);
+    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, Dm = s.D - g.A - g.H - g.J, K = g.K, M = g.M;    // Dm: the columns of the model
+    const int64_t D = Dm - g.fcols, LX = stored_width(g, s.D);      // the columns X stores (with factors: the dense ones) and their padded width
+    // The level lists of a model with factors, before anything is uploaded: per block of 128 observations its places sorted by factor,
+    // level, place (a counting sort), and where each level's list starts
+    const int64_t nb = npad / 128, cols = g.fcols;
+    std::vector<int32_t> hfidx, hfstart, cur;
+    std::vector<unsigned char> hfpos;
+    if (g.F > 0) {
+        hfidx.assign((size_t)(g.F * npad), -1);
+        hfstart.assign((size_t)(nb * (cols + 1)), 0);
+        hfpos.assign((size_t)(nb * 128 * g.F), 0);
+        cur.assign((size_t)cols, 0);
+        for (int64_t f = 0; f < g.F; ++f)
+            for (int64_t i = 0; i < n; ++i) hfidx[(size_t)(f * npad + i)] = g.findex[f * n + i];
+        for (int64_t b = 0; b < nb; ++b) {
+            int32_t *st = &hfstart[(size_t)(b * (cols + 1))];
+            const int64_t m = n - 128 * b < 128 ? n - 128 * b : 128;
+            int64_t e0 = 0;
+            for (int64_t f = 0; f < g.F; e0 += g.levels[f], ++f)
+                for (int64_t ii = 0; ii < m; ++ii) ++st[e0 + g.findex[f * n + 128 * b + ii] + 1];
+            for (int64_t e = 0; e < cols; ++e) { st[e + 1] += st[e]; cur[(size_t)e] = st[e]; }
+            e0 = 0;
+            for (int64_t f = 0; f < g.F; e0 += g.levels[f], ++f)
+                for (int64_t ii = 0; ii < m; ++ii)
+                    hfpos[(size_t)(b * 128 * g.F + cur[(size_t)(e0 + g.findex[f * n + 128 * b + ii])]++)] = (unsigned char)ii;
+        }
+    }
+    std::vector<double> hx((size_t)(npad * LX), 0.0), hxt((size_t)(npad * LX), 0.0), hy((size_t)(M * K * npad), 0.0);
     for (int64_t i = 0; i < n; ++i)
         for (int64_t k = 0; k < D; ++k) {
             const double v = g.X[i * D + k];
-            hx[(size_t)(i * L + k)] = v;
+            hx[(size_t)(i * LX + k)] = v;
             hxt[(size_t)(k * npad + i)] = v;
         }
     for (int64_t m = 0; m < M; ++m)
         for (int64_t i = 0; i < n; ++i)
             for (int64_t k = 0; k < K; ++k) hy[(size_t)((m * K + k) * npad + i)] = g.Y[(m * n + i) * K + k];
     double *dx = nullptr, *dxt = nullptr, *dy = nullptr;
-    if (int rc = dalloc(c, &dx, npad * L)) return rc;
-    if (int rc = dalloc(c, &dxt, npad * L)) return rc;
+    if (int rc = dalloc(c, &dx, npad * LX)) return rc;
+    if (int rc = dalloc(c, &dxt, npad * LX)) return rc;
     if (int rc = dalloc(c, &dy, M * K * npad)) return rc;
     if (glm) {
         double *dc = nullptr;
@@ -210,7 +246,7 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
     if (g.H > 0) {
         // the group of every coordinate: -1 past the columns of X (auxiliary coordinates, log scales, padding)
         hg.assign((size_t)L, -1);
-        for (int64_t k = 0; k < D; ++k) hg[(size_t)k] = g.grp[k];
+        for (int64_t k = 0; k < Dm; ++k) hg[(size_t)k] = g.grp[k];
         int32_t *dg = nullptr;
         if (int rc = dalloc(c, &dg, L)) return rc;
         HIPCHK(hipMemcpyAsync(dg, hg.data(), sizeof(int32_t) * hg.size(), hipMemcpyHostToDevice, c->stream));
@@ -240,7 +276,7 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         // the partner of every coordinate: the k-th flagged column (ascending) and coordinate Dx + A + H + k name each other
         hp.assign((size_t)L, -1);
         int64_t k = s.D - g.J;
-        for (int64_t col = 0; col < D; ++col)
+        for (int64_t col = 0; col < Dm; ++col)
             if (g.local[col]) { hp[(size_t)col] = (int32_t)k; hp[(size_t)k] = (int32_t)col; ++k; }
         int32_t *dp = nullptr;
         if (int rc = dalloc(c, &dp, L)) return rc;
@@ -248,8 +284,28 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         s.lr_lpart = dp;
         s.lr_j = g.J;
         s.lr_inv2 = g.slab > 0.0 ? 1.0 / (g.slab * g.slab) : 0.0;
-        c->glm_local.assign(g.local, g.local + D);
+        c->glm_local.assign(g.local, g.local + Dm);
         c->slab_scale = g.slab;
+    }
+    if (g.F > 0) {
+        int32_t *di = nullptr, *ds = nullptr;
+        unsigned char *dp = nullptr;
+        if (int rc = dalloc(c, &di, (int64_t)hfidx.size())) return rc;
+        if (int rc = dalloc(c, &ds, (int64_t)hfstart.size())) return rc;
+        if (int rc = dalloc(c, &dp, (int64_t)hfpos.size())) return rc;
+        HIPCHK(hipMemcpyAsync(di, hfidx.data(), sizeof(int32_t) * hfidx.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(ds, hfstart.data(), sizeof(int32_t) * hfstart.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dp, hfpos.data(), hfpos.size(), hipMemcpyHostToDevice, c->stream));
+        s.lr_f = g.F;
+        s.lr_fidx = di; s.lr_fstart = ds; s.lr_fpos = dp;
+        s.lr_dd = (int32_t)D; s.lr_lx = (int32_t)LX; s.lr_fcols = (int32_t)cols;
+        int32_t off = (int32_t)D;
+        for (int f = 0; f < 4; ++f) {
+            s.lr_foff[f] = off;
+            if (f < g.F) off += g.levels[f];
+        }
+        c->glm_flevels.assign(g.levels, g.levels + g.F);
+        c->glm_findex.assign(g.findex, g.findex + (int64_t)g.F * n);
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
     s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
@@ -571,13 +627,43 @@ static int validate_local(const idhmc_glm_desc *glm, const idhmc_glm_local *lc, 
     return IDHMC_OK;
 }
 
-// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors and idhmc_create_glm_local
+// The factors of idhmc_create_glm_factors: every check of F, levels and index.  *fcols: the level columns, sum N_f (0: the context is
+// the one without factors)
+static int validate_factors(const idhmc_glm_desc *glm, const idhmc_glm_factors *fc, int64_t *fcols)
+{
+    *fcols = 0;
+    if (!fc) return IDHMC_OK;
+    if (fc->F < 0 || fc->F > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors must be an integer in 0..4", fc->F);
+    if (fc->F == 0) return IDHMC_OK;
+    if (!fc->levels || !fc->index) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors need levels and index (%s is NULL)", fc->F, fc->levels ? "index" : "levels");
+    int64_t cols = 0;
+    for (int f = 0; f < fc->F; ++f) {
+        if (fc->levels[f] < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor %d has levels[%d] = %d: at least one level is needed", f, f, fc->levels[f]);
+        cols += fc->levels[f];
+    }
+    if (glm->Dx - cols < 1)
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: Dd = Dx - sum of levels = %d - %lld = %lld: at least one dense column is needed",
+                    glm->Dx, (long long)cols, (long long)(glm->Dx - cols));
+    for (int f = 0; f < fc->F; ++f)
+        for (int64_t i = 0; i < glm->n; ++i) {
+            const int32_t v = fc->index[(int64_t)f * glm->n + i];
+            if (v < 0 || v >= fc->levels[f])
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: index[%d][%lld] = %d is outside 0..%d (the levels of factor %d)", f, (long long)i, v, fc->levels[f] - 1, f);
+        }
+    *fcols = cols;
+    return IDHMC_OK;
+}
+
+// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local and idhmc_create_glm_factors
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
-                      const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr)
+                      const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
+                      const idhmc_glm_factors *factors = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
+    int64_t fcols = 0;
+    if (int rc = validate_factors(glm, factors, &fcols)) return rc;
     if (glm->A < 0 || glm->A > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: A = %d must be an integer in 0..4", glm->A);
     if (glm->H < 0 || glm->H > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d must be an integer in 0..4", glm->H);
     if (glm->Dx > 1024 - glm->A - glm->H)
@@ -612,6 +698,7 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
     if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
     if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
+    if (fcols > 0) { parts.F = factors->F; parts.fcols = (int32_t)fcols; parts.levels = factors->levels; parts.findex = factors->index; }
     return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
 }
 
@@ -647,6 +734,25 @@ int idhmc_create_glm_local(idhmc_ctx **out, int device, int64_t nchains, int64_t
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_local: null argument");
     const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
     return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local);
+}
+
+int idhmc_create_glm_factors(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                             const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                             const idhmc_glm_factors *factors, int64_t M, int64_t chains_per_response,
+                             const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_factors: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors);
+}
+
+int idhmc_glm_factors_get(const idhmc_ctx *c, int32_t *F, int32_t *levels, int32_t *index)
+{
+    if (!c || !F) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_factors_get: null argument");
+    *F = c->s.lr_f;
+    if (levels) std::copy(c->glm_flevels.begin(), c->glm_flevels.end(), levels);
+    if (index) std::copy(c->glm_findex.begin(), c->glm_findex.end(), index);
+    return IDHMC_OK;
 }
 
 int idhmc_glm_local_get(const idhmc_ctx *c, int32_t *local, double *slab_scale)

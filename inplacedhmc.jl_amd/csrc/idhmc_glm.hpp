@@ -94,6 +94,37 @@
 // again per block as before), and st, h are computed again from q after the loop, as GlmCoop does, rather than held (two more
 // vectors of registers); GlmCoop through the requester's Q row -- q, then b in its place before barrier A; after barrier C the G
 // row is taken into registers, then q, then wl go through the row.  Nothing of the local scales is alive across multiply().
+//
+// Factor terms by level index (idhmc_create_glm_factors): Obs::kFactors, a compile-time flag of the policy (false for
+// the policies above and for every model with F = 0: none of their instructions changes).  F factors, 0 <= F <= 4; factor f has
+// N_f >= 1 levels and an index lvl_f[i] in 0 .. N_f-1 per observation.  With Dd >= 1 dense columns the columns of the model are
+//   c < Dd: dense, X[i][c] stored      off_f = Dd + N_0 + .. + N_{f-1}      c = off_f + k: level k of factor f, not stored
+//   Dx = Dd + sum N_f,   q = [u (Dx) | a (A) | omega (H) | lambda (J)],   D = Dx + A + H + J <= 1024   (unchanged)
+// and b_c is as above for every c < Dx (group scale, local scale).  The arithmetic:
+//   z_i  = the dfma chain over c < Dd ascending of X[i][c] b_c from +0,  then  z_i = z_i + b[off_f + lvl_f[i]]  for f = 0 .. F-1
+//          ascending (plain additions)
+//   (r_i, v_i, s_ij) as above; i >= n overwritten with 0 as above; padded observations carry lvl = -1 and add nothing to z
+//   G_c, c < Dd: as above.   G_{off_f + k} = plain additions, from +0, of r_i over the observations i < n with lvl_f[i] = k, i ascending
+// Everything after G is untouched: auxiliary scores, group chain rule, local scales, prior loop, T, A[rho], P, l.
+// For finite b and r this is bit for bit the arithmetic of the same model with every level written out as an indicator column of X
+// (glm.expand_factors): adding +-0 changes nothing, because a chain from +0 never holds -0 (fma(0, b, z) = z, fma(0, r, G) = G), and
+// fma(1, x, y) is y + x rounded once.  It ends at the non-finite: a non-finite b of one level poisons every z of the expanded model
+// (0 * inf) and here only that level's observations; both are rejected points.  A level with no observation is allowed: its G is +0
+// and the prior alone moves it.
+// Device layout with factors: lr_x is [n_pad][Lx] and lr_xt [Lx][n_pad], Lx = 128 ceil(Dd / 128) (the row stride of X is a run-time
+// member under kFactors and the compile-time L without); lr_fidx holds the index planes, int32 [F][n_pad], -1 in the padding; the level
+// lists, built on the host: per block of 128 observations lr_fpos holds 128 F bytes -- the block's observations (position in the block)
+// of factor 0 sorted by level, positions ascending within a level, then factor 1's, .. -- and lr_fstart [n_pad / 128][sum N_f + 1] where
+// each level's list starts in them (cumulative over the factors: entry e and e + 1 bound the list of column Dd + e).  Every walk of a
+// list is clamped on the device: at most 128 trips, positions inside the block's 128 F bytes, the byte read masked to 0 .. 127, so no list,
+// whatever it held, reads outside the R tile or the wavefront's vector.
+// GlmWave: the z loop runs c < Dd, then adds buf[off_f + lvl] for the lane's two observations (b is staged in buf; the planes are read
+// as int2, lane-offset, like y2); the G loop touches the chunks j < Lx / 128 only; after it each lane adds buf[ii] over the lists of its
+// factor columns into G.c[j] (r is staged in buf[0 .. 127]).  GlmCoop: the Z wavefronts run the matrix loop over the columns
+// < 32 ceil(Dd / 32), then add Q[row][off_f + lvl_f[i]] per accumulator row (the requester writes b there); a G wavefront whose tile
+// starts at or beyond Dd skips the matrix loop, and a tile that holds level columns adds R[b & 1][row][i] over the column's list per
+// lane, after the block's matrix steps where the tile straddles Dd.  No LDS, no tile and no barrier is added; nothing of the factors
+// is alive across multiply() in the requester.
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -324,6 +355,54 @@ IDHMC_DEV double glm_prior(int kind, double nu, double tau, double d, double G, 
     return G + (1.0 - ((nu + 1.0) * e) / (nu + e));
 }
 
+// Factor terms (Obs::kFactors): what both forms take from DevState
+struct GlmFactors {
+    const int32_t *idx, *start;      // lr_fidx [F][n_pad], lr_fstart [n_pad / 128][cols + 1]
+    const unsigned char *pos;        // lr_fpos [n_pad / 128][128 F]
+    int F, dd, lx, cols;             // factors, dense columns, row stride of X and rows of X', sum N_f
+    int off[4];                      // off_f: the column of level 0 of factor f
+    template <class State>
+    IDHMC_DEV void init(const State &s)
+    {
+        idx = s.lr_fidx;
+        start = s.lr_fstart;
+        pos = s.lr_fpos;
+        F = s.lr_f;
+        dd = s.lr_dd;
+        lx = s.lr_lx;
+        cols = s.lr_fcols;
+#pragma unroll
+        for (int f = 0; f < 4; ++f) off[f] = s.lr_foff[f];
+    }
+};
+// the list of level column dd + e in block b: entries s0 .. s0 + cnt - 1 of the block's bytes, cnt clamped to 0 .. 128 (has: the
+// lane's column is a level column at all)
+IDHMC_DEV void glm_list(const GlmFactors &f, int b, int e, bool has, int &s0, int &cnt)
+{
+    s0 = 0;
+    cnt = 0;
+    if (has) {
+        const int32_t *st = f.start + (size_t)b * (size_t)(f.cols + 1) + e;
+        s0 = st[0];
+        cnt = st[1] - s0;
+    }
+    cnt = cnt > 128 ? 128 : cnt;
+}
+// entry t of block b's bytes (t clamped into them): an observation's place in the block, 0 .. 127
+IDHMC_DEV int glm_list_at(const GlmFactors &f, int b, int t)
+{
+    const int last = 128 * f.F - 1;
+    t = t < 0 ? 0 : t > last ? last : t;
+    return f.pos[(size_t)b * (size_t)(128 * f.F) + t] & 127;
+}
+// G of one level column in the per-wave form: plain additions of the block's r (staged in r[0 .. 127]) over the column's list
+IDHMC_DEV void glm_gather(double &G, const GlmFactors &f, int b, int e, bool has, const double *r)
+{
+    int s0, cnt;
+    glm_list(f, b, e, has, s0, cnt);
+    for (int k = 0; k < cnt; ++k) G = G + r[glm_list_at(f, b, s0 + k)];
+}
+
 // v_i and r_i of one observation (y is 0 or 1)
 IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 {
@@ -337,7 +416,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -361,6 +440,7 @@ struct GlmWave {
     const double2 *nu2;
     const int32_t *part;     // the partner of every coordinate, device (Obs::kLocal)
     double inv2;             // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
+    GlmFactors fac;          // the factor terms (Obs::kFactors)
     double *buf;             // this wavefront's LDS vector, L doubles
     int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -384,6 +464,7 @@ struct GlmWave {
             inv2 = s.lr_inv2;
             D -= s.lr_j;
         }
+        if constexpr (Obs::kFactors) fac.init(s);
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -428,12 +509,27 @@ struct GlmWave {
             }
             const double2 *xtp = reinterpret_cast<const double2 *>(xt + 128 * b) + lane;
             double zx = 0.0, zy = 0.0;
+            int dz = D;                                        // the stored columns
+            if constexpr (Obs::kFactors) dz = fac.dd;
 #pragma unroll 4
-            for (int c = 0; c < D; ++c) {
+            for (int c = 0; c < dz; ++c) {
                 const double qc = buf[c];                      // LDS broadcast
                 const double2 xv = xtp[(size_t)c * (npad / 2)];
                 zx = dfma(xv.x, qc, zx);
                 zy = dfma(xv.y, qc, zy);
+            }
+            if constexpr (Obs::kFactors) {
+                // the level columns: b of the observation's level, factors ascending (lvl = -1, the padding, adds nothing)
+                const int2 *lv2 = reinterpret_cast<const int2 *>(fac.idx) + lane + b * 64;
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    if (f < fac.F) {
+                        const int2 lv = lv2[(size_t)f * (npad >> 1)];
+                        const double bx = buf[fac.off[f] + (lv.x > 0 ? lv.x : 0)], by = buf[fac.off[f] + (lv.y > 0 ? lv.y : 0)];
+                        zx = lv.x >= 0 ? zx + bx : zx;
+                        zy = lv.y >= 0 ? zy + by : zy;
+                    }
+                }
             }
             // the K planes of Y (written out: a loop over the planes costs the logistic kernels their register assignment)
             const double2 p0 = y2[b * 64];
@@ -463,15 +559,41 @@ struct GlmWave {
             }
             b2[0] = make_double2(rx, ry);
             const int m = n - 128 * b < 128 ? n - 128 * b : 128;
-            const double2 *xr = reinterpret_cast<const double2 *>(x + (size_t)128 * b * L) + lane;
+            if constexpr (Obs::kFactors) {
+                // rows of Lx doubles: the chunks that hold a stored column, then each level column's list
+                const double2 *xr = reinterpret_cast<const double2 *>(x + (size_t)128 * b * fac.lx) + lane;
+                const int nchx = fac.lx >> 7, xs = fac.lx >> 1;
 #pragma unroll 2
-            for (int ii = 0; ii < m; ++ii) {
-                const double ri = buf[ii];                     // LDS broadcast
+                for (int ii = 0; ii < m; ++ii) {
+                    const double ri = buf[ii];                 // LDS broadcast
+#pragma unroll
+                    for (int j = 0; j < NCH; ++j) {
+                        if (j < nchx) {
+                            const double2 xv = xr[(size_t)ii * xs + j * 64];
+                            G.c[j].x = dfma(xv.x, ri, G.c[j].x);
+                            G.c[j].y = dfma(xv.y, ri, G.c[j].y);
+                        }
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) {
-                    const double2 xv = xr[(size_t)ii * (L / 2) + j * 64];
-                    G.c[j].x = dfma(xv.x, ri, G.c[j].x);
-                    G.c[j].y = dfma(xv.y, ri, G.c[j].y);
+                    if (128 * j + 128 > fac.dd && 128 * j < D) {               // the chunk holds a level column
+                        const int c0 = 128 * j + 2 * lane, e = c0 - fac.dd;
+                        glm_gather(G.c[j].x, fac, b, e, e >= 0 && c0 < D, buf);
+                        glm_gather(G.c[j].y, fac, b, e + 1, e + 1 >= 0 && c0 + 1 < D, buf);
+                    }
+                }
+            } else {
+                const double2 *xr = reinterpret_cast<const double2 *>(x + (size_t)128 * b * L) + lane;
+#pragma unroll 2
+                for (int ii = 0; ii < m; ++ii) {
+                    const double ri = buf[ii];                 // LDS broadcast
+#pragma unroll
+                    for (int j = 0; j < NCH; ++j) {
+                        const double2 xv = xr[(size_t)ii * (L / 2) + j * 64];
+                        G.c[j].x = dfma(xv.x, ri, G.c[j].x);
+                        G.c[j].y = dfma(xv.y, ri, G.c[j].y);
+                    }
                 }
             }
         }
@@ -551,6 +673,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     const double2 *nu2;
     const int32_t *part;         // the partner of every coordinate, device (Obs::kLocal)
     double inv2;                 // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
+    GlmFactors fac;              // the factor terms (Obs::kFactors)
     double *tile;
     int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -567,6 +690,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             kind2 = reinterpret_cast<const int2 *>(s.lr_pkind) + lane_;
             nu2 = reinterpret_cast<const double2 *>(s.lr_pnu) + lane_;
         }
+        if constexpr (Obs::kFactors) fac.init(s);
         x = s.lr_x;
         xt = s.lr_xt;
         y = s.lr_y;
@@ -603,8 +727,10 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         const int vo = (kk * npad + jj) * 8;                  // B[kk][jj] = X'[4 kb + kk][128 b + 16 zt + jj]
         const double *ap = tile + kQ + jj * DS + kk;          // A[jj][kk] = Q[chain jj][4 kb + kk]
         v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
+        int kbn = KB;
+        if constexpr (Obs::kFactors) kbn = 8 * ((fac.dd + 31) >> 5);      // the stored columns, in the loop's steps of 32 (<= Lx / 4)
 #pragma unroll 1
-        for (int kb0 = 0; kb0 < KB; kb0 += 8) {
+        for (int kb0 = 0; kb0 < kbn; kb0 += 8) {
             double bv[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u)
@@ -613,6 +739,21 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * (kb0 + u)], bv[u], acc, 0, 0, 0);
         }
         const int i = 128 * b + 16 * zt + jj;
+        if constexpr (Obs::kFactors) {
+            // the level columns: b of observation i's level from each row's Q, factors ascending (lvl = -1, the padding, adds nothing)
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                if (f < fac.F) {
+                    const int lv = fac.idx[(size_t)f * npad + i];
+                    const double *qp = tile + kQ + kk * DS + fac.off[f] + (lv > 0 ? lv : 0);
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        const double bl = qp[4 * reg * DS];
+                        acc[reg] = lv >= 0 ? acc[reg] + bl : acc[reg];
+                    }
+                }
+            }
+        }
         GlmObs o;
         if constexpr (!Obs::kResponses) {
 #pragma unroll
@@ -652,6 +793,36 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     // (3) for block b: G tile wv += R[b & 1] X[block, 16 wv ..]
     IDHMC_DEV void gphase(int b, int kk, int jj, v4d &gacc) const
     {
+        if constexpr (Obs::kFactors) {
+            // rows of Lx doubles; a tile at or beyond Dd has no stored column and skips the matrix steps
+            if (16 * wv < fac.dd) {
+                const __amdgpu_buffer_rsrc_t rX = buf_rsrc(x + (size_t)128 * b * fac.lx + 16 * wv);
+                const int vo = (kk * fac.lx + jj) * 8;
+                const double *ap = rtile(b) + jj * RS + kk;
+#pragma unroll 1
+                for (int kb0 = 0; kb0 < 32; kb0 += 8) {
+                    double bv[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        bv[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rX, vo + 4 * (kb0 + u) * fac.lx * 8, 0, 0));
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) gacc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * (kb0 + u)], bv[u], gacc, 0, 0, 0);
+                }
+            }
+            // the tile's level columns: lane (kk, jj) holds column 16 wv + jj of rows kk + 4 reg and adds their r over the column's list
+            if (16 * wv + 16 > fac.dd && 16 * wv < dx) {
+                const int c = 16 * wv + jj, e = c - fac.dd;
+                int s0, cnt;
+                glm_list(fac, b, e, e >= 0 && c < dx, s0, cnt);
+                const double *rp = rtile(b) + kk * RS;
+                for (int k = 0; k < cnt; ++k) {
+                    const int ii = glm_list_at(fac, b, s0 + k);
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) gacc[reg] = gacc[reg] + rp[4 * reg * RS + ii];
+                }
+            }
+            return;
+        }
         const __amdgpu_buffer_rsrc_t rX = buf_rsrc(x + (size_t)128 * b * L + 16 * wv);
         const int vo = (kk * L + jj) * 8;                     // B[kk][jj] = X[128 b + 4 kb + kk][16 wv + jj]
         const double *ap = rtile(b) + jj * RS + kk;           // A[jj][kk] = R[chain jj][4 kb + kk]

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <new>
 #include <vector>
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include "idhmc_internal.hpp"
@@ -68,6 +69,8 @@ struct idhmc_ctx {
     std::vector<double> prior_nu;
     std::vector<int32_t> glm_local;    // idhmc_create_glm_local with some column flagged: local as given, Dx entries (empty otherwise)
     double slab_scale = 0.0;           // and its slab scale (0: none)
+    std::vector<int32_t> glm_flevels;  // idhmc_create_glm_factors with F > 0: levels (F entries) and index (F x n) as given (empty otherwise)
+    std::vector<int32_t> glm_findex;
     // IDHMC_EPS_PER_RESPONSE / IDHMC_METRIC_PER_RESPONSE: the context holds resp_n = C / glm_r whole responses (0 in every other mode)
     int64_t resp_n = 0;
     double *resp_da = nullptr;     // [resp_n][6] dual-averaging states of IDHMC_EPS_PER_RESPONSE: mu, m, Hbar, logeps, logeps_bar, eps

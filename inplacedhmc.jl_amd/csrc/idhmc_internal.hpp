@@ -93,6 +93,15 @@ struct DevState {
     const int32_t *lr_lpart;  // [L] the partner of every coordinate: a flagged column's lambda, a lambda's column, -1 elsewhere
     double lr_inv2;           // 1 / slab_scale^2 (0: no slab)
     int32_t lr_j;
+    // a GLM with factor terms (idhmc_create_glm_factors; 0 and null otherwise, and then lr_x is [lr_npad][L] as above).
+    // Appended: every other offset is what it was, so no kernel of a model without factors changes (profiles/r17_glm_factors_kres_*.txt).
+    int32_t lr_f;             // factors, 0..4
+    const int32_t *lr_fidx;   // [lr_f][lr_npad] the level of every observation, -1 in the padding
+    const int32_t *lr_fstart; // [lr_npad / 128][lr_fcols + 1] per block of 128 observations: where each level's list starts in the block's bytes
+    const unsigned char *lr_fpos;   // [lr_npad / 128][128 lr_f] per block: its observations (place in the block) sorted by factor, level, place
+    int32_t lr_dd, lr_lx;     // dense (stored) columns; Lx = 128 ceil(lr_dd / 128): lr_x is [lr_npad][lr_lx], lr_xt [lr_lx][lr_npad]
+    int32_t lr_fcols;         // level columns, sum N_f
+    int32_t lr_foff[4];       // the column of level 0 of factor f
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -142,7 +151,7 @@ struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
 // K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors),
-// s.lr_lpart one with local scales (kLocal)
+// s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmDesc, GlmLocal, GlmPriors, ModelDesc, Options, check
+from ._lib import GlmDesc, GlmFactors, GlmLocal, GlmPriors, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -163,7 +163,7 @@ def _prior(D, prior_mu, prior_tau):
 
 
 def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None, prior_kind=None,
-        prior_nu=None, local=None, slab_scale=None):
+        prior_nu=None, local=None, slab_scale=None, factors=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -211,19 +211,31 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     exp(lambda_k) (exp(lambda_k) in no group), st = s without a slab and s / sqrt(1 + s^2 / S^2) with slab_scale = S > 0 (fixed, not
     sampled; None or 0: no slab; it needs a flagged column).  glm.horseshoe() assembles groups, local, slab_scale and the priors;
     glm.coefficients, glm.group_scales and glm.local_scales read draws.  With no column flagged the model is the one without the
-    keywords.  The Model exposes J, local (int32, or None) and slab_scale (None without a slab); Engine.glm_local() reads them back."""
+    keywords.  The Model exposes J, local (int32, or None) and slab_scale (None without a slab); Engine.glm_local() reads them back.
+
+    factors: a list of up to 4 factor terms by level index (idhmc_create_glm_factors) -- a random intercept per subject, site or item,
+    (1 | subject), without an indicator column per level.  Each entry is an integer array idx of shape (n,), or (idx, N); N, the number
+    of levels, defaults to max(idx) + 1, and idx[i] is in 0 .. N-1.  X holds the Dd dense columns only; the columns of the model are the
+    dense ones, then the levels of factor 0, of factor 1, ..: Dx = Dd + sum N_f, and groups, local, prior_mu, prior_tau, prior_kind and
+    prior_nu count those Dx columns (glm.factor_columns(model, f) is the slice of factor f; glm.random_intercepts() assembles groups and
+    priors).  The model is bit for bit the one with glm.expand_factors(X, factors) as its design matrix, whose indicator columns are
+    never built, stored or multiplied.  An empty list is the model without the keyword.  The Model exposes Dd, F, levels (int32 (F,)) and
+    factor_index (int32 (F, n)), None and 0 without factors; Engine.glm_factors() reads them back."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
     X = np.asarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
         raise ValueError("X must be a non-empty (n, D) matrix, got shape %s" % (X.shape,))
-    n, Dx = X.shape
+    n, Dd = X.shape
+    flev, fidx = _glm.factor_terms(factors, n)
+    F = 0 if flev is None else flev.size
+    Dx = Dd + (int(flev.sum()) if F else 0)
     grp, H = None, 0
     if groups is not None:
         grp = np.asarray(groups)
         if grp.ndim != 1 or grp.shape[0] != Dx:
-            raise ValueError("groups must have one entry per column of X (%d), got shape %s" % (Dx, grp.shape))
+            raise ValueError("groups must have one entry per column of %s (%d), got shape %s" % ("the model" if F else "X", Dx, grp.shape))
         if grp.dtype == np.bool_ or not np.issubdtype(grp.dtype, np.integer):
             raise ValueError("groups must be integers (-1: no group), got dtype %s" % grp.dtype)
         if grp.min() < -1:
@@ -272,7 +284,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     kind, nu = _glm.prior_kinds(prior_kind, prior_nu, D, Dx, tau)
     priors = kind is not None and bool(kind.any())
     K = Y.shape[-1]
-    if H > 0 or R is not None or priors or J > 0:
+    if H > 0 or R is not None or priors or J > 0 or F > 0:
         # handed over in parts (idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local): the packed
         # params are not stretched for the groups, the responses, the priors or the local scales
         m = Model(MODEL_GLM_AUX if A else MODEL_GLM, D, mu=mu, tau=tau, source=source)
@@ -287,6 +299,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.M, m.R = M, R
     m.prior_kind, m.prior_nu = kind, nu
     m.J, m.local, m.slab_scale = J, loc, S
+    m.Dd, m.F, m.levels, m.factor_index = Dd, F, flev, fidx
     return m
 
 
@@ -310,7 +323,19 @@ class Engine:
         self.C, self.D = int(nchains), model.D
         h = C.c_void_p()
         kind = getattr(model, "prior_kind", None)
-        if getattr(model, "J", 0) > 0:
+        if getattr(model, "F", 0) > 0:
+            desc = model.glm_desc()
+            pr = lc = None
+            if kind is not None:
+                pr = C.byref(GlmPriors(kind=kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=_dp(model.prior_nu)))
+            if model.J > 0:
+                lc = C.byref(GlmLocal(local=model.local.ctypes.data_as(C.POINTER(C.c_int32)), slab_scale=model.slab_scale or 0.0))
+            fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
+                            index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
+            R = getattr(model, "R", None)
+            check(self.lib.idhmc_create_glm_factors(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc),
+                                                    model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
+        elif getattr(model, "J", 0) > 0:
             desc = model.glm_desc()
             pr = None
             if kind is not None:
@@ -455,6 +480,17 @@ class Engine:
         loc, S = np.zeros(Dx, np.int32), C.c_double(0.0)
         check(self.lib.idhmc_glm_local_get(self.h, loc.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(S)))
         return loc, float(S.value)
+
+    def glm_factors(self):
+        """(levels int32 (F,), index int32 (F, n)) as the context holds them (GLM(..., factors=)); (None, None) for every model without
+        factor terms"""
+        F = C.c_int32(0)
+        check(self.lib.idhmc_glm_factors_get(self.h, C.byref(F), None, None))
+        if F.value == 0:
+            return None, None
+        lev, idx = np.zeros(F.value, np.int32), np.zeros((F.value, self.model.n), np.int32)
+        check(self.lib.idhmc_glm_factors_get(self.h, C.byref(F), lev.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(C.POINTER(C.c_int32))))
+        return lev, idx
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -87,6 +87,14 @@ half-t(nu_local) on every local scale, half-t(nu_global, global_scale) on the sc
 With a slab every finite q is finite.  Without one, omega_g + lambda_k past 709.78 makes s infinite and the coefficient infinite or
 NaN: l reads as -inf, the ordinary rejected point.  With a slab and s below about 1.5e-154 the square of 1 / s overflows and st is 0
 where it should be s: an absolute error below 1.5e-154 |u| in the coefficient, stated and not engineered around.
+
+Factor terms by level index, GLM(..., factors=[idx, ...]) (idhmc_create_glm_factors): a random intercept per subject,
+site or item, (1 | subject), and every source above works unchanged with them.  X holds the Dd dense columns; factor f has N_f levels and
+an index idx_f[i] in 0 .. N_f-1 per observation, and its levels are the columns off_f .. off_f + N_f - 1 of the model, off_f = Dd + N_0 +
+.. + N_{f-1}, which are never stored: z_i = (X b)_i + sum_f b[off_f + idx_f[i]].  Groups, local scales and priors count all Dx = Dd +
+sum N_f columns.  expand_factors(X, factors) is the same model with its indicator columns written out -- the engine computes the same
+bits on both -- factor_columns(model, f) the slice of factor f, and random_intercepts(Dd, levels, ...) the groups and priors that give
+each factor a sampled scale of its own.
 """
 import collections
 
@@ -421,6 +429,96 @@ def local_flags(local, slab_scale, Dx):
     if J == 0:
         loc = None
     return loc, J, S
+
+
+# ---- factor terms ---------------------------------------------------------------------------------------------------------------------
+def factor_terms(factors, n):
+    """GLM()'s validation of factors: (levels int32 (F,), index int32 (F, n)), or (None, None) for None and for an empty list.  Each
+    entry is an integer array of shape (n,) or a pair (array, N); N defaults to max + 1.  The checks are idhmc_create_glm_factors'."""
+    if factors is None:
+        return None, None
+    if isinstance(factors, np.ndarray) or not isinstance(factors, (list, tuple)):
+        raise ValueError("factors must be a list of index arrays (n,) or of pairs (index, levels), got %s" % type(factors).__name__)
+    if len(factors) == 0:
+        return None, None
+    if len(factors) > 4:
+        raise ValueError("at most 4 factors (got %d)" % len(factors))
+    lev, idx = np.empty(len(factors), np.int32), np.empty((len(factors), n), np.int32)
+    for f, entry in enumerate(factors):
+        N = None
+        if isinstance(entry, tuple):
+            if len(entry) != 2:
+                raise ValueError("factors[%d] must be an index array or a pair (index, levels)" % f)
+            entry, N = entry
+            if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or N < 1:
+                raise ValueError("factors[%d]: the number of levels must be a positive integer (got %r)" % (f, N))
+        raw = np.asarray(entry)
+        if raw.ndim != 1 or raw.shape[0] != n:
+            raise ValueError("factors[%d] must have one index per observation, shape (%d,), got %s" % (f, n, raw.shape))
+        if raw.dtype == np.bool_ or not np.issubdtype(raw.dtype, np.integer):
+            raise ValueError("factors[%d] must be integers (level indices), got dtype %s" % (f, raw.dtype))
+        if raw.min() < 0:
+            raise ValueError("factors[%d]: a level index is 0 .. N-1, got %d" % (f, raw.min()))
+        N = int(raw.max()) + 1 if N is None else int(N)
+        if raw.max() >= N:
+            raise ValueError("factors[%d]: index %d is outside 0..%d (the factor's %d levels)" % (f, raw.max(), N - 1, N))
+        if N > 1024:
+            raise ValueError("factors[%d]: %d levels (a GLM is limited to D <= 1024)" % (f, N))
+        lev[f], idx[f] = N, raw
+    return lev, idx
+
+
+def factor_columns(model, f):
+    """the columns of factor f among the Dx columns of a GLM with factor terms: slice(off_f, off_f + N_f), off_f = Dd + N_0 + .. + N_{f-1}"""
+    F = getattr(model, "F", 0)
+    if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not 0 <= f < F:
+        raise ValueError("factor %r: the model has factors 0..%d" % (f, F - 1) if F else "the model has no factor terms (GLM(..., factors=))")
+    off = model.Dd + int(model.levels[:f].sum())
+    return slice(off, off + int(model.levels[f]))
+
+
+def expand_factors(X, factors):
+    """the n x Dx design matrix with one indicator column per level -- the documented equivalent of GLM(X, ..., factors=factors): the
+    dense columns of X, then for factor 0, 1, .. one column per level holding 1.0 where the observation has that level and 0.0 elsewhere.
+    The engine computes the same bits on both."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be an (n, Dd) matrix, got shape %s" % (X.shape,))
+    lev, idx = factor_terms(factors, X.shape[0])
+    if lev is None:
+        return X.copy()
+    out = np.zeros((X.shape[0], X.shape[1] + int(lev.sum())))
+    out[:, :X.shape[1]] = X
+    off = X.shape[1]
+    rows = np.arange(X.shape[0])
+    for f in range(lev.size):
+        out[rows, off + idx[f]] = 1.0
+        off += int(lev[f])
+    return out
+
+
+def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):
+    """the keyword arguments groups, prior_mu, prior_tau, prior_kind and prior_nu of GLM() for random intercepts: Dd dense columns in no
+    group, then factor f's levels[f] columns forming group f, whose sigma_f = exp(omega_f) is sampled --
+    GLM(X, Y, source, factors=[subject, item], **glm.random_intercepts(X.shape[1], [n_subjects, n_items], scale=glm.half_student_t(3))).
+    u ~ N(0, 1) on every level (so an intercept is N(0, sigma_f^2)), `scale` the spec(s) of the H = len(levels) group scales,
+    `coefficients` those of the Dd dense columns and `aux` those of the auxiliary coordinates, as priors() takes them."""
+    Dd = int(Dd)
+    lev = [int(N) for N in levels]
+    if Dd < 1:
+        raise ValueError("Dd = %d: at least one dense column is needed" % Dd)
+    if len(lev) < 1 or min(lev) < 1:
+        raise ValueError("levels must hold the positive number of levels of each factor, got %r" % (levels,))
+    if len(lev) > 4:
+        raise ValueError("at most 4 factors, each a group of its own (H <= 4), got %d" % len(lev))
+    if coefficients is None or isinstance(coefficients, PriorSpec):
+        coefficients = [normal() if coefficients is None else coefficients] * Dd
+    coefficients = list(coefficients)
+    if len(coefficients) != Dd:
+        raise ValueError("coefficients must be one prior spec or a sequence of Dd = %d" % Dd)
+    kw = priors(Dd + sum(lev), A, len(lev), coefficients=coefficients + [normal()] * sum(lev), aux=aux, scales=scale)
+    kw["groups"] = np.concatenate([np.full(Dd, -1)] + [np.full(N, g) for g, N in enumerate(lev)]).astype(np.int32)
+    return kw
 
 
 # ---- priors ---------------------------------------------------------------------------------------------------------------------------

@@ -45,6 +45,12 @@ every column with a local scale, no slab -- D lambdas more, so L doubles at D = 
 without local scales on 2 D columns, which has the padded length of (ii) and (iii) and so does the same matrix work.  --local-rows picks
 rows (i and iv run on a build without the keywords as well).  Meant to run under --lockstep.
 
+--factor-cost (GLM(..., factors=)) runs, per row DdxLEVELSxN of --factor-rows and chain count, a pair on the same data:
+the Poisson GLM with Dd dense columns and one factor by level index, its levels a group with a sampled scale (H = 1), and the same model on
+the expanded matrix with one indicator column per level.  Both sides run the same trajectories (same_bits), so the ratio of their
+steps/s is a time ratio.  --repeats K makes K engines per side (the best is reported, all are listed).  Meant to run under --lockstep
+with --pairs ''.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
@@ -428,6 +434,22 @@ def responses_model(X, y, q_map, M, C):
     return pkg.GLM(X, Y, pkg.glm.POISSON_LOG, chains_per_response=C // M)
 
 
+def factor_problem(Dd, N, n, seed):
+    """a Poisson regression with Dd dense columns and one factor of N levels in a group of its own (H = 1): (X (n, Dd), y, index, the
+    keywords of both models, a start q and a narrow covariance around it for `run`)"""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, Dd)) / np.sqrt(Dd)
+    X[:, 0] = 1.0
+    idx = rng.integers(0, N, n)
+    sigma = 0.5
+    u = rng.standard_normal(N)
+    beta = np.r_[0.5, 0.3 * rng.standard_normal(Dd - 1)]
+    y = rng.poisson(np.exp(X @ beta + sigma * u[idx])).astype(float)
+    kw = pkg.glm.random_intercepts(Dd, [N])
+    q0 = np.r_[beta, u, np.log(sigma)]
+    return X, y, idx, kw, q0, np.eye(q0.size) * 1e-4
+
+
 def run(form, X, y, q_map, cov, C, T, seed=1, metric=None, mdl=None):
     t0 = time.perf_counter()
     eng = pkg.Engine(model(form, X, y, q_map) if mdl is None else mdl, C, pkg.default_options(metric_mode=pkg.METRIC_SHARED if metric is None else metric,
@@ -557,6 +579,11 @@ def main():
     ap.add_argument("--local-cost", action="store_true", help="the hier design (H = 1, Poisson) without local scales, with one on every "
                     "column, the same with a slab, and a control of twice the columns without any (DESIGN section 19); use --lockstep")
     ap.add_argument("--local-rows", default="i,ii,iii,iv", help="the rows of --local-cost to run")
+    ap.add_argument("--factor-cost", action="store_true", help="per row of --factor-rows a pair on the same data: the Poisson GLM with one "
+                    "factor by level index (H = 1 on its levels) and the same model on the expanded matrix (DESIGN section 20); use --lockstep, "
+                    "and --pairs '' to run nothing else")
+    ap.add_argument("--factor-rows", default="20x200x1000,20x200x10000,20x900x10000,100x20x1000", help="DdxLEVELSxN,...")
+    ap.add_argument("--factor-sides", default="factor,expanded", help="the sides of each pair to run")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -575,6 +602,32 @@ def main():
         torch.zeros(1, device="cuda")      # (torch's device start-up before the first context: the hand-made launches are timed with its events)
     metric = pkg.METRIC_SHARED if a.metric == "shared" else pkg.METRIC_PER_CHAIN
     res = dict(device_peak_fp64_mfma_flops=PEAK_FP64_MFMA, transitions_per_launch=a.transitions, results=[])
+    if a.factor_cost:
+        sides = a.factor_sides.split(",")
+        for spec in a.factor_rows.split(","):
+            Dd, N, n = (int(v) for v in spec.split("x"))
+            X, y, idx, kw, q0, cov = factor_problem(Dd, N, n, seed=Dd * 7919 + N * 31 + n)
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="factor_cost", Dd=Dd, levels=N, n=n, Dx=Dd + N, L=padded(Dd + N + 1), chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                seen = {}
+                for side in sides:
+                    mdl = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=[(idx, N)], **kw) if side == "factor" else \
+                        pkg.GLM(pkg.glm.expand_factors(X, [(idx, N)]), y, pkg.glm.POISSON_LOG, **kw)
+                    runs = [run("glm_" + side, X, y, q0, cov, C, a.transitions, metric=metric, mdl=mdl) for _ in range(a.repeats)]
+                    r = max((u[0] for u in runs), key=lambda u: u["leapfrog_steps_per_s"])
+                    r["repeats_leapfrog_steps_per_s"] = [u[0]["leapfrog_steps_per_s"] for u in runs]
+                    row[side] = r
+                    seen[side] = runs[0][1] + (runs[0][2],)
+                    print("# Dd=%d levels=%d n=%d C=%d %s (form %d): %.4e leapfrog steps/s (%s), %.3f ms/transition, create %.2f s" %
+                          (Dd, N, n, C, side, r["glm_form"], r["leapfrog_steps_per_s"],
+                           " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
+                          file=sys.stderr, flush=True)
+                if len(sides) == 2:
+                    fa, fb = sides
+                    row["same_bits"] = bool(all(np.array_equal(u.view(np.uint64), v.view(np.uint64)) for u, v in zip(seen[fa], seen[fb])))
+                    row["same_steps"] = row[fa]["steps"] == row[fb]["steps"]
+                    row["speedup_%s_over_%s" % (fa, fb)] = row[fa]["leapfrog_steps_per_s"] / row[fb]["leapfrog_steps_per_s"]
+                res["results"].append(row)
     for shape in a.shapes.split(","):
         D, n = (int(v) for v in shape.split("x"))
         L, npad = padded(D), (n + 127) // 128 * 128
