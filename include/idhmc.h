@@ -366,6 +366,34 @@ int idhmc_create_glm_factors(idhmc_ctx **out, int device, int64_t nchains, int64
 /* F, the levels (F entries; room for 4) and the indices (F x n, row-major) as the context was given them; F = 0 for every other
  * context.  levels and index may be NULL (F alone is wanted) */
 int idhmc_glm_factors_get(const idhmc_ctx *ctx, int32_t *F, int32_t *levels, int32_t *index);
+/* Random slopes: factor terms that carry a value per observation, (1 + x | subject).  A term f may carry w_f[i], a
+ * finite double per observation, next to its level index.  Its columns are still off_f .. off_f + N_f - 1 of the model and are never
+ * stored; coordinates, F <= 4, D <= 1024 and Dd >= 1 do not change.  Two terms may share one index array: (1 | s) and (x | s) are two
+ * terms of N columns each.  The arithmetic -- the kernels follow this bit for bit --
+ *   z_i = the dfma chain over c < Dd (as above), then for f = 0 .. F-1 ascending:
+ *           term without values:  z_i = z_i + b[off_f + lvl_f[i]]                 (as above)
+ *           term with values:     z_i = dfma(w_f[i], b[off_f + lvl_f[i]], z_i)
+ *   G_{off_f + k}, term with values = the dfma chain from +0 of dfma(w_f[i], r_i, G) over the observations i < n with lvl_f[i] = k,
+ *           i ascending
+ * and everything after G is untouched.  An observation whose value is exactly 0.0 stays in its level's list: dfma(0, r, G) is
+ * performed, as the expanded model performs it.  For finite b, r and w this is bit for bit the same model on the expanded matrix, whose
+ * column off_f + k holds w_f[i] where lvl_f[i] = k and 0.0 elsewhere: fma(0, x, y) = y as long as y is not -0.  The one new edge, next
+ * to the non-finite one above: a chain from +0 now can reach -0 -- fma(w, b, +0) with w b negative and below half the smallest subnormal
+ * rounds to -0 -- and there the two models may differ in the sign of a zero.  Stated and not engineered around.
+ *
+ * idhmc_create_glm_slopes is idhmc_create_glm_factors with these: values is F x n row-major, has holds F flags, 0 or 1.  values == NULL
+ * or every has[f] == 0 gives exactly the context of idhmc_create_glm_factors: the same kernels, the same bits.  Rows of unflagged terms
+ * are not read.  With a flag set the device also holds the values twice, 16 F n_pad bytes, counted in idhmc_device_bytes.  Refused with
+ * IDHMC_ERR_BAD_ARG before the device is touched: values given with factors == NULL or F == 0; has == NULL; a has entry other than 0 or
+ * 1; values->values == NULL with a flag set; a non-finite value in a flagged row; and everything idhmc_create_glm_factors refuses. */
+typedef struct { const double *values; /* F x n, row-major */ const int32_t *has; /* F flags, 0 or 1 */ } idhmc_glm_factor_values;
+int idhmc_create_glm_slopes(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                            const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                            const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values,
+                            int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
+/* has (F entries; room for 4) and the values (F x n, row-major; rows of unflagged terms 0) as the context was given them; every has is 0
+ * for a context without values, and values is then left alone.  values may be NULL (the flags alone are wanted) */
+int idhmc_glm_factor_values_get(const idhmc_ctx *ctx, int32_t *has, double *values);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

@@ -67,6 +67,8 @@ struct GlmParts {
     int32_t F = 0;             // idhmc_create_glm_factors: factors; X holds the Dd = D - A - H - J - fcols dense columns only
     int32_t fcols = 0;         // their level columns, sum N_f
     const int32_t *levels = nullptr, *findex = nullptr;   // [F], [F][n], F > 0 (never null then; every index checked)
+    const double *fvalues = nullptr;   // idhmc_create_glm_slopes with a flag set: [F][n] (rows of unflagged terms are not read) and
+    const int32_t *fhas = nullptr;     // [F] 0 or 1; both null when no term has values
 };
 // the padded width of the stored columns of X: L of the model, and with factors Lx = 128 ceil(Dd / 128)
 static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
@@ -198,6 +200,7 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
     const int64_t nb = npad / 128, cols = g.fcols;
     std::vector<int32_t> hfidx, hfstart, cur;
     std::vector<unsigned char> hfpos;
+    std::vector<double> hfval, hfwl;       // terms with values: w per observation (1.0 for a plain term, 0.0 in the padding), and in list order
     if (g.F > 0) {
         hfidx.assign((size_t)(g.F * npad), -1);
         hfstart.assign((size_t)(nb * (cols + 1)), 0);
@@ -205,6 +208,12 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         cur.assign((size_t)cols, 0);
         for (int64_t f = 0; f < g.F; ++f)
             for (int64_t i = 0; i < n; ++i) hfidx[(size_t)(f * npad + i)] = g.findex[f * n + i];
+        if (g.fhas) {
+            hfval.assign((size_t)(g.F * npad), 0.0);
+            hfwl.assign((size_t)(nb * 128 * g.F), 0.0);
+            for (int64_t f = 0; f < g.F; ++f)
+                for (int64_t i = 0; i < n; ++i) hfval[(size_t)(f * npad + i)] = g.fhas[f] ? g.fvalues[f * n + i] : 1.0;
+        }
         for (int64_t b = 0; b < nb; ++b) {
             int32_t *st = &hfstart[(size_t)(b * (cols + 1))];
             const int64_t m = n - 128 * b < 128 ? n - 128 * b : 128;
@@ -214,8 +223,11 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
             for (int64_t e = 0; e < cols; ++e) { st[e + 1] += st[e]; cur[(size_t)e] = st[e]; }
             e0 = 0;
             for (int64_t f = 0; f < g.F; e0 += g.levels[f], ++f)
-                for (int64_t ii = 0; ii < m; ++ii)
-                    hfpos[(size_t)(b * 128 * g.F + cur[(size_t)(e0 + g.findex[f * n + 128 * b + ii])]++)] = (unsigned char)ii;
+                for (int64_t ii = 0; ii < m; ++ii) {
+                    const int64_t t = b * 128 * g.F + cur[(size_t)(e0 + g.findex[f * n + 128 * b + ii])]++;
+                    hfpos[(size_t)t] = (unsigned char)ii;
+                    if (g.fhas) hfwl[(size_t)t] = hfval[(size_t)(f * npad + 128 * b + ii)];
+                }
         }
     }
     std::vector<double> hx((size_t)(npad * LX), 0.0), hxt((size_t)(npad * LX), 0.0), hy((size_t)(M * K * npad), 0.0);
@@ -306,6 +318,21 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         }
         c->glm_flevels.assign(g.levels, g.levels + g.F);
         c->glm_findex.assign(g.findex, g.findex + (int64_t)g.F * n);
+        if (g.fhas) {
+            double *dv = nullptr, *dw = nullptr;
+            if (int rc = dalloc(c, &dv, (int64_t)hfval.size())) return rc;
+            if (int rc = dalloc(c, &dw, (int64_t)hfwl.size())) return rc;
+            HIPCHK(hipMemcpyAsync(dv, hfval.data(), sizeof(double) * hfval.size(), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dw, hfwl.data(), sizeof(double) * hfwl.size(), hipMemcpyHostToDevice, c->stream));
+            s.lr_fval = dv; s.lr_fwl = dw;
+            c->glm_fhas.assign(g.fhas, g.fhas + g.F);
+            c->glm_fvalues.assign((size_t)((int64_t)g.F * n), 0.0);
+            for (int f = 0; f < g.F; ++f) {
+                if (!g.fhas[f]) continue;
+                s.lr_fhas |= 1u << f;
+                std::copy(g.fvalues + (int64_t)f * n, g.fvalues + (int64_t)(f + 1) * n, c->glm_fvalues.begin() + (int64_t)f * n);
+            }
+        }
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
     s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
@@ -654,16 +681,42 @@ static int validate_factors(const idhmc_glm_desc *glm, const idhmc_glm_factors *
     return IDHMC_OK;
 }
 
-// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local and idhmc_create_glm_factors
+// The values of idhmc_create_glm_slopes, after validate_factors: every check of has and values.  *any: some term has values (false: the
+// context is the one of idhmc_create_glm_factors)
+static int validate_factor_values(const idhmc_glm_desc *glm, const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_factor_values *fv, bool *any)
+{
+    *any = false;
+    if (!fv) return IDHMC_OK;
+    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor values need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (!fv->has) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor values need has, one flag per term (has is NULL)");
+    for (int f = 0; f < fc->F; ++f) {
+        if (fv->has[f] != 0 && fv->has[f] != 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: has[%d] = %d must be 0 or 1", f, fv->has[f]);
+        if (fv->has[f]) *any = true;
+    }
+    if (!*any) return IDHMC_OK;
+    if (!fv->values) return fail(IDHMC_ERR_BAD_ARG, "GLM: a term is flagged in has and values is NULL");
+    for (int f = 0; f < fc->F; ++f) {
+        if (!fv->has[f]) continue;                         // rows of unflagged terms are not read
+        for (int64_t i = 0; i < glm->n; ++i)
+            if (!std::isfinite(fv->values[(int64_t)f * glm->n + i]))
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: values[%d][%lld] is not finite", f, (long long)i);
+    }
+    return IDHMC_OK;
+}
+
+// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors and
+// idhmc_create_glm_slopes
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
                       const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
-                      const idhmc_glm_factors *factors = nullptr)
+                      const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
     int64_t fcols = 0;
     if (int rc = validate_factors(glm, factors, &fcols)) return rc;
+    bool valued = false;
+    if (int rc = validate_factor_values(glm, factors, fcols, values, &valued)) return rc;
     if (glm->A < 0 || glm->A > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: A = %d must be an integer in 0..4", glm->A);
     if (glm->H < 0 || glm->H > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d must be an integer in 0..4", glm->H);
     if (glm->Dx > 1024 - glm->A - glm->H)
@@ -699,6 +752,7 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
     if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
     if (fcols > 0) { parts.F = factors->F; parts.fcols = (int32_t)fcols; parts.levels = factors->levels; parts.findex = factors->index; }
+    if (valued) { parts.fvalues = values->values; parts.fhas = values->has; }
     return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
 }
 
@@ -744,6 +798,24 @@ int idhmc_create_glm_factors(idhmc_ctx **out, int device, int64_t nchains, int64
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_factors: null argument");
     const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
     return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors);
+}
+
+int idhmc_create_glm_slopes(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                            const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                            const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, int64_t M, int64_t chains_per_response,
+                            const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_slopes: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values);
+}
+
+int idhmc_glm_factor_values_get(const idhmc_ctx *c, int32_t *has, double *values)
+{
+    if (!c || !has) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_factor_values_get: null argument");
+    for (int f = 0; f < c->s.lr_f; ++f) has[f] = f < (int)c->glm_fhas.size() ? c->glm_fhas[(size_t)f] : 0;
+    if (values) std::copy(c->glm_fvalues.begin(), c->glm_fvalues.end(), values);
+    return IDHMC_OK;
 }
 
 int idhmc_glm_factors_get(const idhmc_ctx *c, int32_t *F, int32_t *levels, int32_t *index)

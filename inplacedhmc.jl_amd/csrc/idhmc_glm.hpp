@@ -125,6 +125,31 @@
 // starts at or beyond Dd skips the matrix loop, and a tile that holds level columns adds R[b & 1][row][i] over the column's list per
 // lane, after the block's matrix steps where the tile straddles Dd.  No LDS, no tile and no barrier is added; nothing of the factors
 // is alive across multiply() in the requester.
+//
+// Factor terms that carry a value per observation (idhmc_create_glm_slopes): random slopes, (1 + x | subject).
+// Obs::kSlopes, a compile-time flag of the policy next to kFactors (false for every policy above and for every model none of whose
+// terms has values: none of their instructions changes).  A term f may carry w_f[i], a finite double per observation, next to its level
+// index; its columns are still off_f .. off_f + N_f - 1 of the model and are never stored.  Two terms may share one index array:
+// (1 | s) and (x | s) are two terms of N columns each.  The arithmetic:
+//   z_i  = the dfma chain over c < Dd (as above), then for f = 0 .. F-1 ascending:
+//            term without values:  z_i = z_i + b[off_f + lvl_f[i]]                 (as above)
+//            term with values:     z_i = dfma(w_f[i], b[off_f + lvl_f[i]], z_i)
+//   G_{off_f + k}, term with values = the dfma chain from +0 of dfma(w_f[i], r_i, G) over the observations i < n with lvl_f[i] = k,
+//            i ascending.  An observation with w = 0.0 stays in its level's list: dfma(0, r, G) is performed, as the expanded model does.
+// Everything after G is untouched.  For finite b, r and w this is bit for bit the same model on glm.expand_factors(X, factors), whose
+// column off_f + k holds w_f[i] where lvl_f[i] = k and 0.0 elsewhere: fma(0, x, y) = y as long as y is not -0.  The one new edge next
+// to the non-finite one: a chain from +0 now CAN reach -0, which it could not above -- fma(w, b, +0) with w b negative and below half
+// the smallest subnormal rounds to -0, and the expanded model's next fma(0, x, -0) is +0 for x >= 0 where this one keeps -0.  Stated
+// and not engineered around.
+// Under kSlopes every term reads a value: a term without values has a plane of 1.0, and fma(1, b, z) is z + b rounded once, so its
+// bits are the ones above.  Device layout: lr_fval [F][n_pad] holds w (1.0 for a plain term, 0.0 in the padding, where lvl = -1 adds
+// nothing anyway); lr_fwl [n_pad / 128][128 F] holds the same values a second time in the order of lr_fpos, written by the counting
+// sort that builds the lists, so that the value of list entry t has an address known before the entry's byte arrives -- no second
+// dependent global load behind that byte.  t is clamped as glm_list_at clamps it and the 128-trip cap holds: a bad list still cannot read
+// outside the block's entries.  GlmWave: next to the int2 level read, a double2 from the value plane at the same lane offset;
+// zx = dfma(w.x, bx, zx); the gather does G = dfma(wl, r[ii], G) per list entry.  GlmCoop: zphase reads w once per observation i (it
+// is the same for the four rows), acc[reg] = dfma(w, bl, acc[reg]); gphase gacc[reg] = dfma(wl, R[..][ii], gacc[reg]) per entry.  No
+// LDS, tile or barrier is added; nothing of the values is alive across multiply() in the requester.
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -402,6 +427,30 @@ IDHMC_DEV void glm_gather(double &G, const GlmFactors &f, int b, int e, bool has
     glm_list(f, b, e, has, s0, cnt);
     for (int k = 0; k < cnt; ++k) G = G + r[glm_list_at(f, b, s0 + k)];
 }
+// Values on factor terms (Obs::kSlopes): the value planes and the values in list order
+struct GlmSlopes {
+    const double *val, *wl;          // lr_fval [F][n_pad], lr_fwl [n_pad / 128][128 F]
+    template <class State>
+    IDHMC_DEV void init(const State &s)
+    {
+        val = s.lr_fval;
+        wl = s.lr_fwl;
+    }
+};
+// the value of entry t of block b (t clamped as glm_list_at clamps it): its address does not wait for the entry's byte
+IDHMC_DEV double glm_list_value(const GlmSlopes &v, const GlmFactors &f, int b, int t)
+{
+    const int last = 128 * f.F - 1;
+    t = t < 0 ? 0 : t > last ? last : t;
+    return v.wl[(size_t)b * (size_t)(128 * f.F) + t];
+}
+// glm_gather for terms that read a value: the dfma chain of w r over the column's list
+IDHMC_DEV void glm_gather(double &G, const GlmSlopes &v, const GlmFactors &f, int b, int e, bool has, const double *r)
+{
+    int s0, cnt;
+    glm_list(f, b, e, has, s0, cnt);
+    for (int k = 0; k < cnt; ++k) G = dfma(glm_list_value(v, f, b, s0 + k), r[glm_list_at(f, b, s0 + k)], G);
+}
 
 // v_i and r_i of one observation (y is 0 or 1)
 IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
@@ -416,7 +465,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -441,6 +490,7 @@ struct GlmWave {
     const int32_t *part;     // the partner of every coordinate, device (Obs::kLocal)
     double inv2;             // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     GlmFactors fac;          // the factor terms (Obs::kFactors)
+    GlmSlopes slo;           // their values (Obs::kSlopes)
     double *buf;             // this wavefront's LDS vector, L doubles
     int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -465,6 +515,7 @@ struct GlmWave {
             D -= s.lr_j;
         }
         if constexpr (Obs::kFactors) fac.init(s);
+        if constexpr (Obs::kSlopes) slo.init(s);
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -526,8 +577,15 @@ struct GlmWave {
                     if (f < fac.F) {
                         const int2 lv = lv2[(size_t)f * (npad >> 1)];
                         const double bx = buf[fac.off[f] + (lv.x > 0 ? lv.x : 0)], by = buf[fac.off[f] + (lv.y > 0 ? lv.y : 0)];
-                        zx = lv.x >= 0 ? zx + bx : zx;
-                        zy = lv.y >= 0 ? zy + by : zy;
+                        if constexpr (Obs::kSlopes) {
+                            // the term's value plane at the same lane offset (1.0 for a term without values)
+                            const double2 w = (reinterpret_cast<const double2 *>(slo.val) + lane + b * 64)[(size_t)f * (npad >> 1)];
+                            zx = lv.x >= 0 ? dfma(w.x, bx, zx) : zx;
+                            zy = lv.y >= 0 ? dfma(w.y, by, zy) : zy;
+                        } else {
+                            zx = lv.x >= 0 ? zx + bx : zx;
+                            zy = lv.y >= 0 ? zy + by : zy;
+                        }
                     }
                 }
             }
@@ -579,8 +637,13 @@ struct GlmWave {
                 for (int j = 0; j < NCH; ++j) {
                     if (128 * j + 128 > fac.dd && 128 * j < D) {               // the chunk holds a level column
                         const int c0 = 128 * j + 2 * lane, e = c0 - fac.dd;
-                        glm_gather(G.c[j].x, fac, b, e, e >= 0 && c0 < D, buf);
-                        glm_gather(G.c[j].y, fac, b, e + 1, e + 1 >= 0 && c0 + 1 < D, buf);
+                        if constexpr (Obs::kSlopes) {
+                            glm_gather(G.c[j].x, slo, fac, b, e, e >= 0 && c0 < D, buf);
+                            glm_gather(G.c[j].y, slo, fac, b, e + 1, e + 1 >= 0 && c0 + 1 < D, buf);
+                        } else {
+                            glm_gather(G.c[j].x, fac, b, e, e >= 0 && c0 < D, buf);
+                            glm_gather(G.c[j].y, fac, b, e + 1, e + 1 >= 0 && c0 + 1 < D, buf);
+                        }
                     }
                 }
             } else {
@@ -674,6 +737,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     const int32_t *part;         // the partner of every coordinate, device (Obs::kLocal)
     double inv2;                 // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     GlmFactors fac;              // the factor terms (Obs::kFactors)
+    GlmSlopes slo;               // their values (Obs::kSlopes)
     double *tile;
     int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -691,6 +755,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             nu2 = reinterpret_cast<const double2 *>(s.lr_pnu) + lane_;
         }
         if constexpr (Obs::kFactors) fac.init(s);
+        if constexpr (Obs::kSlopes) slo.init(s);
         x = s.lr_x;
         xt = s.lr_xt;
         y = s.lr_y;
@@ -746,10 +811,15 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 if (f < fac.F) {
                     const int lv = fac.idx[(size_t)f * npad + i];
                     const double *qp = tile + kQ + kk * DS + fac.off[f] + (lv > 0 ? lv : 0);
+                    double w = 0.0;                            // the observation's value, the same for the four rows (Obs::kSlopes)
+                    if constexpr (Obs::kSlopes) w = slo.val[(size_t)f * npad + i];
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg) {
                         const double bl = qp[4 * reg * DS];
-                        acc[reg] = lv >= 0 ? acc[reg] + bl : acc[reg];
+                        if constexpr (Obs::kSlopes)
+                            acc[reg] = lv >= 0 ? dfma(w, bl, acc[reg]) : acc[reg];
+                        else
+                            acc[reg] = lv >= 0 ? acc[reg] + bl : acc[reg];
                     }
                 }
             }
@@ -817,8 +887,14 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 const double *rp = rtile(b) + kk * RS;
                 for (int k = 0; k < cnt; ++k) {
                     const int ii = glm_list_at(fac, b, s0 + k);
+                    if constexpr (Obs::kSlopes) {
+                        const double wl = glm_list_value(slo, fac, b, s0 + k);
 #pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) gacc[reg] = gacc[reg] + rp[4 * reg * RS + ii];
+                        for (int reg = 0; reg < 4; ++reg) gacc[reg] = dfma(wl, rp[4 * reg * RS + ii], gacc[reg]);
+                    } else {
+#pragma unroll
+                        for (int reg = 0; reg < 4; ++reg) gacc[reg] = gacc[reg] + rp[4 * reg * RS + ii];
+                    }
                 }
             }
             return;

@@ -71,6 +71,8 @@ struct idhmc_ctx {
     double slab_scale = 0.0;           // and its slab scale (0: none)
     std::vector<int32_t> glm_flevels;  // idhmc_create_glm_factors with F > 0: levels (F entries) and index (F x n) as given (empty otherwise)
     std::vector<int32_t> glm_findex;
+    std::vector<int32_t> glm_fhas;     // idhmc_create_glm_slopes with a flag set: has (F entries) and values (F x n, rows of unflagged terms 0) (empty otherwise)
+    std::vector<double> glm_fvalues;
     // IDHMC_EPS_PER_RESPONSE / IDHMC_METRIC_PER_RESPONSE: the context holds resp_n = C / glm_r whole responses (0 in every other mode)
     int64_t resp_n = 0;
     double *resp_da = nullptr;     // [resp_n][6] dual-averaging states of IDHMC_EPS_PER_RESPONSE: mu, m, Hbar, logeps, logeps_bar, eps

@@ -102,6 +102,11 @@ struct DevState {
     int32_t lr_dd, lr_lx;     // dense (stored) columns; Lx = 128 ceil(lr_dd / 128): lr_x is [lr_npad][lr_lx], lr_xt [lr_lx][lr_npad]
     int32_t lr_fcols;         // level columns, sum N_f
     int32_t lr_foff[4];       // the column of level 0 of factor f
+    // factor terms that carry a value per observation (idhmc_create_glm_slopes; null and 0 unless some term has values).
+    // Appended again: no kernel of a model without values changes (profiles/r18_glm_slopes_kres_*.txt).
+    const double *lr_fval;    // [lr_f][lr_npad] w of every observation: the values of a valued term, 1.0 for a plain term, 0.0 in the padding
+    const double *lr_fwl;     // [lr_npad / 128][128 lr_f] the same values in the order of lr_fpos: entry t is the value of the observation byte t names
+    uint32_t lr_fhas;         // bit f: term f has values
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -151,7 +156,7 @@ struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
 // K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors),
-// s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors)
+// s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors), s.lr_fval one whose terms read a value (kSlopes)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

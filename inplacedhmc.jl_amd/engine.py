@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmDesc, GlmFactors, GlmLocal, GlmPriors, ModelDesc, Options, check
+from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmLocal, GlmPriors, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -220,7 +220,15 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     prior_nu count those Dx columns (glm.factor_columns(model, f) is the slice of factor f; glm.random_intercepts() assembles groups and
     priors).  The model is bit for bit the one with glm.expand_factors(X, factors) as its design matrix, whose indicator columns are
     never built, stored or multiplied.  An empty list is the model without the keyword.  The Model exposes Dd, F, levels (int32 (F,)) and
-    factor_index (int32 (F, n)), None and 0 without factors; Engine.glm_factors() reads them back."""
+    factor_index (int32 (F, n)), None and 0 without factors; Engine.glm_factors() reads them back.
+    An entry may also be glm.term(idx, values=None, levels=None) (idhmc_create_glm_slopes): with values, a finite number per observation,
+    the term is a random slope -- z_i takes values[i] * b[off_f + idx[i]] where a term without values adds b[off_f + idx[i]] -- and its
+    N columns are columns of the model like any other term's, never stored.  Two terms may share one index: a random intercept and slope
+    per subject, (1 + x | subject), is factors=[subject, glm.term(subject, values=x)] with **glm.random_intercepts(Dd, [N, N]), which
+    gives the intercepts and the slopes a sampled scale each, the two independent; a covariance between intercept and slope is out of
+    scope.  glm.expand_factors writes the values into the term's columns, and the bits stay those of the expanded model as long as no
+    product underflows to -0 (include/idhmc.h).  The Model exposes factor_has (int32 (F,)) and factor_values (float64 (F, n), rows of
+    terms without values 0), None when no term has values; Engine.glm_factor_values() reads them back."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -229,6 +237,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
         raise ValueError("X must be a non-empty (n, D) matrix, got shape %s" % (X.shape,))
     n, Dd = X.shape
     flev, fidx = _glm.factor_terms(factors, n)
+    fhas, fval = _glm.factor_values(factors, n)
     F = 0 if flev is None else flev.size
     Dx = Dd + (int(flev.sum()) if F else 0)
     grp, H = None, 0
@@ -300,6 +309,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.prior_kind, m.prior_nu = kind, nu
     m.J, m.local, m.slab_scale = J, loc, S
     m.Dd, m.F, m.levels, m.factor_index = Dd, F, flev, fidx
+    m.factor_has, m.factor_values = fhas, fval
     return m
 
 
@@ -333,8 +343,13 @@ class Engine:
             fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
                             index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
             R = getattr(model, "R", None)
-            check(self.lib.idhmc_create_glm_factors(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc),
-                                                    model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
+            if getattr(model, "factor_has", None) is not None:
+                fv = GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(C.POINTER(C.c_int32)))
+                check(self.lib.idhmc_create_glm_slopes(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), C.byref(fv),
+                                                       model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
+            else:
+                check(self.lib.idhmc_create_glm_factors(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc),
+                                                        model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
         elif getattr(model, "J", 0) > 0:
             desc = model.glm_desc()
             pr = None
@@ -491,6 +506,19 @@ class Engine:
         lev, idx = np.zeros(F.value, np.int32), np.zeros((F.value, self.model.n), np.int32)
         check(self.lib.idhmc_glm_factors_get(self.h, C.byref(F), lev.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(C.POINTER(C.c_int32))))
         return lev, idx
+
+    def glm_factor_values(self):
+        """(has int32 (F,), values float64 (F, n)) as the context holds them (glm.term(..., values=)); (None, None) for every model none
+        of whose factor terms has values"""
+        has = np.zeros(4, np.int32)
+        check(self.lib.idhmc_glm_factor_values_get(self.h, has.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        if not has.any():
+            return None, None
+        F = C.c_int32(0)
+        check(self.lib.idhmc_glm_factors_get(self.h, C.byref(F), None, None))
+        val = np.zeros((F.value, self.model.n))
+        check(self.lib.idhmc_glm_factor_values_get(self.h, has.ctypes.data_as(C.POINTER(C.c_int32)), _dp(val)))
+        return has[:F.value].copy(), val
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -95,6 +95,14 @@ an index idx_f[i] in 0 .. N_f-1 per observation, and its levels are the columns 
 sum N_f columns.  expand_factors(X, factors) is the same model with its indicator columns written out -- the engine computes the same
 bits on both -- factor_columns(model, f) the slice of factor f, and random_intercepts(Dd, levels, ...) the groups and priors that give
 each factor a sampled scale of its own.
+
+Random slopes, factors=[subject, term(subject, values=x)] (idhmc_create_glm_slopes): a term may carry a finite value
+w_f[i] per observation next to its level index, and then z_i takes w_f[i] b[off_f + idx_f[i]] (one fma) where a plain term adds
+b[off_f + idx_f[i]].  Its N_f columns are columns of the model like any other term's and are never stored; two terms may share one index
+array.  (1 + x | subject) is factors=[subject, term(subject, values=x)] with **random_intercepts(Dd, [N, N]) (random_effects is the same
+function under the name that fits): the intercepts and the slopes each get a sampled scale of their own, and the two are independent --
+a covariance between intercept and slope is out of scope.  expand_factors writes w_f[i] where it writes 1.0 for a plain term, and the
+engine computes the same bits on both; factor_values(factors, n) is GLM()'s validation of the values.
 """
 import collections
 
@@ -432,9 +440,21 @@ def local_flags(local, slab_scale, Dx):
 
 
 # ---- factor terms ---------------------------------------------------------------------------------------------------------------------
+Term = collections.namedtuple("Term", "index values levels")
+
+
+def term(index, values=None, levels=None):
+    """a factor term for GLM(..., factors=[...]): the level index of every observation, optionally a value per observation (a random
+    slope: the term adds values[i] * b[level of i] to z_i where a term without values adds b[level of i]), optionally the number of
+    levels (default: max(index) + 1).  term(idx) is the bare array idx and term(idx, levels=N) the pair (idx, N).  Validated by GLM()
+    (factor_terms, factor_values)."""
+    return Term(index, values, levels)
+
+
 def factor_terms(factors, n):
     """GLM()'s validation of factors: (levels int32 (F,), index int32 (F, n)), or (None, None) for None and for an empty list.  Each
-    entry is an integer array of shape (n,) or a pair (array, N); N defaults to max + 1.  The checks are idhmc_create_glm_factors'."""
+    entry is an integer array of shape (n,), a pair (array, N) or a term(); N defaults to max + 1.  The checks are
+    idhmc_create_glm_factors'.  The values of a term() are factor_values' business."""
     if factors is None:
         return None, None
     if isinstance(factors, np.ndarray) or not isinstance(factors, (list, tuple)):
@@ -445,11 +465,16 @@ def factor_terms(factors, n):
         raise ValueError("at most 4 factors (got %d)" % len(factors))
     lev, idx = np.empty(len(factors), np.int32), np.empty((len(factors), n), np.int32)
     for f, entry in enumerate(factors):
-        N = None
-        if isinstance(entry, tuple):
+        N, given = None, False
+        if isinstance(entry, Term):
+            entry, N = entry.index, entry.levels
+            given = N is not None
+        elif isinstance(entry, tuple):
             if len(entry) != 2:
-                raise ValueError("factors[%d] must be an index array or a pair (index, levels)" % f)
+                raise ValueError("factors[%d] must be an index array, a pair (index, levels) or a glm.term(index, values, levels)" % f)
             entry, N = entry
+            given = True
+        if given:
             if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or N < 1:
                 raise ValueError("factors[%d]: the number of levels must be a positive integer (got %r)" % (f, N))
         raw = np.asarray(entry)
@@ -468,8 +493,32 @@ def factor_terms(factors, n):
     return lev, idx
 
 
+def factor_values(factors, n):
+    """GLM()'s validation of the values of factor terms: (has int32 (F,), values float64 (F, n)), or (None, None) when no entry has
+    values.  has[f] is 1 for a term() with values and its row holds them; the row of every other entry is 0.0 and is not read.  The
+    checks are idhmc_create_glm_slopes', naming the entry: shape (n,), a real numeric dtype (no bool), all finite."""
+    lev, idx = factor_terms(factors, n)
+    if lev is None or not any(isinstance(e, Term) and e.values is not None for e in factors):
+        return None, None
+    has, val = np.zeros(lev.size, np.int32), np.zeros((lev.size, n), np.float64)
+    for f, entry in enumerate(factors):
+        if not isinstance(entry, Term) or entry.values is None:
+            continue
+        raw = np.asarray(entry.values)
+        if raw.ndim != 1 or raw.shape[0] != n:
+            raise ValueError("factors[%d]: values must have one value per observation, shape (%d,), got %s" % (f, n, raw.shape))
+        if raw.dtype == np.bool_ or not (np.issubdtype(raw.dtype, np.integer) or np.issubdtype(raw.dtype, np.floating)):
+            raise ValueError("factors[%d]: values must be real numbers, got dtype %s" % (f, raw.dtype))
+        raw = raw.astype(np.float64)
+        bad = np.flatnonzero(~np.isfinite(raw))
+        if bad.size:
+            raise ValueError("factors[%d]: values[%d] = %r is not finite" % (f, bad[0], float(raw[bad[0]])))
+        has[f], val[f] = 1, raw
+    return has, val
+
+
 def factor_columns(model, f):
-    """the columns of factor f among the Dx columns of a GLM with factor terms: slice(off_f, off_f + N_f), off_f = Dd + N_0 + .. + N_{f-1}"""
+    """the columns of factor f (any term, with values or without) among the Dx columns of a GLM with factor terms: slice(off_f, off_f + N_f), off_f = Dd + N_0 + .. + N_{f-1}"""
     F = getattr(model, "F", 0)
     if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not 0 <= f < F:
         raise ValueError("factor %r: the model has factors 0..%d" % (f, F - 1) if F else "the model has no factor terms (GLM(..., factors=))")
@@ -478,21 +527,22 @@ def factor_columns(model, f):
 
 
 def expand_factors(X, factors):
-    """the n x Dx design matrix with one indicator column per level -- the documented equivalent of GLM(X, ..., factors=factors): the
-    dense columns of X, then for factor 0, 1, .. one column per level holding 1.0 where the observation has that level and 0.0 elsewhere.
-    The engine computes the same bits on both."""
+    """the n x Dx design matrix with one column per level -- the documented equivalent of GLM(X, ..., factors=factors): the dense
+    columns of X, then for factor 0, 1, .. one column per level holding 1.0 (for a term() with values: values[i]) where the observation
+    has that level and 0.0 elsewhere.  The engine computes the same bits on both."""
     X = np.asarray(X, dtype=np.float64)
     if X.ndim != 2:
         raise ValueError("X must be an (n, Dd) matrix, got shape %s" % (X.shape,))
     lev, idx = factor_terms(factors, X.shape[0])
     if lev is None:
         return X.copy()
+    has, val = factor_values(factors, X.shape[0])
     out = np.zeros((X.shape[0], X.shape[1] + int(lev.sum())))
     out[:, :X.shape[1]] = X
     off = X.shape[1]
     rows = np.arange(X.shape[0])
     for f in range(lev.size):
-        out[rows, off + idx[f]] = 1.0
+        out[rows, off + idx[f]] = 1.0 if has is None or not has[f] else val[f]
         off += int(lev[f])
     return out
 
@@ -502,7 +552,10 @@ def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):
     group, then factor f's levels[f] columns forming group f, whose sigma_f = exp(omega_f) is sampled --
     GLM(X, Y, source, factors=[subject, item], **glm.random_intercepts(X.shape[1], [n_subjects, n_items], scale=glm.half_student_t(3))).
     u ~ N(0, 1) on every level (so an intercept is N(0, sigma_f^2)), `scale` the spec(s) of the H = len(levels) group scales,
-    `coefficients` those of the Dd dense columns and `aux` those of the auxiliary coordinates, as priors() takes them."""
+    `coefficients` those of the Dd dense columns and `aux` those of the auxiliary coordinates, as priors() takes them.
+    Every term gets a group of its own, whether it has values or not: a random intercept and slope per subject, (1 + x | subject), is
+    GLM(X, Y, source, factors=[subject, glm.term(subject, values=x)], **glm.random_intercepts(X.shape[1], [N, N])), the scale of the
+    intercepts and the scale of the slopes sampled independently.  A covariance between intercept and slope is out of scope."""
     Dd = int(Dd)
     lev = [int(N) for N in levels]
     if Dd < 1:
@@ -519,6 +572,9 @@ def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):
     kw = priors(Dd + sum(lev), A, len(lev), coefficients=coefficients + [normal()] * sum(lev), aux=aux, scales=scale)
     kw["groups"] = np.concatenate([np.full(Dd, -1)] + [np.full(N, g) for g, N in enumerate(lev)]).astype(np.int32)
     return kw
+
+
+random_effects = random_intercepts      # the name that fits terms with values: glm.random_effects(Dd, [N, N]) for (1 + x | subject)
 
 
 # ---- priors ---------------------------------------------------------------------------------------------------------------------------

@@ -51,6 +51,13 @@ the expanded matrix with one indicator column per level.  Both sides run the sam
 steps/s is a time ratio.  --repeats K makes K engines per side (the best is reported, all are listed).  Meant to run under --lockstep
 with --pairs ''.
 
+--slope-cost (glm.term(index, values=)) runs, per row DdxLEVELSxN of --slope-rows and chain count, three models on the
+same data: "slopes", the Poisson GLM with Dd dense columns, a plain term and a valued term of LEVELS levels each on one index,
+(1 + x | s), each term a group with a sampled scale (H = 2); "expanded", the same model on glm.expand_factors' matrix; and "plain", the
+factor model with the valued term replaced by a plain one (section 20's kernels on the same shape: what the value costs).  slopes and
+expanded run the same trajectories (same_bits), so the ratio of their steps/s is a time ratio; plain is another model with trees of the
+same length under --lockstep.  Meant to run under --lockstep with --pairs ''.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
@@ -450,6 +457,24 @@ def factor_problem(Dd, N, n, seed):
     return X, y, idx, kw, q0, np.eye(q0.size) * 1e-4
 
 
+def slope_problem(Dd, N, n, seed):
+    """a Poisson regression with Dd dense columns and a random intercept and slope per level of one index, (1 + x | s), each of the two
+    terms in a group of its own (H = 2): (X (n, Dd), y, index, x, the keywords of the models, a start q and a narrow covariance around it
+    for `run`)"""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, Dd)) / np.sqrt(Dd)
+    X[:, 0] = 1.0
+    idx = rng.integers(0, N, n)
+    x = 0.5 * rng.standard_normal(n)
+    s0, s1 = 0.5, 0.3
+    u0, u1 = rng.standard_normal(N), rng.standard_normal(N)
+    beta = np.r_[0.5, 0.3 * rng.standard_normal(Dd - 1)]
+    y = rng.poisson(np.exp(X @ beta + s0 * u0[idx] + s1 * x * u1[idx])).astype(float)
+    kw = pkg.glm.random_effects(Dd, [N, N])
+    q0 = np.r_[beta, u0, u1, np.log(s0), np.log(s1)]
+    return X, y, idx, x, kw, q0, np.eye(q0.size) * 1e-4
+
+
 def run(form, X, y, q_map, cov, C, T, seed=1, metric=None, mdl=None):
     t0 = time.perf_counter()
     eng = pkg.Engine(model(form, X, y, q_map) if mdl is None else mdl, C, pkg.default_options(metric_mode=pkg.METRIC_SHARED if metric is None else metric,
@@ -584,6 +609,12 @@ def main():
                     "and --pairs '' to run nothing else")
     ap.add_argument("--factor-rows", default="20x200x1000,20x200x10000,20x900x10000,100x20x1000", help="DdxLEVELSxN,...")
     ap.add_argument("--factor-sides", default="factor,expanded", help="the sides of each pair to run")
+    ap.add_argument("--slope-cost", action="store_true", help="per row of --slope-rows three models on the same data: a plain and a valued "
+                    "term on one index (H = 2), the same model on the expanded matrix, and both terms plain (DESIGN section 21); use "
+                    "--lockstep, and --pairs '' to run nothing else")
+    ap.add_argument("--slope-rows", default="20x100x1000,20x100x10000,20x450x10000,100x10x1000,20x200x1000", help="DdxLEVELSxN,... "
+                    "(LEVELS per term: the model has 2 LEVELS level columns)")
+    ap.add_argument("--slope-sides", default="slopes,expanded,plain", help="the sides of each row to run")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -627,6 +658,36 @@ def main():
                     row["same_bits"] = bool(all(np.array_equal(u.view(np.uint64), v.view(np.uint64)) for u, v in zip(seen[fa], seen[fb])))
                     row["same_steps"] = row[fa]["steps"] == row[fb]["steps"]
                     row["speedup_%s_over_%s" % (fa, fb)] = row[fa]["leapfrog_steps_per_s"] / row[fb]["leapfrog_steps_per_s"]
+                res["results"].append(row)
+    if a.slope_cost:
+        sides = a.slope_sides.split(",")
+        for spec in a.slope_rows.split(","):
+            Dd, N, n = (int(v) for v in spec.split("x"))
+            X, y, idx, x, kw, q0, cov = slope_problem(Dd, N, n, seed=Dd * 7919 + N * 31 + n)
+            valued = [(idx, N), pkg.glm.term(idx, values=x, levels=N)]
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="slope_cost", Dd=Dd, levels=N, n=n, Dx=Dd + 2 * N, L=padded(Dd + 2 * N + 2), chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                seen = {}
+                for side in sides:
+                    mdl = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **kw) if side == "slopes" else \
+                        pkg.GLM(pkg.glm.expand_factors(X, valued), y, pkg.glm.POISSON_LOG, **kw) if side == "expanded" else \
+                        pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=[(idx, N), (idx, N)], **kw)
+                    runs = [run("glm_" + side, X, y, q0, cov, C, a.transitions, metric=metric, mdl=mdl) for _ in range(a.repeats)]
+                    r = max((u[0] for u in runs), key=lambda u: u["leapfrog_steps_per_s"])
+                    r["repeats_leapfrog_steps_per_s"] = [u[0]["leapfrog_steps_per_s"] for u in runs]
+                    row[side] = r
+                    seen[side] = runs[0][1] + (runs[0][2],)
+                    print("# Dd=%d levels=2x%d n=%d C=%d %s (form %d): %.4e leapfrog steps/s (%s), %.3f ms/transition, create %.2f s" %
+                          (Dd, N, n, C, side, r["glm_form"], r["leapfrog_steps_per_s"],
+                           " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
+                          file=sys.stderr, flush=True)
+                if "slopes" in seen and "expanded" in seen:
+                    row["same_bits"] = bool(all(np.array_equal(u.view(np.uint64), v.view(np.uint64)) for u, v in zip(seen["slopes"], seen["expanded"])))
+                    row["same_steps"] = row["slopes"]["steps"] == row["expanded"]["steps"]
+                    row["speedup_slopes_over_expanded"] = row["slopes"]["leapfrog_steps_per_s"] / row["expanded"]["leapfrog_steps_per_s"]
+                if "slopes" in seen and "plain" in seen:
+                    row["plain_same_steps"] = row["slopes"]["steps"] == row["plain"]["steps"]
+                    row["slopes_over_plain"] = row["slopes"]["leapfrog_steps_per_s"] / row["plain"]["leapfrog_steps_per_s"]
                 res["results"].append(row)
     for shape in a.shapes.split(","):
         D, n = (int(v) for v in shape.split("x"))
