@@ -394,6 +394,43 @@ int idhmc_create_glm_slopes(idhmc_ctx **out, int device, int64_t nchains, int64_
 /* has (F entries; room for 4) and the values (F x n, row-major; rows of unflagged terms 0) as the context was given them; every has is 0
  * for a context without values, and values is then left alone.  values may be NULL (the flags alone are wanted) */
 int idhmc_glm_factor_values_get(const idhmc_ctx *ctx, int32_t *has, double *values);
+/* Correlated random effects: a sampled correlation per pair of factor terms -- the covariance of (1 + x | subject).
+ * A model with factor terms may name P pairs of terms, 0 <= P <= 2.  Pair p is (first[p], second[p]), two distinct terms with equal
+ * level counts N_p; a term belongs to at most one pair; either term may have values or not, and the two need not share an index array.
+ * Level k of the first term is paired with level k of the second.  Each pair adds one sampled coordinate zeta_p = atanh rho_p at the end:
+ *   q = [u (Dx) | a (A) | omega (H) | lambda (J) | zeta (P)],   D = Dx + A + H + J + P <= 1024.
+ * Per gradient and pair -- the kernels and the tests' C restatement follow this bit for bit: plain IEEE operations in the association
+ * written, dfma, dexp and dlog1p those of idhmc_math.hpp --
+ *   s = dexp(-|zeta|);  t = s * s;  d = 1 + t;  rho = copysign((1 - t) / d, zeta);  c = (2 * s) / d
+ * (c = sqrt(1 - rho^2) in exact arithmetic; zeta = +0 gives rho = +0, c = 1; past |zeta| of about 745 rho = +-1, c = 0, all finite).
+ * Forward, for k < N_p with c1 = off_first + k and c2 = off_second + k:
+ *   ut_c1 = u_c1;   ut_c2 = dfma(rho, u_c1, c * u_c2);   ut_c = u_c for every other coordinate,
+ * and everything the sections above define runs on ut where it ran on u: b_c from group and local scales, z, (r, v, s), G_c, W_g, the
+ * lambdas and the auxiliary scores.  With the two terms in groups g1 and g2 the effects of level k are
+ *   (b_c1, b_c2) = (sigma_g1 u_c1, sigma_g2 (rho u_c1 + sqrt(1 - rho^2) u_c2)):  b = sigma .* (L u),  L = [[1, 0], [rho, sqrt(1 - rho^2)]].
+ * No combination is refused: groups, local scales (also on paired columns), priors, several responses and values compose.
+ * Backward, after the chain rules above have produced Gh_c = dl / dut_c for the columns and filled omega, lambda and a:
+ *   m_k = Gh_c2 * (c * dfma(c, u_c1, -(rho * u_c2)));   G_c1 = dfma(rho, Gh_c2, Gh_c1);   G_c2 = c * Gh_c2
+ *   M_p[c2 mod 128]: plain additions over chunks ascending, from +0, of the pair's m_k;   G_zeta_p = the canonical 128-residue tree over M_p.
+ * The prior runs on the raw q (the prior of u is on u, not ut).  eta[p] > 0 puts LKJ(eta) on the 2 x 2 correlation, with the Jacobian
+ * of tanh: log p(zeta) = eta log(1 - rho^2), so that (rho + 1) / 2 is Beta(eta, eta); in the prior loop's terms
+ *   T = T + (4 eta) * ((|zeta| + dlog1p(t)) - ln 2);   g = dfma(-2 eta, rho, G)
+ * and the entries of zeta_p in mu, tau, kind and nu must be the defaults (0, 1, 0, 0) and are not applied.  eta[p] == 0: those entries
+ * apply as to any coordinate, kinds 0 and 1 (normal or Student-t on Fisher's z); the log kinds are refused, as on a coefficient.
+ * Covariance among three or more terms is out of scope.
+ *
+ * idhmc_create_glm_corr is idhmc_create_glm_slopes with these; mu, tau, kind and nu have D entries, the zetas last.  pairs == NULL or
+ * P == 0 gives exactly the context of idhmc_create_glm_slopes: the same kernels, bits and footprint.  No LDS is added.  Refused with
+ * IDHMC_ERR_BAD_ARG before the device is touched: P outside 0..2; first, second or eta NULL with P > 0; a term index outside 0..F-1;
+ * first == second; a term in two pairs; unequal level counts; eta negative or not finite; eta > 0 with a non-default prior entry on
+ * that zeta; a log kind on a zeta; pairs without factors; D > 1024 counting P; and everything idhmc_create_glm_slopes refuses. */
+typedef struct { int32_t P; const int32_t *first, *second; const double *eta; } idhmc_glm_pairs;
+int idhmc_create_glm_corr(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                          const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                          const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                          int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
+/* *P, and with non-NULL arrays first, second and eta (P entries each) as the context was given them; 0 for every other context */
+int idhmc_glm_pairs_get(const idhmc_ctx *ctx, int32_t *P, int32_t *first, int32_t *second, double *eta);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

@@ -69,6 +69,11 @@ struct GlmParts {
     const int32_t *levels = nullptr, *findex = nullptr;   // [F], [F][n], F > 0 (never null then; every index checked)
     const double *fvalues = nullptr;   // idhmc_create_glm_slopes with a flag set: [F][n] (rows of unflagged terms are not read) and
     const int32_t *fhas = nullptr;     // [F] 0 or 1; both null when no term has values
+    int32_t P = 0;             // idhmc_create_glm_corr: pairs of terms; the last P coordinates are their zetas
+    const int32_t *pfirst = nullptr, *psecond = nullptr;   // [P] the terms of each pair, P > 0 (never null then; every entry checked)
+    const double *peta = nullptr;      // [P]
+    const int32_t *pkind_pub = nullptr;    // P > 0 with some eta > 0: kind and nu as the caller gave them (pkind / pnu then hold the
+    const double *pnu_pub = nullptr;       // device table, which marks those zetas); null: pkind / pnu are the caller's
 };
 // the padded width of the stored columns of X: L of the model, and with factors Lx = 128 ceil(Dd / 128)
 static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
@@ -76,7 +81,7 @@ static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
     int64_t L = 128;
     while (L < D) L *= 2;
     if (L_out) *L_out = L;
-    return g.F > 0 ? ((int64_t)D - g.A - g.H - g.J - g.fcols + 127) / 128 * 128 : L;
+    return g.F > 0 ? ((int64_t)D - g.A - g.H - g.J - g.P - g.fcols + 127) / 128 * 128 : L;
 }
 // The head of a packed params array into *g: `head` = 0 (a logistic regression's [X | y]), 2 ([K, nc, c | X | Y]) or 3
 // ([K, nc, A, c | X | Y]) doubles in front of the constants.  The entries are checked as doubles (integral, hence finite, and in
@@ -152,7 +157,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
         }
     }
     const int64_t n = g.n, K = g.K, M = g.M;
-    const int64_t Dx = D - g.A - g.H - g.J - g.fcols;      // the columns of X (with factors: the dense ones)
+    const int64_t Dx = D - g.A - g.H - g.J - g.P - g.fcols;      // the columns of X (with factors: the dense ones)
     const int64_t L = stored_width(g, D);
     const int64_t npad = (n + 127) / 128 * 128;
     if (npad * L > ((int64_t)1 << 27))
@@ -193,7 +198,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
 static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
 {
     DevState &s = c->s;
-    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, Dm = s.D - g.A - g.H - g.J, K = g.K, M = g.M;    // Dm: the columns of the model
+    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, Dm = s.D - g.A - g.H - g.J - g.P, K = g.K, M = g.M;    // Dm: the columns of the model
     const int64_t D = Dm - g.fcols, LX = stored_width(g, s.D);      // the columns X stores (with factors: the dense ones) and their padded width
     // The level lists of a model with factors, before anything is uploaded: per block of 128 observations its places sorted by factor,
     // level, place (a counting sort), and where each level's list starts
@@ -280,14 +285,16 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         HIPCHK(hipMemcpyAsync(dnu, hnu.data(), sizeof(double) * hnu.size(), hipMemcpyHostToDevice, c->stream));
         s.lr_pkind = dk;
         s.lr_pnu = dnu;
-        c->prior_kind.assign(g.pkind, g.pkind + Dall);
-        c->prior_nu.assign(g.pnu, g.pnu + Dall);
+        const int32_t *pk = g.pkind_pub ? g.pkind_pub : g.pkind;
+        const double *pn = g.pkind_pub ? g.pnu_pub : g.pnu;
+        c->prior_kind.assign(pk, pk + Dall);
+        c->prior_nu.assign(pn, pn + Dall);
     }
     std::vector<int32_t> hp;
     if (g.J > 0) {
         // the partner of every coordinate: the k-th flagged column (ascending) and coordinate Dx + A + H + k name each other
         hp.assign((size_t)L, -1);
-        int64_t k = s.D - g.J;
+        int64_t k = s.D - g.P - g.J;
         for (int64_t col = 0; col < Dm; ++col)
             if (g.local[col]) { hp[(size_t)col] = (int32_t)k; hp[(size_t)k] = (int32_t)col; ++k; }
         int32_t *dp = nullptr;
@@ -333,6 +340,26 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
                 std::copy(g.fvalues + (int64_t)f * n, g.fvalues + (int64_t)(f + 1) * n, c->glm_fvalues.begin() + (int64_t)f * n);
             }
         }
+    }
+    std::vector<int32_t> hcp;
+    if (g.P > 0) {
+        // the partner of every paired column: level k of the first term and level k of the second name each other
+        hcp.assign((size_t)L, -1);
+        for (int p = 0; p < g.P; ++p) {
+            const int32_t o1 = s.lr_foff[g.pfirst[p]], o2 = s.lr_foff[g.psecond[p]];
+            for (int32_t k = 0; k < g.levels[g.pfirst[p]]; ++k) {
+                hcp[(size_t)(o1 + k)] = (o2 + k) | (p << 10);
+                hcp[(size_t)(o2 + k)] = (o1 + k) | (p << 10) | 2048;
+            }
+        }
+        int32_t *dcp = nullptr;
+        if (int rc = dalloc(c, &dcp, L)) return rc;
+        HIPCHK(hipMemcpyAsync(dcp, hcp.data(), sizeof(int32_t) * hcp.size(), hipMemcpyHostToDevice, c->stream));
+        s.lr_cpart = dcp;
+        s.lr_cp = g.P;
+        c->glm_pfirst.assign(g.pfirst, g.pfirst + g.P);
+        c->glm_psecond.assign(g.psecond, g.psecond + g.P);
+        c->glm_peta.assign(g.peta, g.peta + g.P);
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
     s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
@@ -704,12 +731,55 @@ static int validate_factor_values(const idhmc_glm_desc *glm, const idhmc_glm_fac
     return IDHMC_OK;
 }
 
-// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors and
-// idhmc_create_glm_slopes
+// The pairs of idhmc_create_glm_corr, after validate_factors and validate_local: every check of P, first, second and eta, and of the
+// zetas' entries in the prior arrays.  *P: the pairs (0: the context is the one of idhmc_create_glm_slopes)
+static int validate_pairs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, int J, const idhmc_glm_factors *fc, int64_t fcols,
+                          const idhmc_glm_pairs *pp, int *P)
+{
+    *P = 0;
+    if (!pp) return IDHMC_OK;
+    if (pp->P < 0 || pp->P > 2) return fail(IDHMC_ERR_BAD_ARG, "GLM: P = %d pairs must be an integer in 0..2", pp->P);
+    if (pp->P == 0) return IDHMC_OK;
+    if (!pp->first || !pp->second || !pp->eta)
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: P = %d pairs need first, second and eta (%s is NULL)", pp->P, !pp->first ? "first" : !pp->second ? "second" : "eta");
+    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: pairs need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    bool used[4] = {false, false, false, false};
+    const int cz0 = glm->Dx + glm->A + glm->H + J;
+    for (int p = 0; p < pp->P; ++p) {
+        const int32_t a = pp->first[p], b = pp->second[p];
+        if (a < 0 || a >= fc->F) return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: first = %d is outside 0..%d (the model's terms)", p, a, fc->F - 1);
+        if (b < 0 || b >= fc->F) return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: second = %d is outside 0..%d (the model's terms)", p, b, fc->F - 1);
+        if (a == b) return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: first = second = %d (a pair is two distinct terms)", p, a);
+        if (used[a] || used[b]) return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: term %d is in two pairs", p, used[a] ? a : b);
+        used[a] = used[b] = true;
+        if (fc->levels[a] != fc->levels[b])
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: terms %d and %d have %d and %d levels (a pair needs equal level counts)", p, a, b,
+                        fc->levels[a], fc->levels[b]);
+        const double eta = pp->eta[p];
+        if (!(std::isfinite(eta) && eta >= 0.0)) return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: eta = %g must be finite and >= 0 (0: the prior arrays' entry applies)", p, eta);
+        const int cz = cz0 + p;
+        const int32_t k = pr && pr->kind ? pr->kind[cz] : 0;
+        if (k >= IDHMC_PRIOR_LOG_HALF_NORMAL && k <= IDHMC_PRIOR_LOG_EXPONENTIAL)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: prior kind[%d] = %d is a prior on exp(q): coordinate %d is zeta = atanh rho, not a logarithm "
+                        "(kinds 0 and 1 are for a zeta)", p, cz, k, cz);
+        if (eta > 0.0) {
+            const double nu = pr && pr->kind && pr->nu ? pr->nu[cz] : 0.0;
+            if (k != 0 || nu != 0.0 || (glm->mu && glm->mu[cz] != 0.0) || (glm->tau && glm->tau[cz] != 1.0))
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: eta = %g is the LKJ prior of zeta: the entry of coordinate %d in the prior arrays must "
+                            "be the default (kind 0, mu 0, tau 1, nu 0) and is not applied", p, eta, cz);
+        }
+    }
+    *P = pp->P;
+    return IDHMC_OK;
+}
+
+// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors,
+// idhmc_create_glm_slopes and idhmc_create_glm_corr
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
                       const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
-                      const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr)
+                      const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr,
+                      const idhmc_glm_pairs *pairs = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
@@ -726,6 +796,11 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (glm->Dx + J > 1024 - glm->A - glm->H)
         return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J = %lld: a GLM is limited to D <= 1024 (J = %d local scales)",
                     (long long)glm->Dx + glm->A + glm->H + J, J);
+    if (pairs && pairs->P >= 0 && pairs->P <= 2 && glm->Dx + J + pairs->P > 1024 - glm->A - glm->H)
+        return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + P = %lld: a GLM is limited to D <= 1024 (P = %d pairs)",
+                    (long long)glm->Dx + glm->A + glm->H + J + pairs->P, pairs->P);
+    int P = 0;
+    if (int rc = validate_pairs(glm, priors, J, factors, fcols, pairs, &P)) return rc;
     if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
     if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
     if (glm->H > 0) {
@@ -741,18 +816,36 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     idhmc_model_desc m;
     memset(&m, 0, sizeof m);
     m.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM;
-    m.D = glm->Dx + glm->A + glm->H + J;
+    m.D = glm->Dx + glm->A + glm->H + J + P;
     m.mu = glm->mu;
     m.tau = glm->tau;
     m.source = glm->source;
     std::vector<double> nu;
     bool any = false;
-    if (int rc = validate_priors(glm, priors, J, &nu, &any)) return rc;
+    if (int rc = validate_priors(glm, priors, J + P, &nu, &any)) return rc;
     GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
     if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
     if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
     if (fcols > 0) { parts.F = factors->F; parts.fcols = (int32_t)fcols; parts.levels = factors->levels; parts.findex = factors->index; }
     if (valued) { parts.fvalues = values->values; parts.fhas = values->has; }
+    std::vector<int32_t> kdev, kpub;     // a zeta with eta > 0: the device table marks it (kPriorLkj of idhmc_glm.hpp, eta in nu's place)
+    std::vector<double> nudev, nupub;
+    if (P > 0) {
+        parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta;
+        bool lkj = false;
+        for (int p = 0; p < P; ++p) lkj = lkj || pairs->eta[p] > 0.0;
+        if (lkj) {
+            kpub.assign((size_t)m.D, 0);
+            nupub.assign((size_t)m.D, 0.0);
+            if (any) { kpub.assign(priors->kind, priors->kind + m.D); nupub = nu; }
+            kdev = kpub;
+            nudev = nupub;
+            for (int p = 0; p < P; ++p)
+                if (pairs->eta[p] > 0.0) { kdev[(size_t)(m.D - P + p)] = 5; nudev[(size_t)(m.D - P + p)] = pairs->eta[p]; }
+            parts.pkind = kdev.data(); parts.pnu = nudev.data();
+            parts.pkind_pub = kpub.data(); parts.pnu_pub = nupub.data();
+        }
+    }
     return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
 }
 
@@ -810,6 +903,26 @@ int idhmc_create_glm_slopes(idhmc_ctx **out, int device, int64_t nchains, int64_
     return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values);
 }
 
+int idhmc_create_glm_corr(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                          const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                          const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                          int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_corr: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values, pairs);
+}
+
+int idhmc_glm_pairs_get(const idhmc_ctx *c, int32_t *P, int32_t *first, int32_t *second, double *eta)
+{
+    if (!c || !P) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_pairs_get: null argument");
+    *P = c->s.lr_cp;
+    if (first) std::copy(c->glm_pfirst.begin(), c->glm_pfirst.end(), first);
+    if (second) std::copy(c->glm_psecond.begin(), c->glm_psecond.end(), second);
+    if (eta) std::copy(c->glm_peta.begin(), c->glm_peta.end(), eta);
+    return IDHMC_OK;
+}
+
 int idhmc_glm_factor_values_get(const idhmc_ctx *c, int32_t *has, double *values)
 {
     if (!c || !has) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_factor_values_get: null argument");
@@ -830,7 +943,7 @@ int idhmc_glm_factors_get(const idhmc_ctx *c, int32_t *F, int32_t *levels, int32
 int idhmc_glm_local_get(const idhmc_ctx *c, int32_t *local, double *slab_scale)
 {
     if (!c || !local || !slab_scale) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_local_get: null argument");
-    const int Dx = c->s.D - c->s.lr_a - c->s.lr_h - c->s.lr_j;
+    const int Dx = c->s.D - c->s.lr_a - c->s.lr_h - c->s.lr_j - c->s.lr_cp;
     for (int k = 0; k < Dx; ++k) local[k] = c->glm_local.empty() ? 0 : c->glm_local[(size_t)k];
     *slab_scale = c->slab_scale;
     return IDHMC_OK;

@@ -150,6 +150,31 @@
 // zx = dfma(w.x, bx, zx); the gather does G = dfma(wl, r[ii], G) per list entry.  GlmCoop: zphase reads w once per observation i (it
 // is the same for the four rows), acc[reg] = dfma(w, bl, acc[reg]); gphase gacc[reg] = dfma(wl, R[..][ii], gacc[reg]) per entry.  No
 // LDS, tile or barrier is added; nothing of the values is alive across multiply() in the requester.
+//
+// Correlated random effects (idhmc_create_glm_corr): Obs::kCorr, a compile-time flag of the policy next to kSlopes
+// (false for every policy above and for every model without a pair: none of their instructions changes).  P pairs of factor terms,
+// 0 <= P <= 2; pair p is (first_p, second_p), two distinct terms of N_p levels each, a term in at most one pair, with values or
+// without, on one index array or two; level k of the first is paired with level k of the second.  Each pair adds one sampled
+// coordinate zeta_p = atanh rho_p at the end:  q = [u (Dx) | a (A) | omega (H) | lambda (J) | zeta (P)],  D = Dx + A + H + J + P <= 1024.
+//   per gradient and pair, the same bits in every lane (zeta_p read from its owner lane, as glm_group_scale reads omega_g):
+//     s = dexp(-|zeta|);  t = s s;  d = 1 + t;  rho = copysign((1 - t) / d, zeta);  c = (2 s) / d
+//     (c = sqrt(1 - rho^2) in exact arithmetic; zeta = +0: rho = +0, c = 1; past |zeta| of about 745: rho = +-1, c = 0, finite)
+//   forward, k < N_p, c1 = off_first + k, c2 = off_second + k:  ut_c1 = u_c1;  ut_c2 = dfma(rho, u_c1, c u_c2);  ut = u elsewhere.
+//   Everything above runs on ut where it ran on u: b_c from group and local scales, z, (r, v, s), G_c, W_g, the lambdas, the scores.
+//   backward, after the chain rules above have left Gh_c = dl / dut_c in the columns and filled omega, lambda, a:
+//     m_k = Gh_c2 (c dfma(c, u_c1, -(rho u_c2)));   G_c1 = dfma(rho, Gh_c2, Gh_c1);   G_c2 = c Gh_c2
+//     M_p[c2 mod 128]: plain additions over chunks ascending, from +0, of the pair's m_k (a non-member adds +0)
+//     G_zeta_p = the canonical tree over M_p (wave_sum), placed like a group's
+//   prior: the loop runs on the raw q (the prior of u is on u).  eta_p > 0 is LKJ(eta) on the 2 x 2 correlation with the Jacobian of
+//   tanh, log p(zeta) = eta log(1 - rho^2); the device's kind table holds the internal kind 5 there and eta in nu's place:
+//     T = T + (4 eta) ((|zeta| + dlog1p(t)) - ln 2);   g = dfma(-2 eta, rho, G)        (ln 2 rounded to a double)
+//   eta_p = 0: the coordinate's entry of the prior arrays applies (kinds 0 and 1).  The branch is compiled under kCorr only.
+// DevState::lr_cpart holds, per coordinate, -1 or  partner | pair << 10 | (second ? 2048 : 0)  for a paired column; lr_cp = P.  It is
+// not lr_lpart: kLocal and kCorr are independent.  Both forms read the partner through the wavefront-private LDS vector they already
+// have, written and read by one wavefront in program order (no workgroup barrier): GlmWave through buf, GlmCoop through the
+// requester's Q row -- q, ut from it, then b in its place before barrier A; after barrier C the G row is taken into registers, rho, c
+// and ut are computed again from q (as glm_local_chain computes st again), the chain rules of the scales run on ut, and then q and Gh
+// go through the row for m_k and G_c1.  No LDS, tile or barrier is added; nothing of the pairs is alive across multiply().
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -380,6 +405,116 @@ IDHMC_DEV double glm_prior(int kind, double nu, double tau, double d, double G, 
     return G + (1.0 - ((nu + 1.0) * e) / (nu + e));
 }
 
+// Correlated pairs (Obs::kCorr).  An entry of the partner table: -1, or partner | pair << 10 | (second ? 2048 : 0)
+constexpr int kCorrSecond = 2048, kCorrPair = 1024, kCorrMask = 1023;
+constexpr int kPriorLkj = 5;                         // the device table's mark of a zeta with eta > 0 (eta in nu's place); never a public kind
+constexpr double kLn2 = 0.69314718055994530942;
+// rho and c of the pair whose zeta is coordinate cz of q: read from its owner lane, the same bits in every lane
+template <int NCH>
+IDHMC_DEV void glm_corr_factors(const Vec<NCH> &q, int cz, double &rho, double &c)
+{
+    const double z = read_lane(glm_coord<NCH>(q, cz), (cz & 127) >> 1);
+    const double s = dexp(-__builtin_fabs(z));
+    const double t = s * s, d = 1.0 + t;
+    rho = __builtin_copysign((1.0 - t) / d, z);
+    c = (2.0 * s) / d;
+}
+template <int NCH>
+IDHMC_DEV void glm_corr_pairs(const Vec<NCH> &q, int cz0, int np, double &r0, double &c0, double &r1, double &c1)
+{
+    glm_corr_factors<NCH>(q, cz0, r0, c0);
+    r1 = 0.0;
+    c1 = 1.0;
+    if (np > 1) glm_corr_factors<NCH>(q, cz0 + 1, r1, c1);
+}
+// ut of every coordinate of the lane: dfma(rho, u_c1, c u_c2) for a second column, q itself elsewhere.  vec is the wavefront's own
+// LDS vector (>= 128 NCH doubles, indexed by coordinate): q is staged there and each second column reads its first.
+template <int NCH>
+IDHMC_DEV void glm_corr_mix(Vec<NCH> &ut, const Vec<NCH> &q, const int32_t *cpart, double *vec, int lane, double r0, double c0, double r1, double c1)
+{
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(cpart) + lane;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = q.c[j];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 p = part2[j * 64];
+        const bool sx = p.x >= 0 && (p.x & kCorrSecond), sy = p.y >= 0 && (p.y & kCorrSecond);
+        const double ux = vec[sx ? p.x & kCorrMask : 0], uy = vec[sy ? p.y & kCorrMask : 0];
+        const double rx = (p.x & kCorrPair) ? r1 : r0, cx = (p.x & kCorrPair) ? c1 : c0;
+        const double ry = (p.y & kCorrPair) ? r1 : r0, cy = (p.y & kCorrPair) ? c1 : c0;
+        ut.c[j].x = sx ? dfma(rx, ux, cx * q.c[j].x) : q.c[j].x;
+        ut.c[j].y = sy ? dfma(ry, uy, cy * q.c[j].y) : q.c[j].y;
+    }
+}
+// the chain rule of the mix on the lane's G (Gh in the columns, complete elsewhere but for the zetas): m_k into M_p and by the tree
+// into coordinate cz0 + p, G_c2 = c Gh_c2, and G_c1 = dfma(rho, Gh_c2, Gh_c1) with Gh_c2 read through vec once every u_c1 has been
+template <int NCH>
+IDHMC_DEV void glm_corr_chain(Vec<NCH> &G, const Vec<NCH> &q, const int32_t *cpart, double *vec, int cz0, int np, int lane,
+                              double r0, double c0, double r1, double c1)
+{
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(cpart) + lane;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = q.c[j];
+    double2 M0 = make_double2(0.0, 0.0), M1 = M0;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 p = part2[j * 64];
+        const bool sx = p.x >= 0 && (p.x & kCorrSecond), sy = p.y >= 0 && (p.y & kCorrSecond);
+        const bool px = (p.x & kCorrPair) != 0, py = (p.y & kCorrPair) != 0;
+        const double ux = vec[sx ? p.x & kCorrMask : 0], uy = vec[sy ? p.y & kCorrMask : 0];
+        const double rx = px ? r1 : r0, cx = px ? c1 : c0, ry = py ? r1 : r0, cy = py ? c1 : c0;
+        const double mx = G.c[j].x * (cx * dfma(cx, ux, -(rx * q.c[j].x))), my = G.c[j].y * (cy * dfma(cy, uy, -(ry * q.c[j].y)));
+        M0.x = M0.x + (sx && !px ? mx : 0.0);
+        M0.y = M0.y + (sy && !py ? my : 0.0);
+        M1.x = M1.x + (sx && px ? mx : 0.0);
+        M1.y = M1.y + (sy && py ? my : 0.0);
+    }
+    // every u has been read: Gh takes q's place, and each first column's lane reads its second's
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = G.c[j];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 p = part2[j * 64];
+        const bool ax = p.x >= 0, ay = p.y >= 0;
+        const bool sx = ax && (p.x & kCorrSecond), sy = ay && (p.y & kCorrSecond);
+        const double gx = vec[ax && !sx ? p.x & kCorrMask : 0], gy = vec[ay && !sy ? p.y & kCorrMask : 0];
+        const double rx = (p.x & kCorrPair) ? r1 : r0, cx = (p.x & kCorrPair) ? c1 : c0;
+        const double ry = (p.y & kCorrPair) ? r1 : r0, cy = (p.y & kCorrPair) ? c1 : c0;
+        G.c[j].x = sx ? cx * G.c[j].x : ax ? dfma(rx, gx, G.c[j].x) : G.c[j].x;
+        G.c[j].y = sy ? cy * G.c[j].y : ay ? dfma(ry, gy, G.c[j].y) : G.c[j].y;
+    }
+    glm_group_place<NCH>(G, M0, cz0, lane);
+    if (np > 1) glm_group_place<NCH>(G, M1, cz0 + 1, lane);
+}
+// glm_prior with the LKJ row: d is zeta itself (its mu is 0), nu holds eta
+IDHMC_DEV double glm_prior_corr(int kind, double nu, double tau, double d, double G, double &T)
+{
+    if (kind == kPriorLkj) {
+        const double z = __builtin_fabs(d);
+        const double s = dexp(-z);
+        const double t = s * s;
+        const double rho = __builtin_copysign((1.0 - t) / (1.0 + t), d);
+        T = T + (4.0 * nu) * ((z + dlog1p(t)) - kLn2);
+        return dfma(-2.0 * nu, rho, G);
+    }
+    return glm_prior(kind, nu, tau, d, G, T);
+}
+template <bool CORR>
+IDHMC_DEV double glm_prior_of(int kind, double nu, double tau, double d, double G, double &T)
+{
+    if constexpr (CORR) return glm_prior_corr(kind, nu, tau, d, G, T);
+    else return glm_prior(kind, nu, tau, d, G, T);
+}
+// a when B, else b: the vector the scales and the products run on
+template <bool B, class T>
+IDHMC_DEV const T &glm_pick(const T &a, const T &b)
+{
+    if constexpr (B) return a;
+    else return b;
+}
+
 // Factor terms (Obs::kFactors): what both forms take from DevState
 struct GlmFactors {
     const int32_t *idx, *start;      // lr_fidx [F][n_pad], lr_fstart [n_pad / 128][cols + 1]
@@ -465,7 +600,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -491,6 +626,8 @@ struct GlmWave {
     double inv2;             // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     GlmFactors fac;          // the factor terms (Obs::kFactors)
     GlmSlopes slo;           // their values (Obs::kSlopes)
+    const int32_t *cpart;    // the partner table of the paired columns, device (Obs::kCorr)
+    int cz0, ncp;            // the coordinate of zeta_0 and the pairs (Obs::kCorr)
     double *buf;             // this wavefront's LDS vector, L doubles
     int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -516,6 +653,12 @@ struct GlmWave {
         }
         if constexpr (Obs::kFactors) fac.init(s);
         if constexpr (Obs::kSlopes) slo.init(s);
+        if constexpr (Obs::kCorr) {
+            cpart = s.lr_cpart;
+            ncp = s.lr_cp;
+            cz0 = s.D - s.lr_cp;
+            D -= s.lr_cp;
+        }
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -540,8 +683,15 @@ struct GlmWave {
         }
         double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;         // the groups' scales
         if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, D + Obs::A, e0, e1, e2, e3);
+        double cr0 = 0.0, cc0 = 1.0, cr1 = 0.0, cc1 = 1.0;     // Obs::kCorr: rho and c of the pairs
+        Vec<NCH> qm;                                           // and ut in the columns, q elsewhere
+        if constexpr (Obs::kCorr) {
+            glm_corr_pairs<NCH>(q, cz0, ncp, cr0, cc0, cr1, cc1);
+            glm_corr_mix<NCH>(qm, q, cpart, buf, lane, cr0, cc0, cr1, cc1);
+        }
+        const Vec<NCH> &u = glm_pick<Obs::kCorr>(qm, q);       // what the scales and the products run on
         Vec<NCH> bq;                                           // Obs::kLocal: b, once per gradient
-        if constexpr (Obs::kLocal) glm_local_b<NCH, Obs::H>(bq, q, grp2, part, buf, D, lane, e0, e1, e2, e3, inv2);
+        if constexpr (Obs::kLocal) glm_local_b<NCH, Obs::H>(bq, u, grp2, part, buf, D, lane, e0, e1, e2, e3, inv2);
         double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;
         const int nb = npad >> 7;
         for (int b = 0; b < nb; ++b) {
@@ -553,9 +703,9 @@ struct GlmWave {
                     b2[j * 64] = bq.c[j];
                 } else if constexpr (Obs::H > 0) {
                     const int2 id = grp2[j * 64];
-                    b2[j * 64] = make_double2(glm_scaled<HN>(q.c[j].x, id.x, e0, e1, e2, e3), glm_scaled<HN>(q.c[j].y, id.y, e0, e1, e2, e3));
+                    b2[j * 64] = make_double2(glm_scaled<HN>(u.c[j].x, id.x, e0, e1, e2, e3), glm_scaled<HN>(u.c[j].y, id.y, e0, e1, e2, e3));
                 } else {
-                    b2[j * 64] = q.c[j];
+                    b2[j * 64] = u.c[j];
                 }
             }
             const double2 *xtp = reinterpret_cast<const double2 *>(xt + 128 * b) + lane;
@@ -669,8 +819,11 @@ struct GlmWave {
                 for (int j = 0; j < NCH; ++j) glm_place(G.c[j], j, D + jx, lane, S);
             }
         }
-        if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(G, q, grp2, part, buf, D, D + Obs::A, lane, e0, e1, e2, e3, inv2);
-        else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, q, grp2, D + Obs::A, lane, e0, e1, e2, e3);
+        // (with local scales b was held across the blocks, not ut: it is mixed again from q)
+        if constexpr (Obs::kCorr && Obs::kLocal) glm_corr_mix<NCH>(qm, q, cpart, buf, lane, cr0, cc0, cr1, cc1);
+        if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(G, u, grp2, part, buf, D, D + Obs::A, lane, e0, e1, e2, e3, inv2);
+        else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, u, grp2, D + Obs::A, lane, e0, e1, e2, e3);
+        if constexpr (Obs::kCorr) glm_corr_chain<NCH>(G, q, cpart, buf, cz0, ncp, lane, cr0, cc0, cr1, cc1);
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
@@ -679,8 +832,8 @@ struct GlmWave {
             if constexpr (Obs::kPriors) {
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];
-                g.c[j].x = glm_prior(k.x, nu.x, t.x, dx, G.c[j].x, t0);
-                g.c[j].y = glm_prior(k.y, nu.y, t.y, dy, G.c[j].y, t1);
+                g.c[j].x = glm_prior_of<Obs::kCorr>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
+                g.c[j].y = glm_prior_of<Obs::kCorr>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
             } else {
                 t0 = dfma(t.x * dx, dx, t0);
                 t1 = dfma(t.y * dy, dy, t1);
@@ -738,6 +891,8 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     double inv2;                 // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     GlmFactors fac;              // the factor terms (Obs::kFactors)
     GlmSlopes slo;               // their values (Obs::kSlopes)
+    const int32_t *cpart;        // the partner table of the paired columns, device (Obs::kCorr)
+    int cz0, ncp;                // the coordinate of zeta_0 and the pairs (Obs::kCorr)
     double *tile;
     int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -756,6 +911,12 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         }
         if constexpr (Obs::kFactors) fac.init(s);
         if constexpr (Obs::kSlopes) slo.init(s);
+        if constexpr (Obs::kCorr) {
+            cpart = s.lr_cpart;
+            ncp = s.lr_cp;
+            cz0 = s.D - s.lr_cp;
+            dx -= s.lr_cp;
+        }
         x = s.lr_x;
         xt = s.lr_xt;
         y = s.lr_y;
@@ -955,11 +1116,18 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         Prefetch pf;
         double2 *row = reinterpret_cast<double2 *>(tile + kQ + wv * DS) + lane;
         double e0 = 0.0, e1 = 0.0, e2 = 0.0, e3 = 0.0;        // the groups' scales
+        double cr0 = 0.0, cc0 = 1.0, cr1 = 0.0, cc1 = 1.0;    // Obs::kCorr: rho and c of the pairs
+        Vec<NCH> qm;                                          // and ut in the columns, q elsewhere (q goes through the row for it)
+        if constexpr (Obs::kCorr) {
+            glm_corr_pairs<NCH>(q, cz0, ncp, cr0, cc0, cr1, cc1);
+            glm_corr_mix<NCH>(qm, q, cpart, tile + kQ + wv * DS, lane, cr0, cc0, cr1, cc1);
+        }
+        const Vec<NCH> &u = glm_pick<Obs::kCorr>(qm, q);      // what the scales and the products run on
         if constexpr (Obs::kLocal) {
             // q goes through the row first (each column reads its lambda there), then b takes its place, +0 in every column >= dx
             if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, dx + Obs::A, e0, e1, e2, e3);
             Vec<NCH> bq;
-            glm_local_b<NCH, Obs::H>(bq, q, grp2, part, tile + kQ + wv * DS, dx, lane, e0, e1, e2, e3, inv2);
+            glm_local_b<NCH, Obs::H>(bq, u, grp2, part, tile + kQ + wv * DS, dx, lane, e0, e1, e2, e3, inv2);
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 const int c0 = 128 * j + 2 * lane;
@@ -972,13 +1140,14 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             for (int j = 0; j < NCH; ++j) {
                 const int c0 = 128 * j + 2 * lane;
                 const int2 id = grp2[j * 64];
-                row[j * 64] = make_double2(c0 >= dx ? 0.0 : glm_scaled<HN>(q.c[j].x, id.x, e0, e1, e2, e3), c0 + 1 >= dx ? 0.0 : glm_scaled<HN>(q.c[j].y, id.y, e0, e1, e2, e3));
+                row[j * 64] = make_double2(c0 >= dx ? 0.0 : glm_scaled<HN>(u.c[j].x, id.x, e0, e1, e2, e3), c0 + 1 >= dx ? 0.0 : glm_scaled<HN>(u.c[j].y, id.y, e0, e1, e2, e3));
             }
-        } else if constexpr (Obs::A > 0) {
+        } else if constexpr (Obs::A > 0 || Obs::kCorr) {
+            // (the zetas are coordinates behind the columns like the auxiliary ones: +0 in the row)
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 const int c0 = 128 * j + 2 * lane;
-                row[j * 64] = make_double2(c0 >= dx ? 0.0 : q.c[j].x, c0 + 1 >= dx ? 0.0 : q.c[j].y);
+                row[j * 64] = make_double2(c0 >= dx ? 0.0 : u.c[j].x, c0 + 1 >= dx ? 0.0 : u.c[j].y);
             }
         } else {
 #pragma unroll
@@ -1002,8 +1171,8 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 S[jx] = wave_sum(sp[0], sp[1]);
             }
         }
-        Vec<NCH> Gh;                                          // with groups or local scales: the whole G row, for the chain rule
-        if constexpr (Obs::H > 0 || Obs::kLocal) {
+        Vec<NCH> Gh;                                          // with groups, local scales or pairs: the whole G row, for the chain rule
+        if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr) {
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 Gh.c[j] = row[j * 64];
@@ -1016,16 +1185,25 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             int c0 = dx + Obs::A;
             asm volatile("" : "+s"(c0));                      // (not the value of before barrier A kept alive)
             if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, c0, e0, e1, e2, e3);
+            // (pairs: rho, c and ut again from q, through the row, which is the requester's own until barrier A now that G is in registers)
+            int cz = 0;
+            if constexpr (Obs::kCorr) {
+                cz = cz0;
+                asm volatile("" : "+s"(cz));
+                glm_corr_pairs<NCH>(q, cz, ncp, cr0, cc0, cr1, cc1);
+                glm_corr_mix<NCH>(qm, q, cpart, tile + kQ + wv * DS, lane, cr0, cc0, cr1, cc1);
+            }
             // (local scales: the G row is in registers now, so q and then wl go through the row, which is the requester's own until barrier A)
-            if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(Gh, q, grp2, part, tile + kQ + wv * DS, dx, c0, lane, e0, e1, e2, e3, inv2);
-            else glm_group_chain<NCH, HN>(Gh, q, grp2, c0, lane, e0, e1, e2, e3);
+            if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(Gh, u, grp2, part, tile + kQ + wv * DS, dx, c0, lane, e0, e1, e2, e3, inv2);
+            else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(Gh, u, grp2, c0, lane, e0, e1, e2, e3);
+            if constexpr (Obs::kCorr) glm_corr_chain<NCH>(Gh, q, cpart, tile + kQ + wv * DS, cz, ncp, lane, cr0, cc0, cr1, cc1);
         }
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
             double2 G;
-            if constexpr (Obs::H > 0 || Obs::kLocal) {
+            if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr) {
                 G = Gh.c[j];
             } else {
                 G = row[j * 64];
@@ -1039,8 +1217,8 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 // kinds and nu are read here, after barrier C: nothing of the prior is alive across multiply()
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];
-                g.c[j].x = glm_prior(k.x, nu.x, t.x, dx, G.x, t0);
-                g.c[j].y = glm_prior(k.y, nu.y, t.y, dy, G.y, t1);
+                g.c[j].x = glm_prior_of<Obs::kCorr>(k.x, nu.x, t.x, dx, G.x, t0);
+                g.c[j].y = glm_prior_of<Obs::kCorr>(k.y, nu.y, t.y, dy, G.y, t1);
             } else {
                 t0 = dfma(t.x * dx, dx, t0);
                 t1 = dfma(t.y * dy, dy, t1);

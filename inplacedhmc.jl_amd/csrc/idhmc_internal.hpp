@@ -107,6 +107,10 @@ struct DevState {
     const double *lr_fval;    // [lr_f][lr_npad] w of every observation: the values of a valued term, 1.0 for a plain term, 0.0 in the padding
     const double *lr_fwl;     // [lr_npad / 128][128 lr_f] the same values in the order of lr_fpos: entry t is the value of the observation byte t names
     uint32_t lr_fhas;         // bit f: term f has values
+    // correlated pairs of factor terms (idhmc_create_glm_corr; null and 0 without a pair): the last lr_cp coordinates are
+    // the zetas.  Appended again, and not lr_lpart: no kernel of a model without pairs changes (profiles/r19_glm_corr_kres_*.txt).
+    const int32_t *lr_cpart;  // [L] -1, or for a paired column: partner | pair << 10 | (second of its pair ? 2048 : 0)
+    int32_t lr_cp;            // pairs, 0..2
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -156,7 +160,8 @@ struct JitModule;
 // compiles `source` against the kernel templates for this state's shape; on failure returns non-zero and
 // fills `log` (compiler output, truncated)
 // K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors),
-// s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors), s.lr_fval one whose terms read a value (kSlopes)
+// s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors), s.lr_fval one whose terms read a value (kSlopes),
+// s.lr_cp > 0 one with correlated pairs (kCorr)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

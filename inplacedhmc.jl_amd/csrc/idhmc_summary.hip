@@ -97,10 +97,57 @@ __global__ void k_summary_local_scales(const double *stage, double *scales, int6
     scales[r * W + H + J + k] = st;
 }
 
+// A GLM with correlated pairs: theta = [beta | a raw | sigma | exp(lambda) | rho], beta taken from ut.  One thread per
+// (row, coordinate) writes the whole reported vector of the row, by the expressions of idhmc_glm.hpp (glm_corr_factors, glm_corr_mix,
+// glm_scaled, glm_local_scale); the reduction then runs on it as it runs on raw draws (MODE 3).  A row of "scales" is theta, D doubles.
+__global__ void k_summary_corr_theta(const double *stage, double *theta, int64_t rows, int32_t D, int32_t Dx, int32_t A, int32_t H, int32_t J,
+                                     int32_t P, const int32_t *grp, const int32_t *lpart, const int32_t *cpart, double inv2)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * D) return;
+    const int64_t r = i / D;
+    const int32_t d = (int32_t)(i - r * D);
+    const double *q = stage + r * D;
+    double x = q[d];
+    if (d >= D - P) {
+        const double s = dexp(-__builtin_fabs(x));
+        const double t = s * s;
+        x = __builtin_copysign((1.0 - t) / (1.0 + t), x);
+    } else if (d >= Dx + A) {
+        x = dexp(x);
+    } else if (d < Dx) {
+        const int32_t p = cpart[d];
+        if (p >= 0 && (p & 2048)) {
+            const double z = q[D - P + ((p >> 10) & 1)];
+            const double s = dexp(-__builtin_fabs(z));
+            const double t = s * s, dd = 1.0 + t;
+            const double rho = __builtin_copysign((1.0 - t) / dd, z), c = (2.0 * s) / dd;
+            x = dfma(rho, q[p & 1023], c * x);
+        }
+        const int32_t id = H > 0 ? grp[d] : -1;
+        const int32_t lp = J > 0 ? lpart[d] : -1;
+        if (lp >= 0) {
+            const double f = dexp(q[lp]);
+            const double s = id >= 0 ? dexp(q[Dx + A + id]) * f : f;
+            double st = s;
+            if (inv2 != 0.0) {
+                const double iv = 1.0 / s;
+                const double nn = dfma(iv, iv, inv2);
+                st = 1.0 / __builtin_sqrt(nn);
+            }
+            x = x * st;
+        } else if (id >= 0) {
+            x = x * dexp(q[Dx + A + id]);
+        }
+    }
+    theta[i] = x;
+}
+
 // The reduction.  Lane i owns (segment, d) = (i / D, i % D): consecutive lanes take consecutive d, so a wavefront reads contiguous
 // runs of a row.  The lane visits its segment's chains transition by transition, ascending chain id inside, with its state in
 // registers; HIST: it counts its values' bins in its own LDS row and the workgroup adds the rows to the table at the end.
-// MODE: 0 theta = q; 1 coefficient groups; 2 local scales (with or without groups)
+// MODE: 0 theta = q; 1 coefficient groups; 2 local scales (with or without groups); 3, correlated pairs, is MODE 0 on the theta that
+// k_summary_corr_theta wrote
 template <bool HIST, int MODE>
 IDHMC_DEV void summary_body(const SumArgs &a, uint16_t *lds_cnt)
 {
@@ -316,9 +363,9 @@ static hipError_t launch_summary(const SumArgs &a, hipStream_t st)
 }  // namespace idhmc
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && (c->s.lr_h > 0 || c->s.lr_j > 0); }
-// doubles per row of Summary::scales: e_g, and with local scales f_k and st_k
-static int64_t scales_width(const idhmc_ctx *c) { return c->s.lr_h + 2 * (int64_t)c->s.lr_j; }
+static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && (c->s.lr_h > 0 || c->s.lr_j > 0 || c->s.lr_cp > 0); }
+// doubles per row of Summary::scales: e_g, and with local scales f_k and st_k; with correlated pairs the whole theta
+static int64_t scales_width(const idhmc_ctx *c) { return c->s.lr_cp > 0 ? (int64_t)c->s.D : c->s.lr_h + 2 * (int64_t)c->s.lr_j; }
 static int64_t sum_gd(const idhmc_ctx *c) { return c->sum.groups * (int64_t)c->s.D; }
 
 static void summary_release(idhmc_ctx *c)
@@ -395,7 +442,7 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
 {
     Summary &m = c->sum;
     const DevState &s = c->s;
-    const bool scaled = scaled_theta(c), local = s.lr_j > 0;
+    const bool corr = s.lr_cp > 0, scaled = scaled_theta(c), local = s.lr_j > 0 && !corr;
     if (scaled) {
         const int64_t rows = (int64_t)cnt * s.C;
         if (m.scales_rows < rows) {
@@ -404,7 +451,10 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
             if (int rc = dalloc(c, &m.scales, rows * scales_width(c), false)) return rc;
             m.scales_rows = rows;
         }
-        if (local)
+        if (corr)
+            hipLaunchKernelGGL(k_summary_corr_theta, dim3(blocks_for(rows * s.D, 256)), dim3(256), 0, c->stream, stage, m.scales, rows, s.D,
+                               s.D - s.lr_a - s.lr_h - s.lr_j - s.lr_cp, s.lr_a, s.lr_h, s.lr_j, s.lr_cp, s.lr_grp, s.lr_lpart, s.lr_cpart, s.lr_inv2);
+        else if (local)
             hipLaunchKernelGGL(k_summary_local_scales, dim3(blocks_for(rows * (s.lr_h + s.lr_j), 256)), dim3(256), 0, c->stream, stage, m.scales, rows,
                                s.D, s.lr_h, s.lr_j, s.lr_grp, s.lr_lpart, s.lr_inv2);
         else
@@ -417,8 +467,11 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
     a.D = s.D; a.cnt = cnt; a.spg = m.spg;
     a.bins = m.bins; a.Dx = s.D - s.lr_a - s.lr_h - s.lr_j; a.A = s.lr_a; a.H = s.lr_h;
     a.lpart = s.lr_lpart; a.J = s.lr_j; a.W = (int32_t)scales_width(c);
+    if (corr) a.stage = m.scales;       // MODE 3: the theta written above, reduced as raw draws are
     const bool hist = m.ranged && m.bins > 0;
-    hipError_t e = hist ? (local ? launch_summary<true, 2>(a, c->stream) : scaled ? launch_summary<true, 1>(a, c->stream) : launch_summary<true, 0>(a, c->stream))
+    const bool plain = corr || !scaled;
+    hipError_t e = plain ? (hist ? launch_summary<true, 0>(a, c->stream) : launch_summary<false, 0>(a, c->stream)) :
+                   hist ? (local ? launch_summary<true, 2>(a, c->stream) : scaled ? launch_summary<true, 1>(a, c->stream) : launch_summary<true, 0>(a, c->stream))
                         : (local ? launch_summary<false, 2>(a, c->stream) : scaled ? launch_summary<false, 1>(a, c->stream) : launch_summary<false, 0>(a, c->stream));
     HIPCHK(e);
     m.fed_t += (uint64_t)cnt;

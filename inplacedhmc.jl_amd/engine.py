@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmLocal, GlmPriors, ModelDesc, Options, check
+from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmLocal, GlmPairs, GlmPriors, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -163,7 +163,7 @@ def _prior(D, prior_mu, prior_tau):
 
 
 def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None, prior_kind=None,
-        prior_nu=None, local=None, slab_scale=None, factors=None):
+        prior_nu=None, local=None, slab_scale=None, factors=None, correlated=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -225,10 +225,22 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     the term is a random slope -- z_i takes values[i] * b[off_f + idx[i]] where a term without values adds b[off_f + idx[i]] -- and its
     N columns are columns of the model like any other term's, never stored.  Two terms may share one index: a random intercept and slope
     per subject, (1 + x | subject), is factors=[subject, glm.term(subject, values=x)] with **glm.random_intercepts(Dd, [N, N]), which
-    gives the intercepts and the slopes a sampled scale each, the two independent; a covariance between intercept and slope is out of
-    scope.  glm.expand_factors writes the values into the term's columns, and the bits stay those of the expanded model as long as no
+    gives the intercepts and the slopes a sampled scale each, the two independent unless the terms are paired (correlated, below).
+    glm.expand_factors writes the values into the term's columns, and the bits stay those of the expanded model as long as no
     product underflows to -0 (include/idhmc.h).  The Model exposes factor_has (int32 (F,)) and factor_values (float64 (F, n), rows of
-    terms without values 0), None when no term has values; Engine.glm_factor_values() reads them back."""
+    terms without values 0), None when no term has values; Engine.glm_factor_values() reads them back.
+
+    correlated: a list of up to 2 glm.pair(first, second, eta=2.0) (idhmc_create_glm_corr) -- correlated random effects: two distinct terms
+    with equal level counts, a term in at most one pair, share a sampled correlation rho = tanh(zeta) between level k of the first and
+    level k of the second.  Each pair adds one coordinate at the end: a chain's position is
+    [u (Dx) | a (A) | omega (H) | lambda (J) | zeta (P)], the model's D is Dx + A + H + J + P, and the prior keywords are scalars or of that
+    length.  The second term's column of level k takes rho u_first + sqrt(1 - rho^2) u_second where it took u, before the group and local
+    scales: with a group per term the effects of a level are sigma .* (L u), L = [[1, 0], [rho, sqrt(1 - rho^2)]].  eta > 0 is LKJ(eta) on
+    the 2 x 2 correlation, (rho + 1) / 2 ~ Beta(eta, eta), and zeta's entries in the prior keywords must be the defaults; eta = 0 lets
+    them apply (PRIOR_NORMAL or PRIOR_STUDENT_T on Fisher's z; the log kinds are refused).  glm.correlated_effects() assembles groups,
+    priors and correlated; glm.correlations(model, draws) gives rho, glm.coefficients applies the mix.  An empty list is the model without
+    the keyword; a covariance among three or more terms is out of scope.  The Model exposes P, pairs (a list of glm.Pair, None without),
+    pair_first, pair_second (int32 (P,)) and pair_eta (float64 (P,)); Engine.glm_pairs() reads them back."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -259,7 +271,9 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
         if H == 0:
             grp = None                                          # every column ungrouped: the model without groups
     loc, J, S = _glm.local_flags(local, slab_scale, Dx)
-    D = Dx + A + H + J
+    pfirst, psecond, peta = _glm.pair_terms(correlated, flev)
+    P = 0 if pfirst is None else pfirst.size
+    D = Dx + A + H + J + P
     if D > 1024:
         raise ValueError("a GLM is limited to D <= 1024 (D = %d)" % D)
     if not np.isfinite(X).all():
@@ -291,6 +305,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
         raise ValueError("a GLM needs HIP source defining glm_observation")
     mu, tau = _prior(D, prior_mu, prior_tau)
     kind, nu = _glm.prior_kinds(prior_kind, prior_nu, D, Dx, tau)
+    if P:
+        _glm.pair_priors(peta, D, mu, tau, kind, nu)
     priors = kind is not None and bool(kind.any())
     K = Y.shape[-1]
     if H > 0 or R is not None or priors or J > 0 or F > 0:
@@ -310,6 +326,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.J, m.local, m.slab_scale = J, loc, S
     m.Dd, m.F, m.levels, m.factor_index = Dd, F, flev, fidx
     m.factor_has, m.factor_values = fhas, fval
+    m.P, m.pair_first, m.pair_second, m.pair_eta = P, pfirst, psecond, peta
+    m.pairs = [_glm.Pair(int(a), int(b), float(e)) for a, b, e in zip(pfirst, psecond, peta)] if P else None
     return m
 
 
@@ -343,7 +361,16 @@ class Engine:
             fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
                             index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
             R = getattr(model, "R", None)
-            if getattr(model, "factor_has", None) is not None:
+            if getattr(model, "P", 0) > 0:
+                fv = None
+                if getattr(model, "factor_has", None) is not None:
+                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(C.POINTER(C.c_int32))))
+                ip = C.POINTER(C.c_int32)
+                pp = GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
+                              eta=_dp(model.pair_eta))
+                check(self.lib.idhmc_create_glm_corr(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, C.byref(pp),
+                                                     model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
+            elif getattr(model, "factor_has", None) is not None:
                 fv = GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(C.POINTER(C.c_int32)))
                 check(self.lib.idhmc_create_glm_slopes(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), C.byref(fv),
                                                        model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
@@ -519,6 +546,18 @@ class Engine:
         val = np.zeros((F.value, self.model.n))
         check(self.lib.idhmc_glm_factor_values_get(self.h, has.ctypes.data_as(C.POINTER(C.c_int32)), _dp(val)))
         return has[:F.value].copy(), val
+
+    def glm_pairs(self):
+        """(first int32 (P,), second int32 (P,), eta float64 (P,)) as the context holds them (GLM(..., correlated=)); (None, None, None) for
+        every model without correlated pairs"""
+        P = C.c_int32(0)
+        check(self.lib.idhmc_glm_pairs_get(self.h, C.byref(P), None, None, None))
+        if P.value == 0:
+            return None, None, None
+        a, b, e = np.zeros(P.value, np.int32), np.zeros(P.value, np.int32), np.zeros(P.value)
+        ip = C.POINTER(C.c_int32)
+        check(self.lib.idhmc_glm_pairs_get(self.h, C.byref(P), a.ctypes.data_as(ip), b.ctypes.data_as(ip), _dp(e)))
+        return a, b, e
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

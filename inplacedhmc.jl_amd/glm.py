@@ -100,9 +100,16 @@ Random slopes, factors=[subject, term(subject, values=x)] (idhmc_create_glm_slop
 w_f[i] per observation next to its level index, and then z_i takes w_f[i] b[off_f + idx_f[i]] (one fma) where a plain term adds
 b[off_f + idx_f[i]].  Its N_f columns are columns of the model like any other term's and are never stored; two terms may share one index
 array.  (1 + x | subject) is factors=[subject, term(subject, values=x)] with **random_intercepts(Dd, [N, N]) (random_effects is the same
-function under the name that fits): the intercepts and the slopes each get a sampled scale of their own, and the two are independent --
-a covariance between intercept and slope is out of scope.  expand_factors writes w_f[i] where it writes 1.0 for a plain term, and the
+function under the name that fits): the intercepts and the slopes each get a sampled scale of their own, and the two are independent
+unless the terms are paired (below).  expand_factors writes w_f[i] where it writes 1.0 for a plain term, and the
 engine computes the same bits on both; factor_values(factors, n) is GLM()'s validation of the values.
+
+Correlated random effects, correlated=[pair(0, 1, eta=2.0)] (idhmc_create_glm_corr): up to two pairs of terms with equal
+level counts, each with one more sampled coordinate zeta = atanh rho at the end of q.  Level k's column of the second term becomes
+rho u_first + sqrt(1 - rho^2) u_second before any scale applies; eta > 0 is LKJ(eta) on the correlation, eta = 0 leaves zeta to its entry
+in the prior arrays (normal or Student-t).  correlated_effects(Dd, levels, pairs, eta) assembles groups, priors and correlated;
+correlations(model, draws) gives rho and coefficients(model, draws) applies the mix.  A covariance among three or more terms is out of
+scope.
 """
 import collections
 
@@ -350,9 +357,9 @@ def by_response(model, draws, first_chain=0):
 
 
 def _sampled(model, draws):
-    """draws as float64, checked against the model's D = Dx + A + H + J"""
+    """draws as float64, checked against the model's D = Dx + A + H + J + P"""
     draws = np.asarray(draws, dtype=np.float64)
-    D = model.Dx + model.A + getattr(model, "H", 0) + getattr(model, "J", 0)
+    D = model.Dx + model.A + getattr(model, "H", 0) + getattr(model, "J", 0) + getattr(model, "P", 0)
     if draws.shape[-1] != D:
         raise ValueError("draws must have %d coordinates along the last axis, got %d" % (D, draws.shape[-1]))
     return draws
@@ -370,8 +377,36 @@ def local_scales(model, draws):
     """exp(lambda_k) of a GLM with local scales, shape draws.shape[:-1] + (J,) (J = 0: an empty last axis): the local scale of the k-th
     flagged column, in ascending column order.  Any leading axes, as group_scales."""
     draws = _sampled(model, draws)
+    lam0 = model.Dx + model.A + getattr(model, "H", 0)
     with np.errstate(over="ignore"):                            # (a local scale of inf is a value, not an error: the slab bounds its column)
-        return np.exp(draws[..., model.Dx + model.A + getattr(model, "H", 0):])
+        return np.exp(draws[..., lam0:lam0 + getattr(model, "J", 0)])
+
+
+def _rho_c(zeta):
+    """rho and c of zeta by the device's expressions: s = exp(-|zeta|), t = s s, rho = copysign((1 - t) / (1 + t), zeta), c = 2 s / (1 + t)"""
+    s = np.exp(-np.abs(zeta))
+    t = s * s
+    return np.copysign((1.0 - t) / (1.0 + t), zeta), (2.0 * s) / (1.0 + t)
+
+
+def correlations(model, draws):
+    """rho_p = tanh(zeta_p) of a GLM with correlated pairs of terms (GLM(..., correlated=)), shape draws.shape[:-1] + (P,) (P = 0: an empty
+    last axis), computed as the device computes it: exactly +-1 past |zeta| of about 19, never beyond.  Any leading axes, as group_scales."""
+    draws = _sampled(model, draws)
+    P = getattr(model, "P", 0)
+    return _rho_c(draws[..., draws.shape[-1] - P:])[0]
+
+
+def _mixed(model, draws):
+    """u with the second column of every pair replaced by rho u_first + c u_second (draws checked by _sampled)"""
+    u = draws[..., :model.Dx].copy()
+    P = getattr(model, "P", 0)
+    if P:
+        rho, c = _rho_c(draws[..., draws.shape[-1] - P:])
+        for p in range(P):
+            a, b = factor_columns(model, int(model.pair_first[p])), factor_columns(model, int(model.pair_second[p]))
+            u[..., b] = rho[..., p:p + 1] * draws[..., a] + c[..., p:p + 1] * draws[..., b]
+    return u
 
 
 def coefficients(model, draws):
@@ -379,10 +414,11 @@ def coefficients(model, draws):
     beta_c = exp(omega_g) u_c for a column of group g, u_c for a column in no group (and for a model without groups).  Any leading
     axes: (M, ..., R, D) from by_response works as (..., C, D) does.  With local scales a flagged column has beta_c = u_c st, st from
     s = exp(omega_g) exp(lambda_k) (exp(lambda_k) in no group) by the kernels' operations: s itself without a slab, and with
-    slab_scale S  i = 1 / s, nn = i i + 1 / S^2, st = 1 / sqrt(nn)."""
+    slab_scale S  i = 1 / s, nn = i i + 1 / S^2, st = 1 / sqrt(nn).  With correlated pairs the mix comes first: the second column of a
+    pair is rho u_first + sqrt(1 - rho^2) u_second where the above say u_c, so that the effects of a level are sigma .* (L u)."""
     draws = _sampled(model, draws)
     sigma = group_scales(model, draws)
-    u = draws[..., :model.Dx]
+    u = _mixed(model, draws)
     J = getattr(model, "J", 0)
     if sigma.shape[-1] == 0 and J == 0:
         return u.copy()
@@ -547,6 +583,104 @@ def expand_factors(X, factors):
     return out
 
 
+# ---- correlated pairs of terms --------------------------------------------------------------------------------------------------------
+Pair = collections.namedtuple("Pair", "first second eta")
+
+
+def pair(first, second, eta=2.0):
+    """a correlated pair of factor terms for GLM(..., correlated=[...]): level k of term `first` and level k of term `second` share a
+    sampled correlation rho = tanh(zeta).  eta > 0: LKJ(eta) on the 2 x 2 correlation, (rho + 1) / 2 ~ Beta(eta, eta) (eta = 1: uniform);
+    eta = 0: the entry of zeta in prior_mu, prior_tau, prior_kind, prior_nu applies (normal or Student-t on Fisher's z).  Validated by
+    GLM() (pair_terms, pair_priors)."""
+    return Pair(first, second, eta)
+
+
+def pair_terms(correlated, levels):
+    """GLM()'s validation of correlated: (first int32 (P,), second int32 (P,), eta float64 (P,)), or (None, None, None) for None and for
+    an empty list.  levels: the level counts of the model's terms (None: no factor terms).  The checks are idhmc_create_glm_corr's,
+    naming the pair."""
+    if correlated is None:
+        return None, None, None
+    if not isinstance(correlated, (list, tuple)) or isinstance(correlated, Pair):
+        raise ValueError("correlated must be a list of glm.pair(first, second, eta), got %s" % type(correlated).__name__)
+    if len(correlated) == 0:
+        return None, None, None
+    if len(correlated) > 2:
+        raise ValueError("at most 2 correlated pairs (got %d)" % len(correlated))
+    if levels is None:
+        raise ValueError("correlated pairs need factor terms (GLM(..., factors=))")
+    F = len(levels)
+    first, second, eta = np.empty(len(correlated), np.int32), np.empty(len(correlated), np.int32), np.empty(len(correlated))
+    used = set()
+    for p, entry in enumerate(correlated):
+        if not isinstance(entry, Pair):
+            raise ValueError("correlated[%d] must be a glm.pair(first, second, eta)" % p)
+        for name, t in (("first", entry.first), ("second", entry.second)):
+            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < F:
+                raise ValueError("correlated[%d]: %s = %r is outside 0..%d (the model's terms)" % (p, name, t, F - 1))
+        a, b = int(entry.first), int(entry.second)
+        if a == b:
+            raise ValueError("correlated[%d]: first = second = %d (a pair is two distinct terms)" % (p, a))
+        for t in (a, b):
+            if t in used:
+                raise ValueError("correlated[%d]: term %d is in two pairs" % (p, t))
+            used.add(t)
+        if int(levels[a]) != int(levels[b]):
+            raise ValueError("correlated[%d]: terms %d and %d have %d and %d levels (a pair needs equal level counts)"
+                             % (p, a, b, int(levels[a]), int(levels[b])))
+        e = entry.eta
+        if isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating)) or not (np.isfinite(e) and e >= 0.0):
+            raise ValueError("correlated[%d]: eta = %r must be finite and >= 0 (0: the prior arrays' entry of zeta applies)" % (p, e))
+        first[p], second[p], eta[p] = a, b, float(e)
+    return first, second, eta
+
+
+def pair_priors(eta, D, mu, tau, kind, nu):
+    """GLM()'s checks of the zetas' entries in the prior arrays (the last P of D): no log kind; with eta > 0 the defaults"""
+    P = eta.size
+    for p in range(P):
+        cz = D - P + p
+        k = 0 if kind is None else int(kind[cz])
+        if k >= PRIOR_LOG_HALF_NORMAL:
+            raise ValueError("correlated[%d]: prior_kind[%d] = PRIOR_%s is a prior on exp(q): coordinate %d is zeta = atanh rho, not a logarithm "
+                             "(normal and student_t are for a zeta)" % (p, cz, PRIOR_NAMES[k], cz))
+        if eta[p] > 0.0 and (k != 0 or (nu is not None and nu[cz] != 0.0) or (mu is not None and mu[cz] != 0.0)
+                             or (tau is not None and tau[cz] != 1.0)):
+            raise ValueError("correlated[%d]: eta = %r is the LKJ prior of zeta: the entry of coordinate %d in the prior arrays must be the "
+                             "default (kind 0, mu 0, tau 1, nu 0) and is not applied" % (p, float(eta[p]), cz))
+
+
+def correlated_effects(Dd, levels, pairs, eta=2.0, A=0, scale=None, coefficients=None, aux=None):
+    """the keyword arguments of GLM() for correlated random effects: what random_intercepts(Dd, levels, A, scale, coefficients, aux)
+    returns, its prior arrays extended by the P zetas, plus `correlated` -- (1 + x | subject) with a sampled correlation between
+    intercept and slope is
+    GLM(X, Y, source, factors=[subject, glm.term(subject, values=x)], **glm.correlated_effects(X.shape[1], [N, N], [(0, 1)], eta=2.0)).
+    pairs: up to two (first, second) tuples of term indices; eta: one number or one per pair, LKJ(eta) on each correlation (0 is not
+    offered here: it needs a prior entry on zeta, which GLM()'s keywords take)."""
+    pairs = list(pairs)
+    if len(pairs) > 2:
+        raise ValueError("at most 2 correlated pairs (got %d)" % len(pairs))
+    etas = [eta] * len(pairs) if np.ndim(eta) == 0 else list(eta)
+    if len(etas) != len(pairs):
+        raise ValueError("eta must be one number or one per pair (%d)" % len(pairs))
+    corr = []
+    for p, (ab, e) in enumerate(zip(pairs, etas)):
+        if not isinstance(ab, (tuple, list)) or len(ab) != 2:
+            raise ValueError("pairs[%d] must be (first, second)" % p)
+        if not (np.isfinite(e) and e > 0.0):
+            raise ValueError("pairs[%d]: eta = %r must be finite and > 0" % (p, e))
+        corr.append(pair(ab[0], ab[1], float(e)))
+    pair_terms(corr, [int(N) for N in levels])
+    kw = random_intercepts(Dd, levels, A, scale, coefficients, aux)
+    P = len(corr)
+    kw["prior_mu"] = np.r_[kw["prior_mu"], np.zeros(P)]
+    kw["prior_tau"] = np.r_[kw["prior_tau"], np.ones(P)]
+    kw["prior_kind"] = np.r_[kw["prior_kind"], np.zeros(P, np.int32)].astype(np.int32)
+    kw["prior_nu"] = np.r_[kw["prior_nu"], np.zeros(P)]
+    kw["correlated"] = corr
+    return kw
+
+
 def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):
     """the keyword arguments groups, prior_mu, prior_tau, prior_kind and prior_nu of GLM() for random intercepts: Dd dense columns in no
     group, then factor f's levels[f] columns forming group f, whose sigma_f = exp(omega_f) is sampled --
@@ -555,7 +689,8 @@ def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):
     `coefficients` those of the Dd dense columns and `aux` those of the auxiliary coordinates, as priors() takes them.
     Every term gets a group of its own, whether it has values or not: a random intercept and slope per subject, (1 + x | subject), is
     GLM(X, Y, source, factors=[subject, glm.term(subject, values=x)], **glm.random_intercepts(X.shape[1], [N, N])), the scale of the
-    intercepts and the scale of the slopes sampled independently.  A covariance between intercept and slope is out of scope."""
+    intercepts and the scale of the slopes sampled independently.  A sampled correlation between the two is correlated_effects()
+    (GLM(..., correlated=[glm.pair(0, 1)])); a covariance among three or more terms is out of scope."""
     Dd = int(Dd)
     lev = [int(N) for N in levels]
     if Dd < 1:
@@ -665,15 +800,16 @@ def exponential(mean=1.0):
     return PriorSpec(PRIOR_LOG_EXPONENTIAL, float(np.log(_positive("mean", mean))), 1.0, 0.0)
 
 
-def priors(Dx, A=0, H=0, J=0, coefficients=None, aux=None, scales=None, local_scales=None):
+def priors(Dx, A=0, H=0, J=0, coefficients=None, aux=None, scales=None, local_scales=None, *, P=0, correlations=None):
     """the keyword arguments prior_mu, prior_tau, prior_kind and prior_nu of GLM() for Dx coefficients, A auxiliary coordinates, H
     group scales and J local scales (GLM(..., local=)): GLM(X, Y, source, aux=A, groups=g, **glm.priors(Dx, A, H, coefficients=glm.student_t(3), scales=glm.half_student_t(4))).
     Each role takes one spec (for every coordinate of the role) or a sequence of one spec per coordinate; None is normal(0, 1), today's
     prior (on a and omega: a standard normal on the logarithm).  The specs of sigma = exp(q) -- half_normal, half_student_t,
-    exponential -- are for aux, scales and local_scales only."""
+    exponential -- are for aux, scales and local_scales only.  P, correlations (keyword-only): the P zetas of GLM(..., correlated=), the
+    last coordinates; a spec there (normal or student_t on Fisher's z) is for a pair with eta = 0, a pair with eta > 0 keeps the default."""
     out = []
     for role, count, spec in (("coefficients", int(Dx), coefficients), ("aux", int(A), aux), ("scales", int(H), scales),
-                              ("local_scales", int(J), local_scales)):
+                              ("local_scales", int(J), local_scales), ("correlations", int(P), correlations)):
         if count < 0:
             raise ValueError("%s: a count of %d" % (role, count))
         if spec is None:
@@ -684,10 +820,11 @@ def priors(Dx, A=0, H=0, J=0, coefficients=None, aux=None, scales=None, local_sc
         if len(spec) != count or not all(isinstance(p, PriorSpec) for p in spec):
             raise ValueError("%s must be one prior spec or a sequence of %d (glm.normal, glm.student_t, glm.half_normal, glm.half_student_t, "
                              "glm.exponential)" % (role, count))
-        if role == "coefficients":
+        if role in ("coefficients", "correlations"):
             for c, p in enumerate(spec):
                 if p.kind >= PRIOR_LOG_HALF_NORMAL:
-                    raise ValueError("coefficients[%d]: PRIOR_%s is a prior on exp(q); a coefficient is not a logarithm" % (c, PRIOR_NAMES[p.kind]))
+                    raise ValueError("%s[%d]: PRIOR_%s is a prior on exp(q); %s is not a logarithm"
+                                     % (role, c, PRIOR_NAMES[p.kind], "a coefficient" if role == "coefficients" else "zeta = atanh rho"))
         out += spec
     return {"prior_mu": np.array([p.mu for p in out], np.float64), "prior_tau": np.array([p.tau for p in out], np.float64),
             "prior_kind": np.array([p.kind for p in out], np.int32), "prior_nu": np.array([p.nu for p in out], np.float64)}

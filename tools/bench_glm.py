@@ -58,6 +58,12 @@ factor model with the valued term replaced by a plain one (section 20's kernels 
 expanded run the same trajectories (same_bits), so the ratio of their steps/s is a time ratio; plain is another model with trees of the
 same length under --lockstep.  Meant to run under --lockstep with --pairs ''.
 
+--corr-cost (GLM(..., correlated=)) runs, per row DdxLEVELSxN of --corr-rows and chain count, two models on the data
+of --slope-cost: (1 + x | s) with a sampled correlation between intercept and slope (one pair, LKJ(2), one more coordinate), and the
+same model without `correlated`, which runs the kernels of a build without the feature on the same shape.  Fixed eps and trees of the
+same length under --lockstep: corr_over_uncorr is what the mix and its chain rule cost per gradient.  Meant to run under --lockstep
+with --pairs ''.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
@@ -615,6 +621,10 @@ def main():
     ap.add_argument("--slope-rows", default="20x100x1000,20x100x10000,20x450x10000,100x10x1000,20x200x1000", help="DdxLEVELSxN,... "
                     "(LEVELS per term: the model has 2 LEVELS level columns)")
     ap.add_argument("--slope-sides", default="slopes,expanded,plain", help="the sides of each row to run")
+    ap.add_argument("--corr-cost", action="store_true", help="per row of --corr-rows the model of --slope-cost with the two terms paired "
+                    "(a sampled correlation, LKJ(2)) and without (DESIGN section 22); use --lockstep, and --pairs '' to run nothing else")
+    ap.add_argument("--corr-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 21's rows 1 and 1')")
+    ap.add_argument("--corr-sides", default="corr,uncorr", help="the sides of each row to run")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -688,6 +698,32 @@ def main():
                 if "slopes" in seen and "plain" in seen:
                     row["plain_same_steps"] = row["slopes"]["steps"] == row["plain"]["steps"]
                     row["slopes_over_plain"] = row["slopes"]["leapfrog_steps_per_s"] / row["plain"]["leapfrog_steps_per_s"]
+                res["results"].append(row)
+    if a.corr_cost:
+        sides = a.corr_sides.split(",")
+        for spec in a.corr_rows.split(","):
+            Dd, N, n = (int(v) for v in spec.split("x"))
+            X, y, idx, x, kw, q0, cov = slope_problem(Dd, N, n, seed=Dd * 7919 + N * 31 + n)
+            valued = [(idx, N), pkg.glm.term(idx, values=x, levels=N)]
+            kwc = pkg.glm.correlated_effects(Dd, [N, N], [(0, 1)], eta=2.0)
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="corr_cost", Dd=Dd, levels=N, n=n, Dx=Dd + 2 * N, L=padded(Dd + 2 * N + 3), chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                for side in sides:
+                    if side == "corr":
+                        mdl, qs = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **kwc), np.r_[q0, 0.3]
+                    else:
+                        mdl, qs = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **kw), q0
+                    runs = [run("glm_" + side, X, y, qs, np.eye(qs.size) * 1e-4, C, a.transitions, metric=metric, mdl=mdl) for _ in range(a.repeats)]
+                    r = max((u[0] for u in runs), key=lambda u: u["leapfrog_steps_per_s"])
+                    r["repeats_leapfrog_steps_per_s"] = [u[0]["leapfrog_steps_per_s"] for u in runs]
+                    row[side] = r
+                    print("# Dd=%d levels=2x%d n=%d C=%d %s (form %d): %.4e leapfrog steps/s (%s), %.3f ms/transition, create %.2f s" %
+                          (Dd, N, n, C, side, r["glm_form"], r["leapfrog_steps_per_s"],
+                           " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
+                          file=sys.stderr, flush=True)
+                if "corr" in row and "uncorr" in row:
+                    row["same_steps"] = row["corr"]["steps"] == row["uncorr"]["steps"]
+                    row["corr_over_uncorr"] = row["corr"]["leapfrog_steps_per_s"] / row["uncorr"]["leapfrog_steps_per_s"]
                 res["results"].append(row)
     for shape in a.shapes.split(","):
         D, n = (int(v) for v in shape.split("x"))

@@ -1,18 +1,19 @@
-// jit_rehearsal_factors.hip -- tools/jit_rehearsal.hip for DESIGN section 20: the kernels hipRTC builds for a GLM with factor terms
-// (kFactors = true), compiled ahead of time so that they cross-compile for gfx950 without a device and tools/kres.py shows their
-// resource figures:
-//     tools/kres.py tools/jit_rehearsal_factors.hip k_ -Iinplacedhmc.jl_amd/csrc
-// Poisson (A = 0) without a group and with one, with the priors' table and local scales, and the Gaussian with a sampled scale
-// (A = 1, H = 1): the matrix-core form at NCH = 1 and NCH = 2, the per-wave form at NCH = 4 and NCH = 8.  Not part of the library.
+// jit_rehearsal_corr.hip -- tools/jit_rehearsal.hip for DESIGN section 22: the kernels hipRTC builds for a GLM with correlated pairs of
+// factor terms (kFactors = true, kSlopes = true, kCorr = true), compiled ahead of time so that they cross-compile for gfx950 without a
+// device and tools/kres.py shows their resource figures next to those of tools/jit_rehearsal_slopes.hip:
+//     tools/kres.py tools/jit_rehearsal_corr.hip k_ -Iinplacedhmc.jl_amd/csrc
+// The same policies as there -- Poisson (A = 0) without a group and with one, with the priors' table (the LKJ row) and local scales, and
+// the Gaussian with a sampled scale (A = 1, H = 1): the matrix-core form at NCH = 1 and NCH = 2, the per-wave form at NCH = 4 and
+// NCH = 8.  Not part of the library.
 #include "idhmc_nuts_kernel.hpp"
 #include "idhmc_optimum.hpp"
 #include "idhmc_glm.hpp"
 namespace idhmc {
 
 template <int GROUPS, bool PRIORS, bool LOCAL>
-struct PoissonFactorObs {
+struct PoissonCorrObs {
     static constexpr int K = 1, A = 0, H = GROUPS;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = LOCAL, kFactors = true, kSlopes = false, kCorr = false;
+    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = LOCAL, kFactors = true, kSlopes = true, kCorr = true;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -20,9 +21,9 @@ struct PoissonFactorObs {
         r = o.y[0] - e;
     }
 };
-struct GaussFactorObs {
+struct GaussCorrObs {
     static constexpr int K = 1, A = 1, H = 1;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = true, kSlopes = false, kCorr = false;
+    static constexpr bool kResponses = false, kPriors = true, kLocal = false, kFactors = true, kSlopes = true, kCorr = true;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);
@@ -44,12 +45,12 @@ struct GaussFactorObs {
     template __global__ void k_nuts<8, GlmWave<8 IDHMC_COMMA OBS>, true>(DevState, uint32_t, uint32_t);    \
     template __global__ void k_leapfrog<2, GlmWave<2 IDHMC_COMMA OBS>>(DevState, double, int, int);        \
     template __global__ void k_eval<1, GlmWave<1 IDHMC_COMMA OBS>>(DevState, int);
-using PoissonFactor = PoissonFactorObs<0, false, false>;
-using PoissonFactorGroup = PoissonFactorObs<1, false, false>;
-using PoissonFactorGroupPriorsLocal = PoissonFactorObs<2, true, true>;
-IDHMC_REHEARSE_OBS(PoissonFactor)
-IDHMC_REHEARSE_OBS(PoissonFactorGroup)
-IDHMC_REHEARSE_OBS(PoissonFactorGroupPriorsLocal)
-IDHMC_REHEARSE_OBS(GaussFactorObs)
+using PoissonCorr = PoissonCorrObs<0, false, false>;
+using PoissonCorrGroupLkj = PoissonCorrObs<2, true, false>;
+using PoissonCorrGroupLkjLocal = PoissonCorrObs<2, true, true>;
+IDHMC_REHEARSE_OBS(PoissonCorr)
+IDHMC_REHEARSE_OBS(PoissonCorrGroupLkj)
+IDHMC_REHEARSE_OBS(PoissonCorrGroupLkjLocal)
+IDHMC_REHEARSE_OBS(GaussCorrObs)
 
 }  // namespace idhmc
