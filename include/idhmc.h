@@ -431,6 +431,50 @@ int idhmc_create_glm_corr(idhmc_ctx **out, int device, int64_t nchains, int64_t 
                           int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
 /* *P, and with non-NULL arrays first, second and eta (P entries each) as the context was given them; 0 for every other context */
 int idhmc_glm_pairs_get(const idhmc_ctx *ctx, int32_t *P, int32_t *first, int32_t *second, double *eta);
+/* Structured factor terms: AR(1) and first-order random-walk effects across a term's levels -- a week, age-band or
+ * dose-step effect that is autocorrelated or smooth along its index.  A model with factor terms may name S structured terms, 0 <= S <= 2;
+ * structure i is (term[i], kind[i], eta[i]) with kind IDHMC_STRUCT_AR1 or IDHMC_STRUCT_RW1.  Level k of the term is position k of the
+ * sequence: the index order is the time order.  An AR(1) term adds one sampled coordinate zeta = atanh phi; a random walk adds none.
+ * With Sz the AR(1) terms, their zetas in list order behind the pairs':
+ *   q = [u (Dx) | a (A) | omega (H) | lambda (J) | zeta_pairs (P) | zeta_ar (Sz)],   D = Dx + A + H + J + P + Sz <= 1024.
+ * Per gradient and AR(1) term (phi, c) come from zeta by the expressions of the section above, the same bits in every lane:
+ *   s = dexp(-|zeta|);  t = s * s;  d = 1 + t;  phi = copysign((1 - t) / d, zeta);  c = (2 * s) / d;      a random walk has phi = c = 1.
+ * The process is the stationary unit-variance one, ut_0 = u_0, ut_k = phi ut_{k-1} + c u_k, and its ARITHMETIC is this Kogge-Stone scan,
+ * not the sequential recurrence -- the kernels and the tests' C restatement follow it bit for bit.  With o the term's first column and
+ * N its levels:
+ *   forward:  x_0 = u_o;  x_k = c * u_{o+k} (k >= 1);  p = phi;  h = 1;
+ *             while h < N: every k >= h takes x_k = dfma(p, x_{k-h}, x_k), all from the values before the stage; then p = p * p; h = 2 h;
+ *             ut_{o+k} = x_k, and ut = u on every other coordinate.
+ * Everything the sections above define runs on ut where it ran on u: the group scale of the term, z, (r, v, s), G, W_g, the scores.  A
+ * pair's mix and a term's scan touch disjoint columns.  After the chain rules above have left Gh_c = dl / dut_c:
+ *   backward: y_k = Gh_{o+k};  p = phi;  h = 1;
+ *             while h < N: every k with k + h < N takes y_k = dfma(p, y_{k+h}, y_k), from the values before the stage; p = p * p; h = 2 h;
+ *             lambda_k = y_k;   G_{u_o} = lambda_0;   G_{u_{o+k}} = c * lambda_k (k >= 1);
+ *   AR(1):    m_0 = +0;  m_k = lambda_k * (c * dfma(c, ut_{o+k-1}, -(phi * u_{o+k})))  (k >= 1; ut from the forward scan, run again);
+ *             M[(o+k) mod 128]: plain additions over chunks ascending, from +0;   G_zeta = the canonical 128-residue tree over M.
+ * zeta = +0 gives phi = +0, c = 1 and ut = u: the unstructured model's bits.  Past |zeta| of about 745 phi = +-1 and c = 0, every ut_k is
+ * u_0 (up to sign) and G_zeta = 0, all finite.  The prior of zeta follows a pair's rules: eta > 0 puts Beta(eta, eta) on (phi + 1) / 2
+ * with the Jacobian of tanh (the section above's T and g rows, the device's internal kind 5) and wants the defaults (0, 1, 0, 0) in zeta's
+ * entries of mu, tau, kind and nu; eta == 0 lets those entries apply, kinds 0 and 1; the log kinds are refused.  The prior of u is on u.
+ * Groups (a sampled scale on the term), local scales on other columns, priors, values on the structured term, several responses and pairs
+ * among other terms compose.  Out of scope: second-order walks (RW2), a sum-to-zero constraint, seasonal and spatial (ICAR) structures,
+ * AR(p).  A random walk's level is not identified against an intercept; its u_0 has the prior the prior arrays give it.
+ *
+ * idhmc_create_glm_struct is idhmc_create_glm_corr with these.  structs == NULL or S == 0 gives exactly the context of
+ * idhmc_create_glm_corr: the same kernels, bits and footprint.  No LDS is added.  Refused with IDHMC_ERR_BAD_ARG before the device is
+ * touched: S outside 0..2; term, kind or eta NULL with S > 0; a term index outside 0..F-1; a term listed twice; a kind other than 1 or 2;
+ * eta negative or not finite; eta != 0 on a random walk; a structured term with fewer than 2 levels; a structured term that is in a pair;
+ * a local-scale flag on a column of a structured term; structures without factors; D > 1024 counting Sz; eta > 0 with a non-default prior
+ * entry on that zeta; a log kind on a zeta; and everything idhmc_create_glm_corr refuses. */
+#define IDHMC_STRUCT_AR1 1
+#define IDHMC_STRUCT_RW1 2
+typedef struct { int32_t S; const int32_t *term, *kind; const double *eta; } idhmc_glm_structs;
+int idhmc_create_glm_struct(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                            const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                            const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                            const idhmc_glm_structs *structs, int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
+/* *S, and with non-NULL arrays term, kind and eta (S entries each) as the context was given them; 0 for every other context */
+int idhmc_glm_structs_get(const idhmc_ctx *ctx, int32_t *S, int32_t *term, int32_t *kind, double *eta);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

@@ -74,6 +74,9 @@ struct GlmParts {
     const double *peta = nullptr;      // [P]
     const int32_t *pkind_pub = nullptr;    // P > 0 with some eta > 0: kind and nu as the caller gave them (pkind / pnu then hold the
     const double *pnu_pub = nullptr;       // device table, which marks those zetas); null: pkind / pnu are the caller's
+    int32_t S = 0, SZ = 0;     // idhmc_create_glm_struct: structured terms, and those of them that are AR(1): the last SZ coordinates, behind
+    const int32_t *sterm = nullptr, *skind = nullptr;      // the pairs' zetas, are theirs; [S] term and kind, S > 0 (every entry checked)
+    const double *seta = nullptr;      // [S]
 };
 // the padded width of the stored columns of X: L of the model, and with factors Lx = 128 ceil(Dd / 128)
 static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
@@ -81,7 +84,7 @@ static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
     int64_t L = 128;
     while (L < D) L *= 2;
     if (L_out) *L_out = L;
-    return g.F > 0 ? ((int64_t)D - g.A - g.H - g.J - g.P - g.fcols + 127) / 128 * 128 : L;
+    return g.F > 0 ? ((int64_t)D - g.A - g.H - g.J - g.P - g.SZ - g.fcols + 127) / 128 * 128 : L;
 }
 // The head of a packed params array into *g: `head` = 0 (a logistic regression's [X | y]), 2 ([K, nc, c | X | Y]) or 3
 // ([K, nc, A, c | X | Y]) doubles in front of the constants.  The entries are checked as doubles (integral, hence finite, and in
@@ -157,7 +160,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
         }
     }
     const int64_t n = g.n, K = g.K, M = g.M;
-    const int64_t Dx = D - g.A - g.H - g.J - g.P - g.fcols;      // the columns of X (with factors: the dense ones)
+    const int64_t Dx = D - g.A - g.H - g.J - g.P - g.SZ - g.fcols;      // the columns of X (with factors: the dense ones)
     const int64_t L = stored_width(g, D);
     const int64_t npad = (n + 127) / 128 * 128;
     if (npad * L > ((int64_t)1 << 27))
@@ -198,7 +201,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
 static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
 {
     DevState &s = c->s;
-    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, Dm = s.D - g.A - g.H - g.J - g.P, K = g.K, M = g.M;    // Dm: the columns of the model
+    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, Dm = s.D - g.A - g.H - g.J - g.P - g.SZ, K = g.K, M = g.M;    // Dm: the columns of the model
     const int64_t D = Dm - g.fcols, LX = stored_width(g, s.D);      // the columns X stores (with factors: the dense ones) and their padded width
     // The level lists of a model with factors, before anything is uploaded: per block of 128 observations its places sorted by factor,
     // level, place (a counting sort), and where each level's list starts
@@ -294,7 +297,7 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
     if (g.J > 0) {
         // the partner of every coordinate: the k-th flagged column (ascending) and coordinate Dx + A + H + k name each other
         hp.assign((size_t)L, -1);
-        int64_t k = s.D - g.P - g.J;
+        int64_t k = s.D - g.SZ - g.P - g.J;
         for (int64_t col = 0; col < Dm; ++col)
             if (g.local[col]) { hp[(size_t)col] = (int32_t)k; hp[(size_t)k] = (int32_t)col; ++k; }
         int32_t *dp = nullptr;
@@ -360,6 +363,28 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         c->glm_pfirst.assign(g.pfirst, g.pfirst + g.P);
         c->glm_psecond.assign(g.psecond, g.psecond + g.P);
         c->glm_peta.assign(g.peta, g.peta + g.P);
+    }
+    std::vector<int32_t> hsp;
+    if (g.S > 0) {
+        // the level of every column of a structured term and its slot; the AR(1) slots' zetas are the last coordinates, in list order
+        hsp.assign((size_t)L, -1);
+        int z = 0;
+        for (int i = 0; i < g.S; ++i) {
+            const int32_t o = s.lr_foff[g.sterm[i]], N = g.levels[g.sterm[i]];
+            for (int32_t k = 0; k < N; ++k) hsp[(size_t)(o + k)] = k | (i << 10);
+            s.lr_sn[i] = N;
+            s.lr_skind[i] = g.skind[i];
+            s.lr_scz[i] = g.skind[i] == IDHMC_STRUCT_AR1 ? (int32_t)(s.D - g.SZ + z++) : -1;
+        }
+        int32_t *dsp = nullptr;
+        if (int rc = dalloc(c, &dsp, L)) return rc;
+        HIPCHK(hipMemcpyAsync(dsp, hsp.data(), sizeof(int32_t) * hsp.size(), hipMemcpyHostToDevice, c->stream));
+        s.lr_spart = dsp;
+        s.lr_s = g.S;
+        s.lr_sz = g.SZ;
+        c->glm_sterm.assign(g.sterm, g.sterm + g.S);
+        c->glm_skind.assign(g.skind, g.skind + g.S);
+        c->glm_seta.assign(g.seta, g.seta + g.S);
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
     s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
@@ -773,13 +798,75 @@ static int validate_pairs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
     return IDHMC_OK;
 }
 
+// The structures of idhmc_create_glm_struct, after validate_pairs: every check of S, term, kind and eta, of the terms against the pairs
+// and the local flags, and of the AR(1) zetas' entries in the prior arrays (coordinate cz0 onwards).  *S: the structured terms (0: the
+// context is the one of idhmc_create_glm_corr), *SZ: those that are AR(1)
+static int validate_structs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, const idhmc_glm_local *local, int J, int P,
+                            const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_pairs *pp, const idhmc_glm_structs *st, int *S, int *SZ)
+{
+    *S = *SZ = 0;
+    if (!st) return IDHMC_OK;
+    if (st->S < 0 || st->S > 2) return fail(IDHMC_ERR_BAD_ARG, "GLM: S = %d structured terms must be an integer in 0..2", st->S);
+    if (st->S == 0) return IDHMC_OK;
+    if (!st->term || !st->kind || !st->eta)
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: S = %d structured terms need term, kind and eta (%s is NULL)", st->S, !st->term ? "term" : !st->kind ? "kind" : "eta");
+    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: structured terms need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    int sz = 0;
+    for (int i = 0; i < st->S; ++i) sz += st->kind[i] == IDHMC_STRUCT_AR1;
+    if (glm->Dx + J + P + sz > 1024 - glm->A - glm->H)
+        return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + P + Sz = %lld: a GLM is limited to D <= 1024 (Sz = %d AR(1) terms)",
+                    (long long)glm->Dx + glm->A + glm->H + J + P + sz, sz);
+    const int cz0 = glm->Dx + glm->A + glm->H + J + P;
+    int z = 0;
+    for (int i = 0; i < st->S; ++i) {
+        const int32_t t = st->term[i], kd = st->kind[i];
+        if (t < 0 || t >= fc->F) return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: term = %d is outside 0..%d (the model's terms)", i, t, fc->F - 1);
+        if (i == 1 && st->term[0] == t) return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: term %d is listed twice", i, t);
+        if (kd != IDHMC_STRUCT_AR1 && kd != IDHMC_STRUCT_RW1)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: kind = %d must be IDHMC_STRUCT_AR1 (1) or IDHMC_STRUCT_RW1 (2)", i, kd);
+        const double eta = st->eta[i];
+        if (!(std::isfinite(eta) && eta >= 0.0))
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: eta = %g must be finite and >= 0 (0: the prior arrays' entry applies)", i, eta);
+        if (kd == IDHMC_STRUCT_RW1 && eta != 0.0)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: eta = %g on a random walk, which has no zeta (eta must be 0)", i, eta);
+        if (fc->levels[t] < 2)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: term %d has %d level (a structured term needs at least 2)", i, t, fc->levels[t]);
+        for (int p = 0; p < P; ++p)
+            if (pp->first[p] == t || pp->second[p] == t)
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: term %d is in pair %d (a term is structured or paired, not both)", i, t, p);
+        if (J > 0) {
+            int64_t o = glm->Dx - fcols;
+            for (int f = 0; f < t; ++f) o += fc->levels[f];
+            for (int32_t k = 0; k < fc->levels[t]; ++k)
+                if (local->local[o + k])
+                    return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: local[%lld] is set on level %d of term %d (a structured term takes no local scale)",
+                                i, (long long)(o + k), k, t);
+        }
+        if (kd != IDHMC_STRUCT_AR1) continue;
+        const int cz = cz0 + z++;
+        const int32_t k = pr && pr->kind ? pr->kind[cz] : 0;
+        if (k >= IDHMC_PRIOR_LOG_HALF_NORMAL && k <= IDHMC_PRIOR_LOG_EXPONENTIAL)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: prior kind[%d] = %d is a prior on exp(q): coordinate %d is zeta = atanh phi, not a logarithm "
+                        "(kinds 0 and 1 are for a zeta)", i, cz, k, cz);
+        if (eta > 0.0) {
+            const double nu = pr && pr->kind && pr->nu ? pr->nu[cz] : 0.0;
+            if (k != 0 || nu != 0.0 || (glm->mu && glm->mu[cz] != 0.0) || (glm->tau && glm->tau[cz] != 1.0))
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: eta = %g is the Beta(eta, eta) prior of zeta: the entry of coordinate %d in the prior arrays "
+                            "must be the default (kind 0, mu 0, tau 1, nu 0) and is not applied", i, eta, cz);
+        }
+    }
+    *S = st->S;
+    *SZ = sz;
+    return IDHMC_OK;
+}
+
 // idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors,
-// idhmc_create_glm_slopes and idhmc_create_glm_corr
+// idhmc_create_glm_slopes, idhmc_create_glm_corr and idhmc_create_glm_struct
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
                       const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
                       const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr,
-                      const idhmc_glm_pairs *pairs = nullptr)
+                      const idhmc_glm_pairs *pairs = nullptr, const idhmc_glm_structs *structs = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
@@ -801,6 +888,8 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
                     (long long)glm->Dx + glm->A + glm->H + J + pairs->P, pairs->P);
     int P = 0;
     if (int rc = validate_pairs(glm, priors, J, factors, fcols, pairs, &P)) return rc;
+    int S = 0, SZ = 0;
+    if (int rc = validate_structs(glm, priors, local, J, P, factors, fcols, pairs, structs, &S, &SZ)) return rc;
     if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
     if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
     if (glm->H > 0) {
@@ -816,13 +905,13 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     idhmc_model_desc m;
     memset(&m, 0, sizeof m);
     m.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM;
-    m.D = glm->Dx + glm->A + glm->H + J + P;
+    m.D = glm->Dx + glm->A + glm->H + J + P + SZ;
     m.mu = glm->mu;
     m.tau = glm->tau;
     m.source = glm->source;
     std::vector<double> nu;
     bool any = false;
-    if (int rc = validate_priors(glm, priors, J + P, &nu, &any)) return rc;
+    if (int rc = validate_priors(glm, priors, J + P + SZ, &nu, &any)) return rc;
     GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
     if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
     if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
@@ -830,10 +919,12 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (valued) { parts.fvalues = values->values; parts.fhas = values->has; }
     std::vector<int32_t> kdev, kpub;     // a zeta with eta > 0: the device table marks it (kPriorLkj of idhmc_glm.hpp, eta in nu's place)
     std::vector<double> nudev, nupub;
-    if (P > 0) {
-        parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta;
+    if (P > 0) { parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta; }
+    if (S > 0) { parts.S = S; parts.SZ = SZ; parts.sterm = structs->term; parts.skind = structs->kind; parts.seta = structs->eta; }
+    if (P > 0 || SZ > 0) {
         bool lkj = false;
         for (int p = 0; p < P; ++p) lkj = lkj || pairs->eta[p] > 0.0;
+        for (int i = 0; i < S; ++i) lkj = lkj || structs->eta[i] > 0.0;
         if (lkj) {
             kpub.assign((size_t)m.D, 0);
             nupub.assign((size_t)m.D, 0.0);
@@ -841,7 +932,12 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
             kdev = kpub;
             nudev = nupub;
             for (int p = 0; p < P; ++p)
-                if (pairs->eta[p] > 0.0) { kdev[(size_t)(m.D - P + p)] = 5; nudev[(size_t)(m.D - P + p)] = pairs->eta[p]; }
+                if (pairs->eta[p] > 0.0) { kdev[(size_t)(m.D - SZ - P + p)] = 5; nudev[(size_t)(m.D - SZ - P + p)] = pairs->eta[p]; }
+            for (int i = 0, z = 0; i < S; ++i) {
+                if (structs->kind[i] != IDHMC_STRUCT_AR1) continue;
+                if (structs->eta[i] > 0.0) { kdev[(size_t)(m.D - SZ + z)] = 5; nudev[(size_t)(m.D - SZ + z)] = structs->eta[i]; }
+                ++z;
+            }
             parts.pkind = kdev.data(); parts.pnu = nudev.data();
             parts.pkind_pub = kpub.data(); parts.pnu_pub = nupub.data();
         }
@@ -913,6 +1009,27 @@ int idhmc_create_glm_corr(idhmc_ctx **out, int device, int64_t nchains, int64_t 
     return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values, pairs);
 }
 
+int idhmc_create_glm_struct(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                            const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                            const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                            const idhmc_glm_structs *structs, int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_struct: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
+                      pairs, structs);
+}
+
+int idhmc_glm_structs_get(const idhmc_ctx *c, int32_t *S, int32_t *term, int32_t *kind, double *eta)
+{
+    if (!c || !S) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_structs_get: null argument");
+    *S = c->s.lr_s;
+    if (term) std::copy(c->glm_sterm.begin(), c->glm_sterm.end(), term);
+    if (kind) std::copy(c->glm_skind.begin(), c->glm_skind.end(), kind);
+    if (eta) std::copy(c->glm_seta.begin(), c->glm_seta.end(), eta);
+    return IDHMC_OK;
+}
+
 int idhmc_glm_pairs_get(const idhmc_ctx *c, int32_t *P, int32_t *first, int32_t *second, double *eta)
 {
     if (!c || !P) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_pairs_get: null argument");
@@ -943,7 +1060,7 @@ int idhmc_glm_factors_get(const idhmc_ctx *c, int32_t *F, int32_t *levels, int32
 int idhmc_glm_local_get(const idhmc_ctx *c, int32_t *local, double *slab_scale)
 {
     if (!c || !local || !slab_scale) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_local_get: null argument");
-    const int Dx = c->s.D - c->s.lr_a - c->s.lr_h - c->s.lr_j - c->s.lr_cp;
+    const int Dx = c->s.D - c->s.lr_a - c->s.lr_h - c->s.lr_j - c->s.lr_cp - c->s.lr_sz;
     for (int k = 0; k < Dx; ++k) local[k] = c->glm_local.empty() ? 0 : c->glm_local[(size_t)k];
     *slab_scale = c->slab_scale;
     return IDHMC_OK;

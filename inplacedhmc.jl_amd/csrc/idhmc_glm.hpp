@@ -175,6 +175,27 @@
 // requester's Q row -- q, ut from it, then b in its place before barrier A; after barrier C the G row is taken into registers, rho, c
 // and ut are computed again from q (as glm_local_chain computes st again), the chain rules of the scales run on ut, and then q and Gh
 // go through the row for m_k and G_c1.  No LDS, tile or barrier is added; nothing of the pairs is alive across multiply().
+//
+// Structured terms (idhmc_create_glm_struct): Obs::kStruct, a compile-time flag of the policy next to kCorr (false
+// for every policy above and for every model without a structure: none of their instructions changes).  S structured factor terms,
+// 0 <= S <= 2 (slots 0 and 1); the levels of a structured term, in index order, are an AR(1) sequence with a sampled phi = tanh(zeta),
+// or a first-order random walk (phi = c = 1, no coordinate).  The zetas of the AR(1) terms are the last Sz coordinates, behind the pairs':
+//   q = [u (Dx) | a (A) | omega (H) | lambda (J) | zeta_pairs (P) | zeta_ar (Sz)],   D = Dx + A + H + J + P + Sz <= 1024.
+//   (phi, c) of a slot: glm_corr_factors of its zeta, read from the owner lane, the same bits in every lane.
+//   forward, o the term's first column, N its levels: x_0 = u_o, x_k = c u_{o+k}; p = phi, h = 1; while h < N: every k >= h takes
+//     x_k = dfma(p, x_{k-h}, x_k) from the values before the stage, then p = p p, h = 2 h; ut_{o+k} = x_k, ut = u elsewhere -- the
+//     Kogge-Stone form of ut_0 = u_0, ut_k = phi ut_{k-1} + c u_k, and the definition of the bits (not the sequential recurrence).
+//   Everything above runs on ut where it ran on u.  A pair's mix and a term's scan touch disjoint columns (a term is in a pair or
+//   structured, never both; a structured column has no local scale), so the scan runs on the mixed vector in place.
+//   backward, after the chain rules above have left Gh_c = dl / dut_c: y_k = Gh_{o+k}; p = phi, h = 1; while h < N: every k with
+//     k + h < N takes y_k = dfma(p, y_{k+h}, y_k), then p = p p, h = 2 h; lambda_k = y_k; G_{u_o} = lambda_0, G_{u_{o+k}} = c lambda_k;
+//     AR(1): m_k = lambda_k (c dfma(c, ut_{o+k-1}, -(phi u_{o+k}))), k >= 1; M[(o+k) mod 128] plain additions over chunks ascending
+//     from +0; G_zeta = the canonical tree over M (wave_sum), placed like a group's.  The prior of zeta is a pair's (kPriorLkj).
+// DevState::lr_spart holds, per coordinate, -1 or  k | slot << 10  for level k of a structured term; lr_s = S, lr_sz = Sz, lr_sn the
+// slots' levels, lr_skind their kinds, lr_scz their zeta coordinates (-1: a random walk).  Values stay in registers; the exchange
+// between lanes is the wavefront-private LDS vector both forms already have (GlmWave: buf; GlmCoop: the requester's Q row, at the places
+// the mix and its chain run), written and read by one wavefront in program order.  The two slots share the stage loop (a slot with
+// N <= h has no level left to update).  No LDS, tile or barrier is added; nothing of the structures is alive across multiply().
 #pragma once
 #include "idhmc_device.hpp"
 
@@ -515,6 +536,122 @@ IDHMC_DEV const T &glm_pick(const T &a, const T &b)
     else return b;
 }
 
+// Structured terms (Obs::kStruct).  An entry of the level table: -1, or k | slot << 10 for level k of the term in slot 0 or 1
+constexpr int kStructSlot = 1024, kStructMask = 1023;
+// what both forms take from DevState: the slots' levels (n1 = 0 with one slot) and zeta coordinates (-1: a random walk, phi = c = 1)
+struct GlmStruct {
+    const int32_t *spart;
+    int n0, n1, cz0, cz1;
+    template <class State>
+    IDHMC_DEV void init(const State &s)
+    {
+        spart = s.lr_spart;
+        n0 = s.lr_sn[0];
+        n1 = s.lr_s > 1 ? s.lr_sn[1] : 0;
+        cz0 = s.lr_scz[0];
+        cz1 = s.lr_s > 1 ? s.lr_scz[1] : -1;
+    }
+};
+// (phi, c) of the slots: glm_corr_factors of the slot's zeta, the constants (1, 1) for a random walk and for a slot that is not there
+template <int NCH>
+IDHMC_DEV void glm_struct_factors(const Vec<NCH> &q, const GlmStruct &st, double &f0, double &c0, double &f1, double &c1)
+{
+    f0 = c0 = f1 = c1 = 1.0;
+    if (st.cz0 >= 0) glm_corr_factors<NCH>(q, st.cz0, f0, c0);
+    if (st.cz1 >= 0) glm_corr_factors<NCH>(q, st.cz1, f1, c1);
+}
+// The forward scan, in place on ut (u in the structured columns on entry, whatever the caller has elsewhere): x_0 = u_o, x_k = c u_{o+k},
+// then per stage h = 1, 2, 4, .. < N every k >= h takes dfma(p, x_{k-h}, x_k) from the values before the stage, p = phi^h by squaring.
+// Values stay in registers; vec, the wavefront's own LDS vector (>= 128 NCH doubles, indexed by coordinate), is the exchange, written
+// and read by this wavefront alone in program order.  Both slots share the stage loop: a slot with N <= h has no k >= h left.
+template <int NCH>
+IDHMC_DEV void glm_struct_scan(Vec<NCH> &ut, const GlmStruct &st, double *vec, int lane, double f0, double c0, double f1, double c1)
+{
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(st.spart) + lane;
+    int2 e[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        e[j] = part2[j * 64];
+        const bool mx = e[j].x >= 0 && (e[j].x & kStructMask) >= 1, my = e[j].y >= 0 && (e[j].y & kStructMask) >= 1;
+        ut.c[j].x = mx ? ((e[j].x & kStructSlot) ? c1 : c0) * ut.c[j].x : ut.c[j].x;
+        ut.c[j].y = my ? ((e[j].y & kStructSlot) ? c1 : c0) * ut.c[j].y : ut.c[j].y;
+    }
+    const int nm = st.n0 > st.n1 ? st.n0 : st.n1;
+    double p0 = f0, p1 = f1;
+    for (int h = 1; h < nm; h <<= 1) {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) v2[j * 64] = ut.c[j];
+        asm volatile("" ::: "memory");                        // (the stage's reads stay behind its writes, and ahead of the next stage's)
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c = 128 * j + 2 * lane;
+            const bool ax = e[j].x >= 0 && (e[j].x & kStructMask) >= h, ay = e[j].y >= 0 && (e[j].y & kStructMask) >= h;
+            const double nx = vec[ax ? c - h : 0], ny = vec[ay ? c + 1 - h : 0];
+            ut.c[j].x = ax ? dfma((e[j].x & kStructSlot) ? p1 : p0, nx, ut.c[j].x) : ut.c[j].x;
+            ut.c[j].y = ay ? dfma((e[j].y & kStructSlot) ? p1 : p0, ny, ut.c[j].y) : ut.c[j].y;
+        }
+        asm volatile("" ::: "memory");
+        p0 = p0 * p0;
+        p1 = p1 * p1;
+    }
+}
+// The chain rule of the scan on the lane's G (Gh = dl / dut in the structured columns, complete elsewhere but for their zetas): the
+// mirror-image scan y_k <- dfma(p, y_{k+h}, y_k) for k + h < N gives lambda; m_k = lambda_k (c dfma(c, ut_{k-1}, -(phi u_k))), k >= 1,
+// into M_slot and by the tree into the slot's zeta; G_{u_o} = lambda_0, G_{u_{o+k}} = c lambda_k.  ut: the forward scan's result.
+template <int NCH>
+IDHMC_DEV void glm_struct_chain(Vec<NCH> &G, const Vec<NCH> &q, const Vec<NCH> &ut, const GlmStruct &st, double *vec, int lane,
+                                double f0, double c0, double f1, double c1)
+{
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(st.spart) + lane;
+    int2 e[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) e[j] = part2[j * 64];
+    const int nm = st.n0 > st.n1 ? st.n0 : st.n1;
+    double p0 = f0, p1 = f1;
+    for (int h = 1; h < nm; h <<= 1) {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) v2[j * 64] = G.c[j];
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            const int c = 128 * j + 2 * lane;
+            const bool ax = e[j].x >= 0 && (e[j].x & kStructMask) + h < ((e[j].x & kStructSlot) ? st.n1 : st.n0);
+            const bool ay = e[j].y >= 0 && (e[j].y & kStructMask) + h < ((e[j].y & kStructSlot) ? st.n1 : st.n0);
+            const double nx = vec[ax ? c + h : 0], ny = vec[ay ? c + 1 + h : 0];
+            G.c[j].x = ax ? dfma((e[j].x & kStructSlot) ? p1 : p0, nx, G.c[j].x) : G.c[j].x;
+            G.c[j].y = ay ? dfma((e[j].y & kStructSlot) ? p1 : p0, ny, G.c[j].y) : G.c[j].y;
+        }
+        asm volatile("" ::: "memory");
+        p0 = p0 * p0;
+        p1 = p1 * p1;
+    }
+    // ut goes through the vector: level k reads ut of level k - 1
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = ut.c[j];
+    asm volatile("" ::: "memory");
+    double2 M0 = make_double2(0.0, 0.0), M1 = M0;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = 128 * j + 2 * lane;
+        const bool ax = e[j].x >= 0 && (e[j].x & kStructMask) >= 1, ay = e[j].y >= 0 && (e[j].y & kStructMask) >= 1;
+        const bool sx = (e[j].x & kStructSlot) != 0, sy = (e[j].y & kStructSlot) != 0;
+        const double ux = vec[ax ? c - 1 : 0], uy = vec[ay ? c : 0];
+        const double fx = sx ? f1 : f0, cx = sx ? c1 : c0, fy = sy ? f1 : f0, cy = sy ? c1 : c0;
+        const double mx = G.c[j].x * (cx * dfma(cx, ux, -(fx * q.c[j].x))), my = G.c[j].y * (cy * dfma(cy, uy, -(fy * q.c[j].y)));
+        M0.x = M0.x + (ax && !sx ? mx : 0.0);
+        M0.y = M0.y + (ay && !sy ? my : 0.0);
+        M1.x = M1.x + (ax && sx ? mx : 0.0);
+        M1.y = M1.y + (ay && sy ? my : 0.0);
+        G.c[j].x = ax ? cx * G.c[j].x : G.c[j].x;
+        G.c[j].y = ay ? cy * G.c[j].y : G.c[j].y;
+    }
+    asm volatile("" ::: "memory");
+    if (st.cz0 >= 0) glm_group_place<NCH>(G, M0, st.cz0, lane);
+    if (st.cz1 >= 0) glm_group_place<NCH>(G, M1, st.cz1, lane);
+}
+
 // Factor terms (Obs::kFactors): what both forms take from DevState
 struct GlmFactors {
     const int32_t *idx, *start;      // lr_fidx [F][n_pad], lr_fstart [n_pad / 128][cols + 1]
@@ -600,7 +737,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -628,6 +765,7 @@ struct GlmWave {
     GlmSlopes slo;           // their values (Obs::kSlopes)
     const int32_t *cpart;    // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;            // the coordinate of zeta_0 and the pairs (Obs::kCorr)
+    GlmStruct stc;           // the structured terms (Obs::kStruct)
     double *buf;             // this wavefront's LDS vector, L doubles
     int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -659,6 +797,11 @@ struct GlmWave {
             cz0 = s.D - s.lr_cp;
             D -= s.lr_cp;
         }
+        if constexpr (Obs::kStruct) {
+            stc.init(s);
+            D -= s.lr_sz;
+            if constexpr (Obs::kCorr) cz0 -= s.lr_sz;          // (the pairs' zetas come first)
+        }
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -689,7 +832,13 @@ struct GlmWave {
             glm_corr_pairs<NCH>(q, cz0, ncp, cr0, cc0, cr1, cc1);
             glm_corr_mix<NCH>(qm, q, cpart, buf, lane, cr0, cc0, cr1, cc1);
         }
-        const Vec<NCH> &u = glm_pick<Obs::kCorr>(qm, q);       // what the scales and the products run on
+        double sf0 = 1.0, sc0 = 1.0, sf1 = 1.0, sc1 = 1.0;     // Obs::kStruct: phi and c of the slots; the scan runs on qm, after the mix
+        if constexpr (Obs::kStruct) {                          // (disjoint columns)
+            if constexpr (!Obs::kCorr) qm = q;
+            glm_struct_factors<NCH>(q, stc, sf0, sc0, sf1, sc1);
+            glm_struct_scan<NCH>(qm, stc, buf, lane, sf0, sc0, sf1, sc1);
+        }
+        const Vec<NCH> &u = glm_pick<Obs::kCorr || Obs::kStruct>(qm, q);       // what the scales and the products run on
         Vec<NCH> bq;                                           // Obs::kLocal: b, once per gradient
         if constexpr (Obs::kLocal) glm_local_b<NCH, Obs::H>(bq, u, grp2, part, buf, D, lane, e0, e1, e2, e3, inv2);
         double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;
@@ -821,9 +970,14 @@ struct GlmWave {
         }
         // (with local scales b was held across the blocks, not ut: it is mixed again from q)
         if constexpr (Obs::kCorr && Obs::kLocal) glm_corr_mix<NCH>(qm, q, cpart, buf, lane, cr0, cc0, cr1, cc1);
+        if constexpr (Obs::kStruct && Obs::kLocal) {
+            if constexpr (!Obs::kCorr) qm = q;
+            glm_struct_scan<NCH>(qm, stc, buf, lane, sf0, sc0, sf1, sc1);
+        }
         if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(G, u, grp2, part, buf, D, D + Obs::A, lane, e0, e1, e2, e3, inv2);
         else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, u, grp2, D + Obs::A, lane, e0, e1, e2, e3);
         if constexpr (Obs::kCorr) glm_corr_chain<NCH>(G, q, cpart, buf, cz0, ncp, lane, cr0, cc0, cr1, cc1);
+        if constexpr (Obs::kStruct) glm_struct_chain<NCH>(G, q, u, stc, buf, lane, sf0, sc0, sf1, sc1);
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
@@ -832,8 +986,8 @@ struct GlmWave {
             if constexpr (Obs::kPriors) {
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];
-                g.c[j].x = glm_prior_of<Obs::kCorr>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
-                g.c[j].y = glm_prior_of<Obs::kCorr>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
+                g.c[j].x = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
+                g.c[j].y = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
             } else {
                 t0 = dfma(t.x * dx, dx, t0);
                 t1 = dfma(t.y * dy, dy, t1);
@@ -893,6 +1047,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     GlmSlopes slo;               // their values (Obs::kSlopes)
     const int32_t *cpart;        // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;                // the coordinate of zeta_0 and the pairs (Obs::kCorr)
+    GlmStruct stc;               // the structured terms (Obs::kStruct)
     double *tile;
     int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -916,6 +1071,11 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             ncp = s.lr_cp;
             cz0 = s.D - s.lr_cp;
             dx -= s.lr_cp;
+        }
+        if constexpr (Obs::kStruct) {
+            stc.init(s);
+            dx -= s.lr_sz;
+            if constexpr (Obs::kCorr) cz0 -= s.lr_sz;          // (the pairs' zetas come first)
         }
         x = s.lr_x;
         xt = s.lr_xt;
@@ -1122,7 +1282,13 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             glm_corr_pairs<NCH>(q, cz0, ncp, cr0, cc0, cr1, cc1);
             glm_corr_mix<NCH>(qm, q, cpart, tile + kQ + wv * DS, lane, cr0, cc0, cr1, cc1);
         }
-        const Vec<NCH> &u = glm_pick<Obs::kCorr>(qm, q);      // what the scales and the products run on
+        double sf0 = 1.0, sc0 = 1.0, sf1 = 1.0, sc1 = 1.0;    // Obs::kStruct: phi and c of the slots; the scan runs on qm through the row
+        if constexpr (Obs::kStruct) {
+            if constexpr (!Obs::kCorr) qm = q;
+            glm_struct_factors<NCH>(q, stc, sf0, sc0, sf1, sc1);
+            glm_struct_scan<NCH>(qm, stc, tile + kQ + wv * DS, lane, sf0, sc0, sf1, sc1);
+        }
+        const Vec<NCH> &u = glm_pick<Obs::kCorr || Obs::kStruct>(qm, q);      // what the scales and the products run on
         if constexpr (Obs::kLocal) {
             // q goes through the row first (each column reads its lambda there), then b takes its place, +0 in every column >= dx
             if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, dx + Obs::A, e0, e1, e2, e3);
@@ -1142,7 +1308,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 const int2 id = grp2[j * 64];
                 row[j * 64] = make_double2(c0 >= dx ? 0.0 : glm_scaled<HN>(u.c[j].x, id.x, e0, e1, e2, e3), c0 + 1 >= dx ? 0.0 : glm_scaled<HN>(u.c[j].y, id.y, e0, e1, e2, e3));
             }
-        } else if constexpr (Obs::A > 0 || Obs::kCorr) {
+        } else if constexpr (Obs::A > 0 || Obs::kCorr || Obs::kStruct) {
             // (the zetas are coordinates behind the columns like the auxiliary ones: +0 in the row)
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
@@ -1172,7 +1338,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             }
         }
         Vec<NCH> Gh;                                          // with groups, local scales or pairs: the whole G row, for the chain rule
-        if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr) {
+        if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct) {
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 Gh.c[j] = row[j * 64];
@@ -1193,17 +1359,27 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 glm_corr_pairs<NCH>(q, cz, ncp, cr0, cc0, cr1, cc1);
                 glm_corr_mix<NCH>(qm, q, cpart, tile + kQ + wv * DS, lane, cr0, cc0, cr1, cc1);
             }
+            // (structured terms: phi, c and the forward scan again from q, through the row, as the pairs above)
+            GlmStruct st2;
+            if constexpr (Obs::kStruct) {
+                st2 = stc;
+                asm volatile("" : "+s"(st2.cz0), "+s"(st2.cz1));
+                if constexpr (!Obs::kCorr) qm = q;
+                glm_struct_factors<NCH>(q, st2, sf0, sc0, sf1, sc1);
+                glm_struct_scan<NCH>(qm, st2, tile + kQ + wv * DS, lane, sf0, sc0, sf1, sc1);
+            }
             // (local scales: the G row is in registers now, so q and then wl go through the row, which is the requester's own until barrier A)
             if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(Gh, u, grp2, part, tile + kQ + wv * DS, dx, c0, lane, e0, e1, e2, e3, inv2);
             else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(Gh, u, grp2, c0, lane, e0, e1, e2, e3);
             if constexpr (Obs::kCorr) glm_corr_chain<NCH>(Gh, q, cpart, tile + kQ + wv * DS, cz, ncp, lane, cr0, cc0, cr1, cc1);
+            if constexpr (Obs::kStruct) glm_struct_chain<NCH>(Gh, q, u, st2, tile + kQ + wv * DS, lane, sf0, sc0, sf1, sc1);
         }
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
             double2 G;
-            if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr) {
+            if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct) {
                 G = Gh.c[j];
             } else {
                 G = row[j * 64];
@@ -1217,8 +1393,8 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 // kinds and nu are read here, after barrier C: nothing of the prior is alive across multiply()
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];
-                g.c[j].x = glm_prior_of<Obs::kCorr>(k.x, nu.x, t.x, dx, G.x, t0);
-                g.c[j].y = glm_prior_of<Obs::kCorr>(k.y, nu.y, t.y, dy, G.y, t1);
+                g.c[j].x = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.x, t0);
+                g.c[j].y = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.y, t1);
             } else {
                 t0 = dfma(t.x * dx, dx, t0);
                 t1 = dfma(t.y * dy, dy, t1);

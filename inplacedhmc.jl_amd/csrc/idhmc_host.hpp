@@ -75,6 +75,8 @@ struct idhmc_ctx {
     std::vector<double> glm_fvalues;
     std::vector<int32_t> glm_pfirst, glm_psecond;   // idhmc_create_glm_corr with P > 0: the pairs' terms and eta as given (empty otherwise)
     std::vector<double> glm_peta;
+    std::vector<int32_t> glm_sterm, glm_skind;      // idhmc_create_glm_struct with S > 0: the structured terms, their kinds and eta as given
+    std::vector<double> glm_seta;
     // IDHMC_EPS_PER_RESPONSE / IDHMC_METRIC_PER_RESPONSE: the context holds resp_n = C / glm_r whole responses (0 in every other mode)
     int64_t resp_n = 0;
     double *resp_da = nullptr;     // [resp_n][6] dual-averaging states of IDHMC_EPS_PER_RESPONSE: mu, m, Hbar, logeps, logeps_bar, eps

@@ -111,6 +111,14 @@ struct DevState {
     // the zetas.  Appended again, and not lr_lpart: no kernel of a model without pairs changes (profiles/r19_glm_corr_kres_*.txt).
     const int32_t *lr_cpart;  // [L] -1, or for a paired column: partner | pair << 10 | (second of its pair ? 2048 : 0)
     int32_t lr_cp;            // pairs, 0..2
+    // structured factor terms (idhmc_create_glm_struct; null and 0 without one): the last lr_sz coordinates, behind the
+    // pairs' zetas, are the zetas of the AR(1) terms.  Appended again: no kernel of a model without a structure changes
+    // (profiles/r20_glm_struct_kres_*.txt).
+    const int32_t *lr_spart;  // [L] -1, or for a column of a structured term: k | slot << 10, k its level
+    int32_t lr_s, lr_sz;      // structured terms (slots), 0..2, and those of them that are AR(1)
+    int32_t lr_sn[2];         // the levels of slot i
+    int32_t lr_skind[2];      // IDHMC_STRUCT_AR1 or IDHMC_STRUCT_RW1
+    int32_t lr_scz[2];        // the coordinate of the slot's zeta (AR(1)), -1 for a random walk
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -161,7 +169,7 @@ struct JitModule;
 // fills `log` (compiler output, truncated)
 // K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors),
 // s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors), s.lr_fval one whose terms read a value (kSlopes),
-// s.lr_cp > 0 one with correlated pairs (kCorr)
+// s.lr_cp > 0 one with correlated pairs (kCorr), s.lr_s > 0 one with structured terms (kStruct)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

@@ -143,11 +143,97 @@ __global__ void k_summary_corr_theta(const double *stage, double *theta, int64_t
     theta[i] = x;
 }
 
+// A GLM with structured terms: theta = [beta | a raw | sigma | exp(lambda) | rho | phi], beta taken from ut.  The scan
+// needs a row's neighbours, so a wavefront owns a row: it stages x (u, c u in the levels k >= 1 of a structured term) in its own LDS
+// vector and runs the forward stages of glm_struct_scan between two vectors, lane by lane over the coordinates; then each coordinate
+// takes the pair's mix (P > 0), the scales and the transforms as k_summary_corr_theta does.  Every wavefront of the workgroup runs the
+// same stages (nm is the model's), so the barriers between them are uniform; a wavefront past the last row works on row 0 and writes
+// nothing.  The reduction then runs on theta as on raw draws (MODE 3).
+constexpr int kStructThetaWaves = 2;
+__global__ void __launch_bounds__(64 * kStructThetaWaves)
+k_summary_struct_theta(const double *stage, double *theta, int64_t rows, int32_t D, int32_t Dx, int32_t A, int32_t H, int32_t J, int32_t P,
+                       int32_t Sz, const int32_t *grp, const int32_t *lpart, const int32_t *cpart, const int32_t *spart, int32_t n0, int32_t n1,
+                       int32_t cz0, int32_t cz1, double inv2)
+{
+    __shared__ double vecs[kStructThetaWaves][2][1024];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kStructThetaWaves + w;
+    const bool live = r0 < rows;
+    const double *q = stage + (live ? r0 : 0) * D;
+    double f0 = 1.0, c0 = 1.0, f1 = 1.0, c1 = 1.0;
+    if (cz0 >= 0) {
+        const double z = q[cz0], s = dexp(-__builtin_fabs(z)), t = s * s, d = 1.0 + t;
+        f0 = __builtin_copysign((1.0 - t) / d, z);
+        c0 = (2.0 * s) / d;
+    }
+    if (cz1 >= 0) {
+        const double z = q[cz1], s = dexp(-__builtin_fabs(z)), t = s * s, d = 1.0 + t;
+        f1 = __builtin_copysign((1.0 - t) / d, z);
+        c1 = (2.0 * s) / d;
+    }
+    double *va = vecs[w][0], *vb = vecs[w][1];
+    for (int c = lane; c < Dx; c += 64) {
+        const int32_t e = spart[c];
+        va[c] = e >= 0 && (e & 1023) >= 1 ? ((e & 1024) ? c1 : c0) * q[c] : q[c];
+    }
+    __syncthreads();
+    const int nm = n0 > n1 ? n0 : n1;
+    double p0 = f0, p1 = f1;
+    for (int h = 1; h < nm; h <<= 1) {
+        for (int c = lane; c < Dx; c += 64) {
+            const int32_t e = spart[c];
+            const bool act = e >= 0 && (e & 1023) >= h;
+            vb[c] = act ? dfma((e & 1024) ? p1 : p0, va[c - h], va[c]) : va[c];
+        }
+        __syncthreads();
+        double *tmp = va; va = vb; vb = tmp;
+        p0 = p0 * p0;
+        p1 = p1 * p1;
+    }
+    if (!live) return;
+    for (int d = lane; d < D; d += 64) {
+        double x = q[d];
+        if (d >= D - P - Sz) {
+            const double s = dexp(-__builtin_fabs(x));
+            const double t = s * s;
+            x = __builtin_copysign((1.0 - t) / (1.0 + t), x);
+        } else if (d >= Dx + A) {
+            x = dexp(x);
+        } else if (d < Dx) {
+            x = va[d];
+            const int32_t p = P > 0 ? cpart[d] : -1;
+            if (p >= 0 && (p & 2048)) {
+                const double z = q[D - Sz - P + ((p >> 10) & 1)];
+                const double s = dexp(-__builtin_fabs(z));
+                const double t = s * s, dd = 1.0 + t;
+                const double rho = __builtin_copysign((1.0 - t) / dd, z), c = (2.0 * s) / dd;
+                x = dfma(rho, q[p & 1023], c * x);
+            }
+            const int32_t id = H > 0 ? grp[d] : -1;
+            const int32_t lp = J > 0 ? lpart[d] : -1;
+            if (lp >= 0) {
+                const double f = dexp(q[lp]);
+                const double s = id >= 0 ? dexp(q[Dx + A + id]) * f : f;
+                double st = s;
+                if (inv2 != 0.0) {
+                    const double iv = 1.0 / s;
+                    const double nn = dfma(iv, iv, inv2);
+                    st = 1.0 / __builtin_sqrt(nn);
+                }
+                x = x * st;
+            } else if (id >= 0) {
+                x = x * dexp(q[Dx + A + id]);
+            }
+        }
+        theta[r0 * D + d] = x;
+    }
+}
+
 // The reduction.  Lane i owns (segment, d) = (i / D, i % D): consecutive lanes take consecutive d, so a wavefront reads contiguous
 // runs of a row.  The lane visits its segment's chains transition by transition, ascending chain id inside, with its state in
 // registers; HIST: it counts its values' bins in its own LDS row and the workgroup adds the rows to the table at the end.
-// MODE: 0 theta = q; 1 coefficient groups; 2 local scales (with or without groups); 3, correlated pairs, is MODE 0 on the theta that
-// k_summary_corr_theta wrote
+// MODE: 0 theta = q; 1 coefficient groups; 2 local scales (with or without groups); 3, correlated pairs and structured terms, is MODE 0
+// on the theta that k_summary_corr_theta or k_summary_struct_theta wrote
 template <bool HIST, int MODE>
 IDHMC_DEV void summary_body(const SumArgs &a, uint16_t *lds_cnt)
 {
@@ -363,9 +449,9 @@ static hipError_t launch_summary(const SumArgs &a, hipStream_t st)
 }  // namespace idhmc
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && (c->s.lr_h > 0 || c->s.lr_j > 0 || c->s.lr_cp > 0); }
-// doubles per row of Summary::scales: e_g, and with local scales f_k and st_k; with correlated pairs the whole theta
-static int64_t scales_width(const idhmc_ctx *c) { return c->s.lr_cp > 0 ? (int64_t)c->s.D : c->s.lr_h + 2 * (int64_t)c->s.lr_j; }
+static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && (c->s.lr_h > 0 || c->s.lr_j > 0 || c->s.lr_cp > 0 || c->s.lr_s > 0); }
+// doubles per row of Summary::scales: e_g, and with local scales f_k and st_k; with correlated pairs or structured terms the whole theta
+static int64_t scales_width(const idhmc_ctx *c) { return c->s.lr_cp > 0 || c->s.lr_s > 0 ? (int64_t)c->s.D : c->s.lr_h + 2 * (int64_t)c->s.lr_j; }
 static int64_t sum_gd(const idhmc_ctx *c) { return c->sum.groups * (int64_t)c->s.D; }
 
 static void summary_release(idhmc_ctx *c)
@@ -442,7 +528,7 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
 {
     Summary &m = c->sum;
     const DevState &s = c->s;
-    const bool corr = s.lr_cp > 0, scaled = scaled_theta(c), local = s.lr_j > 0 && !corr;
+    const bool strct = s.lr_s > 0, corr = s.lr_cp > 0 || strct, scaled = scaled_theta(c), local = s.lr_j > 0 && !corr;
     if (scaled) {
         const int64_t rows = (int64_t)cnt * s.C;
         if (m.scales_rows < rows) {
@@ -451,7 +537,12 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
             if (int rc = dalloc(c, &m.scales, rows * scales_width(c), false)) return rc;
             m.scales_rows = rows;
         }
-        if (corr)
+        if (strct)
+            hipLaunchKernelGGL(k_summary_struct_theta, dim3(blocks_for(rows, kStructThetaWaves)), dim3(64 * kStructThetaWaves), 0, c->stream, stage,
+                               m.scales, rows, s.D, s.D - s.lr_a - s.lr_h - s.lr_j - s.lr_cp - s.lr_sz, s.lr_a, s.lr_h, s.lr_j, s.lr_cp, s.lr_sz,
+                               s.lr_grp, s.lr_lpart, s.lr_cpart, s.lr_spart, s.lr_sn[0], s.lr_s > 1 ? s.lr_sn[1] : 0, s.lr_scz[0],
+                               s.lr_s > 1 ? s.lr_scz[1] : -1, s.lr_inv2);
+        else if (corr)
             hipLaunchKernelGGL(k_summary_corr_theta, dim3(blocks_for(rows * s.D, 256)), dim3(256), 0, c->stream, stage, m.scales, rows, s.D,
                                s.D - s.lr_a - s.lr_h - s.lr_j - s.lr_cp, s.lr_a, s.lr_h, s.lr_j, s.lr_cp, s.lr_grp, s.lr_lpart, s.lr_cpart, s.lr_inv2);
         else if (local)

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmLocal, GlmPairs, GlmPriors, ModelDesc, Options, check
+from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmLocal, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -163,7 +163,7 @@ def _prior(D, prior_mu, prior_tau):
 
 
 def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None, prior_kind=None,
-        prior_nu=None, local=None, slab_scale=None, factors=None, correlated=None):
+        prior_nu=None, local=None, slab_scale=None, factors=None, correlated=None, structured=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -240,7 +240,20 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     them apply (PRIOR_NORMAL or PRIOR_STUDENT_T on Fisher's z; the log kinds are refused).  glm.correlated_effects() assembles groups,
     priors and correlated; glm.correlations(model, draws) gives rho, glm.coefficients applies the mix.  An empty list is the model without
     the keyword; a covariance among three or more terms is out of scope.  The Model exposes P, pairs (a list of glm.Pair, None without),
-    pair_first, pair_second (int32 (P,)) and pair_eta (float64 (P,)); Engine.glm_pairs() reads them back."""
+    pair_first, pair_second (int32 (P,)) and pair_eta (float64 (P,)); Engine.glm_pairs() reads them back.
+
+    structured: a list of up to 2 glm.ar1(term, eta=2.0) or glm.rw1(term) (idhmc_create_glm_struct) -- dependence among the levels of one
+    term, level k being position k of the sequence: ut_0 = u_0, ut_k = phi ut_{k-1} + c u_k takes u's place before the scales, the
+    stationary unit-variance AR(1) with phi = tanh(zeta), c = sqrt(1 - phi^2), or the first-order random walk phi = c = 1.  An AR(1)
+    term adds one coordinate zeta = atanh phi at the very end, behind the pairs': a chain's position is
+    [u (Dx) | a (A) | omega (H) | lambda (J) | zeta_pairs (P) | zeta_ar (Sz)] and D = Dx + A + H + J + P + Sz; a random walk adds none.
+    eta > 0 is (phi + 1) / 2 ~ Beta(eta, eta) with zeta's prior entries at their defaults; eta = 0 lets them apply (normal or Student-t;
+    the log kinds are refused).  A structured term has at least 2 levels, is in no pair and carries no local scale; groups (the term's
+    sampled scale), values, priors, responses and pairs among other terms compose.  glm.structured_effects() assembles groups, priors,
+    correlated and structured; glm.autocorrelations(model, draws) gives phi, glm.coefficients applies the scan.  An empty list is the model
+    without the keyword.  RW2, a sum-to-zero constraint, seasonal and spatial (ICAR) structures and AR(p) are out of scope.  The Model
+    exposes S, Sz, structs (a list of glm.Structure, None without), struct_term, struct_kind (int32 (S,)) and struct_eta (float64 (S,));
+    Engine.glm_structs() reads them back."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -273,7 +286,10 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     loc, J, S = _glm.local_flags(local, slab_scale, Dx)
     pfirst, psecond, peta = _glm.pair_terms(correlated, flev)
     P = 0 if pfirst is None else pfirst.size
-    D = Dx + A + H + J + P
+    sterm, skind, seta = _glm.struct_terms(structured, flev, correlated, loc, Dd)
+    NS = 0 if sterm is None else sterm.size
+    Sz = 0 if sterm is None else int((skind == _glm.STRUCT_AR1).sum())
+    D = Dx + A + H + J + P + Sz
     if D > 1024:
         raise ValueError("a GLM is limited to D <= 1024 (D = %d)" % D)
     if not np.isfinite(X).all():
@@ -306,7 +322,9 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     mu, tau = _prior(D, prior_mu, prior_tau)
     kind, nu = _glm.prior_kinds(prior_kind, prior_nu, D, Dx, tau)
     if P:
-        _glm.pair_priors(peta, D, mu, tau, kind, nu)
+        _glm.pair_priors(peta, D - Sz, mu, tau, kind, nu)
+    if Sz:
+        _glm.struct_priors(skind, seta, D, mu, tau, kind, nu)
     priors = kind is not None and bool(kind.any())
     K = Y.shape[-1]
     if H > 0 or R is not None or priors or J > 0 or F > 0:
@@ -328,6 +346,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.factor_has, m.factor_values = fhas, fval
     m.P, m.pair_first, m.pair_second, m.pair_eta = P, pfirst, psecond, peta
     m.pairs = [_glm.Pair(int(a), int(b), float(e)) for a, b, e in zip(pfirst, psecond, peta)] if P else None
+    m.S, m.Sz, m.struct_term, m.struct_kind, m.struct_eta = NS, Sz, sterm, skind, seta
+    m.structs = [_glm.Structure(int(t), int(k), float(e)) for t, k, e in zip(sterm, skind, seta)] if NS else None
     return m
 
 
@@ -361,7 +381,20 @@ class Engine:
             fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
                             index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
             R = getattr(model, "R", None)
-            if getattr(model, "P", 0) > 0:
+            if getattr(model, "S", 0) > 0:
+                fv = pp = None
+                ip = C.POINTER(C.c_int32)
+                if getattr(model, "factor_has", None) is not None:
+                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(ip)))
+                if getattr(model, "P", 0) > 0:
+                    pp = C.byref(GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
+                                          eta=_dp(model.pair_eta)))
+                st = GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
+                                eta=_dp(model.struct_eta))
+                check(self.lib.idhmc_create_glm_struct(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, pp,
+                                                       C.byref(st), model.M if R is not None else 1, R if R is not None else 0,
+                                                       C.byref(self.opt), seed))
+            elif getattr(model, "P", 0) > 0:
                 fv = None
                 if getattr(model, "factor_has", None) is not None:
                     fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(C.POINTER(C.c_int32))))
@@ -558,6 +591,18 @@ class Engine:
         ip = C.POINTER(C.c_int32)
         check(self.lib.idhmc_glm_pairs_get(self.h, C.byref(P), a.ctypes.data_as(ip), b.ctypes.data_as(ip), _dp(e)))
         return a, b, e
+
+    def glm_structs(self):
+        """(term int32 (S,), kind int32 (S,), eta float64 (S,)) as the context holds them (GLM(..., structured=)); (None, None, None) for
+        every model without structured terms"""
+        S = C.c_int32(0)
+        check(self.lib.idhmc_glm_structs_get(self.h, C.byref(S), None, None, None))
+        if S.value == 0:
+            return None, None, None
+        t, k, e = np.zeros(S.value, np.int32), np.zeros(S.value, np.int32), np.zeros(S.value)
+        ip = C.POINTER(C.c_int32)
+        check(self.lib.idhmc_glm_structs_get(self.h, C.byref(S), t.ctypes.data_as(ip), k.ctypes.data_as(ip), _dp(e)))
+        return t, k, e
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -110,6 +110,13 @@ rho u_first + sqrt(1 - rho^2) u_second before any scale applies; eta > 0 is LKJ(
 in the prior arrays (normal or Student-t).  correlated_effects(Dd, levels, pairs, eta) assembles groups, priors and correlated;
 correlations(model, draws) gives rho and coefficients(model, draws) applies the mix.  A covariance among three or more terms is out of
 scope.
+
+Structured terms, structured=[ar1(0, eta=2.0)] or [rw1(0)] (idhmc_create_glm_struct): dependence among the levels of
+one term, level k being position k of the sequence.  ut_0 = u_0, ut_k = phi ut_{k-1} + c u_k takes u's place before any scale applies:
+the stationary unit-variance AR(1) with a sampled phi = tanh(zeta), zeta one more coordinate at the very end of q, or the first-order
+random walk (phi = c = 1, no coordinate).  Up to two structured terms; a structured term is in no pair and takes no local scale.
+structured_effects(Dd, levels, structured) assembles groups, priors and structured; autocorrelations(model, draws) gives phi and
+coefficients(model, draws) applies the scan.  RW2, a sum-to-zero constraint, seasonal and spatial structures and AR(p) are out of scope.
 """
 import collections
 
@@ -357,9 +364,9 @@ def by_response(model, draws, first_chain=0):
 
 
 def _sampled(model, draws):
-    """draws as float64, checked against the model's D = Dx + A + H + J + P"""
+    """draws as float64, checked against the model's D = Dx + A + H + J + P + Sz"""
     draws = np.asarray(draws, dtype=np.float64)
-    D = model.Dx + model.A + getattr(model, "H", 0) + getattr(model, "J", 0) + getattr(model, "P", 0)
+    D = model.Dx + model.A + getattr(model, "H", 0) + getattr(model, "J", 0) + getattr(model, "P", 0) + getattr(model, "Sz", 0)
     if draws.shape[-1] != D:
         raise ValueError("draws must have %d coordinates along the last axis, got %d" % (D, draws.shape[-1]))
     return draws
@@ -393,19 +400,52 @@ def correlations(model, draws):
     """rho_p = tanh(zeta_p) of a GLM with correlated pairs of terms (GLM(..., correlated=)), shape draws.shape[:-1] + (P,) (P = 0: an empty
     last axis), computed as the device computes it: exactly +-1 past |zeta| of about 19, never beyond.  Any leading axes, as group_scales."""
     draws = _sampled(model, draws)
-    P = getattr(model, "P", 0)
-    return _rho_c(draws[..., draws.shape[-1] - P:])[0]
+    P, Sz = getattr(model, "P", 0), getattr(model, "Sz", 0)
+    return _rho_c(draws[..., draws.shape[-1] - Sz - P:draws.shape[-1] - Sz])[0]
+
+
+def autocorrelations(model, draws):
+    """phi = tanh(zeta) of the AR(1) terms of a GLM with structured terms (GLM(..., structured=)), in list order, shape
+    draws.shape[:-1] + (Sz,) (no AR(1) term: an empty last axis), computed as the device computes it.  A random walk has no phi to
+    report (it is 1).  Any leading axes, as group_scales."""
+    draws = _sampled(model, draws)
+    Sz = getattr(model, "Sz", 0)
+    return _rho_c(draws[..., draws.shape[-1] - Sz:])[0]
+
+
+def struct_scan(x, phi, c):
+    """the forward scan of a structured term along the last axis of x (N levels): x_0, c x_k for k >= 1, then per stage h = 1, 2, 4, ..
+    < N every k >= h takes p x_{k-h} + x_k from the values before the stage, p = phi^h by squaring -- ut_0 = u_0,
+    ut_k = phi ut_{k-1} + c u_k in the device's association (numpy rounds the product where the device fuses it).  phi, c: arrays of
+    x.shape[:-1], or numbers"""
+    x = np.array(x, dtype=np.float64)
+    p = np.asarray(phi, dtype=np.float64)[..., None] * np.ones(x.shape[:-1] + (1,))
+    x[..., 1:] = np.asarray(c, dtype=np.float64)[..., None] * x[..., 1:]
+    N, h = x.shape[-1], 1
+    while h < N:
+        x[..., h:] = p * x[..., :N - h] + x[..., h:]
+        p = p * p
+        h *= 2
+    return x
 
 
 def _mixed(model, draws):
     """u with the second column of every pair replaced by rho u_first + c u_second (draws checked by _sampled)"""
     u = draws[..., :model.Dx].copy()
-    P = getattr(model, "P", 0)
+    P, Sz = getattr(model, "P", 0), getattr(model, "Sz", 0)
     if P:
-        rho, c = _rho_c(draws[..., draws.shape[-1] - P:])
+        rho, c = _rho_c(draws[..., draws.shape[-1] - Sz - P:draws.shape[-1] - Sz])
         for p in range(P):
             a, b = factor_columns(model, int(model.pair_first[p])), factor_columns(model, int(model.pair_second[p]))
             u[..., b] = rho[..., p:p + 1] * draws[..., a] + c[..., p:p + 1] * draws[..., b]
+    z = 0
+    for i in range(getattr(model, "S", 0)):
+        cols = factor_columns(model, int(model.struct_term[i]))
+        phi, c = 1.0, 1.0
+        if int(model.struct_kind[i]) == STRUCT_AR1:
+            phi, c = _rho_c(draws[..., draws.shape[-1] - Sz + z])
+            z += 1
+        u[..., cols] = struct_scan(draws[..., cols], phi, c)
     return u
 
 
@@ -415,7 +455,8 @@ def coefficients(model, draws):
     axes: (M, ..., R, D) from by_response works as (..., C, D) does.  With local scales a flagged column has beta_c = u_c st, st from
     s = exp(omega_g) exp(lambda_k) (exp(lambda_k) in no group) by the kernels' operations: s itself without a slab, and with
     slab_scale S  i = 1 / s, nn = i i + 1 / S^2, st = 1 / sqrt(nn).  With correlated pairs the mix comes first: the second column of a
-    pair is rho u_first + sqrt(1 - rho^2) u_second where the above say u_c, so that the effects of a level are sigma .* (L u)."""
+    pair is rho u_first + sqrt(1 - rho^2) u_second where the above say u_c, so that the effects of a level are sigma .* (L u).  With
+    structured terms the scan comes first in the same way: a term's columns are ut_0 = u_0, ut_k = phi ut_{k-1} + c u_k (struct_scan)."""
     draws = _sampled(model, draws)
     sigma = group_scales(model, draws)
     u = _mixed(model, draws)
@@ -681,6 +722,124 @@ def correlated_effects(Dd, levels, pairs, eta=2.0, A=0, scale=None, coefficients
     return kw
 
 
+# ---- structured terms: AR(1) and random-walk effects across a term's levels ------------------------------------------------------------
+STRUCT_AR1, STRUCT_RW1 = 1, 2
+STRUCT_NAMES = {STRUCT_AR1: "ar1", STRUCT_RW1: "rw1"}
+Structure = collections.namedtuple("Structure", "term kind eta")
+
+
+def ar1(term, eta=2.0):
+    """an AR(1) structure on factor term `term` for GLM(..., structured=[...]): its levels, in index order, are the stationary
+    unit-variance process ut_0 = u_0, ut_k = phi ut_{k-1} + sqrt(1 - phi^2) u_k with a sampled phi = tanh(zeta).  eta > 0:
+    (phi + 1) / 2 ~ Beta(eta, eta) (eta = 1: uniform on (-1, 1)); eta = 0: the entry of zeta in prior_mu, prior_tau, prior_kind, prior_nu
+    applies (normal or Student-t on atanh phi).  Validated by GLM() (struct_terms, struct_priors)."""
+    return Structure(term, STRUCT_AR1, eta)
+
+
+def rw1(term):
+    """a first-order random walk on factor term `term` for GLM(..., structured=[...]): ut_k = u_0 + .. + u_k in index order, the
+    increments u_k (k >= 1) being what the term's priors and its group's scale act on.  No coordinate is added."""
+    return Structure(term, STRUCT_RW1, 0.0)
+
+
+def struct_terms(structured, levels, correlated=None, local=None, Dd=0):
+    """GLM()'s validation of structured: (term int32 (S,), kind int32 (S,), eta float64 (S,)), or (None, None, None) for None and for an
+    empty list.  levels: the level counts of the model's terms (None: no factor terms); correlated: the model's pairs (a term is
+    structured or paired, not both); local, Dd: the model's local-scale flags over its columns and its dense columns (a structured term
+    takes no local scale).  The checks are idhmc_create_glm_struct's, naming the entry."""
+    if structured is None:
+        return None, None, None
+    if not isinstance(structured, (list, tuple)) or isinstance(structured, Structure):
+        raise ValueError("structured must be a list of glm.ar1(term, eta) / glm.rw1(term), got %s" % type(structured).__name__)
+    if len(structured) == 0:
+        return None, None, None
+    if len(structured) > 2:
+        raise ValueError("at most 2 structured terms (got %d)" % len(structured))
+    if levels is None:
+        raise ValueError("structured terms need factor terms (GLM(..., factors=))")
+    F = len(levels)
+    term, kind, eta = np.empty(len(structured), np.int32), np.empty(len(structured), np.int32), np.empty(len(structured))
+    paired = {}
+    for p, pr in enumerate(correlated or ()):
+        if isinstance(pr, Pair):
+            paired.setdefault(pr.first, p)
+            paired.setdefault(pr.second, p)
+    off = int(Dd) + np.r_[0, np.cumsum([int(N) for N in levels])]
+    used = set()
+    for i, entry in enumerate(structured):
+        if not isinstance(entry, Structure):
+            raise ValueError("structured[%d] must be a glm.ar1(term, eta) or a glm.rw1(term)" % i)
+        t = entry.term
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < F:
+            raise ValueError("structured[%d]: term = %r is outside 0..%d (the model's terms)" % (i, t, F - 1))
+        t = int(t)
+        if t in used:
+            raise ValueError("structured[%d]: term %d is listed twice" % (i, t))
+        used.add(t)
+        k = entry.kind
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k not in (STRUCT_AR1, STRUCT_RW1):
+            raise ValueError("structured[%d]: kind = %r must be glm.STRUCT_AR1 (1) or glm.STRUCT_RW1 (2)" % (i, k))
+        e = entry.eta
+        if isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating)) or not (np.isfinite(e) and e >= 0.0):
+            raise ValueError("structured[%d]: eta = %r must be finite and >= 0 (0: the prior arrays' entry of zeta applies)" % (i, e))
+        if k == STRUCT_RW1 and e != 0.0:
+            raise ValueError("structured[%d]: eta = %r on a random walk, which has no zeta (eta must be 0)" % (i, e))
+        if int(levels[t]) < 2:
+            raise ValueError("structured[%d]: term %d has %d level (a structured term needs at least 2)" % (i, t, int(levels[t])))
+        if t in paired:
+            raise ValueError("structured[%d]: term %d is in correlated[%d] (a term is structured or paired, not both)" % (i, t, paired[t]))
+        if local is not None:
+            flagged = np.flatnonzero(np.asarray(local)[off[t]:off[t + 1]])
+            if flagged.size:
+                raise ValueError("structured[%d]: local[%d] is set on level %d of term %d (a structured term takes no local scale)"
+                                 % (i, off[t] + flagged[0], flagged[0], t))
+        term[i], kind[i], eta[i] = t, int(k), float(e)
+    return term, kind, eta
+
+
+def struct_priors(kind, eta, D, mu, tau, prior_kind, nu):
+    """GLM()'s checks of the AR(1) zetas' entries in the prior arrays (the last Sz of D, in list order): no log kind; with eta > 0 the
+    defaults"""
+    Sz = int((np.asarray(kind) == STRUCT_AR1).sum())
+    z = 0
+    for i in range(len(kind)):
+        if kind[i] != STRUCT_AR1:
+            continue
+        cz = D - Sz + z
+        z += 1
+        k = 0 if prior_kind is None else int(prior_kind[cz])
+        if k >= PRIOR_LOG_HALF_NORMAL:
+            raise ValueError("structured[%d]: prior_kind[%d] = PRIOR_%s is a prior on exp(q): coordinate %d is zeta = atanh phi, not a logarithm "
+                             "(normal and student_t are for a zeta)" % (i, cz, PRIOR_NAMES[k], cz))
+        if eta[i] > 0.0 and (k != 0 or (nu is not None and nu[cz] != 0.0) or (mu is not None and mu[cz] != 0.0)
+                             or (tau is not None and tau[cz] != 1.0)):
+            raise ValueError("structured[%d]: eta = %r is the Beta(eta, eta) prior of zeta: the entry of coordinate %d in the prior arrays must "
+                             "be the default (kind 0, mu 0, tau 1, nu 0) and is not applied" % (i, float(eta[i]), cz))
+
+
+def structured_effects(Dd, levels, structured, correlated=None, eta=2.0, A=0, scale=None, coefficients=None, aux=None):
+    """the keyword arguments of GLM() for structured effects: what correlated_effects(Dd, levels, correlated, eta, A, scale, coefficients,
+    aux) returns (random_intercepts(...) when no pair is given), its prior arrays extended by the AR(1) terms' zetas, plus `structured`
+    -- a week effect with a sampled scale and autocorrelation, next to a subject intercept, is
+    GLM(X, Y, source, factors=[(week, 52), subject], **glm.structured_effects(X.shape[1], [52, N], [glm.ar1(0)])).
+    structured: up to two glm.ar1(term, eta) / glm.rw1(term); correlated: (first, second) tuples as correlated_effects takes them, with
+    `eta` theirs.  An ar1 with eta = 0 needs a prior entry on its zeta, which GLM()'s keywords take."""
+    structured = list(structured)
+    lev = [int(N) for N in levels]
+    if correlated:
+        kw = correlated_effects(Dd, lev, correlated, eta, A, scale, coefficients, aux)
+    else:
+        kw = random_intercepts(Dd, lev, A, scale, coefficients, aux)
+    struct_terms(structured, lev, kw.get("correlated"))
+    Sz = sum(1 for e in structured if e.kind == STRUCT_AR1)
+    kw["prior_mu"] = np.r_[kw["prior_mu"], np.zeros(Sz)]
+    kw["prior_tau"] = np.r_[kw["prior_tau"], np.ones(Sz)]
+    kw["prior_kind"] = np.r_[kw["prior_kind"], np.zeros(Sz, np.int32)].astype(np.int32)
+    kw["prior_nu"] = np.r_[kw["prior_nu"], np.zeros(Sz)]
+    kw["structured"] = structured
+    return kw
+
+
 def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):
     """the keyword arguments groups, prior_mu, prior_tau, prior_kind and prior_nu of GLM() for random intercepts: Dd dense columns in no
     group, then factor f's levels[f] columns forming group f, whose sigma_f = exp(omega_f) is sampled --
@@ -800,16 +959,20 @@ def exponential(mean=1.0):
     return PriorSpec(PRIOR_LOG_EXPONENTIAL, float(np.log(_positive("mean", mean))), 1.0, 0.0)
 
 
-def priors(Dx, A=0, H=0, J=0, coefficients=None, aux=None, scales=None, local_scales=None, *, P=0, correlations=None):
+def priors(Dx, A=0, H=0, J=0, coefficients=None, aux=None, scales=None, local_scales=None, *, P=0, correlations=None, S=0,
+           autocorrelations=None):
     """the keyword arguments prior_mu, prior_tau, prior_kind and prior_nu of GLM() for Dx coefficients, A auxiliary coordinates, H
     group scales and J local scales (GLM(..., local=)): GLM(X, Y, source, aux=A, groups=g, **glm.priors(Dx, A, H, coefficients=glm.student_t(3), scales=glm.half_student_t(4))).
     Each role takes one spec (for every coordinate of the role) or a sequence of one spec per coordinate; None is normal(0, 1), today's
     prior (on a and omega: a standard normal on the logarithm).  The specs of sigma = exp(q) -- half_normal, half_student_t,
     exponential -- are for aux, scales and local_scales only.  P, correlations (keyword-only): the P zetas of GLM(..., correlated=), the
-    last coordinates; a spec there (normal or student_t on Fisher's z) is for a pair with eta = 0, a pair with eta > 0 keeps the default."""
+    coordinates behind the local scales; a spec there (normal or student_t on Fisher's z) is for a pair with eta = 0, a pair with eta > 0
+    keeps the default.  S, autocorrelations (keyword-only): the S zetas of the AR(1) terms of GLM(..., structured=), the very last
+    coordinates, under the same rules."""
     out = []
     for role, count, spec in (("coefficients", int(Dx), coefficients), ("aux", int(A), aux), ("scales", int(H), scales),
-                              ("local_scales", int(J), local_scales), ("correlations", int(P), correlations)):
+                              ("local_scales", int(J), local_scales), ("correlations", int(P), correlations),
+                              ("autocorrelations", int(S), autocorrelations)):
         if count < 0:
             raise ValueError("%s: a count of %d" % (role, count))
         if spec is None:
@@ -820,11 +983,11 @@ def priors(Dx, A=0, H=0, J=0, coefficients=None, aux=None, scales=None, local_sc
         if len(spec) != count or not all(isinstance(p, PriorSpec) for p in spec):
             raise ValueError("%s must be one prior spec or a sequence of %d (glm.normal, glm.student_t, glm.half_normal, glm.half_student_t, "
                              "glm.exponential)" % (role, count))
-        if role in ("coefficients", "correlations"):
+        if role in ("coefficients", "correlations", "autocorrelations"):
             for c, p in enumerate(spec):
                 if p.kind >= PRIOR_LOG_HALF_NORMAL:
                     raise ValueError("%s[%d]: PRIOR_%s is a prior on exp(q); %s is not a logarithm"
-                                     % (role, c, PRIOR_NAMES[p.kind], "a coefficient" if role == "coefficients" else "zeta = atanh rho"))
+                                     % (role, c, PRIOR_NAMES[p.kind], "a coefficient" if role == "coefficients" else "zeta = atanh rho" if role == "correlations" else "zeta = atanh phi"))
         out += spec
     return {"prior_mu": np.array([p.mu for p in out], np.float64), "prior_tau": np.array([p.tau for p in out], np.float64),
             "prior_kind": np.array([p.kind for p in out], np.int32), "prior_nu": np.array([p.nu for p in out], np.float64)}

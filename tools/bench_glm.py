@@ -64,6 +64,12 @@ same model without `correlated`, which runs the kernels of a build without the f
 same length under --lockstep: corr_over_uncorr is what the mix and its chain rule cost per gradient.  Meant to run under --lockstep
 with --pairs ''.
 
+--struct-cost (GLM(..., structured=)) runs, per row DdxLEVELSxN of --struct-rows and chain count, three models on the
+data of --slope-cost: (1 + x | s) with the intercepts an AR(1) sequence along the level index (Beta(2, 2) on (phi + 1) / 2, one more
+coordinate), with the intercepts a first-order random walk (no coordinate), and the same model without `structured`, which runs the
+kernels of a build without the feature on the same shape.  Fixed eps and trees of the same length under --lockstep: ar1_over_plain and
+rw1_over_plain are what the scan and its mirror image cost per gradient.  Meant to run under --lockstep with --pairs ''.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
@@ -625,6 +631,10 @@ def main():
                     "(a sampled correlation, LKJ(2)) and without (DESIGN section 22); use --lockstep, and --pairs '' to run nothing else")
     ap.add_argument("--corr-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 21's rows 1 and 1')")
     ap.add_argument("--corr-sides", default="corr,uncorr", help="the sides of each row to run")
+    ap.add_argument("--struct-cost", action="store_true", help="per row of --struct-rows the model of --slope-cost with its first term an AR(1) "
+                    "sequence, a random walk, and unstructured (DESIGN section 23); use --lockstep, and --pairs '' to run nothing else")
+    ap.add_argument("--struct-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 22's rows: the matrix cores and the per-wave form)")
+    ap.add_argument("--struct-sides", default="ar1,rw1,plain", help="the sides of each row to run")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -724,6 +734,37 @@ def main():
                 if "corr" in row and "uncorr" in row:
                     row["same_steps"] = row["corr"]["steps"] == row["uncorr"]["steps"]
                     row["corr_over_uncorr"] = row["corr"]["leapfrog_steps_per_s"] / row["uncorr"]["leapfrog_steps_per_s"]
+                res["results"].append(row)
+    if a.struct_cost:
+        sides = a.struct_sides.split(",")
+        for spec in a.struct_rows.split(","):
+            Dd, N, n = (int(v) for v in spec.split("x"))
+            X, y, idx, x, kw, q0, cov = slope_problem(Dd, N, n, seed=Dd * 7919 + N * 31 + n)
+            valued = [(idx, N), pkg.glm.term(idx, values=x, levels=N)]
+            # (a walk's level k is the sum of k + 1 increments: the start's increments are scaled so that its levels stay the size of q0's)
+            qw = q0.copy()
+            qw[Dd + 1:Dd + N] = q0[Dd + 1:Dd + N] / np.sqrt(N)
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="struct_cost", Dd=Dd, levels=N, n=n, Dx=Dd + 2 * N, L=padded(Dd + 2 * N + 3), chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                for side in sides:
+                    if side == "ar1":
+                        mdl, qs = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **pkg.glm.structured_effects(Dd, [N, N], [pkg.glm.ar1(0)])), np.r_[q0, 0.3]
+                    elif side == "rw1":
+                        mdl, qs = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **pkg.glm.structured_effects(Dd, [N, N], [pkg.glm.rw1(0)])), qw
+                    else:
+                        mdl, qs = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **kw), q0
+                    runs = [run("glm_" + side, X, y, qs, np.eye(qs.size) * 1e-4, C, a.transitions, metric=metric, mdl=mdl) for _ in range(a.repeats)]
+                    r = max((u[0] for u in runs), key=lambda u: u["leapfrog_steps_per_s"])
+                    r["repeats_leapfrog_steps_per_s"] = [u[0]["leapfrog_steps_per_s"] for u in runs]
+                    row[side] = r
+                    print("# Dd=%d levels=2x%d n=%d C=%d %s (form %d): %.4e leapfrog steps/s (%s), %.3f ms/transition, create %.2f s" %
+                          (Dd, N, n, C, side, r["glm_form"], r["leapfrog_steps_per_s"],
+                           " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
+                          file=sys.stderr, flush=True)
+                for side in ("ar1", "rw1"):
+                    if side in row and "plain" in row:
+                        row[side + "_same_steps"] = row[side]["steps"] == row["plain"]["steps"]
+                        row[side + "_over_plain"] = row[side]["leapfrog_steps_per_s"] / row["plain"]["leapfrog_steps_per_s"]
                 res["results"].append(row)
     for shape in a.shapes.split(","):
         D, n = (int(v) for v in shape.split("x"))
