@@ -917,7 +917,7 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
     if (fcols > 0) { parts.F = factors->F; parts.fcols = (int32_t)fcols; parts.levels = factors->levels; parts.findex = factors->index; }
     if (valued) { parts.fvalues = values->values; parts.fhas = values->has; }
-    std::vector<int32_t> kdev, kpub;     // a zeta with eta > 0: the device table marks it (kPriorLkj of idhmc_glm.hpp, eta in nu's place)
+    std::vector<int32_t> kdev, kpub;     // a zeta with eta > 0: the device table marks it (kPriorLkj of idhmc_glm_coords.hpp, eta in nu's place)
     std::vector<double> nudev, nupub;
     if (P > 0) { parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta; }
     if (S > 0) { parts.S = S; parts.SZ = SZ; parts.sterm = structs->term; parts.skind = structs->kind; parts.seta = structs->eta; }

@@ -67,7 +67,7 @@ __global__ void k_summary_scales(const double *stage, double *scales, int64_t ro
 }
 
 // The same for a GLM with local scales, one thread per (row, group or local coordinate): e_g = dexp(omega_g) as above; for local
-// coordinate k, column col(k) with id = grp[col(k)], f = dexp(lambda_k) and st by the expressions of idhmc_glm.hpp (glm_local_scale):
+// coordinate k, column col(k) with id = grp[col(k)], f = dexp(lambda_k) and st by the expressions of idhmc_glm_coords.hpp (glm_local_scale):
 //   s = id >= 0 ? e_id * f : f;  no slab: st = s;  slab: i = 1 / s, nn = dfma(i, i, inv2), st = 1 / sqrt(nn)
 // A row of scales is [e (H) | f (J) | st (J)].
 __global__ void k_summary_local_scales(const double *stage, double *scales, int64_t rows, int32_t D, int32_t H, int32_t J, const int32_t *grp,
@@ -98,7 +98,7 @@ __global__ void k_summary_local_scales(const double *stage, double *scales, int6
 }
 
 // A GLM with correlated pairs: theta = [beta | a raw | sigma | exp(lambda) | rho], beta taken from ut.  One thread per
-// (row, coordinate) writes the whole reported vector of the row, by the expressions of idhmc_glm.hpp (glm_corr_factors, glm_corr_mix,
+// (row, coordinate) writes the whole reported vector of the row, by the expressions of idhmc_glm_coords.hpp (glm_corr_factors, glm_corr_mix,
 // glm_scaled, glm_local_scale); the reduction then runs on it as it runs on raw draws (MODE 3).  A row of "scales" is theta, D doubles.
 __global__ void k_summary_corr_theta(const double *stage, double *theta, int64_t rows, int32_t D, int32_t Dx, int32_t A, int32_t H, int32_t J,
                                      int32_t P, const int32_t *grp, const int32_t *lpart, const int32_t *cpart, double inv2)
