@@ -457,8 +457,8 @@ int idhmc_glm_pairs_get(const idhmc_ctx *ctx, int32_t *P, int32_t *first, int32_
  * with the Jacobian of tanh (the section above's T and g rows, the device's internal kind 5) and wants the defaults (0, 1, 0, 0) in zeta's
  * entries of mu, tau, kind and nu; eta == 0 lets those entries apply, kinds 0 and 1; the log kinds are refused.  The prior of u is on u.
  * Groups (a sampled scale on the term), local scales on other columns, priors, values on the structured term, several responses and pairs
- * among other terms compose.  Out of scope: second-order walks (RW2), a sum-to-zero constraint, seasonal and spatial (ICAR) structures,
- * AR(p).  A random walk's level is not identified against an intercept; its u_0 has the prior the prior arrays give it.
+ * among other terms compose.  Second-order walks (RW2), a sum-to-zero constraint, seasonal and spatial (ICAR) structures are GMRF terms
+ * (idhmc_create_glm_gmrf below); out of scope: AR(p).  A random walk's level is not identified against an intercept; its u_0 has the prior the prior arrays give it.
  *
  * idhmc_create_glm_struct is idhmc_create_glm_corr with these.  structs == NULL or S == 0 gives exactly the context of
  * idhmc_create_glm_corr: the same kernels, bits and footprint.  No LDS is added.  Refused with IDHMC_ERR_BAD_ARG before the device is
@@ -475,6 +475,43 @@ int idhmc_create_glm_struct(idhmc_ctx **out, int device, int64_t nchains, int64_
                             const idhmc_glm_structs *structs, int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
 /* *S, and with non-NULL arrays term, kind and eta (S entries each) as the context was given them; 0 for every other context */
 int idhmc_glm_structs_get(const idhmc_ctx *ctx, int32_t *S, int32_t *term, int32_t *kind, double *eta);
+/* Gaussian Markov random field priors on a factor term's levels: ICAR effects over regions, second-order random
+ * walks, seasonal effects, difference penalties, or any "generic" term with a user's sparse precision.  A model with factor terms may
+ * name G GMRF terms, 0 <= G <= 2; term i names factor term term[i] with N_i levels and first column o_i, a symmetric N_i x N_i
+ * precision Q_i in CSR form and a fixed kappa[i] >= 0.  The rows of term 0 come first and then those of term 1: start has
+ * sum N_i + 1 cumulative entries from 0, row k of term i is entries start[r + k] .. start[r + k + 1] - 1 of col and val with
+ * r = 0 for term 0 and N_0 for term 1; col holds columns 0 .. N_i - 1 of the row's own term, strictly ascending within a row, the
+ * diagonal present in every row and > 0, between 1 and 128 entries per row, Q_ij and Q_ji both present and bit-equal.
+ * No coordinate is added.  The levels u of such a term get
+ *   log p(u) = -1/2 u' Q u - 1/2 kappa (sum u)^2        (kappa > 0: a soft sum-to-zero constraint)
+ * in place of the entries of the prior arrays, which must be the defaults (mu, tau, kind, nu = 0, 1, 0, 0) on its columns.  The scale of
+ * the effect is the term's group scale, b = exp(omega_g) u, as for every term; BYM is two terms on one index array, one with a Q and one
+ * without.  Per gradient, on the raw q (a member c = o + k, u_c = q_c; T and g are the prior loop's of the sections above):
+ *   Sr per lane component: plain additions over chunks ascending, from +0, of the members' u_c;  S = the canonical 128-residue tree;
+ *   s = kappa > 0 ? kappa * S : +0;   for e = start[k] .. start[k+1]-1 ascending:  s = dfma(val[e], u_{o + col[e]}, s);
+ *   T = dfma(u_c, s, T);   g = G - s.
+ * With Q = I and kappa = 0 these are the bits of the normal prior with mu = 0, tau = 1 for u and G that are not -0.  A Q that is only
+ * positive semi-definite with kappa = 0 gives an improper prior along its null space (the likelihood has to identify it); the library
+ * checks the table's form, not definiteness.  Groups, values on the term (a spatially varying slope), several responses, pairs and
+ * structures on other terms and local scales on other columns compose.  Still out of scope: AR(p), a sampled CAR or Leroux
+ * autocorrelation, the BYM2 mixing parameter, hard constraints.
+ *
+ * idhmc_create_glm_gmrf is idhmc_create_glm_struct with these.  gmrfs == NULL or G == 0 gives exactly the context of
+ * idhmc_create_glm_struct: the same kernels, bits and footprint.  No LDS is added.  Refused with IDHMC_ERR_BAD_ARG before the device is
+ * touched: G outside 0..2; term, start, col, val or kappa NULL with G > 0; GMRFs without factors; a term outside 0..F-1 or listed
+ * twice; a GMRF term that is in a pair or structured; a local-scale flag on one of its columns; a non-default prior entry on one of its
+ * columns; start not non-decreasing from 0; a row with 0 or more than 128 entries; columns not strictly ascending or outside 0..N-1; a
+ * missing or non-positive diagonal; a non-finite value; Q_ij and Q_ji not bit-equal or one of them absent; kappa negative or not
+ * finite; and everything idhmc_create_glm_struct refuses. */
+typedef struct { int32_t G; const int32_t *term; const int64_t *start; const int32_t *col; const double *val; const double *kappa; } idhmc_glm_gmrfs;
+int idhmc_create_glm_gmrf(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                          const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                          const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                          const idhmc_glm_structs *structs, const idhmc_glm_gmrfs *gmrfs, int64_t M, int64_t chains_per_response,
+                          const idhmc_options *opt, uint64_t seed);
+/* *G, and with non-NULL arrays term, kappa and nnz (the entries of each term's precision; G entries each) as the context was given
+ * them; 0 for every other context */
+int idhmc_glm_gmrfs_get(const idhmc_ctx *ctx, int32_t *G, int32_t *term, double *kappa, int64_t *nnz);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

@@ -77,6 +77,10 @@ struct GlmParts {
     int32_t S = 0, SZ = 0;     // idhmc_create_glm_struct: structured terms, and those of them that are AR(1): the last SZ coordinates, behind
     const int32_t *sterm = nullptr, *skind = nullptr;      // the pairs' zetas, are theirs; [S] term and kind, S > 0 (every entry checked)
     const double *seta = nullptr;      // [S]
+    int32_t G = 0;             // idhmc_create_glm_gmrf: GMRF terms; no coordinate is added
+    const int32_t *gterm = nullptr, *gcol = nullptr;       // [G], and the entries' columns, G > 0 (never null then; every entry checked)
+    const int64_t *gstart = nullptr;   // [sum N + 1]
+    const double *gval = nullptr, *gkappa = nullptr;       // the entries' values, [G]
 };
 // the padded width of the stored columns of X: L of the model, and with factors Lx = 128 ceil(Dd / 128)
 static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
@@ -385,6 +389,38 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         c->glm_sterm.assign(g.sterm, g.sterm + g.S);
         c->glm_skind.assign(g.skind, g.skind + g.S);
         c->glm_seta.assign(g.seta, g.seta + g.S);
+    }
+    std::vector<int32_t> hgp, hgs, hgc;
+    if (g.G > 0) {
+        // the level of every column of a GMRF term and its slot; the tables of the slots one behind the other, start as int32
+        hgp.assign((size_t)L, -1);
+        int64_t rows = 0;
+        for (int i = 0; i < g.G; ++i) {
+            const int32_t o = s.lr_foff[g.gterm[i]], N = g.levels[g.gterm[i]];
+            for (int32_t k = 0; k < N; ++k) hgp[(size_t)(o + k)] = k | (i << 10);
+            s.lr_go[i] = o;
+            s.lr_gn[i] = N;
+            s.lr_gkappa[i] = g.gkappa[i];
+            s.lr_gnz[i] = (int32_t)(g.gstart[rows + N] - g.gstart[rows]);
+            rows += N;
+        }
+        const int64_t nnz = g.gstart[rows];
+        hgs.assign(g.gstart, g.gstart + rows + 1);           // (at most 2 * 1024 * 128 entries)
+        hgc.assign(g.gcol, g.gcol + nnz);
+        int32_t *dgp = nullptr, *dgs = nullptr, *dgc = nullptr;
+        double *dgv = nullptr;
+        if (int rc = dalloc(c, &dgp, L)) return rc;
+        if (int rc = dalloc(c, &dgs, rows + 1)) return rc;
+        if (int rc = dalloc(c, &dgc, nnz)) return rc;
+        if (int rc = dalloc(c, &dgv, nnz)) return rc;
+        HIPCHK(hipMemcpyAsync(dgp, hgp.data(), sizeof(int32_t) * hgp.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dgs, hgs.data(), sizeof(int32_t) * hgs.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dgc, hgc.data(), sizeof(int32_t) * hgc.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dgv, g.gval, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+        s.lr_gpart = dgp; s.lr_gstart = dgs; s.lr_gcol = dgc; s.lr_gval = dgv;
+        s.lr_g = g.G;
+        c->glm_gterm.assign(g.gterm, g.gterm + g.G);
+        c->glm_gkappa.assign(g.gkappa, g.gkappa + g.G);
     }
     HIPCHK(hipStreamSynchronize(c->stream));     // the host copies go out of scope here
     s.lr_x = dx; s.lr_xt = dxt; s.lr_y = dy;
@@ -860,13 +896,95 @@ static int validate_structs(const idhmc_glm_desc *glm, const idhmc_glm_priors *p
     return IDHMC_OK;
 }
 
+// The GMRF terms of idhmc_create_glm_gmrf, after validate_structs: every check of G, term and kappa, of the terms against the pairs, the
+// structures, the local flags and the prior arrays, and of the precisions' tables.  *G: the GMRF terms (0: the context is the one of
+// idhmc_create_glm_struct)
+static int validate_gmrfs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, const idhmc_glm_local *local, int J, int P, int S,
+                          const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_pairs *pp, const idhmc_glm_structs *st,
+                          const idhmc_glm_gmrfs *gm, int *G)
+{
+    *G = 0;
+    if (!gm) return IDHMC_OK;
+    if (gm->G < 0 || gm->G > 2) return fail(IDHMC_ERR_BAD_ARG, "GLM: G = %d GMRF terms must be an integer in 0..2", gm->G);
+    if (gm->G == 0) return IDHMC_OK;
+    if (!gm->term || !gm->start || !gm->col || !gm->val || !gm->kappa)
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: G = %d GMRF terms need term, start, col, val and kappa (%s is NULL)", gm->G,
+                    !gm->term ? "term" : !gm->start ? "start" : !gm->col ? "col" : !gm->val ? "val" : "kappa");
+    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF terms need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (gm->start[0] != 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF start[0] = %lld must be 0", (long long)gm->start[0]);
+    int64_t rows = 0;
+    for (int i = 0; i < gm->G; ++i) {
+        const int32_t t = gm->term[i];
+        if (t < 0 || t >= fc->F) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: term = %d is outside 0..%d (the model's terms)", i, t, fc->F - 1);
+        if (i == 1 && gm->term[0] == t) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: term %d is listed twice", i, t);
+        const double kap = gm->kappa[i];
+        if (!(std::isfinite(kap) && kap >= 0.0)) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: kappa = %g must be finite and >= 0", i, kap);
+        for (int p = 0; p < P; ++p)
+            if (pp->first[p] == t || pp->second[p] == t)
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: term %d is in pair %d (a GMRF term is in no pair)", i, t, p);
+        for (int k = 0; k < S; ++k)
+            if (st->term[k] == t) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: term %d is structure %d (a term is structured or a GMRF, not both)", i, t, k);
+        const int32_t N = fc->levels[t];
+        int64_t o = glm->Dx - fcols;
+        for (int f = 0; f < t; ++f) o += fc->levels[f];
+        for (int32_t k = 0; k < N; ++k) {
+            const int64_t c = o + k;
+            if (J > 0 && local->local[c])
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: local[%lld] is set on level %d of term %d (a GMRF term takes no local scale)", i, (long long)c, k, t);
+            const int32_t kd = pr && pr->kind ? pr->kind[c] : 0;
+            const double nu = pr && pr->kind && pr->nu ? pr->nu[c] : 0.0;
+            if (kd != 0 || nu != 0.0 || (glm->mu && glm->mu[c] != 0.0) || (glm->tau && glm->tau[c] != 1.0))
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: the entry of coordinate %lld (level %d of term %d) in the prior arrays must be the default "
+                            "(kind 0, mu 0, tau 1, nu 0): the precision is its prior", i, (long long)c, k, t);
+        }
+        // the table: rows rows .. rows + N - 1
+        const int64_t *sp = gm->start + rows;
+        for (int32_t k = 0; k < N; ++k) {
+            const int64_t cnt = sp[k + 1] - sp[k];
+            if (cnt < 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: start[%lld] = %lld is below start[%lld] = %lld (start must not decrease)", i,
+                                     (long long)(rows + k + 1), (long long)sp[k + 1], (long long)(rows + k), (long long)sp[k]);
+            if (cnt < 1 || cnt > 128)
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: row %d has %lld entries (1..128: the diagonal is always there)", i, k, (long long)cnt);
+            bool diag = false;
+            for (int64_t e = sp[k]; e < sp[k + 1]; ++e) {
+                const int32_t cj = gm->col[e];
+                if (cj < 0 || cj >= N) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: row %d: col[%lld] = %d is outside 0..%d", i, k, (long long)e, cj, N - 1);
+                if (e > sp[k] && cj <= gm->col[e - 1])
+                    return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: row %d: col[%lld] = %d is not above col[%lld] = %d (columns strictly ascending)", i, k,
+                                (long long)e, cj, (long long)(e - 1), gm->col[e - 1]);
+                if (!std::isfinite(gm->val[e])) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: row %d: val[%lld] = %g is not finite", i, k, (long long)e, gm->val[e]);
+                if (cj == k) {
+                    diag = true;
+                    if (!(gm->val[e] > 0.0)) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: row %d: the diagonal val[%lld] = %g must be > 0", i, k, (long long)e, gm->val[e]);
+                }
+            }
+            if (!diag) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: row %d has no diagonal entry", i, k);
+        }
+        // symmetry, once every row of the term is known to be inside the table: Q_kj and Q_jk both there and bit-equal
+        for (int32_t k = 0; k < N; ++k)
+            for (int64_t e = sp[k]; e < sp[k + 1]; ++e) {
+                const int32_t cj = gm->col[e];
+                const int32_t *b = gm->col + sp[cj], *en = gm->col + sp[cj + 1];
+                const int32_t *it = std::lower_bound(b, en, k);
+                if (it == en || *it != k) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: Q[%d][%d] is given and Q[%d][%d] is absent (Q must be symmetric)", i, k, cj, cj, k);
+                if (memcmp(&gm->val[it - gm->col], &gm->val[e], sizeof(double)) != 0)
+                    return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: Q[%d][%d] = %.17g and Q[%d][%d] = %.17g are not bit-equal (Q must be symmetric)", i, k, cj,
+                                gm->val[e], cj, k, gm->val[it - gm->col]);
+            }
+        rows += N;
+    }
+    *G = gm->G;
+    return IDHMC_OK;
+}
+
 // idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors,
-// idhmc_create_glm_slopes, idhmc_create_glm_corr and idhmc_create_glm_struct
+// idhmc_create_glm_slopes, idhmc_create_glm_corr, idhmc_create_glm_struct and idhmc_create_glm_gmrf
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
                       const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
                       const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr,
-                      const idhmc_glm_pairs *pairs = nullptr, const idhmc_glm_structs *structs = nullptr)
+                      const idhmc_glm_pairs *pairs = nullptr, const idhmc_glm_structs *structs = nullptr,
+                      const idhmc_glm_gmrfs *gmrfs = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
@@ -890,6 +1008,8 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (int rc = validate_pairs(glm, priors, J, factors, fcols, pairs, &P)) return rc;
     int S = 0, SZ = 0;
     if (int rc = validate_structs(glm, priors, local, J, P, factors, fcols, pairs, structs, &S, &SZ)) return rc;
+    int G = 0;
+    if (int rc = validate_gmrfs(glm, priors, local, J, P, S, factors, fcols, pairs, structs, gmrfs, &G)) return rc;
     if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
     if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
     if (glm->H > 0) {
@@ -921,8 +1041,9 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     std::vector<double> nudev, nupub;
     if (P > 0) { parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta; }
     if (S > 0) { parts.S = S; parts.SZ = SZ; parts.sterm = structs->term; parts.skind = structs->kind; parts.seta = structs->eta; }
-    if (P > 0 || SZ > 0) {
-        bool lkj = false;
+    if (G > 0) { parts.G = G; parts.gterm = gmrfs->term; parts.gstart = gmrfs->start; parts.gcol = gmrfs->col; parts.gval = gmrfs->val; parts.gkappa = gmrfs->kappa; }
+    if (P > 0 || SZ > 0 || G > 0) {
+        bool lkj = G > 0;                // (a GMRF term's members are marked too: kPriorGmrf)
         for (int p = 0; p < P; ++p) lkj = lkj || pairs->eta[p] > 0.0;
         for (int i = 0; i < S; ++i) lkj = lkj || structs->eta[i] > 0.0;
         if (lkj) {
@@ -937,6 +1058,11 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
                 if (structs->kind[i] != IDHMC_STRUCT_AR1) continue;
                 if (structs->eta[i] > 0.0) { kdev[(size_t)(m.D - SZ + z)] = 5; nudev[(size_t)(m.D - SZ + z)] = structs->eta[i]; }
                 ++z;
+            }
+            for (int i = 0; i < G; ++i) {
+                int64_t o = glm->Dx - fcols;
+                for (int f = 0; f < gmrfs->term[i]; ++f) o += factors->levels[f];
+                for (int32_t k = 0; k < factors->levels[gmrfs->term[i]]; ++k) kdev[(size_t)(o + k)] = 6;
             }
             parts.pkind = kdev.data(); parts.pnu = nudev.data();
             parts.pkind_pub = kpub.data(); parts.pnu_pub = nupub.data();
@@ -1018,6 +1144,28 @@ int idhmc_create_glm_struct(idhmc_ctx **out, int device, int64_t nchains, int64_
     const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
     return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
                       pairs, structs);
+}
+
+int idhmc_create_glm_gmrf(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                          const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                          const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                          const idhmc_glm_structs *structs, const idhmc_glm_gmrfs *gmrfs, int64_t M, int64_t chains_per_response,
+                          const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_gmrf: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
+                      pairs, structs, gmrfs);
+}
+
+int idhmc_glm_gmrfs_get(const idhmc_ctx *c, int32_t *G, int32_t *term, double *kappa, int64_t *nnz)
+{
+    if (!c || !G) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_gmrfs_get: null argument");
+    *G = c->s.lr_g;
+    if (term) std::copy(c->glm_gterm.begin(), c->glm_gterm.end(), term);
+    if (kappa) std::copy(c->glm_gkappa.begin(), c->glm_gkappa.end(), kappa);
+    if (nnz) for (int i = 0; i < c->s.lr_g; ++i) nnz[i] = c->s.lr_gnz[i];
+    return IDHMC_OK;
 }
 
 int idhmc_glm_structs_get(const idhmc_ctx *c, int32_t *S, int32_t *term, int32_t *kind, double *eta)

@@ -1,4 +1,4 @@
-// idhmc_glm.hpp -- the two forms that evaluate a generalised linear model (DESIGN sections 10-23).  The arithmetic, stage by stage for
+// idhmc_glm.hpp -- the two forms that evaluate a generalised linear model (DESIGN sections 10-25).  The arithmetic, stage by stage for
 // the full model, the device layout and every helper that does not depend on the form are in idhmc_glm_coords.hpp; the stage numbers
 // below are that header's.  Two forms with one arithmetic: GlmWave (one chain per wavefront, every kernel) and GlmCoop (the NUTS kernel
 // at L <= 256: 16 chains per workgroup, both products on the fp64 matrix cores).  The built-in logistic regression
@@ -26,7 +26,8 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 // Bernoulli with the logit link: IDHMC_MODEL_LOGISTIC_REGRESSION
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false,
+                          kGmrf = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -42,7 +43,8 @@ struct LogisticObs {
 // (the planes are read as int2, lane-offset, like y2; [kSlopes] a double2 from the value plane at the same offset, zx = dfma(w.x, bx,
 // zx)); the stored-column loop touches the chunks j < Lx / 128 only -- one loop, whose stride and chunk bound are compile-time constants
 // without factors --; after it each lane walks the lists of its level columns over r staged in buf[0 .. 127] (glm_gather: G + r[ii],
-// [kSlopes] dfma(wl, r[ii], G)).
+// [kSlopes] dfma(wl, r[ii], G)).  [kGmrf] once every chain rule has run, the raw q is staged in buf a last time and stays there for the
+// prior loop: row 6 of a member reads its neighbours' u from it.
 template <int NCH, class Obs>
 struct GlmWave {
     static constexpr bool kHasParams = true;
@@ -65,6 +67,7 @@ struct GlmWave {
     const int32_t *cpart;    // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;            // the coordinate of zeta_0 and the pairs (Obs::kCorr)
     GlmStruct stc;           // the structured terms (Obs::kStruct)
+    GlmGmrf gm;              // the GMRF terms (Obs::kGmrf)
     double *buf;             // this wavefront's LDS vector, L doubles
     int D, n, npad, nc, lane;    // D: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -101,6 +104,7 @@ struct GlmWave {
             D -= s.lr_sz;
             if constexpr (Obs::kCorr) cz0 -= s.lr_sz;          // (the pairs' zetas come first)
         }
+        if constexpr (Obs::kGmrf) gm.init(s);
         n = s.lr_n;
         npad = s.lr_npad;
         nc = (int)s.user_nparams;
@@ -268,12 +272,27 @@ struct GlmWave {
         else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, u, grp2, D + Obs::A, lane, e0, e1, e2, e3);
         if constexpr (Obs::kCorr) glm_corr_chain<NCH>(G, q, cpart, buf, cz0, ncp, lane, cr0, cc0, cr1, cc1);
         if constexpr (Obs::kStruct) glm_struct_chain<NCH>(G, q, u, stc, buf, lane, sf0, sc0, sf1, sc1);
+        double gs0 = 0.0, gs1 = 0.0;                           // Obs::kGmrf: S of the slots; the raw q stays in buf for the loop
+        if constexpr (Obs::kGmrf) {
+            glm_gmrf_sums<NCH>(q, gm, lane, gs0, gs1);
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) b2[j * 64] = q.c[j];
+            asm volatile("" ::: "memory");                     // (the rows' reads stay behind the writes)
+        }
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
             const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
-            if constexpr (Obs::kPriors) {
+            if constexpr (Obs::kPriors && Obs::kGmrf) {
+                // (a member takes row 6, from its table entry; kind2 holds kPriorGmrf there)
+                const int2 k = kind2[j * 64], ge = (reinterpret_cast<const int2 *>(gm.gpart) + lane)[j * 64];
+                const double2 nu = nu2[j * 64];
+                g.c[j].x = ge.x >= 0 ? glm_gmrf_row(gm, ge.x, buf, q.c[j].x, gs0, gs1, G.c[j].x, t0)
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
+                g.c[j].y = ge.y >= 0 ? glm_gmrf_row(gm, ge.y, buf, q.c[j].y, gs0, gs1, G.c[j].y, t1)
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
+            } else if constexpr (Obs::kPriors) {
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];
                 g.c[j].x = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
@@ -315,7 +334,8 @@ struct GlmWave {
 // computed AGAIN from q through it, then wl and Gh go through it for the chain rules.  Held across the round instead, they made
 // the matrix loops of multiply() spill; the coordinates they are read from are laundered through an empty asm so that the
 // compiler does not keep the values of before barrier A alive.  Nothing of a feature is alive across multiply(); the prior's
-// tables are read after barrier C too.
+// tables are read after barrier C too.  [kGmrf] the G row is taken into registers as for the chain rules, and once they have run the
+// raw q goes into the row, which is the requester's own, and stays there for the prior loop: row 6 reads its neighbours' u from it.
 // [kResponses] the 16 rows of a tile are 16 chains of any responses: the requester publishes its offset into Y in column L of its
 // Q row (padding: zphase, gphase and both row accesses of the requester touch columns < L only) and the Z wavefronts read y per
 // accumulator row instead of once per lane.
@@ -355,6 +375,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     const int32_t *cpart;        // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;                // the coordinate of zeta_0 and the pairs (Obs::kCorr)
     GlmStruct stc;               // the structured terms (Obs::kStruct)
+    GlmGmrf gm;                  // the GMRF terms (Obs::kGmrf)
     double *tile;
     int n, npad, nc, dx;         // dx: the columns of X (then Obs::A auxiliary coordinates, Obs::H log scales, the log local scales)
     template <class State>
@@ -384,6 +405,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             dx -= s.lr_sz;
             if constexpr (Obs::kCorr) cz0 -= s.lr_sz;          // (the pairs' zetas come first)
         }
+        if constexpr (Obs::kGmrf) gm.init(s);
         x = s.lr_x;
         xt = s.lr_xt;
         y = s.lr_y;
@@ -647,7 +669,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             }
         }
         Vec<NCH> Gh;                                          // with groups, local scales or pairs: the whole G row, for the chain rule
-        if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct) {
+        if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct || Obs::kGmrf) {
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 Gh.c[j] = row[j * 64];
@@ -683,12 +705,19 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             if constexpr (Obs::kCorr) glm_corr_chain<NCH>(Gh, q, cpart, tile + kQ + wv * DS, cz, ncp, lane, cr0, cc0, cr1, cc1);
             if constexpr (Obs::kStruct) glm_struct_chain<NCH>(Gh, q, u, st2, tile + kQ + wv * DS, lane, sf0, sc0, sf1, sc1);
         }
+        double gs0 = 0.0, gs1 = 0.0;                          // Obs::kGmrf: S of the slots; the raw q stays in the row for the loop
+        if constexpr (Obs::kGmrf) {
+            glm_gmrf_sums<NCH>(q, gm, lane, gs0, gs1);
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) row[j * 64] = q.c[j];
+            asm volatile("" ::: "memory");                    // (the rows' reads stay behind the writes)
+        }
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
             double2 G;
-            if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct) {
+            if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct || Obs::kGmrf) {
                 G = Gh.c[j];
             } else {
                 G = row[j * 64];
@@ -698,7 +727,15 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 }
             }
             const double dx = q.c[j].x - m.x, dy = q.c[j].y - m.y;
-            if constexpr (Obs::kPriors) {
+            if constexpr (Obs::kPriors && Obs::kGmrf) {
+                // (a member takes row 6, from its table entry; kind2 holds kPriorGmrf there)
+                const int2 k = kind2[j * 64], ge = (reinterpret_cast<const int2 *>(gm.gpart) + lane)[j * 64];
+                const double2 nu = nu2[j * 64];
+                g.c[j].x = ge.x >= 0 ? glm_gmrf_row(gm, ge.x, tile + kQ + wv * DS, q.c[j].x, gs0, gs1, G.x, t0)
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.x, t0);
+                g.c[j].y = ge.y >= 0 ? glm_gmrf_row(gm, ge.y, tile + kQ + wv * DS, q.c[j].y, gs0, gs1, G.y, t1)
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.y, t1);
+            } else if constexpr (Obs::kPriors) {
                 // kinds and nu are read here, after barrier C: nothing of the prior is alive across multiply()
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];

@@ -2,11 +2,11 @@
 // not depend on how a kernel evaluates it.  The two forms that do (GlmWave, GlmCoop) and what is theirs alone are in idhmc_glm.hpp.
 //   l(q) = -sum_i v(z_i, y_i) + log prior(q),   v = -log p(y | z) up to a data-only term,   r_i = d log p(y_i | z_i) / dz_i
 // The observation is a policy type Obs: Obs::K data columns per observation (1..4), Obs::A auxiliary coordinates, Obs::H groups, the
-// compile-time flags kResponses, kPriors, kLocal, kFactors, kSlopes, kCorr, kStruct, and
+// compile-time flags kResponses, kPriors, kLocal, kFactors, kSlopes, kCorr, kStruct, kGmrf, and
 //   static void terms(double z, const GlmObs &o, double &r, double &v)                                             (A = 0)
 //   static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)    s[j] = d log p / d a_j
 // A flag that is false (A, H = 0) takes its stage out at compile time: none of the instructions of a model without it changes.  Each
-// feature's record is its DESIGN section (10-23); this comment is the full model in evaluation order, every stage tagged with its
+// feature's record is its DESIGN section (10-25); this comment is the full model in evaluation order, every stage tagged with its
 // flag, and both forms and the tests' C restatements follow it bit for bit.  dfma is one fused multiply-add; every other operation
 // is a plain one in the association written.
 //
@@ -30,6 +30,12 @@
 //           lr_spart holds per coordinate -1 or  k | slot << 10;  lr_s = S, lr_sz = Sz, lr_sn the slots' levels, lr_skind their kinds,
 //           lr_scz their zeta coordinates (-1: a random walk).  A term is in a pair or structured, never both, and a structured column
 //           has no local scale.
+//   gmrf    [kGmrf] up to two GMRF terms (slots 0, 1), no coordinate of their own.  Each names a factor term f with N = N_f levels and
+//           first column o = off_f, a symmetric N x N precision Q in CSR form -- start[N+1], col[], val[], columns ascending within a row,
+//           the diagonal present in every row and > 0, at most 128 entries per row -- and a fixed kappa >= 0.  The term's levels u get
+//           log p(u) = -1/2 u'Qu - 1/2 kappa (sum u)^2 in place of the iid N(0, 1) (PRIOR row 6); the scale of the effect is the term's
+//           group scale, b = exp(omega_g) u, as for every term.  lr_gpart holds per coordinate -1 or  k | slot << 10;  lr_g the slots.
+//           A GMRF term is in no pair and not structured, its columns carry no local scale and the default entries of the prior arrays.
 //   Coordinate c of a chain's vector lives in lane (c & 127) >> 1, chunk c >> 7, component c & 1.
 //
 // FORWARD, per gradient.
@@ -82,6 +88,8 @@
 //      then p = p p, h = 2 h; lambda_k = y_k;  G_{u_o} = lambda_0, G_{u_{o+k}} = c lambda_k;   AR(1): m_k = lambda_k (c dfma(c, ut_{o+k-1},
 //      -(phi u_{o+k}))), k >= 1; M[(o+k) mod 128] plain additions over chunks ascending from +0;  G_zeta = the tree over M.
 //
+// PRIOR, before the loop, [kGmrf] per slot with kappa > 0: Sr per lane component = the plain additions over chunks ascending, from +0, of
+// the member u_c (a non-member adds +0);  S = wave_sum(Sr.x, Sr.y), the canonical tree (glm_gmrf_sums).
 // PRIOR (the last loop of both forms; glm_prior_of), on the raw q (the prior of u is on u), over all D coordinates: d = q_c - mu_c; per lane component T = the sum
 // over chunks ascending of the coordinate's -2 log prior up to a constant, g_c from G_c.  [kPriors] kind_c (lr_pkind) and nu_c (lr_pnu)
 // select the row, without the flag every row is 0; padded coordinates are kind 0:
@@ -94,6 +102,14 @@
 //      tanh, log p(zeta) = eta log(1 - rho^2))   t as in stage 1:
 //                          T = T + (4 eta) ((|zeta| + dlog1p(t)) - ln 2)                g = dfma(-2 eta, rho, G)      (ln 2 rounded to a double)
 //      eta = 0: the coordinate's entry of the prior arrays applies (kinds 0 and 1).
+//   6 (internal, [kGmrf] only, like row 5; glm_gmrf_row)  a member c = o + k, u_c = q_c:
+//                          s = kappa > 0 ? kappa * S : +0;   for e = start[k] .. start[k+1]-1 ascending:  s = dfma(val[e], u_{o + col[e]}, s)
+//                          T = dfma(u_c, s, T)                                          g = G - s
+//      This states log p(u) = -1/2 u'Qu - 1/2 kappa (sum u)^2, since sum_c u_c (Qu)_c = u'Qu and sum_c u_c kappa S = kappa S^2.  The row
+//      REPLACES the coordinate's entry of the prior arrays and sits inside the loop, in chunk order: with Q = I and kappa = 0 it gives
+//      the bits of row 0 with mu = 0, tau = 1 at every L, for u and G that are not -0.  The u_{o+col} are read from vec, which holds
+//      the raw q for the duration of the loop.  Every walk is clamped as the level lists are: at most 128 trips per row, col masked
+//      into 0 .. N-1, entry positions inside the term's table -- a bad table cannot read outside vec or the table.
 // The log kinds are priors on exp(q_c) with scale exp(mu_c) and carry the Jacobian of exp (a lambda is a coordinate like any other: they
 // apply to it).  The two components of a lane, and neighbouring chunks, may be of different kinds: the kinds are branches of one function.
 // Each kind is finite wherever its log density is, and that ends at: kind 1, tau d^2 finite (|d| < 1.3e154 / sqrt(tau)); kinds 2 and 3,
@@ -118,7 +134,9 @@
 // block) of factor 0 sorted by level, positions ascending within a level, then factor 1's, .. -- and lr_fstart [n_pad / 128][sum N_f + 1]
 // where each level's list starts in them (cumulative over the factors: entry e and e + 1 bound the list of column Dd + e).  Every walk of
 // a list is clamped on the device: at most 128 trips, positions inside the block's 128 F bytes, the byte read masked to 0 .. 127, so no
-// list, whatever it held, reads outside the R tile or the wavefront's vector.  [kSlopes] lr_fval [F][n_pad] holds w (1.0 for a plain
+// list, whatever it held, reads outside the R tile or the wavefront's vector.  [kGmrf] lr_gstart [sum N + 1] (int32, cumulative over the
+// slots: the rows of slot 0, then those of slot 1), lr_gcol (int32) and lr_gval (double) hold the precisions' entries, lr_gnz the slots'
+// entry counts, lr_gkappa, lr_go, lr_gn their kappa, first column and levels.  [kSlopes] lr_fval [F][n_pad] holds w (1.0 for a plain
 // term, 0.0 in the padding, where lvl = -1 adds nothing anyway); lr_fwl [n_pad / 128][128 F] holds the same values a second time in the
 // order of lr_fpos, written by the counting sort that builds the lists, so that the value of list entry t has an address known before
 // the entry's byte arrives -- no second dependent global load behind that byte.  t is clamped as glm_list_at clamps it and the 128-trip
@@ -582,6 +600,79 @@ IDHMC_DEV void glm_struct_chain(Vec<NCH> &G, const Vec<NCH> &q, const Vec<NCH> &
     asm volatile("" ::: "memory");
     if (st.cz0 >= 0) glm_group_place<NCH>(G, M0, st.cz0, lane);
     if (st.cz1 >= 0) glm_group_place<NCH>(G, M1, st.cz1, lane);
+}
+
+// GMRF terms (Obs::kGmrf).  An entry of the level table: -1, or k | slot << 10 for level k of the term in slot 0 or 1
+constexpr int kGmrfSlot = 1024, kGmrfMask = 1023;
+constexpr int kPriorGmrf = 6;                        // the device table's mark of a member of a GMRF term; never a public kind
+// what both forms take from DevState: the slots' tables (n1 = z1 = 0 with one slot); z: the entries of a slot's precision
+struct GlmGmrf {
+    const int32_t *gpart, *start, *col;
+    const double *val;
+    double k0, k1;
+    int o0, o1, n0, n1, z0, z1;
+    template <class State>
+    IDHMC_DEV void init(const State &s)
+    {
+        gpart = s.lr_gpart;
+        start = s.lr_gstart;
+        col = s.lr_gcol;
+        val = s.lr_gval;
+        const bool two = s.lr_g > 1;
+        k0 = s.lr_gkappa[0];
+        k1 = two ? s.lr_gkappa[1] : 0.0;
+        o0 = s.lr_go[0];
+        o1 = two ? s.lr_go[1] : 0;
+        n0 = s.lr_gn[0];
+        n1 = two ? s.lr_gn[1] : 0;
+        z0 = s.lr_gnz[0];
+        z1 = two ? s.lr_gnz[1] : 0;
+    }
+};
+// S of the slots with kappa > 0 (+0 for the others): the members' u per lane component, chunks ascending from +0, then the tree
+template <int NCH>
+IDHMC_DEV void glm_gmrf_sums(const Vec<NCH> &q, const GlmGmrf &gm, int lane, double &S0, double &S1)
+{
+    const int2 *part2 = reinterpret_cast<const int2 *>(gm.gpart) + lane;
+    double2 R0 = make_double2(0.0, 0.0), R1 = R0;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 e = part2[j * 64];
+        const bool ax = e.x >= 0, ay = e.y >= 0, sx = (e.x & kGmrfSlot) != 0, sy = (e.y & kGmrfSlot) != 0;
+        R0.x = R0.x + (ax && !sx ? q.c[j].x : 0.0);
+        R0.y = R0.y + (ay && !sy ? q.c[j].y : 0.0);
+        R1.x = R1.x + (ax && sx ? q.c[j].x : 0.0);
+        R1.y = R1.y + (ay && sy ? q.c[j].y : 0.0);
+    }
+    S0 = S1 = 0.0;
+    if (gm.k0 > 0.0) S0 = wave_sum(R0.x, R0.y);
+    if (gm.k1 > 0.0) S1 = wave_sum(R1.x, R1.y);
+}
+// PRIOR row 6 for the member with table entry e >= 0 (u its coordinate, G the likelihood's part of its gradient): adds u (Qu + kappa S)
+// to T and returns g.  vec: the wavefront's own LDS vector holding the raw q, indexed by coordinate.  The walk is clamped: at most 128
+// trips, entry positions inside the slot's part of the table, col into 0 .. N-1, so vec is read inside the term's columns only.
+IDHMC_DEV double glm_gmrf_row(const GlmGmrf &gm, int e, const double *vec, double u, double S0, double S1, double G, double &T)
+{
+    const bool s1 = (e & kGmrfSlot) != 0;
+    const int k = e & kGmrfMask;
+    const int N = s1 ? gm.n1 : gm.n0, o = s1 ? gm.o1 : gm.o0;
+    const int lo = s1 ? gm.z0 : 0, hi = s1 ? gm.z0 + gm.z1 : gm.z0;
+    const double kap = s1 ? gm.k1 : gm.k0;
+    double s = kap > 0.0 ? kap * (s1 ? S1 : S0) : 0.0;
+    const int32_t *st = gm.start + (s1 ? gm.n0 : 0) + (k < N ? k : 0);
+    const int e0 = st[0];
+    int cnt = st[1] - e0;
+    cnt = cnt > 128 ? 128 : cnt;
+    cnt = hi > lo && N > 0 ? cnt : 0;
+    for (int t = 0; t < cnt; ++t) {
+        int p = e0 + t;
+        p = p < lo ? lo : p > hi - 1 ? hi - 1 : p;
+        int c = gm.col[p];
+        c = c < 0 ? 0 : c > N - 1 ? N - 1 : c;
+        s = dfma(gm.val[p], vec[o + c], s);
+    }
+    T = dfma(u, s, T);
+    return G - s;
 }
 
 // Factor terms (Obs::kFactors): what both forms take from DevState

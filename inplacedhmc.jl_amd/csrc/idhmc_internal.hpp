@@ -119,6 +119,19 @@ struct DevState {
     int32_t lr_sn[2];         // the levels of slot i
     int32_t lr_skind[2];      // IDHMC_STRUCT_AR1 or IDHMC_STRUCT_RW1
     int32_t lr_scz[2];        // the coordinate of the slot's zeta (AR(1)), -1 for a random walk
+    // Gaussian Markov random field priors on factor terms (idhmc_create_glm_gmrf; null and 0 without one): no
+    // coordinate is added.  Appended again: the kernels of a model without a GMRF term keep their instructions but for the offsets of the
+    // kernel arguments behind DevState -- and, in the kStruct kernels, which read the fields just above, the grouping of the scalar loads
+    // next to them (profiles/r22_glm_gmrf_asm_diff.txt).
+    const int32_t *lr_gpart;  // [L] -1, or for a column of a GMRF term: k | slot << 10, k its level
+    const int32_t *lr_gstart; // [sum N + 1] where each row's entries start: the rows of slot 0, then those of slot 1, cumulative
+    const int32_t *lr_gcol;   // the entries' columns, 0 .. N-1 of their slot, ascending within a row
+    const double *lr_gval;    // and their values
+    double lr_gkappa[2];      // the slot's kappa (0: no sum-to-zero term)
+    int32_t lr_g;             // GMRF terms (slots), 0..2
+    int32_t lr_go[2];         // the first column of slot i
+    int32_t lr_gn[2];         // its levels
+    int32_t lr_gnz[2];        // its entries
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -169,7 +182,7 @@ struct JitModule;
 // fills `log` (compiler output, truncated)
 // K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors),
 // s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors), s.lr_fval one whose terms read a value (kSlopes),
-// s.lr_cp > 0 one with correlated pairs (kCorr), s.lr_s > 0 one with structured terms (kStruct)
+// s.lr_cp > 0 one with correlated pairs (kCorr), s.lr_s > 0 one with structured terms (kStruct), s.lr_g > 0 one with GMRF terms (kGmrf)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmLocal, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
+from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmGmrfs, GlmLocal, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -163,7 +163,7 @@ def _prior(D, prior_mu, prior_tau):
 
 
 def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, groups=None, chains_per_response=None, prior_kind=None,
-        prior_nu=None, local=None, slab_scale=None, factors=None, correlated=None, structured=None):
+        prior_nu=None, local=None, slab_scale=None, factors=None, correlated=None, structured=None, gmrf=None):
     """A generalised linear model with the user's likelihood (include/idhmc.h, IDHMC_MODEL_GLM), the data shared by every chain:
     l(q) = sum_i log p(y_i | z_i) - 1/2 sum_c tau_c (q_c - mu_c)^2,  z = X q.
     X: (n, D) finite; Y: (n, K) or (n,) finite, K <= 4 data columns per observation; constants: up to 16 finite numbers.
@@ -251,9 +251,21 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     the log kinds are refused).  A structured term has at least 2 levels, is in no pair and carries no local scale; groups (the term's
     sampled scale), values, priors, responses and pairs among other terms compose.  glm.structured_effects() assembles groups, priors,
     correlated and structured; glm.autocorrelations(model, draws) gives phi, glm.coefficients applies the scan.  An empty list is the model
-    without the keyword.  RW2, a sum-to-zero constraint, seasonal and spatial (ICAR) structures and AR(p) are out of scope.  The Model
-    exposes S, Sz, structs (a list of glm.Structure, None without), struct_term, struct_kind (int32 (S,)) and struct_eta (float64 (S,));
-    Engine.glm_structs() reads them back."""
+    without the keyword.  RW2, a sum-to-zero constraint, seasonal and spatial (ICAR) structures are `gmrf` below; AR(p) is out of scope.
+    The Model exposes S, Sz, structs (a list of glm.Structure, None without), struct_term, struct_kind (int32 (S,)) and struct_eta
+    (float64 (S,)); Engine.glm_structs() reads them back.
+
+    gmrf: a list of up to 2 glm.gmrf(term, Q, sum_to_zero=0.0) (idhmc_create_glm_gmrf) -- a Gaussian Markov random field prior on the
+    levels u of one term: log p(u) = -1/2 u' Q u - 1/2 kappa (sum u)^2 with a sparse symmetric precision Q (dense, or an
+    (indptr, indices, data) CSR triple) and kappa = sum_to_zero, in place of the iid N(0, 1).  No coordinate is added, so D, the reported
+    vector, glm.coefficients and the device summaries are those of the model without the keyword; the scale of the effect is the term's
+    group scale.  glm.icar_precision, rw1_precision, rw2_precision and seasonal_precision build the common Q, glm.scale_precision
+    scales one to unit typical marginal variance (INLA's scale.model, BYM2's scaling); glm.gmrf_effects() assembles groups, priors and
+    gmrf.  A GMRF term is in no pair, not structured, carries no local scale and keeps the default entries of the prior arrays on its
+    columns.  A Q that is only semi-definite with sum_to_zero = 0 is accepted and improper along its null space: the likelihood has to
+    identify that direction.  AR(p), a sampled CAR or Leroux autocorrelation, the BYM2 mixing parameter and hard constraints are out of
+    scope.  The Model exposes G, gmrfs (a list of glm.Gmrf, None without), gmrf_term (int32 (G,)), gmrf_kappa (float64 (G,)) and the
+    concatenated tables gmrf_start (int64), gmrf_col (int32), gmrf_val; Engine.glm_gmrfs() reads term, kappa and the entry counts back."""
     if isinstance(aux, bool) or not isinstance(aux, (int, np.integer)) or not 0 <= aux <= 4:
         raise ValueError("aux must be an integer in 0..4 (got %r)" % (aux,))
     A = int(aux)
@@ -325,6 +337,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
         _glm.pair_priors(peta, D - Sz, mu, tau, kind, nu)
     if Sz:
         _glm.struct_priors(skind, seta, D, mu, tau, kind, nu)
+    gterm, gkappa, gstart, gcol, gval = _glm.gmrf_terms(gmrf, flev, correlated, structured, loc, Dd, mu, tau, kind, nu)
+    NG = 0 if gterm is None else gterm.size
     priors = kind is not None and bool(kind.any())
     K = Y.shape[-1]
     if H > 0 or R is not None or priors or J > 0 or F > 0:
@@ -348,6 +362,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.pairs = [_glm.Pair(int(a), int(b), float(e)) for a, b, e in zip(pfirst, psecond, peta)] if P else None
     m.S, m.Sz, m.struct_term, m.struct_kind, m.struct_eta = NS, Sz, sterm, skind, seta
     m.structs = [_glm.Structure(int(t), int(k), float(e)) for t, k, e in zip(sterm, skind, seta)] if NS else None
+    m.G, m.gmrf_term, m.gmrf_kappa, m.gmrf_start, m.gmrf_col, m.gmrf_val = NG, gterm, gkappa, gstart, gcol, gval
+    m.gmrfs = list(gmrf) if NG else None
     return m
 
 
@@ -381,7 +397,23 @@ class Engine:
             fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
                             index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
             R = getattr(model, "R", None)
-            if getattr(model, "S", 0) > 0:
+            if getattr(model, "G", 0) > 0:
+                fv = pp = st = None
+                ip = C.POINTER(C.c_int32)
+                if getattr(model, "factor_has", None) is not None:
+                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(ip)))
+                if getattr(model, "P", 0) > 0:
+                    pp = C.byref(GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
+                                          eta=_dp(model.pair_eta)))
+                if getattr(model, "S", 0) > 0:
+                    st = C.byref(GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
+                                            eta=_dp(model.struct_eta)))
+                gm = GlmGmrfs(G=model.G, term=model.gmrf_term.ctypes.data_as(ip), start=model.gmrf_start.ctypes.data_as(C.POINTER(C.c_int64)),
+                              col=model.gmrf_col.ctypes.data_as(ip), val=_dp(model.gmrf_val), kappa=_dp(model.gmrf_kappa))
+                check(self.lib.idhmc_create_glm_gmrf(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, pp, st,
+                                                     C.byref(gm), model.M if R is not None else 1, R if R is not None else 0,
+                                                     C.byref(self.opt), seed))
+            elif getattr(model, "S", 0) > 0:
                 fv = pp = None
                 ip = C.POINTER(C.c_int32)
                 if getattr(model, "factor_has", None) is not None:
@@ -603,6 +635,18 @@ class Engine:
         ip = C.POINTER(C.c_int32)
         check(self.lib.idhmc_glm_structs_get(self.h, C.byref(S), t.ctypes.data_as(ip), k.ctypes.data_as(ip), _dp(e)))
         return t, k, e
+
+    def glm_gmrfs(self):
+        """(term int32 (G,), kappa float64 (G,), nnz int64 (G,): the entries of each precision) as the context holds them
+        (GLM(..., gmrf=)); (None, None, None) for every model without a GMRF term"""
+        G = C.c_int32(0)
+        check(self.lib.idhmc_glm_gmrfs_get(self.h, C.byref(G), None, None, None))
+        if G.value == 0:
+            return None, None, None
+        t, k, z = np.zeros(G.value, np.int32), np.zeros(G.value), np.zeros(G.value, np.int64)
+        check(self.lib.idhmc_glm_gmrfs_get(self.h, C.byref(G), t.ctypes.data_as(C.POINTER(C.c_int32)), _dp(k),
+                                           z.ctypes.data_as(C.POINTER(C.c_int64))))
+        return t, k, z
 
     def synchronize(self):
         check(self.lib.idhmc_synchronize(self.h))

@@ -116,7 +116,15 @@ one term, level k being position k of the sequence.  ut_0 = u_0, ut_k = phi ut_{
 the stationary unit-variance AR(1) with a sampled phi = tanh(zeta), zeta one more coordinate at the very end of q, or the first-order
 random walk (phi = c = 1, no coordinate).  Up to two structured terms; a structured term is in no pair and takes no local scale.
 structured_effects(Dd, levels, structured) assembles groups, priors and structured; autocorrelations(model, draws) gives phi and
-coefficients(model, draws) applies the scan.  RW2, a sum-to-zero constraint, seasonal and spatial structures and AR(p) are out of scope.
+coefficients(model, draws) applies the scan.  RW2, a sum-to-zero constraint, seasonal and spatial structures are GMRF terms (below);
+AR(p) is out of scope.
+
+GMRF terms, gmrf=[gmrf(0, Q, sum_to_zero=kappa)] (idhmc_create_glm_gmrf): the levels u of one term get
+log p(u) = -1/2 u' Q u - 1/2 kappa (sum u)^2 with a sparse symmetric precision Q in place of the iid N(0, 1); no coordinate is added, so
+coefficients(), the reported vector and the device summaries are unchanged.  icar_precision(edges, N), rw1_precision(N),
+rw2_precision(N) and seasonal_precision(N, period) build the common Q, scale_precision(Q) gives it unit typical marginal variance,
+gmrf_effects(Dd, levels, gmrf) assembles groups, priors and gmrf.  Up to two GMRF terms; such a term is in no pair, not structured and
+takes no local scale.  Still out of scope: AR(p), a sampled CAR or Leroux autocorrelation, the BYM2 mixing parameter, hard constraints.
 """
 import collections
 
@@ -837,6 +845,228 @@ def structured_effects(Dd, levels, structured, correlated=None, eta=2.0, A=0, sc
     kw["prior_kind"] = np.r_[kw["prior_kind"], np.zeros(Sz, np.int32)].astype(np.int32)
     kw["prior_nu"] = np.r_[kw["prior_nu"], np.zeros(Sz)]
     kw["structured"] = structured
+    return kw
+
+
+# ---- GMRF terms: a sparse precision on a term's levels (ICAR, RW2, seasonal, generic) ---------------------------------------------------
+Gmrf = collections.namedtuple("Gmrf", "term indptr indices data kappa")
+
+
+def _csr(Q):
+    """Q, a dense symmetric array or an (indptr, indices, data) CSR triple, as (N, indptr int64, indices int32, data float64) with the
+    columns ascending within a row; a dense Q keeps its non-zero entries and its whole diagonal"""
+    if isinstance(Q, tuple) and len(Q) == 3:
+        indptr, indices, data = (np.asarray(a) for a in Q)
+        if indptr.ndim != 1 or indptr.size < 2 or indices.ndim != 1 or data.ndim != 1 or indices.size != data.size:
+            raise ValueError("Q as (indptr, indices, data): indptr of N + 1 entries and indices, data of equal length")
+        if not (np.issubdtype(indptr.dtype, np.integer) and np.issubdtype(indices.dtype, np.integer)):
+            raise ValueError("Q as (indptr, indices, data): indptr and indices must be integers")
+        if indptr[0] != 0 or indptr[-1] != data.size or (np.diff(indptr) < 0).any():
+            raise ValueError("Q as (indptr, indices, data): indptr must not decrease, from 0 to len(data)")
+        return indptr.size - 1, indptr.astype(np.int64), indices.astype(np.int32), data.astype(np.float64)
+    Q = np.asarray(Q, dtype=np.float64)
+    if Q.ndim != 2 or Q.shape[0] != Q.shape[1] or Q.shape[0] < 1:
+        raise ValueError("Q must be a square matrix or an (indptr, indices, data) triple, got shape %s" % (Q.shape,))
+    keep = (Q != 0.0) | np.eye(Q.shape[0], dtype=bool)
+    rows, cols = np.nonzero(keep)
+    return Q.shape[0], np.r_[0, np.cumsum(keep.sum(1))].astype(np.int64), cols.astype(np.int32), Q[rows, cols]
+
+
+def _dense(N, indptr, indices, data):
+    Q = np.zeros((N, N))
+    for k in range(N):
+        Q[k, indices[indptr[k]:indptr[k + 1]]] = data[indptr[k]:indptr[k + 1]]
+    return Q
+
+
+def gmrf(term, Q, sum_to_zero=0.0):
+    """a Gaussian Markov random field prior on the levels u of factor term `term` for GLM(..., gmrf=[...]):
+    log p(u) = -1/2 u' Q u - 1/2 kappa (sum u)^2, kappa = sum_to_zero >= 0 (a soft sum-to-zero constraint; 0: none).  Q: a dense
+    symmetric (N, N) array or an (indptr, indices, data) CSR triple; every row holds its positive diagonal and at most 128 entries.
+    The table's checks are idhmc_create_glm_gmrf's.  Raises ValueError when numpy.linalg.eigvalsh of the dense Q + kappa 11' has an
+    eigenvalue below -N eps ||Q||_2, the symmetric eigensolver's backward-error bound: such a Q is no precision.  A Q that is only
+    positive semi-definite with kappa = 0 (an ICAR, a random walk) is accepted and improper along its null space -- the likelihood, or
+    sum_to_zero > 0 for the constant direction, has to identify it."""
+    N, indptr, indices, data = _csr(Q)
+    k = sum_to_zero
+    if isinstance(k, bool) or not isinstance(k, (int, float, np.integer, np.floating)) or not (np.isfinite(k) and k >= 0.0):
+        raise ValueError("sum_to_zero = %r must be finite and >= 0" % (k,))
+    if N > 1024:
+        raise ValueError("Q has %d rows: a GLM is limited to D <= 1024" % N)
+    if not np.isfinite(data).all():
+        raise ValueError("Q holds a non-finite value")
+    for r in range(N):
+        cols = indices[indptr[r]:indptr[r + 1]]
+        if cols.size < 1 or cols.size > 128:
+            raise ValueError("row %d of Q has %d entries (1..128: the diagonal is always there)" % (r, cols.size))
+        if cols.min() < 0 or cols.max() >= N or (np.diff(cols) <= 0).any():
+            raise ValueError("row %d of Q: columns must be strictly ascending inside 0..%d" % (r, N - 1))
+        d = data[indptr[r]:indptr[r + 1]][cols == r]
+        if d.size != 1 or not d[0] > 0.0:
+            raise ValueError("row %d of Q: the diagonal must be present and > 0" % r)
+    dense = _dense(N, indptr, indices, data)
+    if not np.array_equal(dense, dense.T) or not np.array_equal(dense != 0.0, (dense != 0.0).T):
+        raise ValueError("Q must be symmetric: Q[i][j] and Q[j][i] both present and bit-equal")
+    pattern = np.zeros((N, N), bool)
+    for r in range(N):
+        pattern[r, indices[indptr[r]:indptr[r + 1]]] = True
+    if not np.array_equal(pattern, pattern.T):
+        raise ValueError("Q must be symmetric: Q[i][j] and Q[j][i] both present and bit-equal")
+    ev = np.linalg.eigvalsh(dense + float(k) * np.ones((N, N)))
+    if ev.min() < -N * np.finfo(np.float64).eps * np.abs(np.linalg.eigvalsh(dense)).max():
+        raise ValueError("Q + kappa 11' has the eigenvalue %g: not a precision (positive semi-definite is the least)" % ev.min())
+    return Gmrf(term, indptr, indices, data, float(k))
+
+
+def icar_precision(edges, N):
+    """D - W of an undirected graph on N regions: edges is a sequence of (i, j) pairs, i != j, each neighbourhood once in either order;
+    the intrinsic CAR's precision (rank N minus the number of connected components).  An isolated region gets the diagonal 1 (an iid
+    N(0, 1) effect), since every row needs a positive diagonal."""
+    N = int(N)
+    W = np.zeros((N, N))
+    for i, j in edges:
+        i, j = int(i), int(j)
+        if not (0 <= i < N and 0 <= j < N) or i == j:
+            raise ValueError("edge (%d, %d): two different regions of 0..%d" % (i, j, N - 1))
+        W[i, j] = W[j, i] = 1.0
+    d = W.sum(1)
+    return np.diag(np.where(d > 0.0, d, 1.0)) - W
+
+
+def _difference_precision(N, stencil):
+    """Delta' Delta of the (N - len(stencil) + 1) x N operator that applies `stencil` along the levels (small integers: exact)"""
+    m = len(stencil)
+    N = int(N)
+    if N < m:
+        raise ValueError("N = %d levels: at least %d are needed" % (N, m))
+    Dm = np.zeros((N - m + 1, N))
+    for r in range(N - m + 1):
+        Dm[r, r:r + m] = stencil
+    return Dm.T @ Dm
+
+
+def rw1_precision(N):
+    """the first-order random walk's precision, Delta' Delta of the first differences (an ICAR on a line; rank N - 1)"""
+    return _difference_precision(N, [-1.0, 1.0])
+
+
+def rw2_precision(N):
+    """the second-order random walk's precision, Delta' Delta of the second differences u_k - 2 u_{k+1} + u_{k+2} (rank N - 2: the
+    level and the slope are free) -- also a penalised spline's second-order difference penalty"""
+    return _difference_precision(N, [1.0, -2.0, 1.0])
+
+
+def seasonal_precision(N, period):
+    """the seasonal effect's precision, Delta' Delta of the sums of `period` consecutive levels (rank N - period + 1)"""
+    period = int(period)
+    if period < 2:
+        raise ValueError("period = %d: at least 2" % period)
+    return _difference_precision(N, [1.0] * period)
+
+
+def scale_precision(Q):
+    """Q scaled so that the geometric mean of the marginal variances -- the diagonal of its generalised inverse under the constraint on
+    its null space -- is 1: INLA's scale.model and BYM2's scaling, which make a group scale's prior mean the same thing for every graph.
+    Q dense symmetric positive semi-definite, N <= 1024 (host numpy: a symmetric eigendecomposition).  Returns c Q with the diagonal of
+    pinv(c Q) of geometric mean 1."""
+    Q = np.asarray(Q, dtype=np.float64)
+    if Q.ndim != 2 or Q.shape[0] != Q.shape[1] or not 1 <= Q.shape[0] <= 1024 or not np.array_equal(Q, Q.T):
+        raise ValueError("Q must be a symmetric matrix of at most 1024 rows, got shape %s" % (Q.shape,))
+    w, V = np.linalg.eigh(Q)
+    keep = w > Q.shape[0] * np.finfo(np.float64).eps * np.abs(w).max()
+    if not keep.any():
+        raise ValueError("Q has no positive eigenvalue")
+    var = ((V[:, keep] ** 2) / w[keep]).sum(1)
+    return Q * np.exp(np.mean(np.log(var)))
+
+
+def gmrf_terms(gmrfs, levels, correlated=None, structured=None, local=None, Dd=0, mu=None, tau=None, prior_kind=None, nu=None):
+    """GLM()'s validation of gmrf: (term int32 (G,), kappa float64 (G,), start int64 (sum N + 1,), col int32, val float64) -- the tables
+    of the terms one behind the other -- or five None for None and for an empty list.  The checks are idhmc_create_glm_gmrf's, naming
+    the entry."""
+    none = (None,) * 5
+    if gmrfs is None:
+        return none
+    if not isinstance(gmrfs, (list, tuple)) or isinstance(gmrfs, Gmrf):
+        raise ValueError("gmrf must be a list of glm.gmrf(term, Q, sum_to_zero), got %s" % type(gmrfs).__name__)
+    if len(gmrfs) == 0:
+        return none
+    if len(gmrfs) > 2:
+        raise ValueError("at most 2 GMRF terms (got %d)" % len(gmrfs))
+    if levels is None:
+        raise ValueError("GMRF terms need factor terms (GLM(..., factors=))")
+    F = len(levels)
+    paired, structd = {}, {}
+    for p, pr in enumerate(correlated or ()):
+        if isinstance(pr, Pair):
+            paired.setdefault(pr.first, p)
+            paired.setdefault(pr.second, p)
+    for i, st in enumerate(structured or ()):
+        if isinstance(st, Structure):
+            structd.setdefault(st.term, i)
+    off = int(Dd) + np.r_[0, np.cumsum([int(N) for N in levels])]
+    term, kappa = np.empty(len(gmrfs), np.int32), np.empty(len(gmrfs))
+    start, col, val, used = [np.zeros(1, np.int64)], [], [], set()
+    for i, e in enumerate(gmrfs):
+        if not isinstance(e, Gmrf):
+            raise ValueError("gmrf[%d] must be a glm.gmrf(term, Q, sum_to_zero)" % i)
+        t = e.term
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < F:
+            raise ValueError("gmrf[%d]: term = %r is outside 0..%d (the model's terms)" % (i, t, F - 1))
+        t = int(t)
+        if t in used:
+            raise ValueError("gmrf[%d]: term %d is listed twice" % (i, t))
+        used.add(t)
+        if e.indptr.size - 1 != int(levels[t]):
+            raise ValueError("gmrf[%d]: Q has %d rows and term %d has %d levels" % (i, e.indptr.size - 1, t, int(levels[t])))
+        if t in paired:
+            raise ValueError("gmrf[%d]: term %d is in correlated[%d] (a GMRF term is in no pair)" % (i, t, paired[t]))
+        if t in structd:
+            raise ValueError("gmrf[%d]: term %d is structured[%d] (a term is structured or a GMRF, not both)" % (i, t, structd[t]))
+        sl = slice(off[t], off[t + 1])
+        if local is not None:
+            flagged = np.flatnonzero(np.asarray(local)[sl])
+            if flagged.size:
+                raise ValueError("gmrf[%d]: local[%d] is set on level %d of term %d (a GMRF term takes no local scale)"
+                                 % (i, off[t] + flagged[0], flagged[0], t))
+        for name, arr, dflt in (("prior_mu", mu, 0.0), ("prior_tau", tau, 1.0), ("prior_kind", prior_kind, 0), ("prior_nu", nu, 0.0)):
+            if arr is not None and (np.asarray(arr)[sl] != dflt).any():
+                c = off[t] + int(np.flatnonzero(np.asarray(arr)[sl] != dflt)[0])
+                raise ValueError("gmrf[%d]: %s[%d] must be the default %r on a column of term %d: the precision is its prior" % (i, name, c, dflt, t))
+        term[i], kappa[i] = t, e.kappa
+        start.append(start[-1][-1] + e.indptr[1:].astype(np.int64))
+        col.append(e.indices.astype(np.int32))
+        val.append(e.data.astype(np.float64))
+    return (term, kappa, np.ascontiguousarray(np.concatenate(start)), np.ascontiguousarray(np.concatenate(col)),
+            np.ascontiguousarray(np.concatenate(val)))
+
+
+def gmrf_precision(model, i):
+    """the dense precision Q of the model's i-th GMRF term, from the tables the Model holds"""
+    if not 0 <= i < getattr(model, "G", 0):
+        raise ValueError("GMRF %r: the model has %d" % (i, getattr(model, "G", 0)))
+    r0 = sum(int(model.levels[int(t)]) for t in model.gmrf_term[:i])
+    N = int(model.levels[int(model.gmrf_term[i])])
+    st = model.gmrf_start[r0:r0 + N + 1]
+    return _dense(N, st - st[0], model.gmrf_col[st[0]:st[-1]], model.gmrf_val[st[0]:st[-1]])
+
+
+def gmrf_effects(Dd, levels, gmrf, structured=None, correlated=None, eta=2.0, A=0, scale=None, coefficients=None, aux=None):
+    """the keyword arguments of GLM() for GMRF effects: what structured_effects(Dd, levels, structured, correlated, eta, A, scale,
+    coefficients, aux) returns (random_intercepts(...) when neither is given), plus `gmrf` -- an ICAR effect over regions with a sampled
+    scale next to an iid one on the same index (BYM) is
+    GLM(X, Y, source, factors=[(region, N), (region, N)], **glm.gmrf_effects(X.shape[1], [N, N], [glm.gmrf(0, glm.scale_precision(glm.icar_precision(edges, N)), sum_to_zero=1e-3 * N)])).
+    Every term gets a group of its own; the columns of a GMRF term keep the default prior entries, which the precision replaces."""
+    gmrf = list(gmrf)
+    lev = [int(N) for N in levels]
+    if structured:
+        kw = structured_effects(Dd, lev, structured, correlated, eta, A, scale, coefficients, aux)
+    elif correlated:
+        kw = correlated_effects(Dd, lev, correlated, eta, A, scale, coefficients, aux)
+    else:
+        kw = random_intercepts(Dd, lev, A, scale, coefficients, aux)
+    gmrf_terms(gmrf, lev, kw.get("correlated"), kw.get("structured"))
+    kw["gmrf"] = gmrf
     return kw
 
 

@@ -70,6 +70,13 @@ coordinate), with the intercepts a first-order random walk (no coordinate), and 
 kernels of a build without the feature on the same shape.  Fixed eps and trees of the same length under --lockstep: ar1_over_plain and
 rw1_over_plain are what the scan and its mirror image cost per gradient.  Meant to run under --lockstep with --pairs ''.
 
+--gmrf-cost (GLM(..., gmrf=)) runs, per row DdxLEVELSxN of --gmrf-rows and chain count, three models on the data of
+--slope-cost: (1 + x | s) with an ICAR prior on the intercepts (the rook graph of a 10 x LEVELS/10 grid, scaled, sum_to_zero = 1), with a
+second-order random walk on them (five entries per row, no sum-to-zero term), and the same model with the iid prior, which runs the
+kernels of a build without the feature on the same shape.  No coordinate is added.  Fixed eps and trees of the same length under
+--lockstep: icar_over_plain and rw2_over_plain are what the prior's sparse rows cost per gradient.  Meant to run under --lockstep with
+--pairs ''.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
@@ -635,6 +642,10 @@ def main():
                     "sequence, a random walk, and unstructured (DESIGN section 23); use --lockstep, and --pairs '' to run nothing else")
     ap.add_argument("--struct-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 22's rows: the matrix cores and the per-wave form)")
     ap.add_argument("--struct-sides", default="ar1,rw1,plain", help="the sides of each row to run")
+    ap.add_argument("--gmrf-cost", action="store_true", help="per row of --gmrf-rows the model of --slope-cost with an ICAR prior on its first "
+                    "term, an RW2 prior, and the iid prior (DESIGN section 25); use --lockstep, and --pairs '' to run nothing else")
+    ap.add_argument("--gmrf-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 23's rows: the matrix cores and the per-wave form)")
+    ap.add_argument("--gmrf-sides", default="icar,rw2,plain", help="the sides of each row to run")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -762,6 +773,37 @@ def main():
                            " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
                           file=sys.stderr, flush=True)
                 for side in ("ar1", "rw1"):
+                    if side in row and "plain" in row:
+                        row[side + "_same_steps"] = row[side]["steps"] == row["plain"]["steps"]
+                        row[side + "_over_plain"] = row[side]["leapfrog_steps_per_s"] / row["plain"]["leapfrog_steps_per_s"]
+                res["results"].append(row)
+    if a.gmrf_cost:
+        sides = a.gmrf_sides.split(",")
+        for spec in a.gmrf_rows.split(","):
+            Dd, N, n = (int(v) for v in spec.split("x"))
+            X, y, idx, x, kw, q0, cov = slope_problem(Dd, N, n, seed=Dd * 7919 + N * 31 + n)
+            valued = [(idx, N), pkg.glm.term(idx, values=x, levels=N)]
+            cols = N // 10
+            edges = [(r * cols + c, r * cols + c + 1) for r in range(10) for c in range(cols - 1)] + \
+                    [(r * cols + c, (r + 1) * cols + c) for r in range(9) for c in range(cols)]
+            prec = {"icar": (pkg.glm.scale_precision(pkg.glm.icar_precision(edges, N)), 1.0), "rw2": (pkg.glm.rw2_precision(N), 0.0)}
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="gmrf_cost", Dd=Dd, levels=N, n=n, Dx=Dd + 2 * N, L=padded(Dd + 2 * N + 2), chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                for side in sides:
+                    if side in prec:
+                        mdl = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **pkg.glm.gmrf_effects(Dd, [N, N], [pkg.glm.gmrf(0, *prec[side])]))
+                        row[side + "_entries"] = int(mdl.gmrf_val.size)
+                    else:
+                        mdl = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **kw)
+                    runs = [run("glm_" + side, X, y, q0, np.eye(q0.size) * 1e-4, C, a.transitions, metric=metric, mdl=mdl) for _ in range(a.repeats)]
+                    r = max((u[0] for u in runs), key=lambda u: u["leapfrog_steps_per_s"])
+                    r["repeats_leapfrog_steps_per_s"] = [u[0]["leapfrog_steps_per_s"] for u in runs]
+                    row[side] = r
+                    print("# Dd=%d levels=2x%d n=%d C=%d %s (form %d): %.4e leapfrog steps/s (%s), %.3f ms/transition, create %.2f s" %
+                          (Dd, N, n, C, side, r["glm_form"], r["leapfrog_steps_per_s"],
+                           " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
+                          file=sys.stderr, flush=True)
+                for side in ("icar", "rw2"):
                     if side in row and "plain" in row:
                         row[side + "_same_steps"] = row[side]["steps"] == row["plain"]["steps"]
                         row[side + "_over_plain"] = row[side]["leapfrog_steps_per_s"] / row["plain"]["leapfrog_steps_per_s"]
