@@ -150,7 +150,9 @@ IDHMC_DEV void dlgamma_psi(double x, double &lg, double &psi)
     T = dfma_c(T, z, 1.0 / 252.0);
     T = dfma_c(T, z, -1.0 / 120.0);
     T = dfma_c(T, z, 1.0 / 12.0);
-    lg = (((w - 0.5) * lw - w) + kHalfLn2Pi) + iw * S;
+    // past 2^1000 every term but w (lw - 1) is below half an ulp of it, and (w - 0.5) * lw would overflow from 2.556e305 on, 0.15 %
+    // before ln Gamma itself does
+    lg = w > 0x1p1000 ? w * (lw - 1.0) : (((w - 0.5) * lw - w) + kHalfLn2Pi) + iw * S;
     if (x < 8.0) lg = lg - dlog(p);
     psi = ((lw - 0.5 * iw) - z * T) - h;
 }

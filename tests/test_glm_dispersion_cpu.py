@@ -47,7 +47,7 @@ static void orc_lgamma_psi(double x, double *lg, double *psi)
     T = fma(T, z, 1.0 / 252.0);
     T = fma(T, z, -1.0 / 120.0);
     T = fma(T, z, 1.0 / 12.0);
-    *lg = (((w - 0.5) * lw - w) + 9.18938533204672741780e-01) + iw * S;
+    *lg = w > 0x1p1000 ? w * (lw - 1.0) : (((w - 0.5) * lw - w) + 9.18938533204672741780e-01) + iw * S;
     if (x < 8.0) *lg = *lg - orc_log(p);
     *psi = ((lw - 0.5 * iw) - z * T) - h;
 }
