@@ -54,7 +54,10 @@
 //      [kLocal]   flagged column c, local coordinate k, id = grp[c]:   f = dexp(lambda_k);  s = id >= 0 ? e_id * f : f
 //                 no slab: st = s (h unused);   slab: i = 1 / s;  nn = dfma(i, i, inv2);  st = 1 / sqrt(nn);  h = 1 - inv2 / nn
 //                 (st = s / sqrt(1 + s^2 / S^2), h = d log st / d log s; s = inf gives st = S, h = 0; s = 0 gives st = 0, h = 1; with s below
-//                  about 1.5e-154 i i overflows and st is 0 where it should be s: an absolute error below 1.5e-154 |u| in b_c)
+//                  about 1.5e-154 i i overflows and st is 0 where it should be s: an absolute error below 1.5e-154 |u| in b_c -- the
+//                  overflow itself sits at 7.5e-155.  h is a difference: accurate to about 1e-16 absolutely and, where s >> S and
+//                  h -> 0, to no relative bound, so the likelihood's part of the gradient in
+//                  lambda and omega, u st h, carries an absolute error of about 1e-16 |u| st there; their priors' part does not)
 //                 b_c = ut_c * st;   every other column as under [H];   neither: b = ut
 //  5 z_i = the dfma chain over the stored columns c < Dd ascending of X[i][c] b_c, from +0; then [kFactors] for f = 0 .. F-1 ascending
 //        z_i = z_i + b[off_f + lvl_f[i]]  (plain addition),   [kSlopes]  z_i = dfma(w_f[i], b[off_f + lvl_f[i]], z_i)
@@ -114,7 +117,12 @@
 // apply to it).  The two components of a lane, and neighbouring chunks, may be of different kinds: the kinds are branches of one function.
 // Each kind is finite wherever its log density is, and that ends at: kind 1, tau d^2 finite (|d| < 1.3e154 / sqrt(tau)); kinds 2 and 3,
 // 2 d < 709.78 (every more negative d is fine: e = 0 and T = -2 d); kind 4, d < 709.08 (2 exp(d) finite).  Past those ends T is +inf (g may
-// be NaN), which the engine reads as l(q) = -inf: the ordinary rejected point.
+// be NaN), which the engine reads as l(q) = -inf: the ordinary rejected point.  The two t kinds also end where nu leaves what their
+// arithmetic holds: s / nu or e / nu overflowing makes T +inf where the density is finite (nu below tau d^2 / 1.8e308), and g is finite
+// while (nu + 1) a, (nu + 1) e are: kind 3's g ends at 2 d < 709.78 - log(nu + 1), before its T does.  Row 5's T is computed as a
+// difference of terms of size |zeta| + ln 2 and is accurate to about 1e-16 eta absolutely; at small zeta, where the true T is
+// 2 eta zeta^2, its relative error is unbounded (its sign included) and g = -2 eta rho, which does not cancel, is what moves the chain.
+// tests/test_glm_terms_edges_cpu.py holds every row to mpmath over these ranges and asserts each end.
 //
 // P AND l.   Per lane component (residues 2l, 2l+1 of 128):  P = dfma(2, A, T);   l = -1/2 wave_sum(P0, P1), -inf where that is not finite.
 //

@@ -1,8 +1,17 @@
 """Ready-made observation sources for GLM(X, Y, source, constants) (include/idhmc.h, IDHMC_MODEL_GLM).
 
 Each defines glm_observation(z, o, r, v): v = -log p(y | z) up to a term that depends on the data only, r = d log p(y | z) / dz.
-None of them returns a NaN for a finite z; each is finite wherever the log density itself is (Poisson: exp of the linear
-predictor below 709.78; everything else: every finite z).
+None of them returns a NaN for a finite z whose product with the count is finite (a count of 2^53 at z = 1e300 is inf - inf in the
+Poisson sources); each is finite wherever the log density itself is a double (Poisson: exp of the linear predictor below 709.78;
+STUDENT_T_IDENTITY: (y - z) / sigma finite, and below |u| = 1e100 nu inside what the arithmetic holds -- u^2 / nu, (nu + 1) |u| and
+sigma (nu + u^2) finite, which every nu between 1e-108 and 1e208 is at sigma = 1; everything else: every finite z).  Two statements hold for every source on this page,
+and tests/test_glm_terms_edges_cpu.py asserts them with every end named below:
+  * The engine accumulates -2 log p, so a chain's l(q) is finite while 2 v is.  Where v is an exponential that ends at
+    709.08 = log(max / 2), not at dexp's own 709.78: Poisson's linear predictor, Weibull's w, gamma's w and a0 + w.  Between the
+    two v, r and s are finite and l(q) reads -inf.
+  * dexp returns 0 below -708.39, where exp is below the smallest normal double 2.2e-308, so a term c exp(x) of v, r or s is dropped
+    there: an absolute error below 2.3e-308 |c| (c a count, phi, k or a distance log t - z), whatever the other terms are.  Apart from
+    that every output is within 1e-12 of the sum of the magnitudes of its terms over the whole promised range.
 
   POISSON_LOG         K = 1: y = count;                     log mu = z
   POISSON_LOG_OFFSET  K = 2: y = (count, log exposure);     log mu = z + log exposure
@@ -21,10 +30,11 @@ transform), v = -log p(y | z, a) including the terms that depend on a, r = d log
 Each is finite wherever the log density itself is, and that ends at the arguments of dexp:
   GAUSSIAN_IDENTITY_LOGSIGMA   a0 > -709.78 (exp(-a0) finite) and |y - z| exp(-a0) < 1.3e154 (its square finite); every larger a0
                                is fine (past 708.4 exp(-a0) is 0 and v = a0).  In particular every |a0| <= 300 with |y - z| <= 1e3.
-  STUDENT_T_IDENTITY_LOGSIGMA  -708.39 < a0 < 709.78 (sigma = exp(a0) neither 0 nor inf) and (y - z) / sigma finite.  In
-                               particular every |a0| <= 700 with |y - z| <= 1e3.
-  WEIBULL_LOG_LOGSHAPE         a0 < 709.78 (k = exp(a0) finite) and w = k (log t - z) < 709.78 (the cumulative hazard exp(w)
-                               finite); every more negative w is fine.
+  STUDENT_T_IDENTITY_LOGSIGMA  a0 > -708.39 (sigma = exp(a0) not 0) and (y - z) / sigma finite; every larger a0 is fine (past 709.78
+                               sigma is inf, u is 0 and v = a0); nu as for STUDENT_T_IDENTITY, and sigma (nu + u^2) a normal double
+                               (it is a product here).  In particular every |a0| <= 700 with |y - z| <= 1e3 at nu = 1 .. 4.
+  WEIBULL_LOG_LOGSHAPE         a0 < 709.78 (k = exp(a0) finite) and w = k (log t - z) < 709.08 (twice the cumulative hazard exp(w)
+                               finite); every more negative finite w is fine (the score w H leaves the doubles before v does).
 Past those ends v is +inf or NaN, which the engine reads as l(q) = -inf: the ordinary rejected point.
 
 Sources whose sampled dispersion sits inside a gamma function, for GLM(..., aux=1); a[0] is the log of the
@@ -40,12 +50,14 @@ Each is finite wherever the log density itself is, and that ends at:
   NEG_BINOMIAL_LOG_LOGPHI  -708.39 < a0 < 703 (phi = exp(a0) not 0, ln Gamma(phi) finite); every |a0| <= 700 with |z| <= 700.
                            At large phi the score phi (psi(y + phi) - psi(phi) - softplus(z - a0)) is a difference of terms of
                            size phi |psi(phi)| and loses about phi 1e-16 |psi(phi)| absolutely as the model approaches its
-                           Poisson limit (1e-10 at phi = 1e5): stated, not engineered around.
-  GAMMA_LOG_LOGSHAPE       -708.39 < a0 < 703 (k = exp(a0) not 0, ln Gamma(k) finite) and k exp(log y - z) finite: w = log y - z
-                           below 709.78 and a0 + w below 709.78; every more negative w is fine.
+                           Poisson limit (1e-10 at phi = 1e5; measured against mpmath: at most 1.3 times that for
+                           phi = 1e5 .. 1e15, counts 0 .. 7 and mu <= phi): stated, not engineered around.
+  GAMMA_LOG_LOGSHAPE       -708.39 < a0 < 703 (k = exp(a0) not 0, ln Gamma(k) finite) and 2 k exp(log y - z) finite: w = log y - z
+                           below 709.08 and a0 + w below 709.08; every more negative w is fine.
   BETA_LOGIT_LOGPHI        -708.39 < a0 < 703 (phi not 0, ln Gamma(phi) finite) and p = phi sigma(z), q = phi sigma(-z) both at
                            least 2.3e-308 (a p or q that underflows to 0 has ln Gamma = +inf, a subnormal one psi = -inf):
-                           -|z| + a0 > -708.  In particular |z| <= 700 with -5 <= a0 <= 700, and |z| <= 40 with |a0| <= 650.
+                           -|z| + a0 > -708 and |z| < 708.39 (past it exp(-|z|) is 0 and so is p or q, whatever a0).  In particular
+                           |z| <= 700 with -5 <= a0 <= 700, and |z| <= 40 with |a0| <= 650.
 Past those ends v is +inf or NaN as above.
 
 Every source above works unchanged with coefficient groups, GLM(..., groups=...): the sampled coordinates are
@@ -70,11 +82,15 @@ group scales) -- and include the Jacobian of exp; they take tau = 1.  priors(Dx,
 four keyword arguments from normal(), student_t(), half_normal(), half_student_t() and exponential().
 
 Each is finite wherever the log density itself is, and that ends at the arguments of dexp and at the square of d:
-  PRIOR_STUDENT_T           tau d^2 finite: |d| < 1.3e154 / sqrt(tau).
+  PRIOR_STUDENT_T           tau d^2 finite: |d| < 1.3e154 / sqrt(tau); and nu inside what the row's arithmetic holds: tau d^2 / nu
+                            finite (below it -2 log p is +inf where the density is not) and (nu + 1) tau |d| finite (the gradient).
   PRIOR_LOG_HALF_NORMAL     2 d < 709.78 (exp(2 d) finite); every more negative d is fine (exp(2 d) is 0 and -2 log p = -2 d).
-  PRIOR_LOG_HALF_STUDENT_T  2 d < 709.78, as above.
+  PRIOR_LOG_HALF_STUDENT_T  2 d < 709.78, as above, for -2 log p; its gradient is finite while (nu + 1) exp(2 d) is:
+                            2 d < 709.78 - log(nu + 1); and exp(2 d) / nu finite, as for PRIOR_STUDENT_T.
   PRIOR_LOG_EXPONENTIAL     d < 709.08 (2 exp(d) finite); every more negative d is fine.
-Past those ends -2 log p is +inf, which the engine reads as l(q) = -inf: the ordinary rejected point.
+Past those ends -2 log p is +inf, which the engine reads as l(q) = -inf: the ordinary rejected point.  Inside them each row is
+within 1e-12 of the magnitude of its terms, with the floor 2.3e-308 max(1, nu + 1, (nu + 1) / nu) for the two t kinds: tau d, tau d^2
+and their quotient by nu are multiples of 4.9e-324 once they are in the subnormals.
 
 Per-coefficient local scales, GLM(..., local=..., slab_scale=...) (idhmc_create_glm_local): the horseshoe and its
 regularised form, and every source above works unchanged with them.  The J flagged columns of X, in ascending column order, each get
@@ -84,9 +100,12 @@ slab and st = s / sqrt(1 + s^2 / S^2) with the fixed slab scale S (evaluated as 
 local_scales(model, draws) gives exp(lambda), coefficients() and group_scales() take the longer vector, priors(Dx, A, H, J,
 local_scales=...) has the fourth role, and horseshoe(Dx, columns, global_scale, ...) assembles the whole model: u ~ N(0, 1),
 half-t(nu_local) on every local scale, half-t(nu_global, global_scale) on the scale of the group the columns form.
-With a slab every finite q is finite.  Without one, omega_g + lambda_k past 709.78 makes s infinite and the coefficient infinite or
+With a slab every finite q is finite but for one corner, omega_g past 709.78 met by lambda_k below -708.39 or the reverse: inf * 0
+is NaN, the rejected point (and accurate while omega_g and lambda_k are each above -708.39: below it dexp gives 0 and
+the product with the other factor is lost, whatever its size).  Without one, omega_g + lambda_k past 709.78 makes s infinite and the coefficient infinite or
 NaN: l reads as -inf, the ordinary rejected point.  With a slab and s below about 1.5e-154 the square of 1 / s overflows and st is 0
-where it should be s: an absolute error below 1.5e-154 |u| in the coefficient, stated and not engineered around.
+where it should be s: an absolute error below 1.5e-154 |u| in the coefficient (the overflow itself sits at 7.5e-155), stated and not
+engineered around.  d log st / d log s is formed as a difference and is accurate to 1e-16 absolutely, not relatively, where s >> S.
 
 Factor terms by level index, GLM(..., factors=[idx, ...]) (idhmc_create_glm_factors): a random intercept per subject,
 site or item, (1 | subject), and every source above works unchanged with them.  X holds the Dd dense columns; factor f has N_f levels and
