@@ -417,7 +417,7 @@ int idhmc_glm_factor_values_get(const idhmc_ctx *ctx, int32_t *has, double *valu
  *   T = T + (4 eta) * ((|zeta| + dlog1p(t)) - ln 2);   g = dfma(-2 eta, rho, G)
  * and the entries of zeta_p in mu, tau, kind and nu must be the defaults (0, 1, 0, 0) and are not applied.  eta[p] == 0: those entries
  * apply as to any coordinate, kinds 0 and 1 (normal or Student-t on Fisher's z); the log kinds are refused, as on a coefficient.
- * Covariance among three or more terms is out of scope.
+ * A covariance among three or four terms is a correlation block (idhmc_create_glm_block below).
  *
  * idhmc_create_glm_corr is idhmc_create_glm_slopes with these; mu, tau, kind and nu have D entries, the zetas last.  pairs == NULL or
  * P == 0 gives exactly the context of idhmc_create_glm_slopes: the same kernels, bits and footprint.  No LDS is added.  Refused with
@@ -512,6 +512,46 @@ int idhmc_create_glm_gmrf(idhmc_ctx **out, int device, int64_t nchains, int64_t 
 /* *G, and with non-NULL arrays term, kappa and nnz (the entries of each term's precision; G entries each) as the context was given
  * them; 0 for every other context */
 int idhmc_glm_gmrfs_get(const idhmc_ctx *ctx, int32_t *G, int32_t *term, double *kappa, int64_t *nnz);
+/* A correlation block of three or four factor terms: (1 + x1 + x2 | subject) with a sampled K x K correlation
+ * matrix.  A model with factor terms may name ONE block of K in {2, 3, 4} distinct terms term[0 .. K-1], all of N levels, with values or
+ * without, on one index array or several.  The order of term[] is the row order of L and is the caller's: level k of every term belongs
+ * together, c_j = off_{term[j]} + k.  A model has pairs or a block, not both (K = 2 is the pair, bit for bit).  The block adds
+ * K (K - 1) / 2 coordinates zeta_ji = atanh z_ji, 1 <= j < K, 0 <= i < j, where the pairs' zetas stand, row-major:
+ *   q = [u (Dx) | a (A) | omega (H) | lambda (J) | zeta_block | zeta_ar (Sz)],   zeta_ji is coordinate cz0 + j (j - 1) / 2 + i,   D <= 1024.
+ * z_ji are the canonical partial correlations of R = L L'.  Per gradient (plain IEEE operations in the association written):
+ *   (z_ji, c_ji) from zeta_ji by the expressions of idhmc_create_glm_corr (rho and c there), the same bits in every lane;
+ *   coef(j, m, .) for -1 <= m < j:  s = 1; for i = m+1 .. j-1: coef(j,m,i) = z_ji * s, then s = s * c_ji; coef(j,m,j) = s, and where s
+ *   is still the initial 1 the other factor is taken itself (no multiplication);  L_ji = coef(j, -1, i), L_00 = 1;
+ *   r_jm = c_j0 * .. * c_j,m-1 left to right, r_j0 = 1.
+ *   mix:     ut_{c_0} = u_{c_0};  j >= 1: x = L_jj * u_{c_j}; for i = 0 .. j-1 ascending x = dfma(L_ji, u_{c_i}, x); ut_{c_j} = x.
+ * Everything the sections above define runs on ut; the prior of u stays on u.  After the chain rules have left Gh = dl / dut:
+ *   zeta_jm: w = coef(j,m,j) * u_{c_j} (u_{c_j} itself when j = m + 1); for i = m+1 .. j-1 ascending w = dfma(coef(j,m,i), u_{c_i}, w);
+ *            e = c_jm * dfma(c_jm, u_{c_m}, -(z_jm * w));  m >= 1: e = r_jm * e;   m_k = Gh_{c_j} * e;
+ *            M_jm[c_j mod 128]: plain additions over chunks ascending, from +0;  G_zeta_jm = the canonical 128-residue tree over M_jm;
+ *   then, from the Gh before any is overwritten:  G_{c_i} = (i == 0 ? Gh_{c_0} : L_ii * Gh_{c_i});
+ *            for j = i+1 .. K-1 ascending G_{c_i} = dfma(L_ji, Gh_{c_j}, G_{c_i}).
+ * eta > 0 is LKJ(eta) on R, which is separable in the partial correlations: zeta_ji gets the LKJ row of idhmc_create_glm_corr with the
+ * exponent beta_ji = eta + (K - 2 - i) / 2 (i the COLUMN), and the zetas' entries of mu, tau, kind and nu must be the defaults and are
+ * not applied.  eta == 0: those entries apply (kinds 0 and 1; the log kinds are refused).  The reported correlations are
+ *   R_j0 = z_j0;   i >= 1: x = L_ji * L_ii; for k = 0 .. i-1 ascending x = dfma(L_jk, L_ik, x); R_ji = x,
+ * and the device summaries report [beta | a | sigma | exp lambda | R (row-major lower triangle) | phi].  Groups, local scales (also on
+ * block columns), priors, values, several responses and an AR(1) or random-walk structure on a remaining term compose; a GMRF prior on a
+ * remaining term is accepted too (the device tests cover no GMRF term next to a block).
+ * Out of scope: more than one block, K > 4, a block next to pairs, a block term that is structured or a GMRF term.
+ *
+ * idhmc_create_glm_block is idhmc_create_glm_gmrf with these.  block == NULL or K == 0 gives exactly the context of
+ * idhmc_create_glm_gmrf: the same kernels, bits and footprint.  No LDS is added.  Refused with IDHMC_ERR_BAD_ARG before the device is
+ * touched: K not in {0, 2, 3, 4}; term NULL; a term outside 0..F-1 or listed twice; unequal level counts; eta negative or not finite;
+ * eta > 0 with a non-default prior entry on one of the zetas; a log kind on a zeta; a block together with pairs; a block term that is
+ * structured or a GMRF term; a block without factors; D > 1024 counting the zetas; and everything idhmc_create_glm_gmrf refuses. */
+typedef struct { int32_t K; const int32_t *term; double eta; } idhmc_glm_block;
+int idhmc_create_glm_block(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                           const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                           const idhmc_glm_structs *structs, const idhmc_glm_gmrfs *gmrfs, const idhmc_glm_block *block,
+                           int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
+/* *K, and with non-NULL term (K entries) and eta as the context was given them; 0 for every other context */
+int idhmc_glm_block_get(const idhmc_ctx *ctx, int32_t *K, int32_t *term, double *eta);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

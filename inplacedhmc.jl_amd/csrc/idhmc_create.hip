@@ -81,6 +81,9 @@ struct GlmParts {
     const int32_t *gterm = nullptr, *gcol = nullptr;       // [G], and the entries' columns, G > 0 (never null then; every entry checked)
     const int64_t *gstart = nullptr;   // [sum N + 1]
     const double *gval = nullptr, *gkappa = nullptr;       // the entries' values, [G]
+    int32_t BK = 0, BZ = 0;    // idhmc_create_glm_block: the block's terms K and its zetas K (K - 1) / 2, which stand where the pairs' would
+    const int32_t *bterm = nullptr;    // [BK] the terms in row order, BK > 0 (never null then; every entry checked)
+    double beta = 0.0;         // the block's eta
 };
 // the padded width of the stored columns of X: L of the model, and with factors Lx = 128 ceil(Dd / 128)
 static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
@@ -88,7 +91,7 @@ static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
     int64_t L = 128;
     while (L < D) L *= 2;
     if (L_out) *L_out = L;
-    return g.F > 0 ? ((int64_t)D - g.A - g.H - g.J - g.P - g.SZ - g.fcols + 127) / 128 * 128 : L;
+    return g.F > 0 ? ((int64_t)D - g.A - g.H - g.J - g.P - g.BZ - g.SZ - g.fcols + 127) / 128 * 128 : L;
 }
 // The head of a packed params array into *g: `head` = 0 (a logistic regression's [X | y]), 2 ([K, nc, c | X | Y]) or 3
 // ([K, nc, A, c | X | Y]) doubles in front of the constants.  The entries are checked as doubles (integral, hence finite, and in
@@ -164,7 +167,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
         }
     }
     const int64_t n = g.n, K = g.K, M = g.M;
-    const int64_t Dx = D - g.A - g.H - g.J - g.P - g.SZ - g.fcols;      // the columns of X (with factors: the dense ones)
+    const int64_t Dx = D - g.A - g.H - g.J - g.P - g.BZ - g.SZ - g.fcols;      // the columns of X (with factors: the dense ones)
     const int64_t L = stored_width(g, D);
     const int64_t npad = (n + 127) / 128 * 128;
     if (npad * L > ((int64_t)1 << 27))
@@ -205,7 +208,7 @@ static int validate_regression(const GlmParts &g, bool glm, const idhmc_model_de
 static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
 {
     DevState &s = c->s;
-    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, Dm = s.D - g.A - g.H - g.J - g.P - g.SZ, K = g.K, M = g.M;    // Dm: the columns of the model
+    const int64_t n = g.n, npad = (n + 127) / 128 * 128, L = s.L, Dm = s.D - g.A - g.H - g.J - g.P - g.BZ - g.SZ, K = g.K, M = g.M;    // Dm: the columns of the model
     const int64_t D = Dm - g.fcols, LX = stored_width(g, s.D);      // the columns X stores (with factors: the dense ones) and their padded width
     // The level lists of a model with factors, before anything is uploaded: per block of 128 observations its places sorted by factor,
     // level, place (a counting sort), and where each level's list starts
@@ -301,7 +304,7 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
     if (g.J > 0) {
         // the partner of every coordinate: the k-th flagged column (ascending) and coordinate Dx + A + H + k name each other
         hp.assign((size_t)L, -1);
-        int64_t k = s.D - g.SZ - g.P - g.J;
+        int64_t k = s.D - g.SZ - g.P - g.BZ - g.J;
         for (int64_t col = 0; col < Dm; ++col)
             if (g.local[col]) { hp[(size_t)col] = (int32_t)k; hp[(size_t)k] = (int32_t)col; ++k; }
         int32_t *dp = nullptr;
@@ -367,6 +370,24 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
         c->glm_pfirst.assign(g.pfirst, g.pfirst + g.P);
         c->glm_psecond.assign(g.psecond, g.psecond + g.P);
         c->glm_peta.assign(g.peta, g.peta + g.P);
+    }
+    std::vector<int32_t> hbp;
+    if (g.BK > 0) {
+        // the level and the row of every column of a block term; row r is term bterm[r]
+        hbp.assign((size_t)L, -1);
+        for (int r = 0; r < g.BK; ++r) {
+            const int32_t o = s.lr_foff[g.bterm[r]];
+            for (int32_t k = 0; k < g.levels[g.bterm[r]]; ++k) hbp[(size_t)(o + k)] = k | (r << 10);
+            s.lr_boff[r] = o;
+        }
+        for (int r = g.BK; r < 4; ++r) s.lr_boff[r] = s.lr_boff[0];
+        int32_t *dbp = nullptr;
+        if (int rc = dalloc(c, &dbp, L)) return rc;
+        HIPCHK(hipMemcpyAsync(dbp, hbp.data(), sizeof(int32_t) * hbp.size(), hipMemcpyHostToDevice, c->stream));
+        s.lr_bpart = dbp;
+        s.lr_bk = g.BK;
+        c->glm_bterm.assign(g.bterm, g.bterm + g.BK);
+        c->glm_beta = g.beta;
     }
     std::vector<int32_t> hsp;
     if (g.S > 0) {
@@ -838,7 +859,8 @@ static int validate_pairs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
 // and the local flags, and of the AR(1) zetas' entries in the prior arrays (coordinate cz0 onwards).  *S: the structured terms (0: the
 // context is the one of idhmc_create_glm_corr), *SZ: those that are AR(1)
 static int validate_structs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, const idhmc_glm_local *local, int J, int P,
-                            const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_pairs *pp, const idhmc_glm_structs *st, int *S, int *SZ)
+                            const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_pairs *pp, const idhmc_glm_structs *st, int *S, int *SZ,
+                            int BZ = 0)      // BZ: the zetas of a block, which stand in front of the AR(1) zetas as the pairs' do
 {
     *S = *SZ = 0;
     if (!st) return IDHMC_OK;
@@ -849,10 +871,10 @@ static int validate_structs(const idhmc_glm_desc *glm, const idhmc_glm_priors *p
     if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: structured terms need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
     int sz = 0;
     for (int i = 0; i < st->S; ++i) sz += st->kind[i] == IDHMC_STRUCT_AR1;
-    if (glm->Dx + J + P + sz > 1024 - glm->A - glm->H)
+    if (glm->Dx + J + P + BZ + sz > 1024 - glm->A - glm->H)
         return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + P + Sz = %lld: a GLM is limited to D <= 1024 (Sz = %d AR(1) terms)",
-                    (long long)glm->Dx + glm->A + glm->H + J + P + sz, sz);
-    const int cz0 = glm->Dx + glm->A + glm->H + J + P;
+                    (long long)glm->Dx + glm->A + glm->H + J + P + BZ + sz, sz);
+    const int cz0 = glm->Dx + glm->A + glm->H + J + P + BZ;
     int z = 0;
     for (int i = 0; i < st->S; ++i) {
         const int32_t t = st->term[i], kd = st->kind[i];
@@ -977,14 +999,64 @@ static int validate_gmrfs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
     return IDHMC_OK;
 }
 
+// The block of idhmc_create_glm_block, after validate_gmrfs: every check of K, term and eta, of the terms against the pairs, the
+// structures and the GMRF terms, and of the zetas' entries in the prior arrays (coordinate Dx + A + H + J onwards).  *K: the block's
+// terms (0: the context is the one of idhmc_create_glm_gmrf)
+static int validate_block(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, int J, int P, int S, int SZ, int G, const idhmc_glm_factors *fc,
+                          int64_t fcols, const idhmc_glm_structs *st, const idhmc_glm_gmrfs *gm, const idhmc_glm_block *bk, int *K)
+{
+    *K = 0;
+    if (!bk) return IDHMC_OK;
+    if (bk->K != 0 && (bk->K < 2 || bk->K > 4)) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block of K = %d terms: K must be 0, 2, 3 or 4", bk->K);
+    if (bk->K == 0) return IDHMC_OK;
+    if (!bk->term) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block of K = %d terms needs term (term is NULL)", bk->K);
+    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block needs factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (P > 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block next to P = %d pairs (a model has pairs or a block, not both)", P);
+    const int nz = (bk->K * (bk->K - 1)) / 2;
+    if (glm->Dx + J + nz + SZ > 1024 - glm->A - glm->H)
+        return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + K (K - 1) / 2 + Sz = %lld: a GLM is limited to D <= 1024 (a block of K = %d terms)",
+                    (long long)glm->Dx + glm->A + glm->H + J + nz + SZ, bk->K);
+    for (int r = 0; r < bk->K; ++r) {
+        const int32_t t = bk->term[r];
+        if (t < 0 || t >= fc->F) return fail(IDHMC_ERR_BAD_ARG, "GLM: block row %d: term = %d is outside 0..%d (the model's terms)", r, t, fc->F - 1);
+        for (int q = 0; q < r; ++q)
+            if (bk->term[q] == t) return fail(IDHMC_ERR_BAD_ARG, "GLM: block row %d: term %d is listed twice", r, t);
+        if (fc->levels[t] != fc->levels[bk->term[0]])
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: block row %d: terms %d and %d have %d and %d levels (a block needs equal level counts)", r,
+                        bk->term[0], t, fc->levels[bk->term[0]], fc->levels[t]);
+        for (int i = 0; i < S; ++i)
+            if (st->term[i] == t) return fail(IDHMC_ERR_BAD_ARG, "GLM: block row %d: term %d is structure %d (a block term is not structured)", r, t, i);
+        for (int i = 0; i < G; ++i)
+            if (gm->term[i] == t) return fail(IDHMC_ERR_BAD_ARG, "GLM: block row %d: term %d is GMRF %d (a block term is no GMRF term)", r, t, i);
+    }
+    const double eta = bk->eta;
+    if (!(std::isfinite(eta) && eta >= 0.0)) return fail(IDHMC_ERR_BAD_ARG, "GLM: block: eta = %g must be finite and >= 0 (0: the prior arrays' entries apply)", eta);
+    const int cz0 = glm->Dx + glm->A + glm->H + J;
+    for (int e = 0; e < nz; ++e) {
+        const int cz = cz0 + e;
+        const int32_t k = pr && pr->kind ? pr->kind[cz] : 0;
+        if (k >= IDHMC_PRIOR_LOG_HALF_NORMAL && k <= IDHMC_PRIOR_LOG_EXPONENTIAL)
+            return fail(IDHMC_ERR_BAD_ARG, "GLM: block: prior kind[%d] = %d is a prior on exp(q): coordinate %d is a zeta = atanh z, not a logarithm "
+                        "(kinds 0 and 1 are for a zeta)", cz, k, cz);
+        if (eta > 0.0) {
+            const double nu = pr && pr->kind && pr->nu ? pr->nu[cz] : 0.0;
+            if (k != 0 || nu != 0.0 || (glm->mu && glm->mu[cz] != 0.0) || (glm->tau && glm->tau[cz] != 1.0))
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: block: eta = %g is the LKJ prior of the zetas: the entry of coordinate %d in the prior arrays must "
+                            "be the default (kind 0, mu 0, tau 1, nu 0) and is not applied", eta, cz);
+        }
+    }
+    *K = bk->K;
+    return IDHMC_OK;
+}
+
 // idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors,
-// idhmc_create_glm_slopes, idhmc_create_glm_corr, idhmc_create_glm_struct and idhmc_create_glm_gmrf
+// idhmc_create_glm_slopes, idhmc_create_glm_corr, idhmc_create_glm_struct, idhmc_create_glm_gmrf and idhmc_create_glm_block
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
                       const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
                       const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr,
                       const idhmc_glm_pairs *pairs = nullptr, const idhmc_glm_structs *structs = nullptr,
-                      const idhmc_glm_gmrfs *gmrfs = nullptr)
+                      const idhmc_glm_gmrfs *gmrfs = nullptr, const idhmc_glm_block *block = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
@@ -1006,10 +1078,23 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
                     (long long)glm->Dx + glm->A + glm->H + J + pairs->P, pairs->P);
     int P = 0;
     if (int rc = validate_pairs(glm, priors, J, factors, fcols, pairs, &P)) return rc;
+    // (the AR(1) zetas stand behind the block's as behind the pairs': a well-formed block's count goes where P goes, and validate_block,
+    // which needs S and G, then checks the block itself)
+    const int BZ0 = P == 0 && block && block->K >= 2 && block->K <= 4 ? (block->K * (block->K - 1)) / 2 : 0;
     int S = 0, SZ = 0;
-    if (int rc = validate_structs(glm, priors, local, J, P, factors, fcols, pairs, structs, &S, &SZ)) return rc;
+    if (BZ0 == 0) {
+        if (int rc = validate_structs(glm, priors, local, J, P, factors, fcols, pairs, structs, &S, &SZ)) return rc;
+    } else {
+        if (glm->Dx + J + BZ0 > 1024 - glm->A - glm->H)
+            return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + K (K - 1) / 2 = %lld: a GLM is limited to D <= 1024 (a block of K = %d terms)",
+                        (long long)glm->Dx + glm->A + glm->H + J + BZ0, block->K);
+        if (int rc = validate_structs(glm, priors, local, J, P, factors, fcols, pairs, structs, &S, &SZ, BZ0)) return rc;
+    }
     int G = 0;
     if (int rc = validate_gmrfs(glm, priors, local, J, P, S, factors, fcols, pairs, structs, gmrfs, &G)) return rc;
+    int BK = 0;
+    if (int rc = validate_block(glm, priors, J, P, S, SZ, G, factors, fcols, structs, gmrfs, block, &BK)) return rc;
+    const int BZ = (BK * (BK - 1)) / 2;
     if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
     if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
     if (glm->H > 0) {
@@ -1025,13 +1110,13 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     idhmc_model_desc m;
     memset(&m, 0, sizeof m);
     m.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM;
-    m.D = glm->Dx + glm->A + glm->H + J + P + SZ;
+    m.D = glm->Dx + glm->A + glm->H + J + P + BZ + SZ;
     m.mu = glm->mu;
     m.tau = glm->tau;
     m.source = glm->source;
     std::vector<double> nu;
     bool any = false;
-    if (int rc = validate_priors(glm, priors, J + P + SZ, &nu, &any)) return rc;
+    if (int rc = validate_priors(glm, priors, J + P + BZ + SZ, &nu, &any)) return rc;
     GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
     if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
     if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
@@ -1042,8 +1127,9 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (P > 0) { parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta; }
     if (S > 0) { parts.S = S; parts.SZ = SZ; parts.sterm = structs->term; parts.skind = structs->kind; parts.seta = structs->eta; }
     if (G > 0) { parts.G = G; parts.gterm = gmrfs->term; parts.gstart = gmrfs->start; parts.gcol = gmrfs->col; parts.gval = gmrfs->val; parts.gkappa = gmrfs->kappa; }
-    if (P > 0 || SZ > 0 || G > 0) {
-        bool lkj = G > 0;                // (a GMRF term's members are marked too: kPriorGmrf)
+    if (BK > 0) { parts.BK = BK; parts.BZ = BZ; parts.bterm = block->term; parts.beta = block->eta; }
+    if (P > 0 || SZ > 0 || G > 0 || BK > 0) {
+        bool lkj = G > 0 || (BK > 0 && block->eta > 0.0);      // (a GMRF term's members are marked too: kPriorGmrf)
         for (int p = 0; p < P; ++p) lkj = lkj || pairs->eta[p] > 0.0;
         for (int i = 0; i < S; ++i) lkj = lkj || structs->eta[i] > 0.0;
         if (lkj) {
@@ -1054,6 +1140,14 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
             nudev = nupub;
             for (int p = 0; p < P; ++p)
                 if (pairs->eta[p] > 0.0) { kdev[(size_t)(m.D - SZ - P + p)] = 5; nudev[(size_t)(m.D - SZ - P + p)] = pairs->eta[p]; }
+            // LKJ(eta) on the block's K x K matrix: zeta_ji takes the row with beta_ji = eta + (K - 2 - i) / 2, i its column
+            if (BK > 0 && block->eta > 0.0)
+                for (int j = 1; j < BK; ++j)
+                    for (int i = 0; i < j; ++i) {
+                        const size_t cz = (size_t)(m.D - SZ - BZ + (j * (j - 1)) / 2 + i);
+                        kdev[cz] = 5;
+                        nudev[cz] = block->eta + 0.5 * (double)(BK - 2 - i);
+                    }
             for (int i = 0, z = 0; i < S; ++i) {
                 if (structs->kind[i] != IDHMC_STRUCT_AR1) continue;
                 if (structs->eta[i] > 0.0) { kdev[(size_t)(m.D - SZ + z)] = 5; nudev[(size_t)(m.D - SZ + z)] = structs->eta[i]; }
@@ -1158,6 +1252,27 @@ int idhmc_create_glm_gmrf(idhmc_ctx **out, int device, int64_t nchains, int64_t 
                       pairs, structs, gmrfs);
 }
 
+int idhmc_create_glm_block(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                           const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                           const idhmc_glm_structs *structs, const idhmc_glm_gmrfs *gmrfs, const idhmc_glm_block *block,
+                           int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_block: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
+                      pairs, structs, gmrfs, block);
+}
+
+int idhmc_glm_block_get(const idhmc_ctx *c, int32_t *K, int32_t *term, double *eta)
+{
+    if (!c || !K) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_block_get: null argument");
+    *K = c->s.lr_bk;
+    if (term) std::copy(c->glm_bterm.begin(), c->glm_bterm.end(), term);
+    if (eta) *eta = c->glm_beta;
+    return IDHMC_OK;
+}
+
 int idhmc_glm_gmrfs_get(const idhmc_ctx *c, int32_t *G, int32_t *term, double *kappa, int64_t *nnz)
 {
     if (!c || !G) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_gmrfs_get: null argument");
@@ -1208,7 +1323,7 @@ int idhmc_glm_factors_get(const idhmc_ctx *c, int32_t *F, int32_t *levels, int32
 int idhmc_glm_local_get(const idhmc_ctx *c, int32_t *local, double *slab_scale)
 {
     if (!c || !local || !slab_scale) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_local_get: null argument");
-    const int Dx = c->s.D - c->s.lr_a - c->s.lr_h - c->s.lr_j - c->s.lr_cp - c->s.lr_sz;
+    const int Dx = c->s.D - c->s.lr_a - c->s.lr_h - c->s.lr_j - c->s.lr_cp - block_zetas(c->s.lr_bk) - c->s.lr_sz;
     for (int k = 0; k < Dx; ++k) local[k] = c->glm_local.empty() ? 0 : c->glm_local[(size_t)k];
     *slab_scale = c->slab_scale;
     return IDHMC_OK;

@@ -1,4 +1,4 @@
-// idhmc_glm.hpp -- the two forms that evaluate a generalised linear model (DESIGN sections 10-25).  The arithmetic, stage by stage for
+// idhmc_glm.hpp -- the two forms that evaluate a generalised linear model (DESIGN sections 10-26).  The arithmetic, stage by stage for
 // the full model, the device layout and every helper that does not depend on the form are in idhmc_glm_coords.hpp; the stage numbers
 // below are that header's.  Two forms with one arithmetic: GlmWave (one chain per wavefront, every kernel) and GlmCoop (the NUTS kernel
 // at L <= 256: 16 chains per workgroup, both products on the fp64 matrix cores).  The built-in logistic regression
@@ -27,7 +27,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
     static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false,
-                          kGmrf = false;
+                          kGmrf = false, kBlock = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -44,7 +44,8 @@ struct LogisticObs {
 // zx)); the stored-column loop touches the chunks j < Lx / 128 only -- one loop, whose stride and chunk bound are compile-time constants
 // without factors --; after it each lane walks the lists of its level columns over r staged in buf[0 .. 127] (glm_gather: G + r[ii],
 // [kSlopes] dfma(wl, r[ii], G)).  [kGmrf] once every chain rule has run, the raw q is staged in buf a last time and stays there for the
-// prior loop: row 6 of a member reads its neighbours' u from it.
+// prior loop: row 6 of a member reads its neighbours' u from it.  [kBlock] the block's factors and its mix take the pairs' places
+// (a model has one or the other): the twelve factors are held across the blocks like the pairs' four.
 template <int NCH, class Obs>
 struct GlmWave {
     static constexpr bool kHasParams = true;
@@ -66,6 +67,7 @@ struct GlmWave {
     GlmSlopes slo;           // their values (Obs::kSlopes)
     const int32_t *cpart;    // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;            // the coordinate of zeta_0 and the pairs (Obs::kCorr)
+    GlmBlock blk;            // the correlation block (Obs::kBlock)
     GlmStruct stc;           // the structured terms (Obs::kStruct)
     GlmGmrf gm;              // the GMRF terms (Obs::kGmrf)
     double *buf;             // this wavefront's LDS vector, L doubles
@@ -98,6 +100,11 @@ struct GlmWave {
             ncp = s.lr_cp;
             cz0 = s.D - s.lr_cp;
             D -= s.lr_cp;
+        }
+        if constexpr (Obs::kBlock) {
+            static_assert(!Obs::kCorr, "a model has pairs or a block");
+            blk.init(s);
+            D -= blk.nz;
         }
         if constexpr (Obs::kStruct) {
             stc.init(s);
@@ -135,13 +142,18 @@ struct GlmWave {
             glm_corr_pairs<NCH>(q, cz0, ncp, cr0, cc0, cr1, cc1);
             glm_corr_mix<NCH>(qm, q, cpart, buf, lane, cr0, cc0, cr1, cc1);
         }
+        GlmBlockZ bz;                                          // Obs::kBlock: z and c of the block's zetas
+        if constexpr (Obs::kBlock) {
+            glm_block_factors<NCH>(q, blk, bz);
+            glm_block_mix<NCH>(qm, q, blk, buf, lane, bz);
+        }
         double sf0 = 1.0, sc0 = 1.0, sf1 = 1.0, sc1 = 1.0;     // Obs::kStruct: phi and c of the slots; the scan runs on qm, after the mix
         if constexpr (Obs::kStruct) {                          // (disjoint columns)
-            if constexpr (!Obs::kCorr) qm = q;
+            if constexpr (!Obs::kCorr && !Obs::kBlock) qm = q;
             glm_struct_factors<NCH>(q, stc, sf0, sc0, sf1, sc1);
             glm_struct_scan<NCH>(qm, stc, buf, lane, sf0, sc0, sf1, sc1);
         }
-        const Vec<NCH> &u = glm_pick<Obs::kCorr || Obs::kStruct>(qm, q);       // what the scales and the products run on
+        const Vec<NCH> &u = glm_pick<Obs::kCorr || Obs::kStruct || Obs::kBlock>(qm, q);    // what the scales and the products run on
         Vec<NCH> bq;                                           // Obs::kLocal: b, once per gradient
         if constexpr (Obs::kLocal) glm_local_b<NCH, Obs::H>(bq, u, grp2, part, buf, D, lane, e0, e1, e2, e3, inv2);
         double2 *b2 = reinterpret_cast<double2 *>(buf) + lane;
@@ -264,13 +276,15 @@ struct GlmWave {
         }
         // (with local scales b was held across the blocks, not ut: it is mixed again from q)
         if constexpr (Obs::kCorr && Obs::kLocal) glm_corr_mix<NCH>(qm, q, cpart, buf, lane, cr0, cc0, cr1, cc1);
+        if constexpr (Obs::kBlock && Obs::kLocal) glm_block_mix<NCH>(qm, q, blk, buf, lane, bz);
         if constexpr (Obs::kStruct && Obs::kLocal) {
-            if constexpr (!Obs::kCorr) qm = q;
+            if constexpr (!Obs::kCorr && !Obs::kBlock) qm = q;
             glm_struct_scan<NCH>(qm, stc, buf, lane, sf0, sc0, sf1, sc1);
         }
         if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(G, u, grp2, part, buf, D, D + Obs::A, lane, e0, e1, e2, e3, inv2);
         else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(G, u, grp2, D + Obs::A, lane, e0, e1, e2, e3);
         if constexpr (Obs::kCorr) glm_corr_chain<NCH>(G, q, cpart, buf, cz0, ncp, lane, cr0, cc0, cr1, cc1);
+        if constexpr (Obs::kBlock) glm_block_chain<NCH>(G, q, blk, buf, lane, bz);
         if constexpr (Obs::kStruct) glm_struct_chain<NCH>(G, q, u, stc, buf, lane, sf0, sc0, sf1, sc1);
         double gs0 = 0.0, gs1 = 0.0;                           // Obs::kGmrf: S of the slots; the raw q stays in buf for the loop
         if constexpr (Obs::kGmrf) {
@@ -289,14 +303,14 @@ struct GlmWave {
                 const int2 k = kind2[j * 64], ge = (reinterpret_cast<const int2 *>(gm.gpart) + lane)[j * 64];
                 const double2 nu = nu2[j * 64];
                 g.c[j].x = ge.x >= 0 ? glm_gmrf_row(gm, ge.x, buf, q.c[j].x, gs0, gs1, G.c[j].x, t0)
-                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
                 g.c[j].y = ge.y >= 0 ? glm_gmrf_row(gm, ge.y, buf, q.c[j].y, gs0, gs1, G.c[j].y, t1)
-                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
             } else if constexpr (Obs::kPriors) {
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];
-                g.c[j].x = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
-                g.c[j].y = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
+                g.c[j].x = glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.x, nu.x, t.x, dx, G.c[j].x, t0);
+                g.c[j].y = glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.y, nu.y, t.y, dy, G.c[j].y, t1);
             } else {
                 t0 = dfma(t.x * dx, dx, t0);
                 t1 = dfma(t.y * dy, dy, t1);
@@ -336,6 +350,7 @@ struct GlmWave {
 // compiler does not keep the values of before barrier A alive.  Nothing of a feature is alive across multiply(); the prior's
 // tables are read after barrier C too.  [kGmrf] the G row is taken into registers as for the chain rules, and once they have run the
 // raw q goes into the row, which is the requester's own, and stays there for the prior loop: row 6 reads its neighbours' u from it.
+// [kBlock] as the pairs: the factors live for the mix only before barrier A and are made again from q after barrier C.
 // [kResponses] the 16 rows of a tile are 16 chains of any responses: the requester publishes its offset into Y in column L of its
 // Q row (padding: zphase, gphase and both row accesses of the requester touch columns < L only) and the Z wavefronts read y per
 // accumulator row instead of once per lane.
@@ -374,6 +389,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     GlmSlopes slo;               // their values (Obs::kSlopes)
     const int32_t *cpart;        // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;                // the coordinate of zeta_0 and the pairs (Obs::kCorr)
+    GlmBlock blk;                // the correlation block (Obs::kBlock)
     GlmStruct stc;               // the structured terms (Obs::kStruct)
     GlmGmrf gm;                  // the GMRF terms (Obs::kGmrf)
     double *tile;
@@ -399,6 +415,11 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             ncp = s.lr_cp;
             cz0 = s.D - s.lr_cp;
             dx -= s.lr_cp;
+        }
+        if constexpr (Obs::kBlock) {
+            static_assert(!Obs::kCorr, "a model has pairs or a block");
+            blk.init(s);
+            dx -= blk.nz;
         }
         if constexpr (Obs::kStruct) {
             stc.init(s);
@@ -613,13 +634,18 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             glm_corr_pairs<NCH>(q, cz0, ncp, cr0, cc0, cr1, cc1);
             glm_corr_mix<NCH>(qm, q, cpart, tile + kQ + wv * DS, lane, cr0, cc0, cr1, cc1);
         }
+        if constexpr (Obs::kBlock) {                          // Obs::kBlock: z and c of the block's zetas live for the mix only
+            GlmBlockZ bz;
+            glm_block_factors<NCH>(q, blk, bz);
+            glm_block_mix<NCH>(qm, q, blk, tile + kQ + wv * DS, lane, bz);
+        }
         double sf0 = 1.0, sc0 = 1.0, sf1 = 1.0, sc1 = 1.0;    // Obs::kStruct: phi and c of the slots; the scan runs on qm through the row
         if constexpr (Obs::kStruct) {
-            if constexpr (!Obs::kCorr) qm = q;
+            if constexpr (!Obs::kCorr && !Obs::kBlock) qm = q;
             glm_struct_factors<NCH>(q, stc, sf0, sc0, sf1, sc1);
             glm_struct_scan<NCH>(qm, stc, tile + kQ + wv * DS, lane, sf0, sc0, sf1, sc1);
         }
-        const Vec<NCH> &u = glm_pick<Obs::kCorr || Obs::kStruct>(qm, q);      // what the scales and the products run on
+        const Vec<NCH> &u = glm_pick<Obs::kCorr || Obs::kStruct || Obs::kBlock>(qm, q);   // what the scales and the products run on
         if constexpr (Obs::kLocal) {
             // q goes through the row first (each column reads its lambda there), then b takes its place, +0 in every column >= dx
             if constexpr (Obs::H > 0) glm_group_scales<NCH, HN>(q, dx + Obs::A, e0, e1, e2, e3);
@@ -639,7 +665,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 const int2 id = grp2[j * 64];
                 row[j * 64] = make_double2(c0 >= dx ? 0.0 : glm_scaled<HN>(u.c[j].x, id.x, e0, e1, e2, e3), c0 + 1 >= dx ? 0.0 : glm_scaled<HN>(u.c[j].y, id.y, e0, e1, e2, e3));
             }
-        } else if constexpr (Obs::A > 0 || Obs::kCorr || Obs::kStruct) {
+        } else if constexpr (Obs::A > 0 || Obs::kCorr || Obs::kStruct || Obs::kBlock) {
             // (the zetas are coordinates behind the columns like the auxiliary ones: +0 in the row)
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
@@ -669,7 +695,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             }
         }
         Vec<NCH> Gh;                                          // with groups, local scales or pairs: the whole G row, for the chain rule
-        if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct || Obs::kGmrf) {
+        if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct || Obs::kGmrf || Obs::kBlock) {
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 Gh.c[j] = row[j * 64];
@@ -690,12 +716,21 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 glm_corr_pairs<NCH>(q, cz, ncp, cr0, cc0, cr1, cc1);
                 glm_corr_mix<NCH>(qm, q, cpart, tile + kQ + wv * DS, lane, cr0, cc0, cr1, cc1);
             }
+            // (a block: z, c and ut again from q, through the row, as the pairs above)
+            GlmBlock bk2;
+            GlmBlockZ bz;
+            if constexpr (Obs::kBlock) {
+                bk2 = blk;
+                asm volatile("" : "+s"(bk2.cz0));
+                glm_block_factors<NCH>(q, bk2, bz);
+                glm_block_mix<NCH>(qm, q, bk2, tile + kQ + wv * DS, lane, bz);
+            }
             // (structured terms: phi, c and the forward scan again from q, through the row, as the pairs above)
             GlmStruct st2;
             if constexpr (Obs::kStruct) {
                 st2 = stc;
                 asm volatile("" : "+s"(st2.cz0), "+s"(st2.cz1));
-                if constexpr (!Obs::kCorr) qm = q;
+                if constexpr (!Obs::kCorr && !Obs::kBlock) qm = q;
                 glm_struct_factors<NCH>(q, st2, sf0, sc0, sf1, sc1);
                 glm_struct_scan<NCH>(qm, st2, tile + kQ + wv * DS, lane, sf0, sc0, sf1, sc1);
             }
@@ -703,6 +738,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             if constexpr (Obs::kLocal) glm_local_chain<NCH, Obs::H>(Gh, u, grp2, part, tile + kQ + wv * DS, dx, c0, lane, e0, e1, e2, e3, inv2);
             else if constexpr (Obs::H > 0) glm_group_chain<NCH, HN>(Gh, u, grp2, c0, lane, e0, e1, e2, e3);
             if constexpr (Obs::kCorr) glm_corr_chain<NCH>(Gh, q, cpart, tile + kQ + wv * DS, cz, ncp, lane, cr0, cc0, cr1, cc1);
+            if constexpr (Obs::kBlock) glm_block_chain<NCH>(Gh, q, bk2, tile + kQ + wv * DS, lane, bz);
             if constexpr (Obs::kStruct) glm_struct_chain<NCH>(Gh, q, u, st2, tile + kQ + wv * DS, lane, sf0, sc0, sf1, sc1);
         }
         double gs0 = 0.0, gs1 = 0.0;                          // Obs::kGmrf: S of the slots; the raw q stays in the row for the loop
@@ -717,7 +753,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         for (int j = 0; j < NCH; ++j) {
             const double2 m = mu2[j * 64], t = tau2[j * 64];
             double2 G;
-            if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct || Obs::kGmrf) {
+            if constexpr (Obs::H > 0 || Obs::kLocal || Obs::kCorr || Obs::kStruct || Obs::kGmrf || Obs::kBlock) {
                 G = Gh.c[j];
             } else {
                 G = row[j * 64];
@@ -732,15 +768,15 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 const int2 k = kind2[j * 64], ge = (reinterpret_cast<const int2 *>(gm.gpart) + lane)[j * 64];
                 const double2 nu = nu2[j * 64];
                 g.c[j].x = ge.x >= 0 ? glm_gmrf_row(gm, ge.x, tile + kQ + wv * DS, q.c[j].x, gs0, gs1, G.x, t0)
-                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.x, t0);
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.x, nu.x, t.x, dx, G.x, t0);
                 g.c[j].y = ge.y >= 0 ? glm_gmrf_row(gm, ge.y, tile + kQ + wv * DS, q.c[j].y, gs0, gs1, G.y, t1)
-                                     : glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.y, t1);
+                                     : glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.y, nu.y, t.y, dy, G.y, t1);
             } else if constexpr (Obs::kPriors) {
                 // kinds and nu are read here, after barrier C: nothing of the prior is alive across multiply()
                 const int2 k = kind2[j * 64];
                 const double2 nu = nu2[j * 64];
-                g.c[j].x = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.x, nu.x, t.x, dx, G.x, t0);
-                g.c[j].y = glm_prior_of<Obs::kCorr || Obs::kStruct>(k.y, nu.y, t.y, dy, G.y, t1);
+                g.c[j].x = glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.x, nu.x, t.x, dx, G.x, t0);
+                g.c[j].y = glm_prior_of<Obs::kCorr || Obs::kStruct || Obs::kBlock>(k.y, nu.y, t.y, dy, G.y, t1);
             } else {
                 t0 = dfma(t.x * dx, dx, t0);
                 t1 = dfma(t.y * dy, dy, t1);

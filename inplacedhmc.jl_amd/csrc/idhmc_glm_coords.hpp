@@ -2,15 +2,16 @@
 // not depend on how a kernel evaluates it.  The two forms that do (GlmWave, GlmCoop) and what is theirs alone are in idhmc_glm.hpp.
 //   l(q) = -sum_i v(z_i, y_i) + log prior(q),   v = -log p(y | z) up to a data-only term,   r_i = d log p(y_i | z_i) / dz_i
 // The observation is a policy type Obs: Obs::K data columns per observation (1..4), Obs::A auxiliary coordinates, Obs::H groups, the
-// compile-time flags kResponses, kPriors, kLocal, kFactors, kSlopes, kCorr, kStruct, kGmrf, and
+// compile-time flags kResponses, kPriors, kLocal, kFactors, kSlopes, kCorr, kStruct, kGmrf, kBlock, and
 //   static void terms(double z, const GlmObs &o, double &r, double &v)                                             (A = 0)
 //   static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)    s[j] = d log p / d a_j
 // A flag that is false (A, H = 0) takes its stage out at compile time: none of the instructions of a model without it changes.  Each
-// feature's record is its DESIGN section (10-25); this comment is the full model in evaluation order, every stage tagged with its
+// feature's record is its DESIGN section (10-26); this comment is the full model in evaluation order, every stage tagged with its
 // flag, and both forms and the tests' C restatements follow it bit for bit.  dfma is one fused multiply-add; every other operation
 // is a plain one in the association written.
 //
 // COORDINATES.   q = [u (Dx) | a (A) | omega (H) | lambda (J) | zeta_pairs (P) | zeta_ar (Sz)],   D = Dx + A + H + J + P + Sz <= 1024
+//   ([kBlock] the K (K - 1) / 2 zetas of the block stand where the pairs' stand: a model has pairs or a block, kCorr && kBlock is never built)
 //   u       the Dx columns of the model.  [kFactors] Dd >= 1 dense columns, stored in X, then the levels of F <= 4 factor terms, never
 //           stored: off_f = Dd + N_0 + .. + N_{f-1}, column off_f + k is level k of term f (N_f >= 1), Dx = Dd + sum N_f.  Without
 //           factors Dd = Dx.  [kSlopes] a term may carry a finite value w_f[i] per observation next to its level index lvl_f[i]; two
@@ -25,6 +26,11 @@
 //           or without, on one index array or two; level k of the first is paired with level k of the second; zeta_p = atanh rho_p.
 //           lr_cpart holds per coordinate -1 or  partner | pair << 10 | (second ? 2048 : 0);  lr_cp = P.  Not lr_lpart: kLocal and kCorr
 //           are independent.
+//   zeta_b  [kBlock] ONE block of K in {2, 3, 4} distinct factor terms t_0 .. t_{K-1} of N levels each, in the user's order, which is the row
+//           order of L; with values or without, on one index array or several; level k of every term belongs together,
+//           c_j = off_{t_j} + k.  zeta_ji = atanh z_ji, 1 <= j < K, 0 <= i < j, is coordinate cz0 + j (j - 1) / 2 + i (row-major), z the
+//           canonical partial correlations of R = L L'.  lr_bpart holds per coordinate -1 or  k | row << 10;  lr_bk = K, lr_boff the rows'
+//           first columns.  A block term is neither structured nor a GMRF term.
 //   zeta_ar [kStruct] S <= 2 structured factor terms (slots 0, 1): the levels in index order are an AR(1) sequence with a sampled
 //           phi = tanh(zeta) -- the Sz such zetas come behind the pairs' -- or a first-order random walk (phi = c = 1, no coordinate).
 //           lr_spart holds per coordinate -1 or  k | slot << 10;  lr_s = S, lr_sz = Sz, lr_sn the slots' levels, lr_skind their kinds,
@@ -43,8 +49,15 @@
 //      [H]        e_g = dexp(omega_g)
 //      [kCorr]    per pair  s = dexp(-|zeta|); t = s s; d = 1 + t; rho = copysign((1 - t) / d, zeta); c = (2 s) / d      (glm_corr_factors)
 //                 (c = sqrt(1 - rho^2) in exact arithmetic; zeta = +0: rho = +0, c = 1; past |zeta| of about 745: rho = +-1, c = 0, finite)
+//      [kBlock]   (z_ji, c_ji) = glm_corr_factors(zeta_ji).  coef(j, m, .) for -1 <= m < j, row j "behind column m":  s = 1; for i = m+1 .. j-1:
+//                 coef(j,m,i) = z_ji s, then s = s c_ji; coef(j,m,j) = s -- and where s is still the initial 1 the other factor is taken
+//                 itself, no multiplication.  L_ji = coef(j, -1, i), L_00 = 1:  L_j0 = z_j0, L_j1 = z_j1 c_j0, L_j2 = z_j2 (c_j0 c_j1),
+//                 L_jj = ((c_j0 c_j1) c_j2).  r_jm = c_j0 .. c_j,m-1 left to right, r_j0 = 1.              (glm_block_factors, glm_block_coef)
 //      [kStruct]  per slot  (phi, c) = glm_corr_factors of its zeta; the constants (1, 1) for a random walk and for a slot that is not there
 //  2 mix [kCorr], k < N_p, c1 = off_first + k, c2 = off_second + k:   ut_c1 = u_c1;   ut_c2 = dfma(rho, u_c1, c u_c2);   ut = u elsewhere
+//    [kBlock] ut_{c_0} = u_{c_0};  j >= 1:  x = L_jj u_{c_j};  for i = 0 .. j-1 ascending  x = dfma(L_ji, u_{c_i}, x);  ut_{c_j} = x   (glm_block_mix)
+//      THE ASSOCIATION: the diagonal product first, then the partners' fmas with the column ascending.  At K = 2 this is the pair's
+//      dfma(rho, u_c1, c u_c2) bit for bit, and every line of the block below is the pair's at K = 2 (coef is 1 or c, r = 1).
 //  3 scan [kStruct], o the term's first column, N its levels: x_0 = u_o, x_k = c u_{o+k}; p = phi, h = 1; while h < N: every k >= h takes
 //      x_k = dfma(p, x_{k-h}, x_k) from the values before the stage, then p = p p, h = 2 h; ut_{o+k} = x_k -- the Kogge-Stone form of
 //      ut_0 = u_0, ut_k = phi ut_{k-1} + c u_k, and the definition of the bits (not the sequential recurrence).  Mix and scan touch disjoint
@@ -87,6 +100,11 @@
 //      This leaves Gh_c = dl / dut_c in the columns.
 // 11 [kCorr] (glm_corr_chain):  m_k = Gh_c2 (c dfma(c, u_c1, -(rho u_c2)));   G_c1 = dfma(rho, Gh_c2, Gh_c1);   G_c2 = c Gh_c2
 //      M_p[c2 mod 128]: plain additions over chunks ascending, from +0, of the pair's m_k (a non-member adds +0);  G_zeta_p = the tree over M_p
+//    [kBlock] (glm_block_chain), per zeta_jm:  w = coef(j,m,j) u_{c_j} (u_{c_j} itself when j = m + 1);  for i = m+1 .. j-1 ascending
+//      w = dfma(coef(j,m,i), u_{c_i}, w);  e = c_jm dfma(c_jm, u_{c_m}, -(z_jm w));  m >= 1: e = r_jm e;  m_k = Gh_{c_j} e
+//      (Gh_j dut_j / dzeta_jm with dut_j / dzeta_jm = r_jm c_jm (c_jm u_m - z_jm w));  M_jm[c_j mod 128]: plain additions over chunks
+//      ascending, from +0 (a non-member adds +0);  G_zeta_jm = the tree over M_jm.  Then, from the Gh before any is overwritten:
+//      G_{c_i} = (i == 0 ? Gh_{c_0} : L_ii Gh_{c_i});  for j = i+1 .. K-1 ascending  G_{c_i} = dfma(L_ji, Gh_{c_j}, G_{c_i}).
 // 12 [kStruct] (glm_struct_chain):  y_k = Gh_{o+k}; p = phi, h = 1; while h < N: every k with k + h < N takes y_k = dfma(p, y_{k+h}, y_k),
 //      then p = p p, h = 2 h; lambda_k = y_k;  G_{u_o} = lambda_0, G_{u_{o+k}} = c lambda_k;   AR(1): m_k = lambda_k (c dfma(c, ut_{o+k-1},
 //      -(phi u_{o+k}))), k >= 1; M[(o+k) mod 128] plain additions over chunks ascending from +0;  G_zeta = the tree over M.
@@ -101,10 +119,12 @@
 //   2 LOG_HALF_NORMAL      e = dexp(2 d);        T = T + (e - 2 d)                        g = G + (1 - e)
 //   3 LOG_HALF_STUDENT_T   e = dexp(2 d);        T = T + ((nu + 1) dlog1p(e / nu) - 2 d)  g = G + (1 - ((nu + 1) e) / (nu + e))
 //   4 LOG_EXPONENTIAL      e = dexp(d);          T = T + 2 (e - d)                        g = G + (1 - e)
-//   5 (internal, [kCorr] or [kStruct] only: a zeta with eta > 0, eta in nu's place; LKJ(eta) on the 2 x 2 correlation with the Jacobian of
+//   5 (internal, [kCorr], [kStruct] or [kBlock] only: a zeta with eta > 0, eta in nu's place; LKJ(eta) on the 2 x 2 correlation with the Jacobian of
 //      tanh, log p(zeta) = eta log(1 - rho^2))   t as in stage 1:
 //                          T = T + (4 eta) ((|zeta| + dlog1p(t)) - ln 2)                g = dfma(-2 eta, rho, G)      (ln 2 rounded to a double)
 //      eta = 0: the coordinate's entry of the prior arrays applies (kinds 0 and 1).
+//      [kBlock] LKJ(eta) on the K x K matrix is separable in the partial correlations: the host marks every zeta_ji with this row and puts
+//      beta_ji = eta + (K - 2 - i) / 2 (i the COLUMN) in nu's place; the row itself is unchanged.
 //   6 (internal, [kGmrf] only, like row 5; glm_gmrf_row)  a member c = o + k, u_c = q_c:
 //                          s = kappa > 0 ? kappa * S : +0;   for e = start[k] .. start[k+1]-1 ascending:  s = dfma(val[e], u_{o + col[e]}, s)
 //                          T = dfma(u_c, s, T)                                          g = G - s
@@ -151,7 +171,7 @@
 // cap holds: a bad list still cannot read outside the block's entries.
 //
 // EXCHANGE BETWEEN LANES.  A column and its lambda, the two columns of a pair, and neighbouring levels of a structured term live in
-// different lanes, chunks and components in general.  The helpers of stages 2-4 and 10-12 take vec, a wavefront-private LDS vector
+// different lanes, chunks and components in general; so do the up to three partners of a block's column.  The helpers of stages 2-4 and 10-12 take vec, a wavefront-private LDS vector
 // (>= 128 NCH doubles, indexed by coordinate), written and read by one wavefront in program order, no workgroup barrier; values stay
 // in registers.  Which vector that is, and when each stage runs, is the form's (idhmc_glm.hpp).
 #pragma once
@@ -485,6 +505,192 @@ IDHMC_DEV double glm_prior_of(int kind, double nu, double tau, double d, double 
 {
     if constexpr (CORR) return glm_prior_corr(kind, nu, tau, d, G, T);
     else return glm_prior(kind, nu, tau, d, G, T);
+}
+// A correlation block (Obs::kBlock).  An entry of the level table: -1, or k | row << 10 for level k of the term in row 0 .. K-1 of L
+constexpr int kBlockRow = 10, kBlockMask = 1023;
+// what both forms take from DevState: the rows' first columns, K, the zetas nz = K (K - 1) / 2 and the coordinate of zeta_10
+struct GlmBlock {
+    const int32_t *bpart;
+    int K, nz, cz0;
+    int off[4];
+    template <class State>
+    IDHMC_DEV void init(const State &s)
+    {
+        bpart = s.lr_bpart;
+        K = s.lr_bk;
+        nz = (K * (K - 1)) >> 1;
+        cz0 = s.D - s.lr_sz - nz;                              // (the block's zetas come first, the AR(1) zetas last)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) off[r] = s.lr_boff[r];
+    }
+};
+// (z_ji, c_ji) of the block at index j (j - 1) / 2 + i, the same bits in every lane; the constants (0, 1) for a zeta that is not there.
+// The indices are compile-time constants everywhere: the twelve doubles are registers, never an indexed array.
+struct GlmBlockZ {
+    double z[6], c[6];
+};
+constexpr int glm_bz(int j, int i) { return ((j * (j - 1)) >> 1) + i; }
+template <int NCH>
+IDHMC_DEV void glm_block_factors(const Vec<NCH> &q, const GlmBlock &bk, GlmBlockZ &f)
+{
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        f.z[e] = 0.0;
+        f.c[e] = 1.0;
+        if (e < bk.nz) glm_corr_factors<NCH>(q, bk.cz0 + e, f.z[e], f.c[e]);
+    }
+}
+// coef(J, M, I) of the header comment, M < I <= J (M = -1: L_JI); where s is still the initial 1 the other factor is taken itself
+template <int J, int M, int I>
+IDHMC_DEV double glm_block_coef(const GlmBlockZ &f)
+{
+    double s = 1.0;
+    bool one = true;
+#pragma unroll
+    for (int i = M + 1; i < I; ++i) {
+        s = one ? f.c[glm_bz(J, i)] : s * f.c[glm_bz(J, i)];
+        one = false;
+    }
+    if constexpr (I == J) return s;
+    else return one ? f.z[glm_bz(J, I)] : f.z[glm_bz(J, I)] * s;
+}
+// L_JI for the row j the lane's column is in (a select over the rows; I <= j)
+template <int I>
+IDHMC_DEV double glm_block_lcol(const GlmBlockZ &f, int j)
+{
+    // rows J > I hold L_JI below the diagonal, row I the diagonal
+    double l = 1.0;
+    if constexpr (I == 0) l = j == 1 ? glm_block_coef<1, -1, 0>(f) : j == 2 ? glm_block_coef<2, -1, 0>(f) : glm_block_coef<3, -1, 0>(f);
+    if constexpr (I == 1) l = j == 1 ? glm_block_coef<1, -1, 1>(f) : j == 2 ? glm_block_coef<2, -1, 1>(f) : glm_block_coef<3, -1, 1>(f);
+    if constexpr (I == 2) l = j == 2 ? glm_block_coef<2, -1, 2>(f) : glm_block_coef<3, -1, 2>(f);
+    if constexpr (I == 3) l = glm_block_coef<3, -1, 3>(f);
+    return l;
+}
+// ut of one column: u its own coordinate, row j >= 1, p0 .. p2 the partners u_{c_0} .. u_{c_2} (those at or past j unused)
+IDHMC_DEV double glm_block_mix1(const GlmBlockZ &f, int j, double u, double p0, double p1, double p2)
+{
+    const double ljj = j == 1 ? glm_block_lcol<1>(f, 1) : j == 2 ? glm_block_lcol<2>(f, 2) : glm_block_lcol<3>(f, 3);
+    double x = ljj * u;
+    x = dfma(glm_block_lcol<0>(f, j), p0, x);
+    x = j > 1 ? dfma(glm_block_lcol<1>(f, j), p1, x) : x;
+    x = j > 2 ? dfma(glm_block_lcol<2>(f, j), p2, x) : x;
+    return x;
+}
+// the partners' values of the column with table entry e (row j): vec[off_i + k] for the rows i < j, vec[0] (unused) elsewhere
+IDHMC_DEV void glm_block_partners(const GlmBlock &bk, const double *vec, int e, double &p0, double &p1, double &p2)
+{
+    const int j = e >= 0 ? e >> kBlockRow : 0, k = e & kBlockMask;
+    p0 = vec[j > 0 ? bk.off[0] + k : 0];
+    p1 = vec[j > 1 ? bk.off[1] + k : 0];
+    p2 = vec[j > 2 ? bk.off[2] + k : 0];
+}
+// ut of every coordinate of the lane: stage 2 for a column of the rows 1 .. K-1, q itself elsewhere.  vec as for glm_corr_mix: q is
+// staged there and each column reads up to three partners.
+template <int NCH>
+IDHMC_DEV void glm_block_mix(Vec<NCH> &ut, const Vec<NCH> &q, const GlmBlock &bk, double *vec, int lane, const GlmBlockZ &f)
+{
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(bk.bpart) + lane;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = q.c[j];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 e = part2[j * 64];
+        double a0, a1, a2, b0, b1, b2;
+        glm_block_partners(bk, vec, e.x, a0, a1, a2);
+        glm_block_partners(bk, vec, e.y, b0, b1, b2);
+        const bool mx = e.x >= (1 << kBlockRow), my = e.y >= (1 << kBlockRow);
+        ut.c[j].x = mx ? glm_block_mix1(f, e.x >> kBlockRow, q.c[j].x, a0, a1, a2) : q.c[j].x;
+        ut.c[j].y = my ? glm_block_mix1(f, e.y >> kBlockRow, q.c[j].y, b0, b1, b2) : q.c[j].y;
+    }
+}
+// e of zeta_JM for a column of row J: u its own coordinate, p[i] = u_{c_i}; m_k = Gh e
+template <int J, int M>
+IDHMC_DEV double glm_block_e(const GlmBlockZ &f, double u, double p0, double p1, double p2)
+{
+    double w = u;
+    if constexpr (J > M + 1) w = glm_block_coef<J, M, J>(f) * u;
+    if constexpr (M + 1 <= 1 && 1 < J) w = dfma(glm_block_coef<J, M, 1>(f), p1, w);
+    if constexpr (M + 1 <= 2 && 2 < J) w = dfma(glm_block_coef<J, M, 2>(f), p2, w);
+    const double um = M == 0 ? p0 : M == 1 ? p1 : p2;
+    const double cm = f.c[glm_bz(J, M)];
+    double e = cm * dfma(cm, um, -(f.z[glm_bz(J, M)] * w));
+    if constexpr (M == 1) e = f.c[glm_bz(J, 0)] * e;
+    if constexpr (M == 2) e = (f.c[glm_bz(J, 0)] * f.c[glm_bz(J, 1)]) * e;
+    return e;
+}
+// G_{c_i} of the column with table entry e (row i, level k): g its own Gh, the Gh of the rows j > i read from vec
+IDHMC_DEV double glm_block_back1(const GlmBlock &bk, const GlmBlockZ &f, const double *vec, int e, double g)
+{
+    const bool in = e >= 0;
+    const int i = in ? e >> kBlockRow : 4, k = e & kBlockMask;
+    const double g1 = vec[i < 1 ? bk.off[1] + k : 0];
+    const double g2 = vec[i < 2 && bk.K > 2 ? bk.off[2] + k : 0];
+    const double g3 = vec[i < 3 && bk.K > 3 ? bk.off[3] + k : 0];
+    const double lii = i == 1 ? glm_block_lcol<1>(f, 1) : i == 2 ? glm_block_lcol<2>(f, 2) : glm_block_lcol<3>(f, 3);
+    double x = i == 0 ? g : lii * g;
+    x = i < 1 ? dfma(glm_block_coef<1, -1, 0>(f), g1, x) : x;
+    const double l2 = i == 0 ? glm_block_coef<2, -1, 0>(f) : glm_block_coef<2, -1, 1>(f);
+    x = i < 2 && bk.K > 2 ? dfma(l2, g2, x) : x;
+    const double l3 = i == 0 ? glm_block_coef<3, -1, 0>(f) : i == 1 ? glm_block_coef<3, -1, 1>(f) : glm_block_coef<3, -1, 2>(f);
+    x = i < 3 && bk.K > 3 ? dfma(l3, g3, x) : x;
+    return in ? x : g;
+}
+template <int J, int M>
+IDHMC_DEV void glm_block_madd(double2 &Mz, const GlmBlockZ &f, int jx, int jy, const double2 &Gh, const double2 &u, double a0, double a1, double a2,
+                              double b0, double b1, double b2)
+{
+    const double mx = Gh.x * glm_block_e<J, M>(f, u.x, a0, a1, a2), my = Gh.y * glm_block_e<J, M>(f, u.y, b0, b1, b2);
+    Mz.x = Mz.x + (jx == J ? mx : 0.0);
+    Mz.y = Mz.y + (jy == J ? my : 0.0);
+}
+// the chain rule of the block on the lane's G (Gh in the columns, complete elsewhere but for the zetas): m_k into M_jm and by the tree
+// into coordinate cz0 + j (j - 1) / 2 + m, then G_{c_i} from the Gh of the rows j >= i, read through vec once every u has been
+template <int NCH>
+IDHMC_DEV void glm_block_chain(Vec<NCH> &G, const Vec<NCH> &q, const GlmBlock &bk, double *vec, int lane, const GlmBlockZ &f)
+{
+    double2 *v2 = reinterpret_cast<double2 *>(vec) + lane;
+    const int2 *part2 = reinterpret_cast<const int2 *>(bk.bpart) + lane;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = q.c[j];
+    double2 M10 = make_double2(0.0, 0.0), M20 = M10, M21 = M10, M30 = M10, M31 = M10, M32 = M10;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 e = part2[j * 64];
+        double a0, a1, a2, b0, b1, b2;
+        glm_block_partners(bk, vec, e.x, a0, a1, a2);
+        glm_block_partners(bk, vec, e.y, b0, b1, b2);
+        const int jx = e.x >= 0 ? e.x >> kBlockRow : 0, jy = e.y >= 0 ? e.y >> kBlockRow : 0;
+        glm_block_madd<1, 0>(M10, f, jx, jy, G.c[j], q.c[j], a0, a1, a2, b0, b1, b2);
+        if (bk.K > 2) {
+            glm_block_madd<2, 0>(M20, f, jx, jy, G.c[j], q.c[j], a0, a1, a2, b0, b1, b2);
+            glm_block_madd<2, 1>(M21, f, jx, jy, G.c[j], q.c[j], a0, a1, a2, b0, b1, b2);
+        }
+        if (bk.K > 3) {
+            glm_block_madd<3, 0>(M30, f, jx, jy, G.c[j], q.c[j], a0, a1, a2, b0, b1, b2);
+            glm_block_madd<3, 1>(M31, f, jx, jy, G.c[j], q.c[j], a0, a1, a2, b0, b1, b2);
+            glm_block_madd<3, 2>(M32, f, jx, jy, G.c[j], q.c[j], a0, a1, a2, b0, b1, b2);
+        }
+    }
+    // every u has been read: Gh takes q's place, and each column reads the Gh of the rows below its own
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) v2[j * 64] = G.c[j];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int2 e = part2[j * 64];
+        G.c[j].x = glm_block_back1(bk, f, vec, e.x, G.c[j].x);
+        G.c[j].y = glm_block_back1(bk, f, vec, e.y, G.c[j].y);
+    }
+    glm_group_place<NCH>(G, M10, bk.cz0, lane);
+    if (bk.K > 2) {
+        glm_group_place<NCH>(G, M20, bk.cz0 + 1, lane);
+        glm_group_place<NCH>(G, M21, bk.cz0 + 2, lane);
+    }
+    if (bk.K > 3) {
+        glm_group_place<NCH>(G, M30, bk.cz0 + 3, lane);
+        glm_group_place<NCH>(G, M31, bk.cz0 + 4, lane);
+        glm_group_place<NCH>(G, M32, bk.cz0 + 5, lane);
+    }
 }
 // a when B, else b: the vector the scales and the products run on
 template <bool B, class T>

@@ -132,6 +132,11 @@ struct DevState {
     int32_t lr_go[2];         // the first column of slot i
     int32_t lr_gn[2];         // its levels
     int32_t lr_gnz[2];        // its entries
+    // a correlation block of K = 2..4 factor terms (idhmc_create_glm_block; null and 0 without one): the
+    // K (K - 1) / 2 zetas stand where the pairs' stand (a model has pairs or a block), in front of the AR(1) zetas.  Appended again.
+    const int32_t *lr_bpart;  // [L] -1, or for a column of a block term: k | row << 10, k its level, row its row of L
+    int32_t lr_bk;            // K, 0 without a block
+    int32_t lr_boff[4];       // the first column of the term in row r
 };
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
@@ -209,6 +214,8 @@ const Backend &separable_backend();   // idhmc_kernels.hip: the Gaussians
 const Backend &dense_backend();       // idhmc_dense.hip
 const Backend &logistic_backend();    // idhmc_logistic.hip
 const Backend &jit_backend();         // idhmc_jit.hip: a custom density or a GLM, compiled at run time
+// the zetas of a correlation block of K terms (DevState::lr_bk; 0 without a block)
+inline int block_zetas(int K) { return (K * (K - 1)) >> 1; }
 inline bool model_is_separable(int model) { return model == IDHMC_MODEL_ISO_GAUSSIAN || model == IDHMC_MODEL_DIAG_GAUSSIAN; }
 inline const Backend *backend(int model)
 {

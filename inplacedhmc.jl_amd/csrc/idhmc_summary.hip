@@ -97,11 +97,63 @@ __global__ void k_summary_local_scales(const double *stage, double *scales, int6
     scales[r * W + H + J + k] = st;
 }
 
+// A correlation block as the theta kernels take it: K = 0 without one.  cz0: the coordinate of zeta_10
+struct SumBlock {
+    const int32_t *bpart;
+    int32_t K, cz0;
+    int32_t off[4];
+};
+// (z, c) of the block's zeta at index e of row q (glm_corr_factors)
+__device__ __forceinline__ void sum_block_zc(const double *q, const SumBlock &b, int e, double &z, double &c)
+{
+    const double x = q[b.cz0 + e];
+    const double s = dexp(-__builtin_fabs(x));
+    const double t = s * s, d = 1.0 + t;
+    z = __builtin_copysign((1.0 - t) / d, x);
+    c = (2.0 * s) / d;
+}
+// L_ji, i <= j, of row q by the header comment of idhmc_glm_coords.hpp: coef(j, -1, i)
+__device__ __forceinline__ double sum_block_l(const double *q, const SumBlock &b, int j, int i)
+{
+    double s = 1.0, z, c;
+    bool one = true;
+    for (int k = 0; k < i; ++k) {
+        sum_block_zc(q, b, ((j * (j - 1)) >> 1) + k, z, c);
+        s = one ? c : s * c;
+        one = false;
+    }
+    if (i == j) return s;
+    sum_block_zc(q, b, ((j * (j - 1)) >> 1) + i, z, c);
+    return one ? z : z * s;
+}
+// What a block makes of coordinate d of row q, x its value so far (u for a column): ut for a column of the rows >= 1 (stage 2 of the
+// header comment of idhmc_glm_coords.hpp), R_ji for the zeta at index j (j - 1) / 2 + i; x itself elsewhere.  Used by both theta kernels.
+__device__ double sum_block_theta(const double *q, const SumBlock &b, int32_t d, int32_t Dx, double x)
+{
+    if (b.K == 0) return x;
+    const int nz = (b.K * (b.K - 1)) >> 1;
+    if (d < Dx) {
+        const int32_t e = b.bpart[d];
+        if (e < 1024) return x;
+        const int j = e >> 10, k = e & 1023;
+        double y = sum_block_l(q, b, j, j) * x;
+        for (int i = 0; i < j; ++i) y = dfma(sum_block_l(q, b, j, i), q[b.off[i] + k], y);
+        return y;
+    }
+    if (d < b.cz0 || d >= b.cz0 + nz) return x;
+    const int e = d - b.cz0;
+    const int j = e < 1 ? 1 : e < 3 ? 2 : 3, i = e - ((j * (j - 1)) >> 1);
+    if (i == 0) return sum_block_l(q, b, j, 0);
+    double y = sum_block_l(q, b, j, i) * sum_block_l(q, b, i, i);
+    for (int k = 0; k < i; ++k) y = dfma(sum_block_l(q, b, j, k), sum_block_l(q, b, i, k), y);
+    return y;
+}
+
 // A GLM with correlated pairs: theta = [beta | a raw | sigma | exp(lambda) | rho], beta taken from ut.  One thread per
 // (row, coordinate) writes the whole reported vector of the row, by the expressions of idhmc_glm_coords.hpp (glm_corr_factors, glm_corr_mix,
 // glm_scaled, glm_local_scale); the reduction then runs on it as it runs on raw draws (MODE 3).  A row of "scales" is theta, D doubles.
 __global__ void k_summary_corr_theta(const double *stage, double *theta, int64_t rows, int32_t D, int32_t Dx, int32_t A, int32_t H, int32_t J,
-                                     int32_t P, const int32_t *grp, const int32_t *lpart, const int32_t *cpart, double inv2)
+                                     int32_t P, const int32_t *grp, const int32_t *lpart, const int32_t *cpart, double inv2, SumBlock blk)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * D) return;
@@ -110,13 +162,19 @@ __global__ void k_summary_corr_theta(const double *stage, double *theta, int64_t
     const double *q = stage + r * D;
     double x = q[d];
     if (d >= D - P) {
-        const double s = dexp(-__builtin_fabs(x));
-        const double t = s * s;
-        x = __builtin_copysign((1.0 - t) / (1.0 + t), x);
+        // (P counts a block's zetas where there is one: their entries report R, the correlations, not tanh zeta)
+        if (blk.K > 0) {
+            x = sum_block_theta(q, blk, d, Dx, x);
+        } else {
+            const double s = dexp(-__builtin_fabs(x));
+            const double t = s * s;
+            x = __builtin_copysign((1.0 - t) / (1.0 + t), x);
+        }
     } else if (d >= Dx + A) {
         x = dexp(x);
     } else if (d < Dx) {
-        const int32_t p = cpart[d];
+        x = sum_block_theta(q, blk, d, Dx, x);
+        const int32_t p = blk.K > 0 ? -1 : cpart[d];
         if (p >= 0 && (p & 2048)) {
             const double z = q[D - P + ((p >> 10) & 1)];
             const double s = dexp(-__builtin_fabs(z));
@@ -153,7 +211,7 @@ constexpr int kStructThetaWaves = 2;
 __global__ void __launch_bounds__(64 * kStructThetaWaves)
 k_summary_struct_theta(const double *stage, double *theta, int64_t rows, int32_t D, int32_t Dx, int32_t A, int32_t H, int32_t J, int32_t P,
                        int32_t Sz, const int32_t *grp, const int32_t *lpart, const int32_t *cpart, const int32_t *spart, int32_t n0, int32_t n1,
-                       int32_t cz0, int32_t cz1, double inv2)
+                       int32_t cz0, int32_t cz1, double inv2, SumBlock blk)
 {
     __shared__ double vecs[kStructThetaWaves][2][1024];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -194,14 +252,19 @@ k_summary_struct_theta(const double *stage, double *theta, int64_t rows, int32_t
     for (int d = lane; d < D; d += 64) {
         double x = q[d];
         if (d >= D - P - Sz) {
-            const double s = dexp(-__builtin_fabs(x));
-            const double t = s * s;
-            x = __builtin_copysign((1.0 - t) / (1.0 + t), x);
+            if (blk.K > 0 && d < D - Sz) {
+                x = sum_block_theta(q, blk, d, Dx, x);
+            } else {
+                const double s = dexp(-__builtin_fabs(x));
+                const double t = s * s;
+                x = __builtin_copysign((1.0 - t) / (1.0 + t), x);
+            }
         } else if (d >= Dx + A) {
             x = dexp(x);
         } else if (d < Dx) {
-            x = va[d];
-            const int32_t p = P > 0 ? cpart[d] : -1;
+            // (a block's columns and a structured term's are disjoint: the scan left u in them)
+            x = sum_block_theta(q, blk, d, Dx, va[d]);
+            const int32_t p = P > 0 && blk.K == 0 ? cpart[d] : -1;
             if (p >= 0 && (p & 2048)) {
                 const double z = q[D - Sz - P + ((p >> 10) & 1)];
                 const double s = dexp(-__builtin_fabs(z));
@@ -449,9 +512,9 @@ static hipError_t launch_summary(const SumArgs &a, hipStream_t st)
 }  // namespace idhmc
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && (c->s.lr_h > 0 || c->s.lr_j > 0 || c->s.lr_cp > 0 || c->s.lr_s > 0); }
+static bool scaled_theta(const idhmc_ctx *c) { return c->s.model == IDHMC_MODEL_GLM && (c->s.lr_h > 0 || c->s.lr_j > 0 || c->s.lr_cp > 0 || c->s.lr_s > 0 || c->s.lr_bk > 0); }
 // doubles per row of Summary::scales: e_g, and with local scales f_k and st_k; with correlated pairs or structured terms the whole theta
-static int64_t scales_width(const idhmc_ctx *c) { return c->s.lr_cp > 0 || c->s.lr_s > 0 ? (int64_t)c->s.D : c->s.lr_h + 2 * (int64_t)c->s.lr_j; }
+static int64_t scales_width(const idhmc_ctx *c) { return c->s.lr_cp > 0 || c->s.lr_s > 0 || c->s.lr_bk > 0 ? (int64_t)c->s.D : c->s.lr_h + 2 * (int64_t)c->s.lr_j; }
 static int64_t sum_gd(const idhmc_ctx *c) { return c->sum.groups * (int64_t)c->s.D; }
 
 static void summary_release(idhmc_ctx *c)
@@ -528,7 +591,10 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
 {
     Summary &m = c->sum;
     const DevState &s = c->s;
-    const bool strct = s.lr_s > 0, corr = s.lr_cp > 0 || strct, scaled = scaled_theta(c), local = s.lr_j > 0 && !corr;
+    const bool strct = s.lr_s > 0, corr = s.lr_cp > 0 || s.lr_bk > 0 || strct, scaled = scaled_theta(c), local = s.lr_j > 0 && !corr;
+    // the zetas in the pairs' place: the pairs' or a block's (a model has one or the other)
+    const int32_t pz = s.lr_cp + block_zetas(s.lr_bk);
+    SumBlock blk{s.lr_bpart, s.lr_bk, s.D - s.lr_sz - pz, {s.lr_boff[0], s.lr_boff[1], s.lr_boff[2], s.lr_boff[3]}};
     if (scaled) {
         const int64_t rows = (int64_t)cnt * s.C;
         if (m.scales_rows < rows) {
@@ -539,12 +605,12 @@ int idhmc::summary_feed(idhmc_ctx *c, const double *stage, int32_t cnt)
         }
         if (strct)
             hipLaunchKernelGGL(k_summary_struct_theta, dim3(blocks_for(rows, kStructThetaWaves)), dim3(64 * kStructThetaWaves), 0, c->stream, stage,
-                               m.scales, rows, s.D, s.D - s.lr_a - s.lr_h - s.lr_j - s.lr_cp - s.lr_sz, s.lr_a, s.lr_h, s.lr_j, s.lr_cp, s.lr_sz,
+                               m.scales, rows, s.D, s.D - s.lr_a - s.lr_h - s.lr_j - pz - s.lr_sz, s.lr_a, s.lr_h, s.lr_j, pz, s.lr_sz,
                                s.lr_grp, s.lr_lpart, s.lr_cpart, s.lr_spart, s.lr_sn[0], s.lr_s > 1 ? s.lr_sn[1] : 0, s.lr_scz[0],
-                               s.lr_s > 1 ? s.lr_scz[1] : -1, s.lr_inv2);
+                               s.lr_s > 1 ? s.lr_scz[1] : -1, s.lr_inv2, blk);
         else if (corr)
             hipLaunchKernelGGL(k_summary_corr_theta, dim3(blocks_for(rows * s.D, 256)), dim3(256), 0, c->stream, stage, m.scales, rows, s.D,
-                               s.D - s.lr_a - s.lr_h - s.lr_j - s.lr_cp, s.lr_a, s.lr_h, s.lr_j, s.lr_cp, s.lr_grp, s.lr_lpart, s.lr_cpart, s.lr_inv2);
+                               s.D - s.lr_a - s.lr_h - s.lr_j - pz, s.lr_a, s.lr_h, s.lr_j, pz, s.lr_grp, s.lr_lpart, s.lr_cpart, s.lr_inv2, blk);
         else if (local)
             hipLaunchKernelGGL(k_summary_local_scales, dim3(blocks_for(rows * (s.lr_h + s.lr_j), 256)), dim3(256), 0, c->stream, stage, m.scales, rows,
                                s.D, s.lr_h, s.lr_j, s.lr_grp, s.lr_lpart, s.lr_inv2);

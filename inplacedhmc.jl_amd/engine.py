@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmDesc, GlmFactors, GlmFactorValues, GlmGmrfs, GlmLocal, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
+from ._lib import GlmBlock, GlmDesc, GlmFactors, GlmFactorValues, GlmGmrfs, GlmLocal, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -239,8 +239,17 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     the 2 x 2 correlation, (rho + 1) / 2 ~ Beta(eta, eta), and zeta's entries in the prior keywords must be the defaults; eta = 0 lets
     them apply (PRIOR_NORMAL or PRIOR_STUDENT_T on Fisher's z; the log kinds are refused).  glm.correlated_effects() assembles groups,
     priors and correlated; glm.correlations(model, draws) gives rho, glm.coefficients applies the mix.  An empty list is the model without
-    the keyword; a covariance among three or more terms is out of scope.  The Model exposes P, pairs (a list of glm.Pair, None without),
+    the keyword.  The Model exposes P, pairs (a list of glm.Pair, None without),
     pair_first, pair_second (int32 (P,)) and pair_eta (float64 (P,)); Engine.glm_pairs() reads them back.
+    A covariance among three or four terms is a correlation block (idhmc_create_glm_block): correlated=[glm.block(terms, eta=2.0)], the
+    single entry of the list -- K = 2, 3 or 4 distinct terms of equal level counts, in the row order of L; the effects of a level are
+    sigma .* (L u) with L the K x K Cholesky factor of a sampled correlation matrix, built from canonical partial correlations
+    z_ji = tanh(zeta_ji).  The block adds K (K - 1) / 2 coordinates, row-major, where the pairs' zetas would stand (in front of the AR(1)
+    zetas).  eta > 0 is LKJ(eta) on the matrix, the zetas' prior entries at their defaults; eta = 0 lets them apply.  A block term is not
+    structured and no GMRF term; more than one block, K > 4 and a block next to pairs are out of scope.  glm.block_effects() assembles
+    groups, priors and correlated; glm.cholesky_factors, glm.correlation_matrix and glm.correlations read draws, glm.coefficients applies
+    the mix.  The Model exposes BK (K, 0 without), Bz (the zetas), block (a glm.Block, None without), block_term (int32 (K,)) and
+    block_eta; Engine.glm_block() reads them back.
 
     structured: a list of up to 2 glm.ar1(term, eta=2.0) or glm.rw1(term) (idhmc_create_glm_struct) -- dependence among the levels of one
     term, level k being position k of the sequence: ut_0 = u_0, ut_k = phi ut_{k-1} + c u_k takes u's place before the scales, the
@@ -298,10 +307,13 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     loc, J, S = _glm.local_flags(local, slab_scale, Dx)
     pfirst, psecond, peta = _glm.pair_terms(correlated, flev)
     P = 0 if pfirst is None else pfirst.size
+    bterm, beta = _glm.block_terms(correlated, flev)
+    BK = 0 if bterm is None else bterm.size
+    Bz = BK * (BK - 1) // 2
     sterm, skind, seta = _glm.struct_terms(structured, flev, correlated, loc, Dd)
     NS = 0 if sterm is None else sterm.size
     Sz = 0 if sterm is None else int((skind == _glm.STRUCT_AR1).sum())
-    D = Dx + A + H + J + P + Sz
+    D = Dx + A + H + J + P + Bz + Sz
     if D > 1024:
         raise ValueError("a GLM is limited to D <= 1024 (D = %d)" % D)
     if not np.isfinite(X).all():
@@ -335,6 +347,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     kind, nu = _glm.prior_kinds(prior_kind, prior_nu, D, Dx, tau)
     if P:
         _glm.pair_priors(peta, D - Sz, mu, tau, kind, nu)
+    if BK:
+        _glm.block_priors(beta, Bz, D - Sz, mu, tau, kind, nu)
     if Sz:
         _glm.struct_priors(skind, seta, D, mu, tau, kind, nu)
     gterm, gkappa, gstart, gcol, gval = _glm.gmrf_terms(gmrf, flev, correlated, structured, loc, Dd, mu, tau, kind, nu)
@@ -360,6 +374,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.factor_has, m.factor_values = fhas, fval
     m.P, m.pair_first, m.pair_second, m.pair_eta = P, pfirst, psecond, peta
     m.pairs = [_glm.Pair(int(a), int(b), float(e)) for a, b, e in zip(pfirst, psecond, peta)] if P else None
+    m.BK, m.Bz, m.block_term, m.block_eta = BK, Bz, bterm, beta
+    m.block = _glm.Block(tuple(int(t) for t in bterm), beta) if BK else None
     m.S, m.Sz, m.struct_term, m.struct_kind, m.struct_eta = NS, Sz, sterm, skind, seta
     m.structs = [_glm.Structure(int(t), int(k), float(e)) for t, k, e in zip(sterm, skind, seta)] if NS else None
     m.G, m.gmrf_term, m.gmrf_kappa, m.gmrf_start, m.gmrf_col, m.gmrf_val = NG, gterm, gkappa, gstart, gcol, gval
@@ -397,7 +413,23 @@ class Engine:
             fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
                             index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
             R = getattr(model, "R", None)
-            if getattr(model, "G", 0) > 0:
+            if getattr(model, "BK", 0) > 0:
+                fv = st = gm = None
+                ip = C.POINTER(C.c_int32)
+                if getattr(model, "factor_has", None) is not None:
+                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(ip)))
+                if getattr(model, "S", 0) > 0:
+                    st = C.byref(GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
+                                            eta=_dp(model.struct_eta)))
+                if getattr(model, "G", 0) > 0:
+                    gm = C.byref(GlmGmrfs(G=model.G, term=model.gmrf_term.ctypes.data_as(ip),
+                                          start=model.gmrf_start.ctypes.data_as(C.POINTER(C.c_int64)), col=model.gmrf_col.ctypes.data_as(ip),
+                                          val=_dp(model.gmrf_val), kappa=_dp(model.gmrf_kappa)))
+                bk = GlmBlock(K=model.BK, term=model.block_term.ctypes.data_as(ip), eta=model.block_eta)
+                check(self.lib.idhmc_create_glm_block(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, None, st,
+                                                      gm, C.byref(bk), model.M if R is not None else 1, R if R is not None else 0,
+                                                      C.byref(self.opt), seed))
+            elif getattr(model, "G", 0) > 0:
                 fv = pp = st = None
                 ip = C.POINTER(C.c_int32)
                 if getattr(model, "factor_has", None) is not None:
@@ -611,6 +643,17 @@ class Engine:
         val = np.zeros((F.value, self.model.n))
         check(self.lib.idhmc_glm_factor_values_get(self.h, has.ctypes.data_as(C.POINTER(C.c_int32)), _dp(val)))
         return has[:F.value].copy(), val
+
+    def glm_block(self):
+        """(terms int32 (K,), eta) of the correlation block as the context holds it (GLM(..., correlated=[glm.block(..)])); (None, None) for
+        every model without a block"""
+        K = C.c_int32(0)
+        check(self.lib.idhmc_glm_block_get(self.h, C.byref(K), None, None))
+        if K.value == 0:
+            return None, None
+        t, e = np.zeros(K.value, np.int32), C.c_double(0.0)
+        check(self.lib.idhmc_glm_block_get(self.h, C.byref(K), t.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(e)))
+        return t, e.value
 
     def glm_pairs(self):
         """(first int32 (P,), second int32 (P,), eta float64 (P,)) as the context holds them (GLM(..., correlated=)); (None, None, None) for

@@ -127,7 +127,10 @@ Correlated random effects, correlated=[pair(0, 1, eta=2.0)] (idhmc_create_glm_co
 level counts, each with one more sampled coordinate zeta = atanh rho at the end of q.  Level k's column of the second term becomes
 rho u_first + sqrt(1 - rho^2) u_second before any scale applies; eta > 0 is LKJ(eta) on the correlation, eta = 0 leaves zeta to its entry
 in the prior arrays (normal or Student-t).  correlated_effects(Dd, levels, pairs, eta) assembles groups, priors and correlated;
-correlations(model, draws) gives rho and coefficients(model, draws) applies the mix.  A covariance among three or more terms is out of
+correlations(model, draws) gives rho and coefficients(model, draws) applies the mix.  A covariance among three or four terms is a
+correlation block, correlated=[block((0, 1, 2), eta=2.0)] (idhmc_create_glm_block): the effects of a level are
+sigma .* (L u) with L the K x K Cholesky factor of a sampled correlation matrix, LKJ(eta) on it; block_effects assembles the model,
+cholesky_factors, correlation_matrix and correlations read draws.  More than one block, K > 4 and a block next to pairs are out of
 scope.
 
 Structured terms, structured=[ar1(0, eta=2.0)] or [rw1(0)] (idhmc_create_glm_struct): dependence among the levels of
@@ -391,9 +394,10 @@ def by_response(model, draws, first_chain=0):
 
 
 def _sampled(model, draws):
-    """draws as float64, checked against the model's D = Dx + A + H + J + P + Sz"""
+    """draws as float64, checked against the model's D = Dx + A + H + J + P + Bz + Sz"""
     draws = np.asarray(draws, dtype=np.float64)
-    D = model.Dx + model.A + getattr(model, "H", 0) + getattr(model, "J", 0) + getattr(model, "P", 0) + getattr(model, "Sz", 0)
+    D = (model.Dx + model.A + getattr(model, "H", 0) + getattr(model, "J", 0) + getattr(model, "P", 0) + getattr(model, "Bz", 0)
+         + getattr(model, "Sz", 0))
     if draws.shape[-1] != D:
         raise ValueError("draws must have %d coordinates along the last axis, got %d" % (D, draws.shape[-1]))
     return draws
@@ -428,7 +432,50 @@ def correlations(model, draws):
     last axis), computed as the device computes it: exactly +-1 past |zeta| of about 19, never beyond.  Any leading axes, as group_scales."""
     draws = _sampled(model, draws)
     P, Sz = getattr(model, "P", 0), getattr(model, "Sz", 0)
+    if getattr(model, "BK", 0):
+        # a block: the K (K - 1) / 2 lower entries R_ji of its correlation matrix, row-major, where the pairs' rho would stand
+        R = correlation_matrix(model, draws)
+        return np.stack([R[..., j, i] for j in range(1, model.BK) for i in range(j)], -1)
     return _rho_c(draws[..., draws.shape[-1] - Sz - P:draws.shape[-1] - Sz])[0]
+
+
+def cholesky_factors(model, draws):
+    """L of a GLM with a correlation block (GLM(..., correlated=[glm.block(..)])), shape draws.shape[:-1] + (K, K), lower triangular with
+    L_00 = 1, from the canonical partial correlations z_ji = tanh(zeta_ji) by the device's expressions: L_j0 = z_j0,
+    L_j1 = z_j1 c_j0, L_j2 = z_j2 (c_j0 c_j1), L_jj = c_j0 .. c_j,j-1, c = sqrt(1 - z^2) computed as 2 s / (1 + s^2), s = exp(-|zeta|).
+    Row j is the block's j-th term, in the order the block names them.  Any leading axes, as group_scales."""
+    draws = _sampled(model, draws)
+    K, Sz = getattr(model, "BK", 0), getattr(model, "Sz", 0)
+    if not K:
+        raise ValueError("the model has no correlation block (GLM(..., correlated=[glm.block(terms)]))")
+    nz = K * (K - 1) // 2
+    z, c = _rho_c(draws[..., draws.shape[-1] - Sz - nz:draws.shape[-1] - Sz])
+    L = np.zeros(draws.shape[:-1] + (K, K))
+    L[..., 0, 0] = 1.0
+    for j in range(1, K):
+        s = None
+        for i in range(j):
+            e = j * (j - 1) // 2 + i
+            L[..., j, i] = z[..., e] if s is None else z[..., e] * s
+            s = c[..., e] if s is None else s * c[..., e]
+        L[..., j, j] = s
+    return L
+
+
+def correlation_matrix(model, draws):
+    """R = L L' of a GLM with a correlation block, shape draws.shape[:-1] + (K, K): symmetric, the diagonal exactly 1, the lower entries
+    as the device summaries report them -- R_j0 = z_j0, and for i >= 1 L_ji L_ii + sum_k<i L_jk L_ik, k ascending."""
+    L = cholesky_factors(model, draws)
+    K = L.shape[-1]
+    R = np.zeros_like(L)
+    for j in range(K):
+        R[..., j, j] = 1.0
+        for i in range(j):
+            x = L[..., j, 0] if i == 0 else L[..., j, i] * L[..., i, i]
+            for k in range(i):
+                x = L[..., j, k] * L[..., i, k] + x
+            R[..., j, i] = R[..., i, j] = x
+    return R
 
 
 def autocorrelations(model, draws):
@@ -465,6 +512,15 @@ def _mixed(model, draws):
         for p in range(P):
             a, b = factor_columns(model, int(model.pair_first[p])), factor_columns(model, int(model.pair_second[p]))
             u[..., b] = rho[..., p:p + 1] * draws[..., a] + c[..., p:p + 1] * draws[..., b]
+    if getattr(model, "BK", 0):
+        # a block: row j >= 1 takes L_jj u_j + sum_i<j L_ji u_i, i ascending, from the raw u of the block's terms
+        L = cholesky_factors(model, draws)
+        cols = [factor_columns(model, int(t)) for t in model.block_term]
+        for j in range(1, model.BK):
+            x = L[..., j, j, None] * draws[..., cols[j]]
+            for i in range(j):
+                x = L[..., j, i, None] * draws[..., cols[i]] + x
+            u[..., cols[j]] = x
     z = 0
     for i in range(getattr(model, "S", 0)):
         cols = factor_columns(model, int(model.struct_term[i]))
@@ -669,9 +725,12 @@ def pair_terms(correlated, levels):
     naming the pair."""
     if correlated is None:
         return None, None, None
-    if not isinstance(correlated, (list, tuple)) or isinstance(correlated, Pair):
+    if not isinstance(correlated, (list, tuple)) or isinstance(correlated, (Pair, Block)):
         raise ValueError("correlated must be a list of glm.pair(first, second, eta), got %s" % type(correlated).__name__)
     if len(correlated) == 0:
+        return None, None, None
+    if any(isinstance(e, Block) for e in correlated):
+        block_terms(correlated, levels)                         # (a block is the single entry: no pairs)
         return None, None, None
     if len(correlated) > 2:
         raise ValueError("at most 2 correlated pairs (got %d)" % len(correlated))
@@ -716,6 +775,83 @@ def pair_priors(eta, D, mu, tau, kind, nu):
                              or (tau is not None and tau[cz] != 1.0)):
             raise ValueError("correlated[%d]: eta = %r is the LKJ prior of zeta: the entry of coordinate %d in the prior arrays must be the "
                              "default (kind 0, mu 0, tau 1, nu 0) and is not applied" % (p, float(eta[p]), cz))
+
+
+# ---- a correlation block of three or four terms ------------------------------------------------------------------------------------------
+Block = collections.namedtuple("Block", "terms eta")
+
+
+def block(terms, eta=2.0):
+    """a correlation block of factor terms for GLM(..., correlated=[glm.block(terms, eta)]), its single entry: K = 2, 3 or 4 distinct terms
+    of equal level counts whose effects at level k share a sampled K x K correlation matrix R = L L' -- (1 + x1 + x2 | subject) is
+    block((0, 1, 2)).  The order of `terms` is the row order of L.  The block adds K (K - 1) / 2 coordinates zeta_ji = atanh z_ji (z the
+    canonical partial correlations), row-major, where a pair's zeta would stand.  eta > 0: LKJ(eta) on R (eta = 1: uniform over
+    correlation matrices); eta = 0: the zetas' entries in prior_mu, prior_tau, prior_kind, prior_nu apply (normal or Student-t).
+    Validated by GLM() (block_terms, block_priors)."""
+    return Block(tuple(terms) if isinstance(terms, (list, tuple, np.ndarray)) else terms, eta)
+
+
+def block_terms(correlated, levels):
+    """GLM()'s validation of a block in correlated: (terms int32 (K,), eta float), or (None, None) when correlated holds none.  levels: the
+    level counts of the model's terms (None: no factor terms).  The checks are idhmc_create_glm_block's."""
+    if not isinstance(correlated, (list, tuple)) or isinstance(correlated, (Pair, Block)) or not any(isinstance(e, Block) for e in correlated):
+        return None, None
+    if len(correlated) != 1:
+        raise ValueError("correlated: a glm.block is the single entry of correlated (a model has pairs or one block, not both; got %d entries)"
+                         % len(correlated))
+    b = correlated[0]
+    if levels is None:
+        raise ValueError("a correlation block needs factor terms (GLM(..., factors=))")
+    F = len(levels)
+    if not isinstance(b.terms, tuple) or len(b.terms) not in (2, 3, 4):
+        raise ValueError("correlated[0]: a block names K = 2, 3 or 4 terms (got %r)" % (b.terms,))
+    out = []
+    for r, t in enumerate(b.terms):
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t < F:
+            raise ValueError("correlated[0]: terms[%d] = %r is outside 0..%d (the model's terms)" % (r, t, F - 1))
+        if int(t) in out:
+            raise ValueError("correlated[0]: term %d is listed twice" % int(t))
+        out.append(int(t))
+        if int(levels[int(t)]) != int(levels[out[0]]):
+            raise ValueError("correlated[0]: terms %d and %d have %d and %d levels (a block needs equal level counts)"
+                             % (out[0], int(t), int(levels[out[0]]), int(levels[int(t)])))
+    e = b.eta
+    if isinstance(e, bool) or not isinstance(e, (int, float, np.integer, np.floating)) or not (np.isfinite(e) and e >= 0.0):
+        raise ValueError("correlated[0]: eta = %r must be finite and >= 0 (0: the prior arrays' entries of the zetas apply)" % (e,))
+    return np.array(out, np.int32), float(e)
+
+
+def block_priors(eta, nz, D, mu, tau, kind, nu):
+    """GLM()'s checks of the block's zetas' entries in the prior arrays (the last nz of D): no log kind; with eta > 0 the defaults"""
+    for cz in range(D - nz, D):
+        k = 0 if kind is None else int(kind[cz])
+        if k >= PRIOR_LOG_HALF_NORMAL:
+            raise ValueError("correlated[0]: prior_kind[%d] = PRIOR_%s is a prior on exp(q): coordinate %d is a zeta = atanh z, not a logarithm "
+                             "(normal and student_t are for a zeta)" % (cz, PRIOR_NAMES[k], cz))
+        if eta > 0.0 and (k != 0 or (nu is not None and nu[cz] != 0.0) or (mu is not None and mu[cz] != 0.0)
+                          or (tau is not None and tau[cz] != 1.0)):
+            raise ValueError("correlated[0]: eta = %r is the LKJ prior of the zetas: the entry of coordinate %d in the prior arrays must be the "
+                             "default (kind 0, mu 0, tau 1, nu 0) and is not applied" % (eta, cz))
+
+
+def block_effects(Dd, levels, terms, eta=2.0, A=0, scale=None, coefficients=None, aux=None):
+    """the keyword arguments of GLM() for a correlation block: what random_intercepts(Dd, levels, A, scale, coefficients, aux) returns, its
+    prior arrays extended by the K (K - 1) / 2 zetas, plus `correlated` = [glm.block(terms, eta)] -- (1 + x1 + x2 | subject) is
+    GLM(X, Y, source, factors=[subject, glm.term(subject, values=x1), glm.term(subject, values=x2)],
+        **glm.block_effects(X.shape[1], [N, N, N], (0, 1, 2), eta=2.0)).
+    eta: LKJ(eta) on the correlation matrix (0 is not offered here: it needs prior entries on the zetas, which GLM()'s keywords take)."""
+    if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or not (np.isfinite(eta) and eta > 0.0):
+        raise ValueError("eta = %r must be finite and > 0" % (eta,))
+    corr = [block(terms, float(eta))]
+    t, _ = block_terms(corr, [int(N) for N in levels])
+    kw = random_intercepts(Dd, levels, A, scale, coefficients, aux)
+    nz = t.size * (t.size - 1) // 2
+    kw["prior_mu"] = np.r_[kw["prior_mu"], np.zeros(nz)]
+    kw["prior_tau"] = np.r_[kw["prior_tau"], np.ones(nz)]
+    kw["prior_kind"] = np.r_[kw["prior_kind"], np.zeros(nz, np.int32)].astype(np.int32)
+    kw["prior_nu"] = np.r_[kw["prior_nu"], np.zeros(nz)]
+    kw["correlated"] = corr
+    return kw
 
 
 def correlated_effects(Dd, levels, pairs, eta=2.0, A=0, scale=None, coefficients=None, aux=None):
@@ -791,6 +927,9 @@ def struct_terms(structured, levels, correlated=None, local=None, Dd=0):
         if isinstance(pr, Pair):
             paired.setdefault(pr.first, p)
             paired.setdefault(pr.second, p)
+        elif isinstance(pr, Block):                             # (a block's terms are refused as a pair's are)
+            for t in pr.terms:
+                paired.setdefault(t, p)
     off = int(Dd) + np.r_[0, np.cumsum([int(N) for N in levels])]
     used = set()
     for i, entry in enumerate(structured):
@@ -1020,6 +1159,9 @@ def gmrf_terms(gmrfs, levels, correlated=None, structured=None, local=None, Dd=0
         if isinstance(pr, Pair):
             paired.setdefault(pr.first, p)
             paired.setdefault(pr.second, p)
+        elif isinstance(pr, Block):                             # (a block's terms are refused as a pair's are)
+            for t in pr.terms:
+                paired.setdefault(t, p)
     for i, st in enumerate(structured or ()):
         if isinstance(st, Structure):
             structd.setdefault(st.term, i)
@@ -1098,7 +1240,7 @@ def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):
     Every term gets a group of its own, whether it has values or not: a random intercept and slope per subject, (1 + x | subject), is
     GLM(X, Y, source, factors=[subject, glm.term(subject, values=x)], **glm.random_intercepts(X.shape[1], [N, N])), the scale of the
     intercepts and the scale of the slopes sampled independently.  A sampled correlation between the two is correlated_effects()
-    (GLM(..., correlated=[glm.pair(0, 1)])); a covariance among three or more terms is out of scope."""
+    (GLM(..., correlated=[glm.pair(0, 1)])); a covariance among three or four terms is block_effects() (glm.block)."""
     Dd = int(Dd)
     lev = [int(N) for N in levels]
     if Dd < 1:

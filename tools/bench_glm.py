@@ -64,6 +64,12 @@ same model without `correlated`, which runs the kernels of a build without the f
 same length under --lockstep: corr_over_uncorr is what the mix and its chain rule cost per gradient.  Meant to run under --lockstep
 with --pairs ''.
 
+--block-cost (GLM(..., correlated=[glm.block(..)])) runs, per row DdxLEVELSxN of --block-rows and chain count, two
+models on the data of --slope-cost with a third valued term on the same index, (1 + x1 + x2 | s): the three terms in a K = 3 correlation
+block (LKJ(2), three more coordinates), and the first two paired with the third independent (one more coordinate), which runs the kernels
+of a build without the feature on the same shape.  Fixed eps and trees of the same length under --lockstep: block_over_pair is what the
+wider mix and chain rule cost per gradient.  Meant to run under --lockstep with --pairs ''.
+
 --struct-cost (GLM(..., structured=)) runs, per row DdxLEVELSxN of --struct-rows and chain count, three models on the
 data of --slope-cost: (1 + x | s) with the intercepts an AR(1) sequence along the level index (Beta(2, 2) on (phi + 1) / 2, one more
 coordinate), with the intercepts a first-order random walk (no coordinate), and the same model without `structured`, which runs the
@@ -638,6 +644,12 @@ def main():
                     "(a sampled correlation, LKJ(2)) and without (DESIGN section 22); use --lockstep, and --pairs '' to run nothing else")
     ap.add_argument("--corr-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 21's rows 1 and 1')")
     ap.add_argument("--corr-sides", default="corr,uncorr", help="the sides of each row to run")
+    ap.add_argument("--block-cost", action="store_true", help="per row of --block-rows (1 + x1 + x2 | s) with the three terms in a K = 3 "
+                    "correlation block, and with the first two paired and the third independent (DESIGN section 26); use --lockstep, and "
+                    "--pairs '' to run nothing else")
+    ap.add_argument("--block-rows", default="20x70x1000,20x150x1000", help="DdxLEVELSxN,... (LEVELS per term, three terms: the matrix cores "
+                    "at L = 256 and the per-wave form at L = 512)")
+    ap.add_argument("--block-sides", default="block,pair", help="the sides of each row to run")
     ap.add_argument("--struct-cost", action="store_true", help="per row of --struct-rows the model of --slope-cost with its first term an AR(1) "
                     "sequence, a random walk, and unstructured (DESIGN section 23); use --lockstep, and --pairs '' to run nothing else")
     ap.add_argument("--struct-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 22's rows: the matrix cores and the per-wave form)")
@@ -745,6 +757,34 @@ def main():
                 if "corr" in row and "uncorr" in row:
                     row["same_steps"] = row["corr"]["steps"] == row["uncorr"]["steps"]
                     row["corr_over_uncorr"] = row["corr"]["leapfrog_steps_per_s"] / row["uncorr"]["leapfrog_steps_per_s"]
+                res["results"].append(row)
+    if a.block_cost:
+        sides = a.block_sides.split(",")
+        for spec in a.block_rows.split(","):
+            Dd, N, n = (int(v) for v in spec.split("x"))
+            X, y, idx, x, kw, q0, cov = slope_problem(Dd, N, n, seed=Dd * 7919 + N * 31 + n)
+            x2 = 0.5 * np.random.default_rng(N + n).standard_normal(n)
+            valued = [(idx, N), pkg.glm.term(idx, values=x, levels=N), pkg.glm.term(idx, values=x2, levels=N)]
+            u2 = 0.1 * np.random.default_rng(N + n + 1).standard_normal(N)
+            q3 = np.r_[q0[:Dd + 2 * N], u2, q0[Dd + 2 * N:], np.log(0.3)]                  # [beta | u0 u1 u2 | omega0 omega1 omega2]
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="block_cost", Dd=Dd, levels=N, n=n, Dx=Dd + 3 * N, L=padded(Dd + 3 * N + 6), chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                for side in sides:
+                    if side == "block":
+                        mdl, qs = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **pkg.glm.block_effects(Dd, [N, N, N], (0, 1, 2), eta=2.0)), np.r_[q3, 0.3, -0.2, 0.1]
+                    else:
+                        mdl, qs = pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=valued, **pkg.glm.correlated_effects(Dd, [N, N, N], [(0, 1)], eta=2.0)), np.r_[q3, 0.3]
+                    runs = [run("glm_" + side, X, y, qs, np.eye(qs.size) * 1e-4, C, a.transitions, metric=metric, mdl=mdl) for _ in range(a.repeats)]
+                    r = max((u[0] for u in runs), key=lambda u: u["leapfrog_steps_per_s"])
+                    r["repeats_leapfrog_steps_per_s"] = [u[0]["leapfrog_steps_per_s"] for u in runs]
+                    row[side] = r
+                    print("# Dd=%d levels=3x%d n=%d C=%d %s (form %d): %.4e leapfrog steps/s (%s), %.3f ms/transition, create %.2f s" %
+                          (Dd, N, n, C, side, r["glm_form"], r["leapfrog_steps_per_s"],
+                           " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
+                          file=sys.stderr, flush=True)
+                if "block" in row and "pair" in row:
+                    row["same_steps"] = row["block"]["steps"] == row["pair"]["steps"]
+                    row["block_over_pair"] = row["block"]["leapfrog_steps_per_s"] / row["pair"]["leapfrog_steps_per_s"]
                 res["results"].append(row)
     if a.struct_cost:
         sides = a.struct_sides.split(",")
