@@ -552,6 +552,44 @@ int idhmc_create_glm_block(idhmc_ctx **out, int device, int64_t nchains, int64_t
                            int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
 /* *K, and with non-NULL term (K entries) and eta as the context was given them; 0 for every other context */
 int idhmc_glm_block_get(const idhmc_ctx *ctx, int32_t *K, int32_t *term, double *eta);
+/* Factor terms with several weighted levels per observation: penalised spline smooths s(x) -- a cubic B-spline
+ * gives every observation four adjacent basis functions, and with an RW2 precision as the term's GMRF prior that is a P-spline --,
+ * multi-membership effects (a pupil of two schools, weights summing to 1), a match between two teams (+1 / -1), any sparse block of the
+ * design with a bounded number of entries per row.  Term f has a WIDTH M_f in 1..4: observation i has M_f entries
+ * (lvl_{f,m}[i], w_{f,m}[i]), m < M_f.  The term's columns are still off_f .. off_f + N_f - 1 of the model and nothing is stored in X
+ * for them; F <= 4 as before, and the planes P = sum M_f are limited to 8.  An entry may be absent (lvl = -1, its value ignored) when
+ * an observation has fewer than M_f members: the present entries come first, and within a term their levels are STRICTLY ASCENDING,
+ * hence distinct; an observation with no present entry in a term is allowed.  The arithmetic -- the kernels follow this bit for bit --
+ *   z_i = the dfma chain over c < Dd (as above), then for f = 0 .. F-1 ascending and within f for m = 0 .. M_f-1 ascending:
+ *           z_i = dfma(w_{f,m}[i], b[off_f + lvl_{f,m}[i]], z_i)   for every present entry (a term given without values: w = 1.0)
+ *   G_{off_f + k} = the dfma chain from +0 of dfma(w, r_i, G) over the observations i < n that have level k in any plane of term f,
+ *           i ascending (levels are distinct within an observation, so it appears at most once); a w of exactly 0.0 stays in its list
+ * and everything after G is untouched.  Because the levels ascend, this is bit for bit the same model on the expanded matrix, whose
+ * column off_f + k holds w_{f,m}[i] where lvl_{f,m}[i] = k and 0.0 elsewhere, under the conditions of idhmc_create_glm_slopes (finite b,
+ * r, w; the -0 edge stated there).  A wide term may be grouped, carry local scales, be a GMRF term or be structured; many responses
+ * compose.  Out of scope: width > 4, more than 8 planes, a wide term in a pair or a block.
+ *
+ * idhmc_create_glm_multi is idhmc_create_glm_block with these.  members == NULL gives exactly the context of idhmc_create_glm_block.
+ * With members, factors gives F and levels and its index must be NULL, and values (the idhmc_glm_factor_values argument) must be NULL.
+ * If every width is 1 (and then no entry may be absent) the context is the one idhmc_create_glm_block builds from those planes: the
+ * same kernels, bits and footprint.  Otherwise the device holds the planes, 4 P n_pad + 16 P n_pad + P n_pad bytes plus the starts,
+ * counted in idhmc_device_bytes.  No LDS is added.  Refused with IDHMC_ERR_BAD_ARG before the device is touched, each message naming the
+ * term, plane and observation: a width outside 1..4 or P > 8; members without factors; both index sources or both value sources given;
+ * a level outside -1 .. N_f-1; -1 in a term of width 1; a present entry behind an absent one; levels of an observation not strictly
+ * ascending; a non-finite value on a present entry; a term of width > 1 named by a pair or a block; and everything
+ * idhmc_create_glm_block refuses. */
+typedef struct { const int32_t *width;   /* F entries, 1..4, sum <= 8 */
+                 const int32_t *index;   /* P x n row-major, planes of term 0 first; -1 = absent */
+                 const double  *values;  /* P x n row-major, or NULL: every present entry 1.0 */ } idhmc_glm_members;
+int idhmc_create_glm_multi(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                           const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                           const idhmc_glm_structs *structs, const idhmc_glm_gmrfs *gmrfs, const idhmc_glm_block *block,
+                           const idhmc_glm_members *members, int64_t M, int64_t chains_per_response, const idhmc_options *opt, uint64_t seed);
+/* width (F entries; room for 4), and with non-NULL index and values the P x n planes as the context was given them (values: 1.0 on the
+ * present entries of a table given without values, 0.0 on absent ones).  A context without a wide term reports its F terms as planes of
+ * width 1.  With a wide term idhmc_glm_factors_get reports the first plane of every term. */
+int idhmc_glm_members_get(const idhmc_ctx *ctx, int32_t *width, int32_t *index, double *values);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

@@ -59,6 +59,10 @@ class GlmBlock(C.Structure):
     _fields_ = [("K", C.c_int32), ("term", C.POINTER(C.c_int32)), ("eta", C.c_double)]
 
 
+class GlmMembers(C.Structure):
+    _fields_ = [("width", C.POINTER(C.c_int32)), ("index", C.POINTER(C.c_int32)), ("values", C.POINTER(C.c_double))]
+
+
 class Options(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("min_delta", C.c_double),
                 ("da_delta", C.c_double), ("da_gamma", C.c_double), ("da_kappa", C.c_double),
@@ -124,6 +128,10 @@ SYMBOLS = {
                                          C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), C.POINTER(GlmPairs), C.POINTER(GlmStructs),
                                          C.POINTER(GlmGmrfs), C.POINTER(GlmBlock), _i64, _i64, C.POINTER(Options), _u64]),
     "idhmc_glm_block_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double)]),
+    "idhmc_create_glm_multi": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
+                                         C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), C.POINTER(GlmPairs), C.POINTER(GlmStructs),
+                                         C.POINTER(GlmGmrfs), C.POINTER(GlmBlock), C.POINTER(GlmMembers), _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_glm_members_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double)]),
     "idhmc_destroy": (C.c_int, [_vp]),
     "idhmc_set_stream": (C.c_int, [_vp, _vp]),
     "idhmc_synchronize": (C.c_int, [_vp]),

@@ -1,6 +1,7 @@
 // idhmc_create.hip -- a context's life: the argument checks of the creation entry points (every one answers before the
 // device is looked for), set-up, idhmc_destroy, the default options and what a context can be asked about itself.
 #include "idhmc_host.hpp"
+#include "idhmc_members.hpp"
 
 void idhmc_default_options(idhmc_options *o)
 {
@@ -84,6 +85,9 @@ struct GlmParts {
     int32_t BK = 0, BZ = 0;    // idhmc_create_glm_block: the block's terms K and its zetas K (K - 1) / 2, which stand where the pairs' would
     const int32_t *bterm = nullptr;    // [BK] the terms in row order, BK > 0 (never null then; every entry checked)
     double beta = 0.0;         // the block's eta
+    int32_t MP = 0;            // idhmc_create_glm_multi with a wide term: the planes, sum of the widths (findex and fvalues are then unused)
+    const int32_t *mwidth = nullptr, *mindex = nullptr;    // [F], [MP][n], MP > 0 (never null then; every entry checked)
+    const double *mvalues = nullptr;   // [MP][n], or null: 1.0 on every present entry
 };
 // the padded width of the stored columns of X: L of the model, and with factors Lx = 128 ceil(Dd / 128)
 static int64_t stored_width(const GlmParts &g, int D, int64_t *L_out = nullptr)
@@ -212,39 +216,28 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
     const int64_t D = Dm - g.fcols, LX = stored_width(g, s.D);      // the columns X stores (with factors: the dense ones) and their padded width
     // The level lists of a model with factors, before anything is uploaded: per block of 128 observations its places sorted by factor,
     // level, place (a counting sort), and where each level's list starts
-    const int64_t nb = npad / 128, cols = g.fcols;
-    std::vector<int32_t> hfidx, hfstart, cur;
-    std::vector<unsigned char> hfpos;
-    std::vector<double> hfval, hfwl;       // terms with values: w per observation (1.0 for a plain term, 0.0 in the padding), and in list order
+    const int64_t cols = g.fcols;
+    Planes pl;                             // a plain term is one plane; a wide term (g.MP > 0) one per level an observation can have in it
+    LevelLists ll;
+    const bool fvalued = g.fhas || g.MP > 0;      // every plane reads a value
     if (g.F > 0) {
-        hfidx.assign((size_t)(g.F * npad), -1);
-        hfstart.assign((size_t)(nb * (cols + 1)), 0);
-        hfpos.assign((size_t)(nb * 128 * g.F), 0);
-        cur.assign((size_t)cols, 0);
-        for (int64_t f = 0; f < g.F; ++f)
-            for (int64_t i = 0; i < n; ++i) hfidx[(size_t)(f * npad + i)] = g.findex[f * n + i];
-        if (g.fhas) {
-            hfval.assign((size_t)(g.F * npad), 0.0);
-            hfwl.assign((size_t)(nb * 128 * g.F), 0.0);
-            for (int64_t f = 0; f < g.F; ++f)
-                for (int64_t i = 0; i < n; ++i) hfval[(size_t)(f * npad + i)] = g.fhas[f] ? g.fvalues[f * n + i] : 1.0;
-        }
-        for (int64_t b = 0; b < nb; ++b) {
-            int32_t *st = &hfstart[(size_t)(b * (cols + 1))];
-            const int64_t m = n - 128 * b < 128 ? n - 128 * b : 128;
-            int64_t e0 = 0;
-            for (int64_t f = 0; f < g.F; e0 += g.levels[f], ++f)
-                for (int64_t ii = 0; ii < m; ++ii) ++st[e0 + g.findex[f * n + 128 * b + ii] + 1];
-            for (int64_t e = 0; e < cols; ++e) { st[e + 1] += st[e]; cur[(size_t)e] = st[e]; }
-            e0 = 0;
-            for (int64_t f = 0; f < g.F; e0 += g.levels[f], ++f)
-                for (int64_t ii = 0; ii < m; ++ii) {
-                    const int64_t t = b * 128 * g.F + cur[(size_t)(e0 + g.findex[f * n + 128 * b + ii])]++;
-                    hfpos[(size_t)t] = (unsigned char)ii;
-                    if (g.fhas) hfwl[(size_t)t] = hfval[(size_t)(f * npad + 128 * b + ii)];
+        for (int f = 0; f < g.F; ++f)
+            for (int m = 0; m < (g.MP > 0 ? g.mwidth[f] : 1); ++m, ++pl.P) {
+                pl.term[pl.P] = f;
+                if (g.MP > 0) {
+                    pl.idx[pl.P] = g.mindex + (int64_t)pl.P * n;
+                    pl.val[pl.P] = g.mvalues ? g.mvalues + (int64_t)pl.P * n : nullptr;
+                } else {
+                    pl.idx[pl.P] = g.findex + (int64_t)f * n;
+                    pl.val[pl.P] = g.fhas && g.fhas[f] ? g.fvalues + (int64_t)f * n : nullptr;
                 }
-        }
+            }
+        // (a wide model's plane table, eight entries, stands behind the starts: filled in below, once the offsets are known)
+        build_level_lists(pl, g.F, g.levels, n, fvalued, g.MP > 0 ? kMaxPlanes : 0, &ll);
     }
+    std::vector<int32_t> &hfidx = ll.fidx, &hfstart = ll.fstart;
+    std::vector<unsigned char> &hfpos = ll.fpos;
+    std::vector<double> &hfval = ll.fval, &hfwl = ll.fwl;
     std::vector<double> hx((size_t)(npad * LX), 0.0), hxt((size_t)(npad * LX), 0.0), hy((size_t)(M * K * npad), 0.0);
     for (int64_t i = 0; i < n; ++i)
         for (int64_t k = 0; k < D; ++k) {
@@ -319,6 +312,12 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
     if (g.F > 0) {
         int32_t *di = nullptr, *ds = nullptr;
         unsigned char *dp = nullptr;
+        if (g.MP > 0) {
+            // the first column of the term each plane belongs to (planes past the last repeat it: the table is read inside its eight entries)
+            int32_t toff[4], o = (int32_t)D;
+            for (int f = 0; f < g.F; o += g.levels[f], ++f) toff[f] = o;
+            for (int p = 0; p < kMaxPlanes; ++p) hfstart[hfstart.size() - kMaxPlanes + p] = toff[pl.term[p < pl.P ? p : pl.P - 1]];
+        }
         if (int rc = dalloc(c, &di, (int64_t)hfidx.size())) return rc;
         if (int rc = dalloc(c, &ds, (int64_t)hfstart.size())) return rc;
         if (int rc = dalloc(c, &dp, (int64_t)hfpos.size())) return rc;
@@ -334,8 +333,24 @@ static int upload_regression(idhmc_ctx *c, const GlmParts &g, bool glm)
             if (f < g.F) off += g.levels[f];
         }
         c->glm_flevels.assign(g.levels, g.levels + g.F);
-        c->glm_findex.assign(g.findex, g.findex + (int64_t)g.F * n);
-        if (g.fhas) {
+        if (g.MP > 0) {
+            // (idhmc_glm_factors_get reports the first plane of every term)
+            s.lr_mp = g.MP;
+            c->glm_mwidth.assign(g.mwidth, g.mwidth + g.F);
+            c->glm_mindex.assign(g.mindex, g.mindex + (int64_t)g.MP * n);
+            if (g.mvalues) c->glm_mvalues.assign(g.mvalues, g.mvalues + (int64_t)g.MP * n);
+            for (int p = 0; p < pl.P; ++p)
+                if (p == 0 || pl.term[p] != pl.term[p - 1]) c->glm_findex.insert(c->glm_findex.end(), pl.idx[p], pl.idx[p] + n);
+            double *dv = nullptr, *dw = nullptr;
+            if (int rc = dalloc(c, &dv, (int64_t)hfval.size())) return rc;
+            if (int rc = dalloc(c, &dw, (int64_t)hfwl.size())) return rc;
+            HIPCHK(hipMemcpyAsync(dv, hfval.data(), sizeof(double) * hfval.size(), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dw, hfwl.data(), sizeof(double) * hfwl.size(), hipMemcpyHostToDevice, c->stream));
+            s.lr_fval = dv; s.lr_fwl = dw;
+        } else {
+            c->glm_findex.assign(g.findex, g.findex + (int64_t)g.F * n);
+        }
+        if (g.fhas && g.MP == 0) {
             double *dv = nullptr, *dw = nullptr;
             if (int rc = dalloc(c, &dv, (int64_t)hfval.size())) return rc;
             if (int rc = dalloc(c, &dw, (int64_t)hfwl.size())) return rc;
@@ -765,13 +780,15 @@ static int validate_local(const idhmc_glm_desc *glm, const idhmc_glm_local *lc, 
 
 // The factors of idhmc_create_glm_factors: every check of F, levels and index.  *fcols: the level columns, sum N_f (0: the context is
 // the one without factors)
-static int validate_factors(const idhmc_glm_desc *glm, const idhmc_glm_factors *fc, int64_t *fcols)
+static int validate_factors(const idhmc_glm_desc *glm, const idhmc_glm_factors *fc, int64_t *fcols, bool members = false)
 {
     *fcols = 0;
     if (!fc) return IDHMC_OK;
     if (fc->F < 0 || fc->F > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors must be an integer in 0..4", fc->F);
     if (fc->F == 0) return IDHMC_OK;
-    if (!fc->levels || !fc->index) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors need levels and index (%s is NULL)", fc->F, fc->levels ? "index" : "levels");
+    if (members && fc->index)
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: members and factors->index are both given: with members the levels come from members->index (factors->index must be NULL)");
+    if (!fc->levels || (!fc->index && !members)) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors need levels and index (%s is NULL)", fc->F, fc->levels ? "index" : "levels");
     int64_t cols = 0;
     for (int f = 0; f < fc->F; ++f) {
         if (fc->levels[f] < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor %d has levels[%d] = %d: at least one level is needed", f, f, fc->levels[f]);
@@ -780,7 +797,7 @@ static int validate_factors(const idhmc_glm_desc *glm, const idhmc_glm_factors *
     if (glm->Dx - cols < 1)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: Dd = Dx - sum of levels = %d - %lld = %lld: at least one dense column is needed",
                     glm->Dx, (long long)cols, (long long)(glm->Dx - cols));
-    for (int f = 0; f < fc->F; ++f)
+    for (int f = 0; f < fc->F && !members; ++f)               // (a table of members is checked by check_members)
         for (int64_t i = 0; i < glm->n; ++i) {
             const int32_t v = fc->index[(int64_t)f * glm->n + i];
             if (v < 0 || v >= fc->levels[f])
@@ -1050,18 +1067,44 @@ static int validate_block(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
 }
 
 // idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors,
-// idhmc_create_glm_slopes, idhmc_create_glm_corr, idhmc_create_glm_struct, idhmc_create_glm_gmrf and idhmc_create_glm_block
+// idhmc_create_glm_slopes, idhmc_create_glm_corr, idhmc_create_glm_struct, idhmc_create_glm_gmrf, idhmc_create_glm_block and
+// idhmc_create_glm_multi
 static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
                       bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
                       const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
                       const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr,
                       const idhmc_glm_pairs *pairs = nullptr, const idhmc_glm_structs *structs = nullptr,
-                      const idhmc_glm_gmrfs *gmrfs = nullptr, const idhmc_glm_block *block = nullptr)
+                      const idhmc_glm_gmrfs *gmrfs = nullptr, const idhmc_glm_block *block = nullptr,
+                      const idhmc_glm_members *members = nullptr)
 {
     *out = nullptr;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
     int64_t fcols = 0;
-    if (int rc = validate_factors(glm, factors, &fcols)) return rc;
+    if (members && (!factors || factors->F == 0))
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: members need factor terms: factors gives F and levels (factors is %s)", factors ? "given with F = 0" : "NULL");
+    if (members && values)
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: members and factor values are both given: with members the values come from members->values (values must be NULL)");
+    if (int rc = validate_factors(glm, factors, &fcols, members != nullptr)) return rc;
+    // A table of members every term of which has width 1 is F plain index rows, with values where it gives some: from here on it IS
+    // that model (the same context, kernels and footprint).  MP > 0: a wide term.
+    int MP = 0;
+    idhmc_glm_factors plain_f;
+    idhmc_glm_factor_values plain_v;
+    const int32_t plain_has[4] = {1, 1, 1, 1};
+    if (members) {
+        char msg[320];
+        bool wide = false;
+        if (!check_members(factors->F, factors->levels, glm->n, members->width, members->index, members->values, &MP, &wide, msg, sizeof msg))
+            return fail(IDHMC_ERR_BAD_ARG, "%s", msg);
+        if (!wide) {
+            plain_f = idhmc_glm_factors{factors->F, factors->levels, members->index};
+            plain_v = idhmc_glm_factor_values{members->values, plain_has};
+            factors = &plain_f;
+            values = members->values ? &plain_v : nullptr;
+            members = nullptr;
+            MP = 0;
+        }
+    }
     bool valued = false;
     if (int rc = validate_factor_values(glm, factors, fcols, values, &valued)) return rc;
     if (glm->A < 0 || glm->A > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: A = %d must be an integer in 0..4", glm->A);
@@ -1094,6 +1137,17 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (int rc = validate_gmrfs(glm, priors, local, J, P, S, factors, fcols, pairs, structs, gmrfs, &G)) return rc;
     int BK = 0;
     if (int rc = validate_block(glm, priors, J, P, S, SZ, G, factors, fcols, structs, gmrfs, block, &BK)) return rc;
+    if (members) {
+        // (a pair or a block takes level k of one term with level k of another, one level per observation each)
+        for (int p = 0; p < P; ++p)
+            for (const int32_t t : {pairs->first[p], pairs->second[p]})
+                if (members->width[t] > 1)
+                    return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d names term %d, which has width %d: a term with several levels per observation is in no pair", p, t, members->width[t]);
+        for (int r = 0; r < BK; ++r)
+            if (members->width[block->term[r]] > 1)
+                return fail(IDHMC_ERR_BAD_ARG, "GLM: the block names term %d, which has width %d: a term with several levels per observation is in no block",
+                            block->term[r], members->width[block->term[r]]);
+    }
     const int BZ = (BK * (BK - 1)) / 2;
     if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
     if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
@@ -1122,6 +1176,7 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
     if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
     if (fcols > 0) { parts.F = factors->F; parts.fcols = (int32_t)fcols; parts.levels = factors->levels; parts.findex = factors->index; }
     if (valued) { parts.fvalues = values->values; parts.fhas = values->has; }
+    if (members) { parts.MP = MP; parts.mwidth = members->width; parts.mindex = members->index; parts.mvalues = members->values; }
     std::vector<int32_t> kdev, kpub;     // a zeta with eta > 0: the device table marks it (kPriorLkj of idhmc_glm_coords.hpp, eta in nu's place)
     std::vector<double> nudev, nupub;
     if (P > 0) { parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta; }
@@ -1262,6 +1317,41 @@ int idhmc_create_glm_block(idhmc_ctx **out, int device, int64_t nchains, int64_t
     const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
     return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
                       pairs, structs, gmrfs, block);
+}
+
+int idhmc_create_glm_multi(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_desc *glm, const idhmc_glm_priors *priors, const idhmc_glm_local *local,
+                           const idhmc_glm_factors *factors, const idhmc_glm_factor_values *values, const idhmc_glm_pairs *pairs,
+                           const idhmc_glm_structs *structs, const idhmc_glm_gmrfs *gmrfs, const idhmc_glm_block *block,
+                           const idhmc_glm_members *members, int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_multi: null argument");
+    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
+    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
+                      pairs, structs, gmrfs, block, members);
+}
+
+int idhmc_glm_members_get(const idhmc_ctx *c, int32_t *width, int32_t *index, double *values)
+{
+    if (!c || !width) return fail(IDHMC_ERR_BAD_ARG, "idhmc_glm_members_get: null argument");
+    const int F = c->s.lr_f;
+    const int64_t n = c->s.lr_n;
+    if (c->s.lr_mp > 0) {
+        std::copy(c->glm_mwidth.begin(), c->glm_mwidth.end(), width);
+        if (index) std::copy(c->glm_mindex.begin(), c->glm_mindex.end(), index);
+        if (values)
+            for (size_t k = 0; k < c->glm_mindex.size(); ++k)
+                values[k] = c->glm_mindex[k] < 0 ? 0.0 : c->glm_mvalues.empty() ? 1.0 : c->glm_mvalues[k];
+        return IDHMC_OK;
+    }
+    // no wide term: F planes of width 1, the values of a term that has some and 1.0 elsewhere
+    for (int f = 0; f < F; ++f) width[f] = 1;
+    if (index) std::copy(c->glm_findex.begin(), c->glm_findex.end(), index);
+    if (values)
+        for (int f = 0; f < F; ++f)
+            for (int64_t i = 0; i < n; ++i)
+                values[f * n + i] = f < (int)c->glm_fhas.size() && c->glm_fhas[(size_t)f] ? c->glm_fvalues[(size_t)(f * n + i)] : 1.0;
+    return IDHMC_OK;
 }
 
 int idhmc_glm_block_get(const idhmc_ctx *c, int32_t *K, int32_t *term, double *eta)

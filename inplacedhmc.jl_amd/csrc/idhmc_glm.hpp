@@ -1,4 +1,4 @@
-// idhmc_glm.hpp -- the two forms that evaluate a generalised linear model (DESIGN sections 10-26).  The arithmetic, stage by stage for
+// idhmc_glm.hpp -- the two forms that evaluate a generalised linear model (DESIGN sections 10-27).  The arithmetic, stage by stage for
 // the full model, the device layout and every helper that does not depend on the form are in idhmc_glm_coords.hpp; the stage numbers
 // below are that header's.  Two forms with one arithmetic: GlmWave (one chain per wavefront, every kernel) and GlmCoop (the NUTS kernel
 // at L <= 256: 16 chains per workgroup, both products on the fp64 matrix cores).  The built-in logistic regression
@@ -27,7 +27,7 @@ IDHMC_DEV void logistic_terms(double z, double y, double &r, double &v)
 struct LogisticObs {
     static constexpr int K = 1, A = 0, H = 0;
     static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false,
-                          kGmrf = false, kBlock = false;
+                          kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v) { logistic_terms(z, o.y[0], r, v); }
 };
 
@@ -46,6 +46,9 @@ struct LogisticObs {
 // [kSlopes] dfma(wl, r[ii], G)).  [kGmrf] once every chain rule has run, the raw q is staged in buf a last time and stays there for the
 // prior loop: row 6 of a member reads its neighbours' u from it.  [kBlock] the block's factors and its mix take the pairs' places
 // (a model has one or the other): the twelve factors are held across the blocks like the pairs' four.
+// [kMulti] the z loop's level stage runs over the planes p < P instead of the terms: index and value of plane p at the lane offset, b
+// from buf[poff_p + lvl], the planes' loads independent of z and of each other; the lists are walked with the planes' block size, four
+// entries per trip (glm_gather's overload for GlmMulti).
 template <int NCH, class Obs>
 struct GlmWave {
     static constexpr bool kHasParams = true;
@@ -65,6 +68,7 @@ struct GlmWave {
     double inv2;             // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     GlmFactors fac;          // the factor terms (Obs::kFactors)
     GlmSlopes slo;           // their values (Obs::kSlopes)
+    GlmMulti mul;            // the planes of terms with several levels per observation (Obs::kMulti)
     const int32_t *cpart;    // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;            // the coordinate of zeta_0 and the pairs (Obs::kCorr)
     GlmBlock blk;            // the correlation block (Obs::kBlock)
@@ -95,6 +99,10 @@ struct GlmWave {
         }
         if constexpr (Obs::kFactors) fac.init(s);
         if constexpr (Obs::kSlopes) slo.init(s);
+        if constexpr (Obs::kMulti) {
+            static_assert(Obs::kFactors && Obs::kSlopes, "every plane of a wide term reads a value");
+            mul.init(s);
+        }
         if constexpr (Obs::kCorr) {
             cpart = s.lr_cpart;
             ncp = s.lr_cp;
@@ -183,7 +191,23 @@ struct GlmWave {
                 zx = dfma(xv.x, qc, zx);
                 zy = dfma(xv.y, qc, zy);
             }
-            if constexpr (Obs::kFactors) {
+            if constexpr (Obs::kMulti) {
+                // the level columns by plane, terms ascending and within a term its planes ascending: every plane reads a value, and an
+                // absent entry (lvl = -1, the padding too) adds nothing.  The index and the value of a plane wait for nothing but the
+                // block, so the loads of four planes go out together ahead of their LDS reads.
+                const int2 *lv2 = reinterpret_cast<const int2 *>(fac.idx) + lane + b * 64;
+                const double2 *w2 = reinterpret_cast<const double2 *>(slo.val) + lane + b * 64;
+                const int np = mul.P < 8 ? mul.P : 8;
+#pragma unroll 4
+                for (int p = 0; p < np; ++p) {
+                    const int o = mul.poff[p];
+                    const int2 lv = lv2[(size_t)p * (npad >> 1)];
+                    const double2 w = w2[(size_t)p * (npad >> 1)];
+                    const double bx = buf[o + (lv.x > 0 ? lv.x : 0)], by = buf[o + (lv.y > 0 ? lv.y : 0)];
+                    zx = lv.x >= 0 ? dfma(w.x, bx, zx) : zx;
+                    zy = lv.y >= 0 ? dfma(w.y, by, zy) : zy;
+                }
+            } else if constexpr (Obs::kFactors) {
                 // the level columns: b of the observation's level, factors ascending (lvl = -1, the padding, adds nothing)
                 const int2 *lv2 = reinterpret_cast<const int2 *>(fac.idx) + lane + b * 64;
 #pragma unroll
@@ -254,7 +278,10 @@ struct GlmWave {
                 for (int j = 0; j < NCH; ++j) {
                     if (128 * j + 128 > fac.dd && 128 * j < D) {               // the chunk holds a level column
                         const int c0 = 128 * j + 2 * lane, e = c0 - fac.dd;
-                        if constexpr (Obs::kSlopes) {
+                        if constexpr (Obs::kMulti) {
+                            glm_gather(G.c[j].x, mul, slo, fac, b, e, e >= 0 && c0 < D, buf);
+                            glm_gather(G.c[j].y, mul, slo, fac, b, e + 1, e + 1 >= 0 && c0 + 1 < D, buf);
+                        } else if constexpr (Obs::kSlopes) {
                             glm_gather(G.c[j].x, slo, fac, b, e, e >= 0 && c0 < D, buf);
                             glm_gather(G.c[j].y, slo, fac, b, e + 1, e + 1 >= 0 && c0 + 1 < D, buf);
                         } else {
@@ -359,6 +386,8 @@ struct GlmWave {
 // G wavefront whose tile starts at or beyond Dd skips the matrix loop; gphase spells that loop out twice, with the run-time
 // stride Lx and with the compile-time L.  A tile that holds level columns adds R[b & 1][row][i] over the column's list per lane
 // ([kSlopes] gacc[reg] = dfma(wl, R[..][ii], gacc[reg])), after the block's matrix steps where the tile straddles Dd.
+// [kMulti] the Z wavefronts add Q[row][poff_p + lvl_p[i]] per plane p < P, w_p[i] read once per observation; the G wavefronts walk the
+// lists with the planes' block size, four entries per trip, the chain in list order.
 template <int NCH, class Obs>
 struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     static constexpr bool kHasParams = true;
@@ -387,6 +416,7 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
     double inv2;                 // 1 / slab_scale^2, 0 without a slab (Obs::kLocal)
     GlmFactors fac;              // the factor terms (Obs::kFactors)
     GlmSlopes slo;               // their values (Obs::kSlopes)
+    GlmMulti mul;                // the planes of terms with several levels per observation (Obs::kMulti)
     const int32_t *cpart;        // the partner table of the paired columns, device (Obs::kCorr)
     int cz0, ncp;                // the coordinate of zeta_0 and the pairs (Obs::kCorr)
     GlmBlock blk;                // the correlation block (Obs::kBlock)
@@ -410,6 +440,10 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
         }
         if constexpr (Obs::kFactors) fac.init(s);
         if constexpr (Obs::kSlopes) slo.init(s);
+        if constexpr (Obs::kMulti) {
+            static_assert(Obs::kFactors && Obs::kSlopes, "every plane of a wide term reads a value");
+            mul.init(s);
+        }
         if constexpr (Obs::kCorr) {
             cpart = s.lr_cpart;
             ncp = s.lr_cp;
@@ -475,7 +509,22 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
             for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * (kb0 + u)], bv[u], acc, 0, 0, 0);
         }
         const int i = 128 * b + 16 * zt + jj;
-        if constexpr (Obs::kFactors) {
+        if constexpr (Obs::kMulti) {
+            // the level columns by plane, terms ascending and within a term its planes ascending: b of observation i's level from each
+            // row's Q, the observation's value the same for the four rows (an absent entry, lvl = -1, adds nothing)
+            const int np = mul.P < 8 ? mul.P : 8;
+#pragma unroll 4
+            for (int p = 0; p < np; ++p) {
+                const int lv = fac.idx[(size_t)p * npad + i];
+                const double w = slo.val[(size_t)p * npad + i];
+                const double *qp = tile + kQ + kk * DS + mul.poff[p] + (lv > 0 ? lv : 0);
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const double bl = qp[4 * reg * DS];
+                    acc[reg] = lv >= 0 ? dfma(w, bl, acc[reg]) : acc[reg];
+                }
+            }
+        } else if constexpr (Obs::kFactors) {
             // the level columns: b of observation i's level from each row's Q, factors ascending (lvl = -1, the padding, adds nothing)
 #pragma unroll
             for (int f = 0; f < 4; ++f) {
@@ -558,6 +607,19 @@ struct GlmCoop : CoopRounds<GlmCoop<NCH, Obs>> {
                 int s0, cnt;
                 glm_list(fac, b, e, e >= 0 && c < dx, s0, cnt);
                 const double *rp = rtile(b) + kk * RS;
+                if constexpr (Obs::kMulti) {
+                    // (the block's entries are 128 P: the list is walked with the planes' clamps, four entries at a time)
+                    for (int k = 0; k < cnt; k += kListBatch) {
+                        GlmListBatch q;
+                        glm_list_batch(q, mul, slo, fac, b, s0 + k);
+#pragma unroll
+                        for (int u = 0; u < kListBatch; ++u) {
+#pragma unroll
+                            for (int reg = 0; reg < 4; ++reg) gacc[reg] = k + u < cnt ? dfma(q.wl[u], rp[4 * reg * RS + q.ii[u]], gacc[reg]) : gacc[reg];
+                        }
+                    }
+                    return;
+                }
                 for (int k = 0; k < cnt; ++k) {
                     const int ii = glm_list_at(fac, b, s0 + k);
                     if constexpr (Obs::kSlopes) {

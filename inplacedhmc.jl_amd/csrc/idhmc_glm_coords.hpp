@@ -2,11 +2,11 @@
 // not depend on how a kernel evaluates it.  The two forms that do (GlmWave, GlmCoop) and what is theirs alone are in idhmc_glm.hpp.
 //   l(q) = -sum_i v(z_i, y_i) + log prior(q),   v = -log p(y | z) up to a data-only term,   r_i = d log p(y_i | z_i) / dz_i
 // The observation is a policy type Obs: Obs::K data columns per observation (1..4), Obs::A auxiliary coordinates, Obs::H groups, the
-// compile-time flags kResponses, kPriors, kLocal, kFactors, kSlopes, kCorr, kStruct, kGmrf, kBlock, and
+// compile-time flags kResponses, kPriors, kLocal, kFactors, kSlopes, kCorr, kStruct, kGmrf, kBlock, kMulti, and
 //   static void terms(double z, const GlmObs &o, double &r, double &v)                                             (A = 0)
 //   static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)    s[j] = d log p / d a_j
 // A flag that is false (A, H = 0) takes its stage out at compile time: none of the instructions of a model without it changes.  Each
-// feature's record is its DESIGN section (10-26); this comment is the full model in evaluation order, every stage tagged with its
+// feature's record is its DESIGN section (10-27); this comment is the full model in evaluation order, every stage tagged with its
 // flag, and both forms and the tests' C restatements follow it bit for bit.  dfma is one fused multiply-add; every other operation
 // is a plain one in the association written.
 //
@@ -15,7 +15,11 @@
 //   u       the Dx columns of the model.  [kFactors] Dd >= 1 dense columns, stored in X, then the levels of F <= 4 factor terms, never
 //           stored: off_f = Dd + N_0 + .. + N_{f-1}, column off_f + k is level k of term f (N_f >= 1), Dx = Dd + sum N_f.  Without
 //           factors Dd = Dx.  [kSlopes] a term may carry a finite value w_f[i] per observation next to its level index lvl_f[i]; two
-//           terms may share one index array ((1 | s) and (x | s) are two terms of N columns each).
+//           terms may share one index array ((1 | s) and (x | s) are two terms of N columns each).  [kMulti] term f has a WIDTH M_f in
+//           1..4: observation i has M_f entries (lvl_{f,m}[i], w_{f,m}[i]), m < M_f, the planes P = sum M_f <= 8.  An entry may be absent
+//           (lvl = -1, the value ignored): the present entries of an observation come first and within a term their levels are strictly
+//           ascending, hence distinct; an observation with no present entry in a term is allowed.  The columns are what they were,
+//           off_f .. off_f + N_f - 1, and a wide term is in no pair and no block.
 //   a       [A > 0] auxiliary coordinates: every observation sees them, no product with X does.
 //   omega   [H > 0] log scales of the coefficient groups; grp[c] in {-1, 0 .. H-1} (DevState::lr_grp; -1: not in a group, and every
 //           coordinate >= Dx).
@@ -76,6 +80,8 @@
 //        z_i = z_i + b[off_f + lvl_f[i]]  (plain addition),   [kSlopes]  z_i = dfma(w_f[i], b[off_f + lvl_f[i]], z_i)
 //      Padded observations carry lvl = -1 and add nothing.  Under kSlopes EVERY term reads a value: a term without values has a plane of
 //      1.0, and fma(1, b, z) is z + b rounded once, so its bits are those of the plain addition.
+//      [kMulti] for f ascending and within f for m = 0 .. M_f-1 ascending:  z_i = dfma(w_{f,m}[i], b[off_f + lvl_{f,m}[i]], z_i)  for the
+//      present entries.  Every plane reads a value, as under kSlopes (a term given without values has planes of 1.0).
 //  6 (r_i, v_i, s_i0 ..) = Obs::terms(z_i, {y_i0 .. y_i,K-1; constants}, a), one call; for i >= n all are overwritten with 0 (the terms are
 //      computed, then overwritten: a NaN there does not leak).  [kResponses] Y is M sets of K planes, [M][K][n_pad], and the chain of
 //      GLOBAL id g samples response g / R (lr_r), whatever context or tile it runs in: only the address of y_i differs, and a kernel binds
@@ -89,6 +95,9 @@
 //      [kSlopes] the dfma chain from +0 of dfma(w_f[i], r_i, G) over them.  An observation with w = 0.0 stays in its level's list:
 //      dfma(0, r, G) is performed, as the expanded model does.  A level with no observation is allowed: its G is +0 and the prior alone
 //      moves it.
+//      [kMulti] the same chain over the observations i < n that have level k in ANY plane of term f, i ascending, each with the w of the
+//      plane that names k.  Levels are distinct within an observation, so it appears at most once per level: a level's list in a block of
+//      128 still has at most 128 entries and the clamps below stay valid.  A w of exactly 0.0 stays in its list.
 //  9 [A] scores:  S_j[rho], rho = i mod 128: plain additions over observation blocks ascending, from +0;  G_{Dx+j} = the canonical
 //      128-residue tree over S_j (wave_sum, lane l holding residues 2l, 2l + 1).   A[rho] accumulates v_i the same way.
 //
@@ -153,7 +162,10 @@
 // poisons every z of the expanded model (0 * inf) and here only that level's observations; both are rejected points.  With values the
 // expanded column off_f + k holds w_f[i] where lvl_f[i] = k and 0.0 elsewhere, and there is one more edge: a chain from +0 now CAN reach
 // -0 -- fma(w, b, +0) with w b negative and below half the smallest subnormal rounds to -0, and the expanded model's next fma(0, x, -0)
-// is +0 for x >= 0 where this one keeps -0.  Stated and not engineered around.
+// is +0 for x >= 0 where this one keeps -0.  Stated and not engineered around.  [kMulti] the expanded column off_f + k holds w_{f,m}[i]
+// where lvl_{f,m}[i] = k and 0.0 elsewhere, and it is the ascending levels that keep the bits: the expanded chain of z_i meets the
+// columns of a term in ascending order, which is then the order of the planes, and everything between two of them is fma(0, b, z) = z.
+// The same conditions, the same two edges.
 //
 // DEVICE LAYOUT (DevState).  X [n_pad][Lx] (lr_x), X' [Lx][n_pad] (lr_xt), Y as K planes [K][n_pad] per response (lr_y), all zero-padded
 // (+0 in every column >= Dd); a GLM's constants in user_params (user_nparams of them).  Lx = 128 ceil(Dd / 128) is a run-time member
@@ -168,7 +180,12 @@
 // term, 0.0 in the padding, where lvl = -1 adds nothing anyway); lr_fwl [n_pad / 128][128 F] holds the same values a second time in the
 // order of lr_fpos, written by the counting sort that builds the lists, so that the value of list entry t has an address known before
 // the entry's byte arrives -- no second dependent global load behind that byte.  t is clamped as glm_list_at clamps it and the 128-trip
-// cap holds: a bad list still cannot read outside the block's entries.
+// cap holds: a bad list still cannot read outside the block's entries.  [kMulti] (lr_mp = P > 0) the layout goes by PLANE, the planes of
+// term 0 first: lr_fidx and lr_fval [P][n_pad] (-1 and 0.0 where an entry is absent), lr_fpos and lr_fwl with 128 P entries per block --
+// the counting sort puts every present entry of every plane of a term into that term's level lists, places ascending within a level, the
+// entry's value into lr_fwl at the same position -- and eight more int32 behind the last row of lr_fstart: the first column of the term
+// each plane belongs to (GlmMulti::poff; uniform, so a scalar load).  lr_fstart stays per column and lr_foff per TERM: pairs, blocks,
+// structures and GMRF slots index it as before.  The reason lr_fwl exists applies unchanged.
 //
 // EXCHANGE BETWEEN LANES.  A column and its lambda, the two columns of a pair, and neighbouring levels of a structured term live in
 // different lanes, chunks and components in general; so do the up to three partners of a block's column.  The helpers of stages 2-4 and 10-12 take vec, a wavefront-private LDS vector
@@ -959,6 +976,62 @@ IDHMC_DEV void glm_gather(double &G, const GlmSlopes &v, const GlmFactors &f, in
     int s0, cnt;
     glm_list(f, b, e, has, s0, cnt);
     for (int k = 0; k < cnt; ++k) G = dfma(glm_list_value(v, f, b, s0 + k), r[glm_list_at(f, b, s0 + k)], G);
+}
+// Terms with several weighted levels per observation (Obs::kMulti, with kFactors and kSlopes): the index planes, the value planes and
+// the blocks' bytes and values are laid out by PLANE -- lr_fidx and lr_fval [P][n_pad], lr_fpos and lr_fwl 128 P entries per block --
+// and the plane's first column comes from a table of eight entries in device memory, which stands behind lr_fstart's last row.  The
+// address is uniform: a scalar load, no register held across the gradient.  lr_fstart itself stays per column.
+struct GlmMulti {
+    const int32_t *poff;             // [8] the column of level 0 of the term plane p belongs to (planes >= P: that of the last plane)
+    int P;                           // planes, sum M_f <= 8
+    template <class State>
+    IDHMC_DEV void init(const State &s)
+    {
+        poff = s.lr_fstart + (size_t)(s.lr_npad >> 7) * (size_t)(s.lr_fcols + 1);
+        P = s.lr_mp;
+    }
+};
+// glm_list_at and glm_list_value over blocks of 128 P entries: t clamped into the block's entries, the byte masked to 0 .. 127
+IDHMC_DEV int glm_list_at(const GlmMulti &m, const GlmFactors &f, int b, int t)
+{
+    const int last = 128 * m.P - 1;
+    t = t < 0 ? 0 : t > last ? last : t;
+    return f.pos[(size_t)b * (size_t)(128 * m.P) + t] & 127;
+}
+IDHMC_DEV double glm_list_value(const GlmMulti &m, const GlmSlopes &v, int b, int t)
+{
+    const int last = 128 * m.P - 1;
+    t = t < 0 ? 0 : t > last ? last : t;
+    return v.wl[(size_t)b * (size_t)(128 * m.P) + t];
+}
+// Four entries of a list at a time: the lists of a wide term are M times as long as a plain term's, and walked one entry at a time each
+// trip waits for its byte.  The bytes and values of entries t .. t + 3 have addresses known from t alone, so the eight loads go out
+// together; an entry past the list's end is read (clamped into the block's entries, as ever) and not used.
+constexpr int kListBatch = 4;
+struct GlmListBatch {
+    int ii[kListBatch];
+    double wl[kListBatch];
+};
+IDHMC_DEV void glm_list_batch(GlmListBatch &q, const GlmMulti &m, const GlmSlopes &v, const GlmFactors &f, int b, int t)
+{
+#pragma unroll
+    for (int u = 0; u < kListBatch; ++u) {
+        q.ii[u] = glm_list_at(m, f, b, t + u);
+        q.wl[u] = glm_list_value(m, v, b, t + u);
+    }
+}
+// glm_gather over them: an observation is in a level's list once (its levels are distinct), so the list still has at most 128 entries.
+// The chain is the list's order, entry by entry, as written in stage 8.
+IDHMC_DEV void glm_gather(double &G, const GlmMulti &m, const GlmSlopes &v, const GlmFactors &f, int b, int e, bool has, const double *r)
+{
+    int s0, cnt;
+    glm_list(f, b, e, has, s0, cnt);
+    for (int k = 0; k < cnt; k += kListBatch) {
+        GlmListBatch q;
+        glm_list_batch(q, m, v, f, b, s0 + k);
+#pragma unroll
+        for (int u = 0; u < kListBatch; ++u) G = k + u < cnt ? dfma(q.wl[u], r[q.ii[u]], G) : G;
+    }
 }
 
 }  // namespace idhmc

@@ -81,6 +81,8 @@ struct idhmc_ctx {
     std::vector<double> glm_gkappa;
     std::vector<int32_t> glm_bterm;                 // idhmc_create_glm_block with K > 0: the block's terms in row order and eta as given
     double glm_beta = 0.0;
+    std::vector<int32_t> glm_mwidth, glm_mindex;    // idhmc_create_glm_multi with a wide term: width (F entries), index (P x n) and, where
+    std::vector<double> glm_mvalues;                // given, values (P x n) as given (empty otherwise)
     // IDHMC_EPS_PER_RESPONSE / IDHMC_METRIC_PER_RESPONSE: the context holds resp_n = C / glm_r whole responses (0 in every other mode)
     int64_t resp_n = 0;
     double *resp_da = nullptr;     // [resp_n][6] dual-averaging states of IDHMC_EPS_PER_RESPONSE: mu, m, Hbar, logeps, logeps_bar, eps

@@ -137,7 +137,13 @@ struct DevState {
     const int32_t *lr_bpart;  // [L] -1, or for a column of a block term: k | row << 10, k its level, row its row of L
     int32_t lr_bk;            // K, 0 without a block
     int32_t lr_boff[4];       // the first column of the term in row r
+    // factor terms with several weighted levels per observation (idhmc_create_glm_multi; 0 without a wide term).  With
+    // lr_mp > 0 the arrays above are laid out by PLANE: lr_fidx and lr_fval [lr_mp][lr_npad], lr_fpos and lr_fwl 128 lr_mp entries per
+    // block, and eight more int32 stand behind the last row of lr_fstart: the first column of the term each plane belongs to.  The one
+    // field takes the four bytes the struct ended on: its size, and with it every kernel argument's offset, is what it was.
+    int32_t lr_mp;            // planes, sum of the terms' widths, 2..8
 };
+static_assert(sizeof(DevState) == 864, "DevState keeps its size: the kernel arguments behind it keep their offsets");
 // A density whose data depend on the chain (Model::kBindsChain: a GLM with several responses) is told the GLOBAL id of the chain a
 // kernel is about to evaluate, wherever a kernel takes a chain; for every other density nothing is compiled.
 template <class Model, class = void>
@@ -187,7 +193,8 @@ struct JitModule;
 // fills `log` (compiler output, truncated)
 // K, A and H of a GLM; s.lr_m > 1 makes its policy one of several responses (kResponses), s.lr_pkind one with priors (kPriors),
 // s.lr_lpart one with local scales (kLocal), s.lr_f > 0 one with factor terms (kFactors), s.lr_fval one whose terms read a value (kSlopes),
-// s.lr_cp > 0 one with correlated pairs (kCorr), s.lr_s > 0 one with structured terms (kStruct), s.lr_g > 0 one with GMRF terms (kGmrf)
+// s.lr_cp > 0 one with correlated pairs (kCorr), s.lr_s > 0 one with structured terms (kStruct), s.lr_g > 0 one with GMRF terms (kGmrf),
+// s.lr_bk > 0 one with a correlation block (kBlock), s.lr_mp > 0 one with a wide term (kMulti)
 int jit_build(const DevState &s, const char *source, JitModule **out, char *log, size_t log_cap, int glm_k = 0, int glm_a = 0, int glm_h = 0);
 void jit_destroy(JitModule *m);
 

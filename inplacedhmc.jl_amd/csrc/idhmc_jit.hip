@@ -14,7 +14,8 @@
 // a sampled correlation (idhmc_create_glm_corr with P > 0: kCorr), and so is whether a term's levels form an AR(1) or
 // random-walk sequence (idhmc_create_glm_struct with S > 0: kStruct), and so is whether a term's levels carry a sparse
 // precision (idhmc_create_glm_gmrf with G > 0: kGmrf), and so is whether three or four terms form a correlation block
-// (idhmc_create_glm_block with K > 0: kBlock; never together with kCorr).
+// (idhmc_create_glm_block with K > 0: kBlock; never together with kCorr), and so is whether a term has several
+// weighted levels per observation (idhmc_create_glm_multi with a width > 1 or an absent entry: kMulti).
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 #include <dlfcn.h>
@@ -76,7 +77,7 @@ int jit_build(const DevState &s, const char *source, JitModule **out, char *log,
                ", kLocal = " + (s.lr_lpart ? "true" : "false") + ", kFactors = " + (s.lr_f > 0 ? "true" : "false") +
                ", kSlopes = " + (s.lr_fval ? "true" : "false") + ", kCorr = " + (s.lr_cp > 0 ? "true" : "false") +
                ", kStruct = " + (s.lr_s > 0 ? "true" : "false") + ", kGmrf = " + (s.lr_g > 0 ? "true" : "false") +
-               ", kBlock = " + (s.lr_bk > 0 ? "true" : "false") + ";\n";
+               ", kBlock = " + (s.lr_bk > 0 ? "true" : "false") + ", kMulti = " + (s.lr_mp > 0 ? "true" : "false") + ";\n";
         // with auxiliary coordinates the observation also takes a (A of them) and returns the scores s
         src += glm_a > 0 ? "    IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s) "
                            "{ glm_observation(z, o, a, r, v, s); }\n};\n}\n"

@@ -22,7 +22,7 @@ bool glm_coop(int nch, int aux, bool shared)
 
 // the tiles depend on the observation through its A alone
 template <int AUX>
-struct GlmShapeObs { static constexpr int K = 1, A = AUX, H = 0; static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false; };
+struct GlmShapeObs { static constexpr int K = 1, A = AUX, H = 0; static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false; };
 // dynamic LDS of a GLM's NUTS kernel: the launch_nuts_t sizing of the form glm_coop picks
 template <int NCH, int AUX>
 static size_t glm_nuts_lds_t(bool shared)

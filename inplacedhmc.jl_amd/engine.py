@@ -5,7 +5,7 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmBlock, GlmDesc, GlmFactors, GlmFactorValues, GlmGmrfs, GlmLocal, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
+from ._lib import GlmBlock, GlmDesc, GlmFactors, GlmFactorValues, GlmGmrfs, GlmLocal, GlmMembers, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -229,6 +229,15 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     glm.expand_factors writes the values into the term's columns, and the bits stay those of the expanded model as long as no
     product underflows to -0 (include/idhmc.h).  The Model exposes factor_has (int32 (F,)) and factor_values (float64 (F, n), rows of
     terms without values 0), None when no term has values; Engine.glm_factor_values() reads them back.
+    An entry may also be glm.members(index, weights=None, levels=None) (idhmc_create_glm_multi): a term of WIDTH M in 1..4 -- index and
+    weights are (n, M), observation i has the levels index[i, m] >= 0 with weights[i, m] (-1: absent; present entries first, levels
+    strictly ascending) and z_i takes sum_m weights[i, m] * b[off_f + index[i, m]].  The widths of all terms sum to at most 8.  That is
+    a multi-membership effect, a Bradley-Terry match (+1, -1) or a spline basis: glm.bspline(x, n_basis) is such a term of width 4, and
+    GLM(X, Y, source, factors=[glm.bspline(x, 20)], **glm.smooth_effects(Dd, [20])) is y ~ 1 + s(x), a P-spline whose penalty is the
+    term's GMRF prior.  The bits stay those of glm.expand_factors.  A wide term may be grouped, carry local scales, be structured or a
+    GMRF term, and is in no pair and no block.  The Model exposes member_width (int32 (F,)), member_index (int32 (P, n)) and
+    member_values (float64 (P, n)), None without such an entry (then every term is in the table, a plain one as a plane of 1.0, and
+    factor_has is None); Engine.glm_members() reads them back.
 
     correlated: a list of up to 2 glm.pair(first, second, eta=2.0) (idhmc_create_glm_corr) -- correlated random effects: two distinct terms
     with equal level counts, a term in at most one pair, share a sampled correlation rho = tanh(zeta) between level k of the first and
@@ -284,6 +293,9 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     n, Dd = X.shape
     flev, fidx = _glm.factor_terms(factors, n)
     fhas, fval = _glm.factor_values(factors, n)
+    mwidth, midx, mval = _glm.factor_members(factors, n)
+    if mwidth is not None:
+        fhas = fval = None                                      # (every term's values are in the table of members)
     F = 0 if flev is None else flev.size
     Dx = Dd + (int(flev.sum()) if F else 0)
     grp, H = None, 0
@@ -310,6 +322,12 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     bterm, beta = _glm.block_terms(correlated, flev)
     BK = 0 if bterm is None else bterm.size
     Bz = BK * (BK - 1) // 2
+    if mwidth is not None:
+        for what, terms in (("correlated: pair", () if pfirst is None else np.r_[pfirst, psecond]), ("correlated: block", () if bterm is None else bterm)):
+            for t in terms:
+                if mwidth[int(t)] > 1:
+                    raise ValueError("%s names term %d, a glm.members term of width %d: a term with several levels per observation is in "
+                                     "no pair and no block" % (what, int(t), int(mwidth[int(t)])))
     sterm, skind, seta = _glm.struct_terms(structured, flev, correlated, loc, Dd)
     NS = 0 if sterm is None else sterm.size
     Sz = 0 if sterm is None else int((skind == _glm.STRUCT_AR1).sum())
@@ -372,6 +390,7 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     m.J, m.local, m.slab_scale = J, loc, S
     m.Dd, m.F, m.levels, m.factor_index = Dd, F, flev, fidx
     m.factor_has, m.factor_values = fhas, fval
+    m.member_width, m.member_index, m.member_values = mwidth, midx, mval
     m.P, m.pair_first, m.pair_second, m.pair_eta = P, pfirst, psecond, peta
     m.pairs = [_glm.Pair(int(a), int(b), float(e)) for a, b, e in zip(pfirst, psecond, peta)] if P else None
     m.BK, m.Bz, m.block_term, m.block_eta = BK, Bz, bterm, beta
@@ -413,7 +432,29 @@ class Engine:
             fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
                             index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
             R = getattr(model, "R", None)
-            if getattr(model, "BK", 0) > 0:
+            if getattr(model, "member_width", None) is not None:
+                # a table of members: every optional part goes along, and factors gives F and levels only
+                fc.index = None
+                pp = st = gm = bk = None
+                ip = C.POINTER(C.c_int32)
+                if getattr(model, "P", 0) > 0:
+                    pp = C.byref(GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
+                                          eta=_dp(model.pair_eta)))
+                if getattr(model, "S", 0) > 0:
+                    st = C.byref(GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
+                                            eta=_dp(model.struct_eta)))
+                if getattr(model, "G", 0) > 0:
+                    gm = C.byref(GlmGmrfs(G=model.G, term=model.gmrf_term.ctypes.data_as(ip),
+                                          start=model.gmrf_start.ctypes.data_as(C.POINTER(C.c_int64)), col=model.gmrf_col.ctypes.data_as(ip),
+                                          val=_dp(model.gmrf_val), kappa=_dp(model.gmrf_kappa)))
+                if getattr(model, "BK", 0) > 0:
+                    bk = C.byref(GlmBlock(K=model.BK, term=model.block_term.ctypes.data_as(ip), eta=model.block_eta))
+                mm = GlmMembers(width=model.member_width.ctypes.data_as(ip), index=model.member_index.ctypes.data_as(ip),
+                                values=_dp(model.member_values))
+                check(self.lib.idhmc_create_glm_multi(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), None, pp, st,
+                                                      gm, bk, C.byref(mm), model.M if R is not None else 1, R if R is not None else 0,
+                                                      C.byref(self.opt), seed))
+            elif getattr(model, "BK", 0) > 0:
                 fv = st = gm = None
                 ip = C.POINTER(C.c_int32)
                 if getattr(model, "factor_has", None) is not None:
@@ -643,6 +684,20 @@ class Engine:
         val = np.zeros((F.value, self.model.n))
         check(self.lib.idhmc_glm_factor_values_get(self.h, has.ctypes.data_as(C.POINTER(C.c_int32)), _dp(val)))
         return has[:F.value].copy(), val
+
+    def glm_members(self):
+        """(width int32 (F,), index int32 (P, n), values float64 (P, n)) as the context holds them (glm.members, glm.bspline); a model
+        without such a term reports its F terms as planes of width 1; (None, None, None) for every model without factor terms"""
+        F = C.c_int32(0)
+        check(self.lib.idhmc_glm_factors_get(self.h, C.byref(F), None, None))
+        if F.value == 0:
+            return None, None, None
+        width = np.zeros(4, np.int32)
+        check(self.lib.idhmc_glm_members_get(self.h, width.ctypes.data_as(C.POINTER(C.c_int32)), None, None))
+        P = int(width[:F.value].sum())
+        idx, val = np.zeros((P, self.model.n), np.int32), np.zeros((P, self.model.n))
+        check(self.lib.idhmc_glm_members_get(self.h, width.ctypes.data_as(C.POINTER(C.c_int32)), idx.ctypes.data_as(C.POINTER(C.c_int32)), _dp(val)))
+        return width[:F.value].copy(), idx, val
 
     def glm_block(self):
         """(terms int32 (K,), eta) of the correlation block as the context holds it (GLM(..., correlated=[glm.block(..)])); (None, None) for

@@ -611,10 +611,92 @@ def term(index, values=None, levels=None):
     return Term(index, values, levels)
 
 
+Members = collections.namedtuple("Members", "index weights levels")
+
+
+def members(index, weights=None, levels=None):
+    """a factor term of WIDTH M for GLM(..., factors=[...]) (idhmc_create_glm_multi): observation i has up to M levels index[i, m] with
+    weights[i, m] and the term adds sum_m weights[i, m] * b[index[i, m]] to z_i -- a multi-membership effect (weights summing to 1 over
+    the members), a match between two teams (+1, -1), a spline basis (glm.bspline).  index is (n, M) integers, M in 1..4, -1 marking an
+    absent entry: the present entries of a row come first and their levels are strictly ascending.  weights is (n, M), default 1.0 on
+    every present entry; the weight of an absent entry is ignored.  levels defaults to max(index) + 1.  Validated by GLM()
+    (factor_terms, factor_members)."""
+    return Members(index, weights, levels)
+
+
+def _member_planes(f, entry, n):
+    """(N, index int32 (M, n), weights float64 (M, n)) of a members() entry; every check of idhmc_create_glm_multi's on it, naming the entry"""
+    raw = np.asarray(entry.index)
+    if raw.ndim != 2 or raw.shape[0] != n:
+        raise ValueError("factors[%d]: the index of glm.members must have shape (%d, M), got %s" % (f, n, raw.shape))
+    if raw.dtype == np.bool_ or not np.issubdtype(raw.dtype, np.integer):
+        raise ValueError("factors[%d] must be integers (level indices), got dtype %s" % (f, raw.dtype))
+    M = raw.shape[1]
+    if not 1 <= M <= 4:
+        raise ValueError("factors[%d]: width %d (a term has 1..4 levels per observation)" % (f, M))
+    N = entry.levels
+    if N is not None and (isinstance(N, bool) or not isinstance(N, (int, np.integer)) or N < 1):
+        raise ValueError("factors[%d]: the number of levels must be a positive integer (got %r)" % (f, N))
+    N = max(int(raw.max()) + 1, 1) if N is None else int(N)
+    if N > 1024:
+        raise ValueError("factors[%d]: %d levels (a GLM is limited to D <= 1024)" % (f, N))
+    bad = np.argwhere((raw < -1) | (raw >= N))
+    if bad.size:
+        i, m = bad[0]
+        raise ValueError("factors[%d]: plane %d, observation %d: level %d is outside -1..%d" % (f, m, i, raw[i, m], N - 1))
+    if M == 1 and (raw < 0).any():
+        raise ValueError("factors[%d]: plane 0, observation %d: an absent entry (-1) in a term of width 1" % (f, np.flatnonzero(raw[:, 0] < 0)[0]))
+    for m in range(1, M):
+        bad = np.flatnonzero((raw[:, m] >= 0) & (raw[:, m - 1] < 0))
+        if bad.size:
+            raise ValueError("factors[%d]: plane %d, observation %d: a present entry behind an absent one" % (f, m, bad[0]))
+        bad = np.flatnonzero((raw[:, m] >= 0) & (raw[:, m] <= raw[:, m - 1]))
+        if bad.size:
+            raise ValueError("factors[%d]: plane %d, observation %d: level %d after level %d (the levels of an observation must be strictly "
+                             "ascending)" % (f, m, bad[0], raw[bad[0], m], raw[bad[0], m - 1]))
+    if entry.weights is None:
+        w = np.ones(raw.shape)
+    else:
+        w = np.asarray(entry.weights)
+        if w.shape != raw.shape:
+            raise ValueError("factors[%d]: weights must have the shape of index, %s, got %s" % (f, raw.shape, w.shape))
+        if w.dtype == np.bool_ or not (np.issubdtype(w.dtype, np.integer) or np.issubdtype(w.dtype, np.floating)):
+            raise ValueError("factors[%d]: weights must be real numbers, got dtype %s" % (f, w.dtype))
+        w = w.astype(np.float64)
+        bad = np.argwhere(~np.isfinite(w) & (raw >= 0))
+        if bad.size:
+            raise ValueError("factors[%d]: plane %d, observation %d: the weight is not finite" % (f, bad[0][1], bad[0][0]))
+    w = np.where(raw >= 0, w, 0.0)
+    return N, np.ascontiguousarray(raw.T, dtype=np.int32), np.ascontiguousarray(w.T)
+
+
+def factor_members(factors, n):
+    """GLM()'s table of members: (width int32 (F,), index int32 (P, n), values float64 (P, n)) with the planes of term 0 first, or three
+    None when no entry is a members().  With one, EVERY term is in the table: a plain term is one plane of 1.0, a term() with values one
+    plane of its values.  Absent entries carry the value 0.0.  The checks are idhmc_create_glm_multi's."""
+    lev, idx = factor_terms(factors, n)
+    if lev is None or not any(isinstance(e, Members) for e in factors):
+        return None, None, None
+    has, val = factor_values(factors, n)
+    width, planes, values = np.empty(lev.size, np.int32), [], []
+    for f, entry in enumerate(factors):
+        if isinstance(entry, Members):
+            _, pi, pv = _member_planes(f, entry, n)
+        else:
+            pi, pv = idx[f][None], (val[f][None] if has is not None and has[f] else np.ones((1, n)))
+        width[f] = pi.shape[0]
+        planes.append(pi)
+        values.append(pv)
+    if int(width.sum()) > 8:
+        raise ValueError("the widths of the terms sum to %d planes: at most 8" % int(width.sum()))
+    return width, np.ascontiguousarray(np.concatenate(planes), dtype=np.int32), np.ascontiguousarray(np.concatenate(values))
+
+
 def factor_terms(factors, n):
     """GLM()'s validation of factors: (levels int32 (F,), index int32 (F, n)), or (None, None) for None and for an empty list.  Each
-    entry is an integer array of shape (n,), a pair (array, N) or a term(); N defaults to max + 1.  The checks are
-    idhmc_create_glm_factors'.  The values of a term() are factor_values' business."""
+    entry is an integer array of shape (n,), a pair (array, N), a term() or a members(); N defaults to max + 1.  The checks are
+    idhmc_create_glm_factors'.  The values of a term() are factor_values' business; of a members() entry the row holds its first plane
+    (-1 where the observation has no member), and the whole table is factor_members' business."""
     if factors is None:
         return None, None
     if isinstance(factors, np.ndarray) or not isinstance(factors, (list, tuple)):
@@ -626,12 +708,17 @@ def factor_terms(factors, n):
     lev, idx = np.empty(len(factors), np.int32), np.empty((len(factors), n), np.int32)
     for f, entry in enumerate(factors):
         N, given = None, False
+        if isinstance(entry, Members):
+            lev[f], planes, _ = _member_planes(f, entry, n)
+            idx[f] = planes[0]
+            continue
         if isinstance(entry, Term):
             entry, N = entry.index, entry.levels
             given = N is not None
         elif isinstance(entry, tuple):
             if len(entry) != 2:
-                raise ValueError("factors[%d] must be an index array, a pair (index, levels) or a glm.term(index, values, levels)" % f)
+                raise ValueError("factors[%d] must be an index array, a pair (index, levels) or a glm.term(index, values, levels) -- or a "
+                                 "glm.members(index, weights, levels)" % f)
             entry, N = entry
             given = True
         if given:
@@ -689,7 +776,8 @@ def factor_columns(model, f):
 def expand_factors(X, factors):
     """the n x Dx design matrix with one column per level -- the documented equivalent of GLM(X, ..., factors=factors): the dense
     columns of X, then for factor 0, 1, .. one column per level holding 1.0 (for a term() with values: values[i]) where the observation
-    has that level and 0.0 elsewhere.  The engine computes the same bits on both."""
+    has that level and 0.0 elsewhere; for a members() entry weights[i, m] in the column of level index[i, m], every present entry.  The
+    engine computes the same bits on both."""
     X = np.asarray(X, dtype=np.float64)
     if X.ndim != 2:
         raise ValueError("X must be an (n, Dd) matrix, got shape %s" % (X.shape,))
@@ -697,14 +785,76 @@ def expand_factors(X, factors):
     if lev is None:
         return X.copy()
     has, val = factor_values(factors, X.shape[0])
+    width, midx, mval = factor_members(factors, X.shape[0])
     out = np.zeros((X.shape[0], X.shape[1] + int(lev.sum())))
     out[:, :X.shape[1]] = X
     off = X.shape[1]
     rows = np.arange(X.shape[0])
     for f in range(lev.size):
-        out[rows, off + idx[f]] = 1.0 if has is None or not has[f] else val[f]
+        if width is not None:
+            # (the levels of an observation are distinct within a term: no entry is written twice)
+            for p in range(int(width[:f].sum()), int(width[:f + 1].sum())):
+                here = midx[p] >= 0
+                out[rows[here], off + midx[p][here]] = mval[p][here]
+        else:
+            out[rows, off + idx[f]] = 1.0 if has is None or not has[f] else val[f]
         off += int(lev[f])
     return out
+
+
+def bspline_knots(n_basis, degree=3, lo=0.0, hi=1.0):
+    """the n_basis + degree + 1 uniform knots of glm.bspline: t[degree] = lo and t[n_basis] = hi exactly, the interior ones
+    lo + j h with h = (hi - lo) / (n_basis - degree), and degree more at spacing h on either side"""
+    K = n_basis - degree
+    h = (hi - lo) / K
+    t = np.empty(n_basis + degree + 1)
+    for j in range(K):
+        t[degree + j] = lo + j * h
+    t[n_basis] = hi
+    for j in range(1, degree + 1):
+        t[degree - j] = lo - j * h
+        t[n_basis + j] = hi + j * h
+    return t
+
+
+def bspline(x, n_basis, degree=3, lo=None, hi=None):
+    """a B-spline basis as a factor term: glm.members(index, weights, levels=n_basis) of width degree + 1 (degree 1..3), observation i
+    having the degree + 1 adjacent basis functions that are non-zero at x[i], evaluated by the Cox-de Boor recursion on uniform knots
+    (bspline_knots) over [lo, hi], which defaults to the range of x.  The weights of a row are >= 0 and sum to 1.  With an RW2 precision
+    on the term's levels (glm.smooth_effects) this is a penalised spline, s(x); the basis is never stored as columns.  x outside
+    [lo, hi] is refused; x = hi belongs to the last interval."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 1 or x.size < 1 or not np.isfinite(x).all():
+        raise ValueError("x must be a non-empty vector of finite numbers, got shape %s" % (x.shape,))
+    if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)) or not 1 <= degree <= 3:
+        raise ValueError("degree = %r must be 1, 2 or 3" % (degree,))
+    degree = int(degree)
+    if isinstance(n_basis, bool) or not isinstance(n_basis, (int, np.integer)) or not degree + 1 <= n_basis <= 1024:
+        raise ValueError("n_basis = %r must be an integer in degree + 1 = %d .. 1024" % (n_basis, degree + 1))
+    n_basis = int(n_basis)
+    lo = float(x.min()) if lo is None else float(lo)
+    hi = float(x.max()) if hi is None else float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError("[lo, hi] = [%r, %r] must be a finite interval of positive length" % (lo, hi))
+    bad = np.flatnonzero((x < lo) | (x > hi))
+    if bad.size:
+        raise ValueError("x[%d] = %r is outside [lo, hi] = [%r, %r]" % (bad[0], float(x[bad[0]]), lo, hi))
+    t = bspline_knots(n_basis, degree, lo, hi)
+    # the knot interval of every x: t[k] <= x < t[k + 1], k in degree .. n_basis - 1 (x = hi: the last one)
+    k = np.clip(np.searchsorted(t, x, side="right") - 1, degree, n_basis - 1)
+    # de Boor's triangular scheme for the degree + 1 functions that are non-zero on the interval (N[j] is B_{k - degree + j})
+    N = np.zeros((degree + 1, x.size))
+    N[0] = 1.0
+    for j in range(1, degree + 1):
+        saved = np.zeros(x.size)
+        for r in range(j):
+            right, left = t[k + r + 1] - x, x - t[k + 1 - j + r]
+            tmp = N[r] / (t[k + r + 1] - t[k + 1 - j + r])
+            N[r] = saved + right * tmp
+            saved = left * tmp
+        N[j] = saved
+    index = (k - degree)[:, None] + np.arange(degree + 1)[None, :]
+    return Members(np.ascontiguousarray(index, dtype=np.int32), np.ascontiguousarray(N.T), n_basis)
 
 
 # ---- correlated pairs of terms --------------------------------------------------------------------------------------------------------
@@ -1229,6 +1379,23 @@ def gmrf_effects(Dd, levels, gmrf, structured=None, correlated=None, eta=2.0, A=
     gmrf_terms(gmrf, lev, kw.get("correlated"), kw.get("structured"))
     kw["gmrf"] = gmrf
     return kw
+
+
+def smooth_effects(Dd, n_basis_list, order=2, sum_to_zero=1.0, levels=(), A=0, scale=None, coefficients=None, aux=None):
+    """the keyword arguments of GLM() for penalised spline smooths: the first len(n_basis_list) <= 2 terms are glm.bspline terms of
+    n_basis_list[f] basis functions each, then come the further terms of `levels`; what gmrf_effects(Dd, n_basis_list + levels,
+    [glm.gmrf(f, glm.scale_precision(glm.rw2_precision(N)), sum_to_zero) ..]) returns -- every term a group of its own, whose sampled
+    scale is the smooth's (the inverse of the smoothing parameter), the second-order difference penalty (order=1: the first-order one,
+    rw1_precision) in place of the iid prior, and kappa = sum_to_zero holding the smooth's level against the intercept --
+    GLM(X, Y, source, factors=[glm.bspline(x, 20)], **glm.smooth_effects(X.shape[1], [20])) is y ~ 1 + s(x)."""
+    if order not in (1, 2):
+        raise ValueError("order = %r must be 1 or 2 (the order of the difference penalty)" % (order,))
+    nb = [int(N) for N in n_basis_list]
+    if not 1 <= len(nb) <= 2:
+        raise ValueError("one or two smooths (a model has at most 2 GMRF terms), got %d" % len(nb))
+    prec = rw2_precision if order == 2 else rw1_precision
+    terms = [gmrf(f, scale_precision(prec(N)), sum_to_zero) for f, N in enumerate(nb)]
+    return gmrf_effects(Dd, nb + [int(N) for N in levels], terms, A=A, scale=scale, coefficients=coefficients, aux=aux)
 
 
 def random_intercepts(Dd, levels, A=0, scale=None, coefficients=None, aux=None):

@@ -83,6 +83,12 @@ kernels of a build without the feature on the same shape.  No coordinate is adde
 --lockstep: icar_over_plain and rw2_over_plain are what the prior's sparse rows cost per gradient.  Meant to run under --lockstep with
 --pairs ''.
 
+--multi-cost (glm.members, glm.bspline) runs, per row BASISxN of --multi-rows and chain count, one cubic smooth of x
+(y ~ 1 + x + s(x), Poisson, the iid prior and a sampled scale on the BASIS coefficients) in three ways on the same data: `wide`, the
+basis as a factor term of width 4; `expanded`, the same model on glm.expand_factors (BASIS dense columns, four of them non-zero per
+observation; the same bits, checked); `width1`, the same columns in a term of width 1 that keeps the first plane alone -- another
+model, whose distance to `wide` is what the three further planes cost.  Meant to run under --lockstep with --pairs ''.
+
     python tools/bench_glm.py [--shapes 100x1000,25x1000] [--chains 16384,65536] [--pairs poisson,logistic,gaussian,hier,negbin]
                               [--transitions 5] [--aux-cost] [--hier-cost] [--dispersion-cost] [--metric shared|per_chain] [--lockstep]
                               [--responses 1,4096] [--chains-per-response 16] [--repeats 1] [--adapt per-chain|per-response] [--stage-steps 25]
@@ -500,6 +506,18 @@ def slope_problem(Dd, N, n, seed):
     return X, y, idx, x, kw, q0, np.eye(q0.size) * 1e-4
 
 
+def smooth_problem(N, n, seed):
+    """a Poisson regression y ~ 1 + x + s(x): (X (n, 2), y, the cubic B-spline term of N basis functions, the keywords of the models --
+    the term's N columns a group of its own -- and a start q for `run`)"""
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(0.0, 1.0, n)
+    X = np.c_[np.ones(n), x - 0.5]
+    term = pkg.glm.bspline(x, N, lo=0.0, hi=1.0)
+    sigma, u = 0.5, rng.standard_normal(N)
+    y = rng.poisson(np.exp(0.5 + 0.3 * (x - 0.5) + sigma * (term.weights * u[term.index]).sum(1))).astype(float)
+    return X, y, term, pkg.glm.random_intercepts(2, [N]), np.r_[0.5, 0.3, u, np.log(sigma)]
+
+
 def run(form, X, y, q_map, cov, C, T, seed=1, metric=None, mdl=None):
     t0 = time.perf_counter()
     eng = pkg.Engine(model(form, X, y, q_map) if mdl is None else mdl, C, pkg.default_options(metric_mode=pkg.METRIC_SHARED if metric is None else metric,
@@ -658,6 +676,10 @@ def main():
                     "term, an RW2 prior, and the iid prior (DESIGN section 25); use --lockstep, and --pairs '' to run nothing else")
     ap.add_argument("--gmrf-rows", default="20x100x1000,20x200x1000", help="DdxLEVELSxN,... (section 23's rows: the matrix cores and the per-wave form)")
     ap.add_argument("--gmrf-sides", default="icar,rw2,plain", help="the sides of each row to run")
+    ap.add_argument("--multi-cost", action="store_true", help="per row of --multi-rows one cubic smooth (DESIGN section 27) in three ways on the "
+                    "same data: its basis as a term of width 4, as dense columns (glm.expand_factors), and the same columns in a term of width 1")
+    ap.add_argument("--multi-rows", default="24x16384", help="BASISxN,...")
+    ap.add_argument("--multi-sides", default="wide,expanded,width1", help="the sides of each row to run")
     ap.add_argument("--responses", default="", help="M,...: the Poisson regression with M responses of chains / M chains each on one design "
                     "(DESIGN section 15); 1 is the plain GLM")
     ap.add_argument("--chains-per-response", default="", help="R,...: the rows of --responses with M = chains / R")
@@ -847,6 +869,37 @@ def main():
                     if side in row and "plain" in row:
                         row[side + "_same_steps"] = row[side]["steps"] == row["plain"]["steps"]
                         row[side + "_over_plain"] = row[side]["leapfrog_steps_per_s"] / row["plain"]["leapfrog_steps_per_s"]
+                res["results"].append(row)
+    if a.multi_cost:
+        # one cubic smooth of x, the iid prior and a sampled scale on its N coefficients (the penalty is the prior loop's business and
+        # costs what --gmrf-cost shows): the basis as a term of width 4, as N dense columns, and -- the price of the three further
+        # planes -- the same N columns in a term of width 1 that keeps the first plane alone
+        sides = a.multi_sides.split(",")
+        for spec in a.multi_rows.split(","):
+            N, n = (int(v) for v in spec.split("x"))
+            X, y, term, kw, q0 = smooth_problem(N, n, seed=N * 31 + n)
+            one = pkg.glm.term(term.index[:, 0], values=term.weights[:, 0], levels=N)
+            for C in (int(c) for c in a.chains.split(",")):
+                row = dict(pair="multi_cost", Dd=2, levels=N, n=n, Dx=2 + N, L=padded(2 + N + 1), chains=C, metric=a.metric, lockstep=LOCKSTEP)
+                seen = {}
+                for side in sides:
+                    mdl = pkg.GLM(pkg.glm.expand_factors(X, [term]), y, pkg.glm.POISSON_LOG, **kw) if side == "expanded" else \
+                        pkg.GLM(X, y, pkg.glm.POISSON_LOG, factors=[term if side == "wide" else one], **kw)
+                    runs = [run("glm_" + side, X, y, q0, np.eye(q0.size) * 1e-4, C, a.transitions, metric=metric, mdl=mdl) for _ in range(a.repeats)]
+                    r = max((u[0] for u in runs), key=lambda u: u["leapfrog_steps_per_s"])
+                    r["repeats_leapfrog_steps_per_s"] = [u[0]["leapfrog_steps_per_s"] for u in runs]
+                    row[side] = r
+                    seen[side] = runs[0][1] + (runs[0][2],)
+                    print("# smooth N=%d n=%d C=%d %s (form %d): %.4e leapfrog steps/s (%s), %.3f ms/transition, create %.2f s" %
+                          (N, n, C, side, r["glm_form"], r["leapfrog_steps_per_s"],
+                           " ".join("%.4e" % v for v in r["repeats_leapfrog_steps_per_s"]), r["ms_per_transition"], r["create_s"]),
+                          file=sys.stderr, flush=True)
+                if "wide" in row and "expanded" in row:
+                    row["same_bits"] = bool(all(np.array_equal(u.view(np.uint64), v.view(np.uint64)) for u, v in zip(seen["wide"], seen["expanded"])))
+                    row["same_steps"] = row["wide"]["steps"] == row["expanded"]["steps"]
+                    row["speedup_wide_over_expanded"] = row["wide"]["leapfrog_steps_per_s"] / row["expanded"]["leapfrog_steps_per_s"]
+                if "wide" in row and "width1" in row:
+                    row["wide_over_width1"] = row["wide"]["leapfrog_steps_per_s"] / row["width1"]["leapfrog_steps_per_s"]
                 res["results"].append(row)
     for shape in a.shapes.split(","):
         D, n = (int(v) for v in shape.split("x"))

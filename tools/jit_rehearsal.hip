@@ -44,7 +44,7 @@ __device__ void glm_observation(double z, const GlmObs &o, const double *a, doub
 }
 struct UserGlmObs {
     static constexpr int K = 1, A = 1, H = 0;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         glm_observation(z, o, a, r, v, s);

@@ -15,7 +15,7 @@ template <int GROUPS, bool PRIORS, bool LOCAL, bool STRUCT>
 struct PoissonBlockObs {
     static constexpr int K = 1, A = 0, H = GROUPS;
     static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = LOCAL, kFactors = true, kSlopes = true, kCorr = false, kStruct = STRUCT,
-                          kGmrf = false, kBlock = true;
+                          kGmrf = false, kBlock = true, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -26,7 +26,7 @@ struct PoissonBlockObs {
 struct GaussBlockObs {
     static constexpr int K = 1, A = 1, H = 1;
     static constexpr bool kResponses = false, kPriors = true, kLocal = false, kFactors = true, kSlopes = true, kCorr = false, kStruct = false,
-                          kGmrf = false, kBlock = true;
+                          kGmrf = false, kBlock = true, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);

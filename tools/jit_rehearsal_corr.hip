@@ -13,7 +13,7 @@ namespace idhmc {
 template <int GROUPS, bool PRIORS, bool LOCAL>
 struct PoissonCorrObs {
     static constexpr int K = 1, A = 0, H = GROUPS;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = LOCAL, kFactors = true, kSlopes = true, kCorr = true, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = LOCAL, kFactors = true, kSlopes = true, kCorr = true, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -23,7 +23,7 @@ struct PoissonCorrObs {
 };
 struct GaussCorrObs {
     static constexpr int K = 1, A = 1, H = 1;
-    static constexpr bool kResponses = false, kPriors = true, kLocal = false, kFactors = true, kSlopes = true, kCorr = true, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = true, kLocal = false, kFactors = true, kSlopes = true, kCorr = true, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);

@@ -12,7 +12,7 @@ namespace idhmc {
 template <int GROUPS, bool PRIORS, bool LOCAL>
 struct PoissonFactorObs {
     static constexpr int K = 1, A = 0, H = GROUPS;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = LOCAL, kFactors = true, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = LOCAL, kFactors = true, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -22,7 +22,7 @@ struct PoissonFactorObs {
 };
 struct GaussFactorObs {
     static constexpr int K = 1, A = 1, H = 1;
-    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = true, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = false, kLocal = false, kFactors = true, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);

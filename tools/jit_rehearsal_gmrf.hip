@@ -14,7 +14,7 @@ template <int GROUPS, bool LOCAL, bool SLOPES, bool CORR, bool STRUCT>
 struct PoissonGmrfObs {
     static constexpr int K = 1, A = 0, H = GROUPS;
     static constexpr bool kResponses = false, kPriors = true, kLocal = LOCAL, kFactors = true, kSlopes = SLOPES, kCorr = CORR, kStruct = STRUCT,
-                          kGmrf = true, kBlock = false;
+                          kGmrf = true, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -25,7 +25,7 @@ struct PoissonGmrfObs {
 struct GaussGmrfObs {
     static constexpr int K = 1, A = 1, H = 1;
     static constexpr bool kResponses = false, kPriors = true, kLocal = false, kFactors = true, kSlopes = true, kCorr = false, kStruct = false,
-                          kGmrf = true, kBlock = false;
+                          kGmrf = true, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);

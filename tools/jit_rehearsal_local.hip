@@ -11,7 +11,7 @@ namespace idhmc {
 template <int GROUPS, bool PRIORS>
 struct PoissonLocalObs {
     static constexpr int K = 1, A = 0, H = GROUPS;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = true, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = true, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -21,7 +21,7 @@ struct PoissonLocalObs {
 };
 struct HierGaussLocalObs {
     static constexpr int K = 1, A = 1, H = 4;
-    static constexpr bool kResponses = false, kPriors = true, kLocal = true, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = true, kLocal = true, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);

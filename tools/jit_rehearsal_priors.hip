@@ -12,7 +12,7 @@ namespace idhmc {
 template <bool PRIORS>
 struct PoissonObs {
     static constexpr int K = 1, A = 0, H = 0;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, double &r, double &v)
     {
         const double e = dexp(z);
@@ -23,7 +23,7 @@ struct PoissonObs {
 template <bool PRIORS>
 struct HierGaussObs {
     static constexpr int K = 1, A = 1, H = 4;
-    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false;
+    static constexpr bool kResponses = false, kPriors = PRIORS, kLocal = false, kFactors = false, kSlopes = false, kCorr = false, kStruct = false, kGmrf = false, kBlock = false, kMulti = false;
     IDHMC_DEV static void terms(double z, const GlmObs &o, const double *a, double &r, double &v, double *s)
     {
         const double w = dexp(-a[0]);
