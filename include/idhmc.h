@@ -237,6 +237,12 @@ const char *idhmc_build_digest(void);
  * src/warmup.jl:100-129): kappa = I, Tree arena, state vectors. */
 int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
                  const idhmc_model_desc *model, const idhmc_options *opt, uint64_t seed);
+/* A GLM handed over in parts is created by ONE function, idhmc_create_glm_model (declared behind the parts, below): zero-initialise an
+ * idhmc_glm_model, set glm and the parts the model has, and leave the rest NULL; a later version appends its parts at the struct's end.
+ * It behaves as idhmc_create_glm_multi does with the same parts.  (M, chains_per_response) = (1, 0), or the (0, 0) of a zeroed struct, is
+ * one response, the context of idhmc_create_glm; anything else is the context of idhmc_create_glm_responses, with its refusals.  The
+ * eleven functions idhmc_create_glm .. idhmc_create_glm_multi that follow, one per part in the order the parts were added, are it with
+ * the later parts NULL: they stay, with their signatures and messages, and the text of each states what its part means and refuses. */
 /* A GLM from an explicit descriptor: IDHMC_MODEL_GLM (A = 0) or IDHMC_MODEL_GLM_AUX (A > 0), optionally with H coefficient groups
  * (above).  X is n x Dx and Y n x K row-major, constants has nc entries (may be NULL when nc = 0), groups has Dx entries (NULL iff
  * H = 0), mu / tau have Dx + A + H entries or are NULL (0 and 1).  With H = 0 the context is the one idhmc_create makes of kinds 5
@@ -590,6 +596,21 @@ int idhmc_create_glm_multi(idhmc_ctx **out, int device, int64_t nchains, int64_t
  * present entries of a table given without values, 0.0 on absent ones).  A context without a wide term reports its F terms as planes of
  * width 1.  With a wide term idhmc_glm_factors_get reports the first plane of every term. */
 int idhmc_glm_members_get(const idhmc_ctx *ctx, int32_t *width, int32_t *index, double *values);
+typedef struct {                             /* a GLM in parts, whole (the head of the GLM part, above) */
+    const idhmc_glm_desc          *glm;      /* required */
+    const idhmc_glm_priors        *priors;   /* each of the following: NULL = absent, exactly as the legacy argument */
+    const idhmc_glm_local         *local;
+    const idhmc_glm_factors       *factors;
+    const idhmc_glm_factor_values *values;
+    const idhmc_glm_pairs         *pairs;
+    const idhmc_glm_structs       *structs;
+    const idhmc_glm_gmrfs         *gmrfs;
+    const idhmc_glm_block         *block;
+    const idhmc_glm_members       *members;
+    int64_t M, chains_per_response;          /* (1, 0) or (0, 0): one response, the context of idhmc_create_glm */
+} idhmc_glm_model;
+int idhmc_create_glm_model(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_model *model, const idhmc_options *opt, uint64_t seed);
 int idhmc_destroy(idhmc_ctx *ctx);
 /* run on a caller-owned hipStream_t (e.g. a torch.cuda.Stream); NULL = the library's own non-blocking stream.
  * NB the legacy default stream's handle IS NULL: it cannot be selected, and it does not order itself against the

@@ -63,6 +63,13 @@ class GlmMembers(C.Structure):
     _fields_ = [("width", C.POINTER(C.c_int32)), ("index", C.POINTER(C.c_int32)), ("values", C.POINTER(C.c_double))]
 
 
+class GlmModel(C.Structure):
+    _fields_ = [("glm", C.POINTER(GlmDesc)), ("priors", C.POINTER(GlmPriors)), ("local", C.POINTER(GlmLocal)),
+                ("factors", C.POINTER(GlmFactors)), ("values", C.POINTER(GlmFactorValues)), ("pairs", C.POINTER(GlmPairs)),
+                ("structs", C.POINTER(GlmStructs)), ("gmrfs", C.POINTER(GlmGmrfs)), ("block", C.POINTER(GlmBlock)),
+                ("members", C.POINTER(GlmMembers)), ("M", C.c_int64), ("chains_per_response", C.c_int64)]
+
+
 class Options(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("min_delta", C.c_double),
                 ("da_delta", C.c_double), ("da_gamma", C.c_double), ("da_kappa", C.c_double),
@@ -91,46 +98,41 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 # every symbol include/idhmc.h declares: name -> (restype, argtypes)
 _vp, _dp, _i32, _u32, _i64, _u64, _dbl = (C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_uint32,
                                           C.c_int64, C.c_uint64, C.c_double)
+_GLM_PARTS = [GlmDesc, GlmPriors, GlmLocal, GlmFactors, GlmFactorValues, GlmPairs, GlmStructs, GlmGmrfs, GlmBlock, GlmMembers]
+
+
+def _glm_parts_entry(k):
+    """the creation entry that takes the descriptor and the first k parts as positional arguments (the ones before idhmc_create_glm_model)"""
+    return C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64] + [C.POINTER(t) for t in _GLM_PARTS[:k + 1]] + [_i64, _i64, C.POINTER(Options), _u64]
+
+
 SYMBOLS = {
     "idhmc_default_options": (None, [C.POINTER(Options)]),
     "idhmc_last_error": (C.c_char_p, []),
     "idhmc_version": (C.c_int, []),
     "idhmc_build_digest": (C.c_char_p, []),
     "idhmc_create": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(ModelDesc), C.POINTER(Options), _u64]),
+    "idhmc_create_glm_model": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmModel), C.POINTER(Options), _u64]),
     "idhmc_create_glm": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(Options), _u64]),
     "idhmc_create_glm_responses": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), _i64, _i64, C.POINTER(Options), _u64]),
     "idhmc_glm_responses": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
-    "idhmc_create_glm_priors": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), _i64, _i64,
-                                          C.POINTER(Options), _u64]),
+    "idhmc_create_glm_priors": _glm_parts_entry(1),
     "idhmc_glm_priors_get": (C.c_int, [_vp, C.POINTER(_i32), _dp]),
-    "idhmc_create_glm_local": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                         _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_create_glm_local": _glm_parts_entry(2),
     "idhmc_glm_local_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_double)]),
-    "idhmc_create_glm_factors": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                           C.POINTER(GlmFactors), _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_create_glm_factors": _glm_parts_entry(3),
     "idhmc_glm_factors_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
-    "idhmc_create_glm_slopes": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                          C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_create_glm_slopes": _glm_parts_entry(4),
     "idhmc_glm_factor_values_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_double)]),
-    "idhmc_create_glm_corr": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                        C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), C.POINTER(GlmPairs), _i64, _i64,
-                                        C.POINTER(Options), _u64]),
+    "idhmc_create_glm_corr": _glm_parts_entry(5),
     "idhmc_glm_pairs_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double)]),
-    "idhmc_create_glm_struct": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                          C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), C.POINTER(GlmPairs), C.POINTER(GlmStructs),
-                                          _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_create_glm_struct": _glm_parts_entry(6),
     "idhmc_glm_structs_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double)]),
-    "idhmc_create_glm_gmrf": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                        C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), C.POINTER(GlmPairs), C.POINTER(GlmStructs),
-                                        C.POINTER(GlmGmrfs), _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_create_glm_gmrf": _glm_parts_entry(7),
     "idhmc_glm_gmrfs_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double), C.POINTER(_i64)]),
-    "idhmc_create_glm_block": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                         C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), C.POINTER(GlmPairs), C.POINTER(GlmStructs),
-                                         C.POINTER(GlmGmrfs), C.POINTER(GlmBlock), _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_create_glm_block": _glm_parts_entry(8),
     "idhmc_glm_block_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double)]),
-    "idhmc_create_glm_multi": (C.c_int, [C.POINTER(_vp), C.c_int, _i64, _i64, C.POINTER(GlmDesc), C.POINTER(GlmPriors), C.POINTER(GlmLocal),
-                                         C.POINTER(GlmFactors), C.POINTER(GlmFactorValues), C.POINTER(GlmPairs), C.POINTER(GlmStructs),
-                                         C.POINTER(GlmGmrfs), C.POINTER(GlmBlock), C.POINTER(GlmMembers), _i64, _i64, C.POINTER(Options), _u64]),
+    "idhmc_create_glm_multi": _glm_parts_entry(9),
     "idhmc_glm_members_get": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double)]),
     "idhmc_destroy": (C.c_int, [_vp]),
     "idhmc_set_stream": (C.c_int, [_vp, _vp]),

@@ -48,8 +48,8 @@ int idhmc_destroy(idhmc_ctx *c)
 
 
 // The data of a regression model -- a logistic regression ([X | y] in idhmc_model_desc::params), a GLM packed into params
-// ([K, nc, c | X | Y]; with auxiliary coordinates [K, nc, A, c | X | Y]) or handed over in parts (idhmc_create_glm,
-// idhmc_create_glm_responses) -- as the one validation and the one upload below read it.  Any other model: the defaults.
+// ([K, nc, c | X | Y]; with auxiliary coordinates [K, nc, A, c | X | Y]) or handed over in parts (idhmc_create_glm_model;
+// a field's comment names the entry its part came with) -- as the one validation and the one upload below read it.  Any other model: the defaults.
 struct GlmParts {
     const char *what = "";     // the model's name in messages
     int64_t n = 0;             // observations
@@ -726,16 +726,25 @@ int idhmc_create(idhmc_ctx **out, int device, int64_t nchains, int64_t first_cha
     return create_context(out, device, nchains, first_chain_id, model, opt_in, seed, nullptr);
 }
 
-// The priors of idhmc_create_glm_priors: every check of kind and nu.  *any: some kind is not 0 (none is: the context is the one
-// without priors).  nu_out: nu with 0 wherever the caller passed none.
-static int validate_priors(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, int J, std::vector<double> *nu_out, bool *any)
+// What create_glm derives from an idhmc_glm_model as its validation proceeds: every validate_* below takes the model and these, reads
+// the counts of the steps before it and sets its own (0, false: the part is absent and the context is the one without it).
+struct GlmCounts {
+    int64_t fcols = 0;         // the level columns, sum N_f
+    bool valued = false;       // some term has values
+    int J = 0, P = 0, S = 0, SZ = 0, G = 0, BK = 0, BZ = 0, MP = 0;   // local scales, pairs, structured terms (SZ: AR(1) ones), GMRF terms, block terms and zetas, planes of a wide table
+};
+
+// The priors of idhmc_create_glm_priors: every check of kind and nu over all D coordinates, so after every count is known.  *any: some
+// kind is not 0 (none is: the context is the one without priors).  nu_out: nu with 0 wherever the caller passed none.
+static int validate_priors(const idhmc_glm_model &m, const GlmCounts &n, std::vector<double> *nu_out, bool *any)
 {
+    const auto *glm = m.glm; const auto *pr = m.priors;
     *any = false;
     if (!pr || !pr->kind) {
         if (pr && pr->nu) return fail(IDHMC_ERR_BAD_ARG, "GLM: priors->nu without priors->kind");
         return IDHMC_OK;
     }
-    const int D = glm->Dx + glm->A + glm->H + J;
+    const int D = glm->Dx + glm->A + glm->H + n.J + n.P + n.BZ + n.SZ;
     nu_out->assign((size_t)D, 0.0);
     for (int c = 0; c < D; ++c) {
         const int32_t k = pr->kind[c];
@@ -760,35 +769,35 @@ static int validate_priors(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr
     return IDHMC_OK;
 }
 
-// The local scales of idhmc_create_glm_local: every check of local and slab_scale.  *J: the flagged columns (0: the context is the one
-// without local scales)
-static int validate_local(const idhmc_glm_desc *glm, const idhmc_glm_local *lc, int *J)
+// The local scales of idhmc_create_glm_local: every check of local and slab_scale.  J: the flagged columns
+static int validate_local(const idhmc_glm_model &m, GlmCounts *n)
 {
-    *J = 0;
+    const idhmc_glm_local *lc = m.local;
     if (!lc) return IDHMC_OK;
     if (!(std::isfinite(lc->slab_scale) && lc->slab_scale >= 0.0))
         return fail(IDHMC_ERR_BAD_ARG, "GLM: slab_scale = %g must be finite and >= 0 (0: no slab)", lc->slab_scale);
+    int J = 0;
     if (lc->local)
-        for (int c = 0; c < glm->Dx; ++c) {
+        for (int c = 0; c < m.glm->Dx; ++c) {
             if (lc->local[c] != 0 && lc->local[c] != 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: local[%d] = %d is neither 0 nor 1", c, lc->local[c]);
-            *J += lc->local[c];
+            J += lc->local[c];
         }
-    if (lc->slab_scale > 0.0 && *J == 0)
+    if (lc->slab_scale > 0.0 && J == 0)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: slab_scale = %g without a column that has a local scale (local is NULL or all zeros)", lc->slab_scale);
+    n->J = J;
     return IDHMC_OK;
 }
 
-// The factors of idhmc_create_glm_factors: every check of F, levels and index.  *fcols: the level columns, sum N_f (0: the context is
-// the one without factors)
-static int validate_factors(const idhmc_glm_desc *glm, const idhmc_glm_factors *fc, int64_t *fcols, bool members = false)
+// The factors of idhmc_create_glm_factors: every check of F, levels and index (with members: of F and levels).  fcols: the level columns
+static int validate_factors(const idhmc_glm_model &m, GlmCounts *n)
 {
-    *fcols = 0;
+    const auto *glm = m.glm; const auto *fc = m.factors;
     if (!fc) return IDHMC_OK;
     if (fc->F < 0 || fc->F > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors must be an integer in 0..4", fc->F);
     if (fc->F == 0) return IDHMC_OK;
-    if (members && fc->index)
+    if (m.members && fc->index)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: members and factors->index are both given: with members the levels come from members->index (factors->index must be NULL)");
-    if (!fc->levels || (!fc->index && !members)) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors need levels and index (%s is NULL)", fc->F, fc->levels ? "index" : "levels");
+    if (!fc->levels || (!fc->index && !m.members)) return fail(IDHMC_ERR_BAD_ARG, "GLM: F = %d factors need levels and index (%s is NULL)", fc->F, fc->levels ? "index" : "levels");
     int64_t cols = 0;
     for (int f = 0; f < fc->F; ++f) {
         if (fc->levels[f] < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor %d has levels[%d] = %d: at least one level is needed", f, f, fc->levels[f]);
@@ -797,53 +806,53 @@ static int validate_factors(const idhmc_glm_desc *glm, const idhmc_glm_factors *
     if (glm->Dx - cols < 1)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: Dd = Dx - sum of levels = %d - %lld = %lld: at least one dense column is needed",
                     glm->Dx, (long long)cols, (long long)(glm->Dx - cols));
-    for (int f = 0; f < fc->F && !members; ++f)               // (a table of members is checked by check_members)
+    for (int f = 0; f < fc->F && !m.members; ++f)               // (a table of members is checked by check_members)
         for (int64_t i = 0; i < glm->n; ++i) {
             const int32_t v = fc->index[(int64_t)f * glm->n + i];
             if (v < 0 || v >= fc->levels[f])
                 return fail(IDHMC_ERR_BAD_ARG, "GLM: index[%d][%lld] = %d is outside 0..%d (the levels of factor %d)", f, (long long)i, v, fc->levels[f] - 1, f);
         }
-    *fcols = cols;
+    n->fcols = cols;
     return IDHMC_OK;
 }
 
-// The values of idhmc_create_glm_slopes, after validate_factors: every check of has and values.  *any: some term has values (false: the
-// context is the one of idhmc_create_glm_factors)
-static int validate_factor_values(const idhmc_glm_desc *glm, const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_factor_values *fv, bool *any)
+// The values of idhmc_create_glm_slopes, after validate_factors: every check of has and values.  valued: some term has values
+static int validate_factor_values(const idhmc_glm_model &m, GlmCounts *n)
 {
-    *any = false;
+    const auto *fc = m.factors; const auto *fv = m.values;
     if (!fv) return IDHMC_OK;
-    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor values need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (!fc || n->fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor values need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
     if (!fv->has) return fail(IDHMC_ERR_BAD_ARG, "GLM: factor values need has, one flag per term (has is NULL)");
+    bool any = false;
     for (int f = 0; f < fc->F; ++f) {
         if (fv->has[f] != 0 && fv->has[f] != 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: has[%d] = %d must be 0 or 1", f, fv->has[f]);
-        if (fv->has[f]) *any = true;
+        if (fv->has[f]) any = true;
     }
-    if (!*any) return IDHMC_OK;
+    if (!any) return IDHMC_OK;
     if (!fv->values) return fail(IDHMC_ERR_BAD_ARG, "GLM: a term is flagged in has and values is NULL");
     for (int f = 0; f < fc->F; ++f) {
         if (!fv->has[f]) continue;                         // rows of unflagged terms are not read
-        for (int64_t i = 0; i < glm->n; ++i)
-            if (!std::isfinite(fv->values[(int64_t)f * glm->n + i]))
+        for (int64_t i = 0; i < m.glm->n; ++i)
+            if (!std::isfinite(fv->values[(int64_t)f * m.glm->n + i]))
                 return fail(IDHMC_ERR_BAD_ARG, "GLM: values[%d][%lld] is not finite", f, (long long)i);
     }
+    n->valued = true;
     return IDHMC_OK;
 }
 
 // The pairs of idhmc_create_glm_corr, after validate_factors and validate_local: every check of P, first, second and eta, and of the
-// zetas' entries in the prior arrays.  *P: the pairs (0: the context is the one of idhmc_create_glm_slopes)
-static int validate_pairs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, int J, const idhmc_glm_factors *fc, int64_t fcols,
-                          const idhmc_glm_pairs *pp, int *P)
+// zetas' entries in the prior arrays.  P: the pairs
+static int validate_pairs(const idhmc_glm_model &m, GlmCounts *n)
 {
-    *P = 0;
+    const auto *glm = m.glm; const auto *pr = m.priors; const auto *fc = m.factors; const auto *pp = m.pairs;
     if (!pp) return IDHMC_OK;
     if (pp->P < 0 || pp->P > 2) return fail(IDHMC_ERR_BAD_ARG, "GLM: P = %d pairs must be an integer in 0..2", pp->P);
     if (pp->P == 0) return IDHMC_OK;
     if (!pp->first || !pp->second || !pp->eta)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: P = %d pairs need first, second and eta (%s is NULL)", pp->P, !pp->first ? "first" : !pp->second ? "second" : "eta");
-    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: pairs need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (!fc || n->fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: pairs need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
     bool used[4] = {false, false, false, false};
-    const int cz0 = glm->Dx + glm->A + glm->H + J;
+    const int cz0 = glm->Dx + glm->A + glm->H + n->J;
     for (int p = 0; p < pp->P; ++p) {
         const int32_t a = pp->first[p], b = pp->second[p];
         if (a < 0 || a >= fc->F) return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d: first = %d is outside 0..%d (the model's terms)", p, a, fc->F - 1);
@@ -868,24 +877,23 @@ static int validate_pairs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
                             "be the default (kind 0, mu 0, tau 1, nu 0) and is not applied", p, eta, cz);
         }
     }
-    *P = pp->P;
+    n->P = pp->P;
     return IDHMC_OK;
 }
 
 // The structures of idhmc_create_glm_struct, after validate_pairs: every check of S, term, kind and eta, of the terms against the pairs
-// and the local flags, and of the AR(1) zetas' entries in the prior arrays (coordinate cz0 onwards).  *S: the structured terms (0: the
-// context is the one of idhmc_create_glm_corr), *SZ: those that are AR(1)
-static int validate_structs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, const idhmc_glm_local *local, int J, int P,
-                            const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_pairs *pp, const idhmc_glm_structs *st, int *S, int *SZ,
-                            int BZ = 0)      // BZ: the zetas of a block, which stand in front of the AR(1) zetas as the pairs' do
+// and the local flags, and of the AR(1) zetas' entries in the prior arrays (coordinate cz0 onwards: behind the pairs' zetas or, n->BZ,
+// a block's).  S: the structured terms, SZ: those that are AR(1)
+static int validate_structs(const idhmc_glm_model &m, GlmCounts *n)
 {
-    *S = *SZ = 0;
+    const auto *glm = m.glm; const auto *pr = m.priors; const auto *fc = m.factors; const auto *pp = m.pairs; const auto *st = m.structs;
+    const int J = n->J, P = n->P, BZ = n->BZ;
     if (!st) return IDHMC_OK;
     if (st->S < 0 || st->S > 2) return fail(IDHMC_ERR_BAD_ARG, "GLM: S = %d structured terms must be an integer in 0..2", st->S);
     if (st->S == 0) return IDHMC_OK;
     if (!st->term || !st->kind || !st->eta)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: S = %d structured terms need term, kind and eta (%s is NULL)", st->S, !st->term ? "term" : !st->kind ? "kind" : "eta");
-    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: structured terms need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (!fc || n->fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: structured terms need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
     int sz = 0;
     for (int i = 0; i < st->S; ++i) sz += st->kind[i] == IDHMC_STRUCT_AR1;
     if (glm->Dx + J + P + BZ + sz > 1024 - glm->A - glm->H)
@@ -910,10 +918,10 @@ static int validate_structs(const idhmc_glm_desc *glm, const idhmc_glm_priors *p
             if (pp->first[p] == t || pp->second[p] == t)
                 return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: term %d is in pair %d (a term is structured or paired, not both)", i, t, p);
         if (J > 0) {
-            int64_t o = glm->Dx - fcols;
+            int64_t o = glm->Dx - n->fcols;
             for (int f = 0; f < t; ++f) o += fc->levels[f];
             for (int32_t k = 0; k < fc->levels[t]; ++k)
-                if (local->local[o + k])
+                if (m.local->local[o + k])
                     return fail(IDHMC_ERR_BAD_ARG, "GLM: structure %d: local[%lld] is set on level %d of term %d (a structured term takes no local scale)",
                                 i, (long long)(o + k), k, t);
         }
@@ -930,26 +938,25 @@ static int validate_structs(const idhmc_glm_desc *glm, const idhmc_glm_priors *p
                             "must be the default (kind 0, mu 0, tau 1, nu 0) and is not applied", i, eta, cz);
         }
     }
-    *S = st->S;
-    *SZ = sz;
+    n->S = st->S;
+    n->SZ = sz;
     return IDHMC_OK;
 }
 
 // The GMRF terms of idhmc_create_glm_gmrf, after validate_structs: every check of G, term and kappa, of the terms against the pairs, the
-// structures, the local flags and the prior arrays, and of the precisions' tables.  *G: the GMRF terms (0: the context is the one of
-// idhmc_create_glm_struct)
-static int validate_gmrfs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, const idhmc_glm_local *local, int J, int P, int S,
-                          const idhmc_glm_factors *fc, int64_t fcols, const idhmc_glm_pairs *pp, const idhmc_glm_structs *st,
-                          const idhmc_glm_gmrfs *gm, int *G)
+// structures, the local flags and the prior arrays, and of the precisions' tables.  G: the GMRF terms
+static int validate_gmrfs(const idhmc_glm_model &m, GlmCounts *n)
 {
-    *G = 0;
+    const auto *glm = m.glm; const auto *pr = m.priors; const auto *fc = m.factors; const auto *pp = m.pairs; const auto *st = m.structs;
+    const auto *gm = m.gmrfs;
+    const int J = n->J, P = n->P, S = n->S;
     if (!gm) return IDHMC_OK;
     if (gm->G < 0 || gm->G > 2) return fail(IDHMC_ERR_BAD_ARG, "GLM: G = %d GMRF terms must be an integer in 0..2", gm->G);
     if (gm->G == 0) return IDHMC_OK;
     if (!gm->term || !gm->start || !gm->col || !gm->val || !gm->kappa)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: G = %d GMRF terms need term, start, col, val and kappa (%s is NULL)", gm->G,
                     !gm->term ? "term" : !gm->start ? "start" : !gm->col ? "col" : !gm->val ? "val" : "kappa");
-    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF terms need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (!fc || n->fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF terms need factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
     if (gm->start[0] != 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF start[0] = %lld must be 0", (long long)gm->start[0]);
     int64_t rows = 0;
     for (int i = 0; i < gm->G; ++i) {
@@ -964,11 +971,11 @@ static int validate_gmrfs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
         for (int k = 0; k < S; ++k)
             if (st->term[k] == t) return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: term %d is structure %d (a term is structured or a GMRF, not both)", i, t, k);
         const int32_t N = fc->levels[t];
-        int64_t o = glm->Dx - fcols;
+        int64_t o = glm->Dx - n->fcols;
         for (int f = 0; f < t; ++f) o += fc->levels[f];
         for (int32_t k = 0; k < N; ++k) {
             const int64_t c = o + k;
-            if (J > 0 && local->local[c])
+            if (J > 0 && m.local->local[c])
                 return fail(IDHMC_ERR_BAD_ARG, "GLM: GMRF %d: local[%lld] is set on level %d of term %d (a GMRF term takes no local scale)", i, (long long)c, k, t);
             const int32_t kd = pr && pr->kind ? pr->kind[c] : 0;
             const double nu = pr && pr->kind && pr->nu ? pr->nu[c] : 0.0;
@@ -1012,22 +1019,23 @@ static int validate_gmrfs(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
             }
         rows += N;
     }
-    *G = gm->G;
+    n->G = gm->G;
     return IDHMC_OK;
 }
 
 // The block of idhmc_create_glm_block, after validate_gmrfs: every check of K, term and eta, of the terms against the pairs, the
-// structures and the GMRF terms, and of the zetas' entries in the prior arrays (coordinate Dx + A + H + J onwards).  *K: the block's
-// terms (0: the context is the one of idhmc_create_glm_gmrf)
-static int validate_block(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr, int J, int P, int S, int SZ, int G, const idhmc_glm_factors *fc,
-                          int64_t fcols, const idhmc_glm_structs *st, const idhmc_glm_gmrfs *gm, const idhmc_glm_block *bk, int *K)
+// structures and the GMRF terms, and of the zetas' entries in the prior arrays (coordinate Dx + A + H + J onwards).  BK: the block's
+// terms (BZ, their zetas, is create_glm's: validate_structs needed it)
+static int validate_block(const idhmc_glm_model &m, GlmCounts *n)
 {
-    *K = 0;
+    const auto *glm = m.glm; const auto *pr = m.priors; const auto *fc = m.factors; const auto *st = m.structs; const auto *gm = m.gmrfs;
+    const auto *bk = m.block;
+    const int J = n->J, P = n->P, S = n->S, SZ = n->SZ, G = n->G;
     if (!bk) return IDHMC_OK;
     if (bk->K != 0 && (bk->K < 2 || bk->K > 4)) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block of K = %d terms: K must be 0, 2, 3 or 4", bk->K);
     if (bk->K == 0) return IDHMC_OK;
     if (!bk->term) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block of K = %d terms needs term (term is NULL)", bk->K);
-    if (!fc || fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block needs factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
+    if (!fc || n->fcols == 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block needs factor terms (factors is %s)", fc ? "given with F = 0" : "NULL");
     if (P > 0) return fail(IDHMC_ERR_BAD_ARG, "GLM: a block next to P = %d pairs (a model has pairs or a block, not both)", P);
     const int nz = (bk->K * (bk->K - 1)) / 2;
     if (glm->Dx + J + nz + SZ > 1024 - glm->A - glm->H)
@@ -1062,93 +1070,95 @@ static int validate_block(const idhmc_glm_desc *glm, const idhmc_glm_priors *pr,
                             "be the default (kind 0, mu 0, tau 1, nu 0) and is not applied", eta, cz);
         }
     }
-    *K = bk->K;
+    n->BK = bk->K;
     return IDHMC_OK;
 }
 
-// idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local, idhmc_create_glm_factors,
-// idhmc_create_glm_slopes, idhmc_create_glm_corr, idhmc_create_glm_struct, idhmc_create_glm_gmrf, idhmc_create_glm_block and
-// idhmc_create_glm_multi
-static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_desc *glm,
-                      bool responses, int64_t M, int64_t R, const idhmc_options *opt_in, uint64_t seed,
-                      const idhmc_glm_priors *priors = nullptr, const idhmc_glm_local *local = nullptr,
-                      const idhmc_glm_factors *factors = nullptr, const idhmc_glm_factor_values *values = nullptr,
-                      const idhmc_glm_pairs *pairs = nullptr, const idhmc_glm_structs *structs = nullptr,
-                      const idhmc_glm_gmrfs *gmrfs = nullptr, const idhmc_glm_block *block = nullptr,
-                      const idhmc_glm_members *members = nullptr)
+// The upload description of a validated model: every part the counts say is there (a part that is not keeps GlmParts' defaults)
+static GlmParts glm_parts(const idhmc_glm_model &m, const GlmCounts &n, bool responses)
+{
+    const idhmc_glm_desc *glm = m.glm;
+    GlmParts g{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, m.M, m.chains_per_response};
+    if (n.J > 0) { g.J = n.J; g.local = m.local->local; g.slab = m.local->slab_scale; }
+    if (n.fcols > 0) { g.F = m.factors->F; g.fcols = (int32_t)n.fcols; g.levels = m.factors->levels; g.findex = m.factors->index; }
+    if (n.valued) { g.fvalues = m.values->values; g.fhas = m.values->has; }
+    if (n.MP > 0) { g.MP = n.MP; g.mwidth = m.members->width; g.mindex = m.members->index; g.mvalues = m.members->values; }
+    if (n.P > 0) { g.P = n.P; g.pfirst = m.pairs->first; g.psecond = m.pairs->second; g.peta = m.pairs->eta; }
+    if (n.S > 0) { g.S = n.S; g.SZ = n.SZ; g.sterm = m.structs->term; g.skind = m.structs->kind; g.seta = m.structs->eta; }
+    if (n.G > 0) { g.G = n.G; g.gterm = m.gmrfs->term; g.gstart = m.gmrfs->start; g.gcol = m.gmrfs->col; g.gval = m.gmrfs->val; g.gkappa = m.gmrfs->kappa; }
+    if (n.BK > 0) { g.BK = n.BK; g.BZ = n.BZ; g.bterm = m.block->term; g.beta = m.block->eta; }
+    return g;
+}
+
+// The one road of every GLM handed over in parts: idhmc_create_glm_model and the eleven entries that are it with the later parts NULL.
+// `responses`: the context of idhmc_create_glm_responses whatever (M, chains_per_response) is; it is that for anything but (1, 0) anyway.
+// The order of the checks is the order of the messages a doubly wrong call gets: DESIGN section 28.
+static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id, const idhmc_glm_model &model, bool responses,
+                      const idhmc_options *opt_in, uint64_t seed)
 {
     *out = nullptr;
+    idhmc_glm_model m = model;         // (the caller's is not written to: a table of members of width 1 is rewritten below)
+    const idhmc_glm_desc *glm = m.glm;
+    responses = responses || !(m.M == 1 && m.chains_per_response == 0);
+    GlmCounts n;
     if (glm->Dx < 1) return fail(IDHMC_ERR_BAD_ARG, "GLM: Dx = %d: at least one coefficient is needed", glm->Dx);
-    int64_t fcols = 0;
-    if (members && (!factors || factors->F == 0))
-        return fail(IDHMC_ERR_BAD_ARG, "GLM: members need factor terms: factors gives F and levels (factors is %s)", factors ? "given with F = 0" : "NULL");
-    if (members && values)
+    if (m.members && (!m.factors || m.factors->F == 0))
+        return fail(IDHMC_ERR_BAD_ARG, "GLM: members need factor terms: factors gives F and levels (factors is %s)", m.factors ? "given with F = 0" : "NULL");
+    if (m.members && m.values)
         return fail(IDHMC_ERR_BAD_ARG, "GLM: members and factor values are both given: with members the values come from members->values (values must be NULL)");
-    if (int rc = validate_factors(glm, factors, &fcols, members != nullptr)) return rc;
+    if (int rc = validate_factors(m, &n)) return rc;
     // A table of members every term of which has width 1 is F plain index rows, with values where it gives some: from here on it IS
     // that model (the same context, kernels and footprint).  MP > 0: a wide term.
-    int MP = 0;
     idhmc_glm_factors plain_f;
     idhmc_glm_factor_values plain_v;
     const int32_t plain_has[4] = {1, 1, 1, 1};
-    if (members) {
+    if (m.members) {
         char msg[320];
         bool wide = false;
-        if (!check_members(factors->F, factors->levels, glm->n, members->width, members->index, members->values, &MP, &wide, msg, sizeof msg))
+        if (!check_members(m.factors->F, m.factors->levels, glm->n, m.members->width, m.members->index, m.members->values, &n.MP, &wide, msg, sizeof msg))
             return fail(IDHMC_ERR_BAD_ARG, "%s", msg);
         if (!wide) {
-            plain_f = idhmc_glm_factors{factors->F, factors->levels, members->index};
-            plain_v = idhmc_glm_factor_values{members->values, plain_has};
-            factors = &plain_f;
-            values = members->values ? &plain_v : nullptr;
-            members = nullptr;
-            MP = 0;
+            plain_f = idhmc_glm_factors{m.factors->F, m.factors->levels, m.members->index};
+            plain_v = idhmc_glm_factor_values{m.members->values, plain_has};
+            m.factors = &plain_f;
+            m.values = m.members->values ? &plain_v : nullptr;
+            m.members = nullptr;
+            n.MP = 0;
         }
     }
-    bool valued = false;
-    if (int rc = validate_factor_values(glm, factors, fcols, values, &valued)) return rc;
+    if (int rc = validate_factor_values(m, &n)) return rc;
     if (glm->A < 0 || glm->A > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: A = %d must be an integer in 0..4", glm->A);
     if (glm->H < 0 || glm->H > 4) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d must be an integer in 0..4", glm->H);
     if (glm->Dx > 1024 - glm->A - glm->H)
         return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H = %lld: a GLM is limited to D <= 1024", (long long)glm->Dx + glm->A + glm->H);
-    int J = 0;
-    if (int rc = validate_local(glm, local, &J)) return rc;
-    if (glm->Dx + J > 1024 - glm->A - glm->H)
+    if (int rc = validate_local(m, &n)) return rc;
+    if (glm->Dx + n.J > 1024 - glm->A - glm->H)
         return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J = %lld: a GLM is limited to D <= 1024 (J = %d local scales)",
-                    (long long)glm->Dx + glm->A + glm->H + J, J);
-    if (pairs && pairs->P >= 0 && pairs->P <= 2 && glm->Dx + J + pairs->P > 1024 - glm->A - glm->H)
+                    (long long)glm->Dx + glm->A + glm->H + n.J, n.J);
+    if (m.pairs && m.pairs->P >= 0 && m.pairs->P <= 2 && glm->Dx + n.J + m.pairs->P > 1024 - glm->A - glm->H)
         return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + P = %lld: a GLM is limited to D <= 1024 (P = %d pairs)",
-                    (long long)glm->Dx + glm->A + glm->H + J + pairs->P, pairs->P);
-    int P = 0;
-    if (int rc = validate_pairs(glm, priors, J, factors, fcols, pairs, &P)) return rc;
+                    (long long)glm->Dx + glm->A + glm->H + n.J + m.pairs->P, m.pairs->P);
+    if (int rc = validate_pairs(m, &n)) return rc;
     // (the AR(1) zetas stand behind the block's as behind the pairs': a well-formed block's count goes where P goes, and validate_block,
-    // which needs S and G, then checks the block itself)
-    const int BZ0 = P == 0 && block && block->K >= 2 && block->K <= 4 ? (block->K * (block->K - 1)) / 2 : 0;
-    int S = 0, SZ = 0;
-    if (BZ0 == 0) {
-        if (int rc = validate_structs(glm, priors, local, J, P, factors, fcols, pairs, structs, &S, &SZ)) return rc;
-    } else {
-        if (glm->Dx + J + BZ0 > 1024 - glm->A - glm->H)
-            return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + K (K - 1) / 2 = %lld: a GLM is limited to D <= 1024 (a block of K = %d terms)",
-                        (long long)glm->Dx + glm->A + glm->H + J + BZ0, block->K);
-        if (int rc = validate_structs(glm, priors, local, J, P, factors, fcols, pairs, structs, &S, &SZ, BZ0)) return rc;
-    }
-    int G = 0;
-    if (int rc = validate_gmrfs(glm, priors, local, J, P, S, factors, fcols, pairs, structs, gmrfs, &G)) return rc;
-    int BK = 0;
-    if (int rc = validate_block(glm, priors, J, P, S, SZ, G, factors, fcols, structs, gmrfs, block, &BK)) return rc;
-    if (members) {
+    // which needs S and G, then checks the block itself: it passes a block only with this count, and with none only when this is 0)
+    if (n.P == 0 && m.block && m.block->K >= 2 && m.block->K <= 4) n.BZ = (m.block->K * (m.block->K - 1)) / 2;
+    if (n.BZ > 0 && glm->Dx + n.J + n.BZ > 1024 - glm->A - glm->H)
+        return fail(IDHMC_ERR_BAD_ARG, "D = Dx + A + H + J + K (K - 1) / 2 = %lld: a GLM is limited to D <= 1024 (a block of K = %d terms)",
+                    (long long)glm->Dx + glm->A + glm->H + n.J + n.BZ, m.block->K);
+    if (int rc = validate_structs(m, &n)) return rc;
+    if (int rc = validate_gmrfs(m, &n)) return rc;
+    if (int rc = validate_block(m, &n)) return rc;
+    if (m.members) {
         // (a pair or a block takes level k of one term with level k of another, one level per observation each)
-        for (int p = 0; p < P; ++p)
-            for (const int32_t t : {pairs->first[p], pairs->second[p]})
-                if (members->width[t] > 1)
-                    return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d names term %d, which has width %d: a term with several levels per observation is in no pair", p, t, members->width[t]);
-        for (int r = 0; r < BK; ++r)
-            if (members->width[block->term[r]] > 1)
+        for (int p = 0; p < n.P; ++p)
+            for (const int32_t t : {m.pairs->first[p], m.pairs->second[p]})
+                if (m.members->width[t] > 1)
+                    return fail(IDHMC_ERR_BAD_ARG, "GLM: pair %d names term %d, which has width %d: a term with several levels per observation is in no pair", p, t, m.members->width[t]);
+        for (int r = 0; r < n.BK; ++r)
+            if (m.members->width[m.block->term[r]] > 1)
                 return fail(IDHMC_ERR_BAD_ARG, "GLM: the block names term %d, which has width %d: a term with several levels per observation is in no block",
-                            block->term[r], members->width[block->term[r]]);
+                            m.block->term[r], m.members->width[m.block->term[r]]);
     }
-    const int BZ = (BK * (BK - 1)) / 2;
     if (glm->H > 0 && !glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: H = %d groups need the group of every column (groups is NULL)", glm->H);
     if (glm->H == 0 && glm->groups) return fail(IDHMC_ERR_BAD_ARG, "GLM: groups must be NULL with H = 0");
     if (glm->H > 0) {
@@ -1161,70 +1171,70 @@ static int create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t firs
         for (int g = 0; g < glm->H; ++g)
             if (!used[g]) return fail(IDHMC_ERR_BAD_ARG, "GLM: group %d has no column", g);
     }
-    idhmc_model_desc m;
-    memset(&m, 0, sizeof m);
-    m.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM;
-    m.D = glm->Dx + glm->A + glm->H + J + P + BZ + SZ;
-    m.mu = glm->mu;
-    m.tau = glm->tau;
-    m.source = glm->source;
+    const int P = n.P, S = n.S, SZ = n.SZ, G = n.G, BK = n.BK, BZ = n.BZ;
+    const idhmc_model_desc md = {.kind = glm->A > 0 ? IDHMC_MODEL_GLM_AUX : IDHMC_MODEL_GLM, .D = glm->Dx + glm->A + glm->H + n.J + P + BZ + SZ,
+                                 .mu = glm->mu, .tau = glm->tau, .source = glm->source};
     std::vector<double> nu;
     bool any = false;
-    if (int rc = validate_priors(glm, priors, J + P + BZ + SZ, &nu, &any)) return rc;
-    GlmParts parts{"", glm->n, glm->K, glm->nc, glm->A, glm->H, glm->X, glm->Y, glm->constants, glm->groups, responses, M, R};
-    if (any) { parts.pkind = priors->kind; parts.pnu = nu.data(); }
-    if (J > 0) { parts.J = J; parts.local = local->local; parts.slab = local->slab_scale; }
-    if (fcols > 0) { parts.F = factors->F; parts.fcols = (int32_t)fcols; parts.levels = factors->levels; parts.findex = factors->index; }
-    if (valued) { parts.fvalues = values->values; parts.fhas = values->has; }
-    if (members) { parts.MP = MP; parts.mwidth = members->width; parts.mindex = members->index; parts.mvalues = members->values; }
+    if (int rc = validate_priors(m, n, &nu, &any)) return rc;
+    GlmParts parts = glm_parts(m, n, responses);
+    if (any) { parts.pkind = m.priors->kind; parts.pnu = nu.data(); }
     std::vector<int32_t> kdev, kpub;     // a zeta with eta > 0: the device table marks it (kPriorLkj of idhmc_glm_coords.hpp, eta in nu's place)
     std::vector<double> nudev, nupub;
-    if (P > 0) { parts.P = P; parts.pfirst = pairs->first; parts.psecond = pairs->second; parts.peta = pairs->eta; }
-    if (S > 0) { parts.S = S; parts.SZ = SZ; parts.sterm = structs->term; parts.skind = structs->kind; parts.seta = structs->eta; }
-    if (G > 0) { parts.G = G; parts.gterm = gmrfs->term; parts.gstart = gmrfs->start; parts.gcol = gmrfs->col; parts.gval = gmrfs->val; parts.gkappa = gmrfs->kappa; }
-    if (BK > 0) { parts.BK = BK; parts.BZ = BZ; parts.bterm = block->term; parts.beta = block->eta; }
     if (P > 0 || SZ > 0 || G > 0 || BK > 0) {
-        bool lkj = G > 0 || (BK > 0 && block->eta > 0.0);      // (a GMRF term's members are marked too: kPriorGmrf)
-        for (int p = 0; p < P; ++p) lkj = lkj || pairs->eta[p] > 0.0;
-        for (int i = 0; i < S; ++i) lkj = lkj || structs->eta[i] > 0.0;
+        bool lkj = G > 0 || (BK > 0 && m.block->eta > 0.0);      // (a GMRF term's members are marked too: kPriorGmrf)
+        for (int p = 0; p < P; ++p) lkj = lkj || m.pairs->eta[p] > 0.0;
+        for (int i = 0; i < S; ++i) lkj = lkj || m.structs->eta[i] > 0.0;
         if (lkj) {
-            kpub.assign((size_t)m.D, 0);
-            nupub.assign((size_t)m.D, 0.0);
-            if (any) { kpub.assign(priors->kind, priors->kind + m.D); nupub = nu; }
+            kpub.assign((size_t)md.D, 0);
+            nupub.assign((size_t)md.D, 0.0);
+            if (any) { kpub.assign(m.priors->kind, m.priors->kind + md.D); nupub = nu; }
             kdev = kpub;
             nudev = nupub;
             for (int p = 0; p < P; ++p)
-                if (pairs->eta[p] > 0.0) { kdev[(size_t)(m.D - SZ - P + p)] = 5; nudev[(size_t)(m.D - SZ - P + p)] = pairs->eta[p]; }
+                if (m.pairs->eta[p] > 0.0) { kdev[(size_t)(md.D - SZ - P + p)] = 5; nudev[(size_t)(md.D - SZ - P + p)] = m.pairs->eta[p]; }
             // LKJ(eta) on the block's K x K matrix: zeta_ji takes the row with beta_ji = eta + (K - 2 - i) / 2, i its column
-            if (BK > 0 && block->eta > 0.0)
+            if (BK > 0 && m.block->eta > 0.0)
                 for (int j = 1; j < BK; ++j)
                     for (int i = 0; i < j; ++i) {
-                        const size_t cz = (size_t)(m.D - SZ - BZ + (j * (j - 1)) / 2 + i);
+                        const size_t cz = (size_t)(md.D - SZ - BZ + (j * (j - 1)) / 2 + i);
                         kdev[cz] = 5;
-                        nudev[cz] = block->eta + 0.5 * (double)(BK - 2 - i);
+                        nudev[cz] = m.block->eta + 0.5 * (double)(BK - 2 - i);
                     }
             for (int i = 0, z = 0; i < S; ++i) {
-                if (structs->kind[i] != IDHMC_STRUCT_AR1) continue;
-                if (structs->eta[i] > 0.0) { kdev[(size_t)(m.D - SZ + z)] = 5; nudev[(size_t)(m.D - SZ + z)] = structs->eta[i]; }
+                if (m.structs->kind[i] != IDHMC_STRUCT_AR1) continue;
+                if (m.structs->eta[i] > 0.0) { kdev[(size_t)(md.D - SZ + z)] = 5; nudev[(size_t)(md.D - SZ + z)] = m.structs->eta[i]; }
                 ++z;
             }
             for (int i = 0; i < G; ++i) {
-                int64_t o = glm->Dx - fcols;
-                for (int f = 0; f < gmrfs->term[i]; ++f) o += factors->levels[f];
-                for (int32_t k = 0; k < factors->levels[gmrfs->term[i]]; ++k) kdev[(size_t)(o + k)] = 6;
+                int64_t o = glm->Dx - n.fcols;
+                for (int f = 0; f < m.gmrfs->term[i]; ++f) o += m.factors->levels[f];
+                for (int32_t k = 0; k < m.factors->levels[m.gmrfs->term[i]]; ++k) kdev[(size_t)(o + k)] = 6;
             }
             parts.pkind = kdev.data(); parts.pnu = nudev.data();
             parts.pkind_pub = kpub.data(); parts.pnu_pub = nupub.data();
         }
     }
-    return create_context(out, device, nchains, first_chain_id, &m, opt_in, seed, &parts);
+    return create_context(out, device, nchains, first_chain_id, &md, opt_in, seed, &parts);
 }
 
+int idhmc_create_glm_model(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
+                           const idhmc_glm_model *model, const idhmc_options *opt_in, uint64_t seed)
+{
+    if (!out || !model || !model->glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_model: null argument");
+    idhmc_glm_model m = *model;
+    if (m.M == 0 && m.chains_per_response == 0) m.M = 1;          // a zero-initialised struct with glm set is a plain model
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
+}
+
+// The eleven entries from before idhmc_create_glm_model: each is it with the parts it has no argument for NULL and (M, chains_per_response)
+// as given ((0, 0) is refused as it always was).  They differ in the fields they set; idhmc_create_glm_responses also forces its context.
 int idhmc_create_glm(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
                      const idhmc_glm_desc *glm, const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm: null argument");
-    return create_glm(out, device, nchains, first_chain_id, glm, false, 1, 0, opt_in, seed);
+    const idhmc_glm_model m = {.glm = glm, .M = 1, .chains_per_response = 0};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1232,7 +1242,8 @@ int idhmc_create_glm_responses(idhmc_ctx **out, int device, int64_t nchains, int
                                const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_responses: null argument");
-    return create_glm(out, device, nchains, first_chain_id, glm, true, M, chains_per_response, opt_in, seed);
+    const idhmc_glm_model m = {.glm = glm, .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, true, opt_in, seed);
 }
 
 int idhmc_create_glm_priors(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1240,9 +1251,8 @@ int idhmc_create_glm_priors(idhmc_ctx **out, int device, int64_t nchains, int64_
                             int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_priors: null argument");
-    // (1, 0): the context of idhmc_create_glm; anything else: the one of idhmc_create_glm_responses, which refuses what it refuses
-    const bool responses = !(M == 1 && chains_per_response == 0);
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_local(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1250,8 +1260,8 @@ int idhmc_create_glm_local(idhmc_ctx **out, int device, int64_t nchains, int64_t
                            int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_local: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_factors(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1260,8 +1270,8 @@ int idhmc_create_glm_factors(idhmc_ctx **out, int device, int64_t nchains, int64
                              const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_factors: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .factors = factors, .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_slopes(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1270,8 +1280,9 @@ int idhmc_create_glm_slopes(idhmc_ctx **out, int device, int64_t nchains, int64_
                             const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_slopes: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .factors = factors, .values = values,
+                               .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_corr(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1280,8 +1291,9 @@ int idhmc_create_glm_corr(idhmc_ctx **out, int device, int64_t nchains, int64_t 
                           int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_corr: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values, pairs);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .factors = factors, .values = values, .pairs = pairs,
+                               .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_struct(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1290,9 +1302,9 @@ int idhmc_create_glm_struct(idhmc_ctx **out, int device, int64_t nchains, int64_
                             const idhmc_glm_structs *structs, int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_struct: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
-                      pairs, structs);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .factors = factors, .values = values, .pairs = pairs, .structs = structs,
+                               .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_gmrf(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1302,9 +1314,10 @@ int idhmc_create_glm_gmrf(idhmc_ctx **out, int device, int64_t nchains, int64_t 
                           const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_gmrf: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
-                      pairs, structs, gmrfs);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .factors = factors, .values = values,
+                               .pairs = pairs, .structs = structs, .gmrfs = gmrfs,
+                               .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_block(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1314,9 +1327,10 @@ int idhmc_create_glm_block(idhmc_ctx **out, int device, int64_t nchains, int64_t
                            int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_block: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
-                      pairs, structs, gmrfs, block);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .factors = factors, .values = values,
+                               .pairs = pairs, .structs = structs, .gmrfs = gmrfs, .block = block,
+                               .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_create_glm_multi(idhmc_ctx **out, int device, int64_t nchains, int64_t first_chain_id,
@@ -1326,9 +1340,10 @@ int idhmc_create_glm_multi(idhmc_ctx **out, int device, int64_t nchains, int64_t
                            const idhmc_glm_members *members, int64_t M, int64_t chains_per_response, const idhmc_options *opt_in, uint64_t seed)
 {
     if (!out || !glm) return fail(IDHMC_ERR_BAD_ARG, "idhmc_create_glm_multi: null argument");
-    const bool responses = !(M == 1 && chains_per_response == 0);      // as idhmc_create_glm_priors
-    return create_glm(out, device, nchains, first_chain_id, glm, responses, M, chains_per_response, opt_in, seed, priors, local, factors, values,
-                      pairs, structs, gmrfs, block, members);
+    const idhmc_glm_model m = {.glm = glm, .priors = priors, .local = local, .factors = factors, .values = values,
+                               .pairs = pairs, .structs = structs, .gmrfs = gmrfs, .block = block, .members = members,
+                               .M = M, .chains_per_response = chains_per_response};
+    return create_glm(out, device, nchains, first_chain_id, m, false, opt_in, seed);
 }
 
 int idhmc_glm_members_get(const idhmc_ctx *c, int32_t *width, int32_t *index, double *values)

@@ -5,7 +5,8 @@ import numpy as np
 
 from . import _lib
 from . import glm as _glm
-from ._lib import GlmBlock, GlmDesc, GlmFactors, GlmFactorValues, GlmGmrfs, GlmLocal, GlmMembers, GlmPairs, GlmPriors, GlmStructs, ModelDesc, Options, check
+from ._lib import (GlmBlock, GlmDesc, GlmFactors, GlmFactorValues, GlmGmrfs, GlmLocal, GlmMembers, GlmModel, GlmPairs, GlmPriors, GlmStructs,
+                   ModelDesc, Options, check)
 
 # reference TreeStatisticsNUTS (src/NUTS.jl:229-242), 32 bytes
 TREE_STATS_DTYPE = np.dtype([("pi", "<f8"), ("acceptance_rate", "<f8"), ("term_left", "<i4"),
@@ -74,6 +75,36 @@ class Model:
         if self.tau is not None:
             d.tau = _dp(self.tau)
         return d
+
+    def glm_model(self):
+        """the idhmc_glm_model of idhmc_create_glm_model: every part this model has, built once.  The part structs are kept on the
+        returned struct as .parts, because a ctypes pointer field does not keep what it points to alive"""
+        def i32(a):
+            return a.ctypes.data_as(C.POINTER(C.c_int32))
+        members = self.member_width is not None      # a table of members: factors gives F and levels only, and there are no values
+        parts = {"glm": self.glm_desc()}
+        if self.prior_kind is not None:
+            parts["priors"] = GlmPriors(kind=i32(self.prior_kind), nu=_dp(self.prior_nu))
+        if self.J > 0:
+            parts["local"] = GlmLocal(local=i32(self.local), slab_scale=self.slab_scale or 0.0)
+        if self.F > 0:
+            parts["factors"] = GlmFactors(F=self.F, levels=i32(self.levels), index=None if members else i32(self.factor_index))
+        if self.factor_has is not None:
+            parts["values"] = GlmFactorValues(values=_dp(self.factor_values), has=i32(self.factor_has))
+        if self.P > 0:
+            parts["pairs"] = GlmPairs(P=self.P, first=i32(self.pair_first), second=i32(self.pair_second), eta=_dp(self.pair_eta))
+        if self.S > 0:
+            parts["structs"] = GlmStructs(S=self.S, term=i32(self.struct_term), kind=i32(self.struct_kind), eta=_dp(self.struct_eta))
+        if self.G > 0:
+            parts["gmrfs"] = GlmGmrfs(G=self.G, term=i32(self.gmrf_term), start=self.gmrf_start.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      col=i32(self.gmrf_col), val=_dp(self.gmrf_val), kappa=_dp(self.gmrf_kappa))
+        if self.BK > 0:
+            parts["block"] = GlmBlock(K=self.BK, term=i32(self.block_term), eta=self.block_eta)
+        if members:
+            parts["members"] = GlmMembers(width=i32(self.member_width), index=i32(self.member_index), values=_dp(self.member_values))
+        gm = GlmModel(M=self.M if self.R is not None else 1, chains_per_response=self.R or 0, **{k: C.pointer(v) for k, v in parts.items()})
+        gm.parts = parts
+        return gm
 
     def desc(self):
         d = ModelDesc(kind=self.kind, D=self.D)
@@ -374,8 +405,8 @@ def GLM(X, Y, source, constants=None, prior_mu=None, prior_tau=None, aux=0, grou
     priors = kind is not None and bool(kind.any())
     K = Y.shape[-1]
     if H > 0 or R is not None or priors or J > 0 or F > 0:
-        # handed over in parts (idhmc_create_glm, idhmc_create_glm_responses, idhmc_create_glm_priors, idhmc_create_glm_local): the packed
-        # params are not stretched for the groups, the responses, the priors or the local scales
+        # handed over in parts (Model.glm_model, idhmc_create_glm_model): the packed params are not stretched for the groups, the
+        # responses, the priors, the local scales or the factors.  No params and X, Y kept as arrays is what Engine reads as "in parts"
         m = Model(MODEL_GLM_AUX if A else MODEL_GLM, D, mu=mu, tau=tau, source=source)
         m.X, m.Y, m.constants = np.ascontiguousarray(X), np.ascontiguousarray(Y), np.ascontiguousarray(c)
     elif A == 0:
@@ -416,133 +447,31 @@ class Engine:
     """All chains of one device (one context per device, include/idhmc.h)."""
 
     def __init__(self, model, nchains, options=None, seed=1, first_chain=0, device=0):
-        self.lib = _lib.load()
-        self.model = model
-        self.opt = options if options is not None else default_options()
-        self.C, self.D = int(nchains), model.D
+        lib = _lib.load()
+        opt = options if options is not None else default_options()
         h = C.c_void_p()
-        kind = getattr(model, "prior_kind", None)
-        if getattr(model, "F", 0) > 0:
-            desc = model.glm_desc()
-            pr = lc = None
-            if kind is not None:
-                pr = C.byref(GlmPriors(kind=kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=_dp(model.prior_nu)))
-            if model.J > 0:
-                lc = C.byref(GlmLocal(local=model.local.ctypes.data_as(C.POINTER(C.c_int32)), slab_scale=model.slab_scale or 0.0))
-            fc = GlmFactors(F=model.F, levels=model.levels.ctypes.data_as(C.POINTER(C.c_int32)),
-                            index=model.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
-            R = getattr(model, "R", None)
-            if getattr(model, "member_width", None) is not None:
-                # a table of members: every optional part goes along, and factors gives F and levels only
-                fc.index = None
-                pp = st = gm = bk = None
-                ip = C.POINTER(C.c_int32)
-                if getattr(model, "P", 0) > 0:
-                    pp = C.byref(GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
-                                          eta=_dp(model.pair_eta)))
-                if getattr(model, "S", 0) > 0:
-                    st = C.byref(GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
-                                            eta=_dp(model.struct_eta)))
-                if getattr(model, "G", 0) > 0:
-                    gm = C.byref(GlmGmrfs(G=model.G, term=model.gmrf_term.ctypes.data_as(ip),
-                                          start=model.gmrf_start.ctypes.data_as(C.POINTER(C.c_int64)), col=model.gmrf_col.ctypes.data_as(ip),
-                                          val=_dp(model.gmrf_val), kappa=_dp(model.gmrf_kappa)))
-                if getattr(model, "BK", 0) > 0:
-                    bk = C.byref(GlmBlock(K=model.BK, term=model.block_term.ctypes.data_as(ip), eta=model.block_eta))
-                mm = GlmMembers(width=model.member_width.ctypes.data_as(ip), index=model.member_index.ctypes.data_as(ip),
-                                values=_dp(model.member_values))
-                check(self.lib.idhmc_create_glm_multi(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), None, pp, st,
-                                                      gm, bk, C.byref(mm), model.M if R is not None else 1, R if R is not None else 0,
-                                                      C.byref(self.opt), seed))
-            elif getattr(model, "BK", 0) > 0:
-                fv = st = gm = None
-                ip = C.POINTER(C.c_int32)
-                if getattr(model, "factor_has", None) is not None:
-                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(ip)))
-                if getattr(model, "S", 0) > 0:
-                    st = C.byref(GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
-                                            eta=_dp(model.struct_eta)))
-                if getattr(model, "G", 0) > 0:
-                    gm = C.byref(GlmGmrfs(G=model.G, term=model.gmrf_term.ctypes.data_as(ip),
-                                          start=model.gmrf_start.ctypes.data_as(C.POINTER(C.c_int64)), col=model.gmrf_col.ctypes.data_as(ip),
-                                          val=_dp(model.gmrf_val), kappa=_dp(model.gmrf_kappa)))
-                bk = GlmBlock(K=model.BK, term=model.block_term.ctypes.data_as(ip), eta=model.block_eta)
-                check(self.lib.idhmc_create_glm_block(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, None, st,
-                                                      gm, C.byref(bk), model.M if R is not None else 1, R if R is not None else 0,
-                                                      C.byref(self.opt), seed))
-            elif getattr(model, "G", 0) > 0:
-                fv = pp = st = None
-                ip = C.POINTER(C.c_int32)
-                if getattr(model, "factor_has", None) is not None:
-                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(ip)))
-                if getattr(model, "P", 0) > 0:
-                    pp = C.byref(GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
-                                          eta=_dp(model.pair_eta)))
-                if getattr(model, "S", 0) > 0:
-                    st = C.byref(GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
-                                            eta=_dp(model.struct_eta)))
-                gm = GlmGmrfs(G=model.G, term=model.gmrf_term.ctypes.data_as(ip), start=model.gmrf_start.ctypes.data_as(C.POINTER(C.c_int64)),
-                              col=model.gmrf_col.ctypes.data_as(ip), val=_dp(model.gmrf_val), kappa=_dp(model.gmrf_kappa))
-                check(self.lib.idhmc_create_glm_gmrf(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, pp, st,
-                                                     C.byref(gm), model.M if R is not None else 1, R if R is not None else 0,
-                                                     C.byref(self.opt), seed))
-            elif getattr(model, "S", 0) > 0:
-                fv = pp = None
-                ip = C.POINTER(C.c_int32)
-                if getattr(model, "factor_has", None) is not None:
-                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(ip)))
-                if getattr(model, "P", 0) > 0:
-                    pp = C.byref(GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
-                                          eta=_dp(model.pair_eta)))
-                st = GlmStructs(S=model.S, term=model.struct_term.ctypes.data_as(ip), kind=model.struct_kind.ctypes.data_as(ip),
-                                eta=_dp(model.struct_eta))
-                check(self.lib.idhmc_create_glm_struct(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, pp,
-                                                       C.byref(st), model.M if R is not None else 1, R if R is not None else 0,
-                                                       C.byref(self.opt), seed))
-            elif getattr(model, "P", 0) > 0:
-                fv = None
-                if getattr(model, "factor_has", None) is not None:
-                    fv = C.byref(GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(C.POINTER(C.c_int32))))
-                ip = C.POINTER(C.c_int32)
-                pp = GlmPairs(P=model.P, first=model.pair_first.ctypes.data_as(ip), second=model.pair_second.ctypes.data_as(ip),
-                              eta=_dp(model.pair_eta))
-                check(self.lib.idhmc_create_glm_corr(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), fv, C.byref(pp),
-                                                     model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
-            elif getattr(model, "factor_has", None) is not None:
-                fv = GlmFactorValues(values=_dp(model.factor_values), has=model.factor_has.ctypes.data_as(C.POINTER(C.c_int32)))
-                check(self.lib.idhmc_create_glm_slopes(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc), C.byref(fv),
-                                                       model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
-            else:
-                check(self.lib.idhmc_create_glm_factors(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, lc, C.byref(fc),
-                                                        model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
-        elif getattr(model, "J", 0) > 0:
-            desc = model.glm_desc()
-            pr = None
-            if kind is not None:
-                pr = C.byref(GlmPriors(kind=kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=_dp(model.prior_nu)))
-            lc = GlmLocal(local=model.local.ctypes.data_as(C.POINTER(C.c_int32)), slab_scale=model.slab_scale or 0.0)
-            R = getattr(model, "R", None)
-            check(self.lib.idhmc_create_glm_local(C.byref(h), device, self.C, first_chain, C.byref(desc), pr, C.byref(lc),
-                                                  model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
-        elif kind is not None and kind.any():
-            desc = model.glm_desc()
-            pr = GlmPriors(kind=kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=_dp(model.prior_nu))
-            R = getattr(model, "R", None)
-            check(self.lib.idhmc_create_glm_priors(C.byref(h), device, self.C, first_chain, C.byref(desc), C.byref(pr),
-                                                   model.M if R is not None else 1, R if R is not None else 0, C.byref(self.opt), seed))
-        elif getattr(model, "R", None) is not None:
-            desc = model.glm_desc()
-            check(self.lib.idhmc_create_glm_responses(C.byref(h), device, self.C, first_chain, C.byref(desc), model.M, model.R,
-                                                      C.byref(self.opt), seed))
-        elif getattr(model, "H", 0) > 0:
-            desc = model.glm_desc()
-            check(self.lib.idhmc_create_glm(C.byref(h), device, self.C, first_chain, C.byref(desc), C.byref(self.opt), seed))
+        if model.kind in (MODEL_GLM, MODEL_GLM_AUX) and model.params is None:
+            # a GLM handed over in parts (GLM() packs no params and keeps X and Y as arrays): the one entry for all of them
+            gm = model.glm_model()
+            check(lib.idhmc_create_glm_model(C.byref(h), device, int(nchains), first_chain, C.byref(gm), C.byref(opt), seed))
         else:
             desc = model.desc()
-            check(self.lib.idhmc_create(C.byref(h), device, self.C, first_chain, C.byref(desc),
-                                        C.byref(self.opt), seed))
-        self.h = h
+            check(lib.idhmc_create(C.byref(h), device, int(nchains), first_chain, C.byref(desc), C.byref(opt), seed))
+        self._set(model, h, nchains, opt)
+
+    def _set(self, model, handle, nchains, options):
+        self.lib = _lib.load()
+        self.model, self.opt = model, options
+        self.C, self.D = int(nchains), model.D
+        self.h = handle
         self._hook = None
+
+    @classmethod
+    def _adopt(cls, model, handle, nchains, options):
+        """an Engine around a context made elsewhere (a test's direct call of a creation function); it owns the handle"""
+        eng = object.__new__(cls)
+        eng._set(model, handle, nchains, options)
+        return eng
 
     def close(self):
         if getattr(self, "h", None):

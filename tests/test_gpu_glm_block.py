@@ -317,8 +317,6 @@ def test_no_block_through_the_new_entry_point(idhmc):
     ip = C.POINTER(C.c_int32)
     engs = [idhmc.Engine(m, C_, opt, seed=3)]
     for bk in (None, _lib.GlmBlock(K=0)):
-        eng = object.__new__(idhmc.Engine)         # an Engine around the context of the new entry point: what Engine.__init__ sets
-        eng.lib, eng.model, eng.opt, eng.C, eng.D, eng._hook = lib, m, opt, C_, m.D, None
         desc = m.glm_desc()
         pr = _lib.GlmPriors(kind=m.prior_kind.ctypes.data_as(ip), nu=m.prior_nu.ctypes.data_as(C.POINTER(C.c_double)))
         fc = _lib.GlmFactors(F=m.F, levels=m.levels.ctypes.data_as(ip), index=m.factor_index.ctypes.data_as(ip))
@@ -326,7 +324,7 @@ def test_no_block_through_the_new_entry_point(idhmc):
         h = C.c_void_p()
         _lib.check(lib.idhmc_create_glm_block(C.byref(h), 0, C_, 0, C.byref(desc), C.byref(pr), None, C.byref(fc), C.byref(fv), None, None, None,
                                               None if bk is None else C.byref(bk), 1, 0, C.byref(opt), 3))
-        eng.h = h
+        eng = idhmc.Engine._adopt(m, h, C_, opt)     # an Engine around that context
         engs.append(eng)
     for e in engs:
         assert e.glm_form() == form and e.glm_block() == (None, None) and e.glm_pairs() == (None, None, None)

@@ -256,8 +256,6 @@ def engine_through(idhmc, entry, m, opt, seed, gmrfs=()):
     from inplacedhmc_jl_amd import _lib
     lib = idhmc.load_library()
     ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-    eng = object.__new__(idhmc.Engine)
-    eng.lib, eng.model, eng.opt, eng.C, eng.D, eng._hook = lib, m, opt, C_, m.D, None
     desc = m.glm_desc()
     pr = _lib.GlmPriors(kind=m.prior_kind.ctypes.data_as(ip), nu=m.prior_nu.ctypes.data_as(dp))
     fc = _lib.GlmFactors(F=m.F, levels=m.levels.ctypes.data_as(ip), index=m.factor_index.ctypes.data_as(ip))
@@ -269,7 +267,7 @@ def engine_through(idhmc, entry, m, opt, seed, gmrfs=()):
     h = C.c_void_p()
     extra = tuple(None if g is None else C.byref(g) for g in gmrfs)
     _lib.check(getattr(lib, entry)(C.byref(h), 0, C_, 0, C.byref(desc), C.byref(pr), None, C.byref(fc), fv, pp, st, *extra, 1, 0, C.byref(opt), seed))
-    eng.h = h
+    eng = idhmc.Engine._adopt(m, h, C_, opt)     # an Engine around that context
     return eng
 
 

@@ -377,8 +377,6 @@ def test_widths_of_one_through_the_new_entry_point(idhmc, valued):
     index = np.ascontiguousarray([i0, i1], dtype=np.int32)
     vals = np.ascontiguousarray(w)
     for members in (True, False):
-        eng = object.__new__(idhmc.Engine)     # an Engine around the context of the new entry point: what Engine.__init__ sets
-        eng.lib, eng.model, eng.opt, eng.C, eng.D, eng._hook = lib, m, opt, Cn, m.D, None
         desc = m.glm_desc()
         fc = _lib.GlmFactors(F=2, levels=m.levels.ctypes.data_as(ip), index=None if members else index.ctypes.data_as(ip))
         mm = _lib.GlmMembers(width=width.ctypes.data_as(ip), index=index.ctypes.data_as(ip), values=vals.ctypes.data_as(dp) if valued else None)
@@ -387,7 +385,7 @@ def test_widths_of_one_through_the_new_entry_point(idhmc, valued):
         _lib.check(lib.idhmc_create_glm_multi(C.byref(h), 0, Cn, 0, C.byref(desc), None, None, C.byref(fc),
                                               C.byref(fv) if valued and not members else None, None, None, None, None,
                                               C.byref(mm) if members else None, 1, 0, C.byref(opt), 3))
-        eng.h = h
+        eng = idhmc.Engine._adopt(m, h, Cn, opt)     # an Engine around that context
         engs.append(eng)
     for e in engs:
         assert e.glm_form() == 1 and list(e.glm_factors()[0]) == [7, 50] and np.array_equal(e.glm_factors()[1], index)

@@ -367,15 +367,13 @@ def test_plain_models_through_the_new_entry_point(idhmc):
     zeros = np.zeros(2, np.int32)
     engs = [idhmc.Engine(m, C_, opt, seed=3)]
     for fv in (None, _lib.GlmFactorValues(values=None, has=zeros.ctypes.data_as(C.POINTER(C.c_int32)))):
-        eng = object.__new__(idhmc.Engine)         # an Engine around the context of the new entry point: what Engine.__init__ sets
-        eng.lib, eng.model, eng.opt, eng.C, eng.D, eng._hook = lib, m, opt, C_, m.D, None
         desc = m.glm_desc()
         pr = _lib.GlmPriors(kind=m.prior_kind.ctypes.data_as(C.POINTER(C.c_int32)), nu=m.prior_nu.ctypes.data_as(C.POINTER(C.c_double)))
         fc = _lib.GlmFactors(F=m.F, levels=m.levels.ctypes.data_as(C.POINTER(C.c_int32)), index=m.factor_index.ctypes.data_as(C.POINTER(C.c_int32)))
         h = C.c_void_p()
         _lib.check(lib.idhmc_create_glm_slopes(C.byref(h), 0, C_, 0, C.byref(desc), C.byref(pr), None, C.byref(fc),
                                                None if fv is None else C.byref(fv), 1, 0, C.byref(opt), 3))
-        eng.h = h
+        eng = idhmc.Engine._adopt(m, h, C_, opt)     # an Engine around that context
         engs.append(eng)
     for e in engs:
         assert e.glm_form() == form and e.glm_factor_values() == (None, None) and list(e.glm_factors()[0]) == [7, 50]

@@ -298,8 +298,6 @@ def test_no_structure_through_the_new_entry_point(idhmc, null):
     ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
     engs = [idhmc.Engine(m, C_, opt, seed=3)]
     for st in ((None,) if null else (_lib.GlmStructs(S=0),)):
-        eng = object.__new__(idhmc.Engine)         # an Engine around the context of the new entry point: what Engine.__init__ sets
-        eng.lib, eng.model, eng.opt, eng.C, eng.D, eng._hook = lib, m, opt, C_, m.D, None
         desc = m.glm_desc()
         pr = _lib.GlmPriors(kind=m.prior_kind.ctypes.data_as(ip), nu=m.prior_nu.ctypes.data_as(dp))
         lc = _lib.GlmLocal(local=m.local.ctypes.data_as(ip), slab_scale=m.slab_scale)
@@ -309,7 +307,7 @@ def test_no_structure_through_the_new_entry_point(idhmc, null):
         h = C.c_void_p()
         _lib.check(lib.idhmc_create_glm_struct(C.byref(h), 0, C_, 0, C.byref(desc), C.byref(pr), C.byref(lc), C.byref(fc), C.byref(fv), C.byref(pp),
                                                None if st is None else C.byref(st), 1, 0, C.byref(opt), 3))
-        eng.h = h
+        eng = idhmc.Engine._adopt(m, h, C_, opt)     # an Engine around that context
         engs.append(eng)
     for e in engs:
         assert e.glm_form() == form and e.glm_structs() == (None, None, None) and list(e.glm_pairs()[0]) == [2]
